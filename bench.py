@@ -13,6 +13,12 @@ is used only for the start/stop barrier and the max-over-ranks of the elapsed ti
 relays rank 0's JSON line and exits with the child's code.  Under a launcher (WORLD_SIZE set) `--gpus` must
 agree with it.  `n_gpus` in the JSON line is the number of ranks that actually joined the process group.
 
+A plain run sets up, warms up, times `--steps` steps and prints the line (`ms_per_step` = wall time of one timed step).
+`--full` adds the legs that take runs of their own: the comparison of the timed output with the pool path (`verified`),
+one frame per launch (`single_frame`) and the CPU baseline (`cpu_baseline`).  `--dump-outputs DIR` writes what the last
+timed step computed as float32 .npy files (dump_outputs()); the inputs are seeded, so runs with the same arguments see
+the same frames.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -270,6 +276,39 @@ def verify_against_pool_path(torch, SangNom2, clip, dev_index, stream, kw, src, 
                 "planes": len(dst), "seconds": round(time.perf_counter() - t0, 3)}
 
 
+DUMP_BUDGET_SAMPLES = 14_000_000  # float32 samples written by --dump-outputs: 56 MB in all
+DUMP_FRAMES = 16  # frames of the batch sampled by --dump-outputs: the first, the last and a seeded choice of the others
+
+
+def dump_outputs(torch, out_dir, dst, batch) -> dict:
+    """`--dump-outputs DIR`: what the last timed step wrote, as DIR/plane<p>.npy (float32, shape (frames, rows, width)).  A
+    fixed sample keeps the files within DUMP_BUDGET_SAMPLES: DUMP_FRAMES frames of the batch and, where those frames are still
+    too large, the same seeded choice of rows in each of them (whole frames where they fit).  The sample depends only on the
+    batch and the plane shapes, so two builds run with the same arguments write comparable files."""
+    rng = np.random.default_rng(20240601)
+    inner = np.arange(1, batch - 1)  # the frames between the first and the last
+    pick = rng.choice(inner, size=min(len(inner), DUMP_FRAMES - 2), replace=False) if len(inner) else []
+    frames = sorted({0, batch - 1} | {int(f) for f in pick})
+    per_frame = sum(t.shape[1] * t.shape[2] for t in dst)
+    share = min(1.0, DUMP_BUDGET_SAMPLES / (len(frames) * per_frame))
+    os.makedirs(out_dir, exist_ok=True)
+    fi = torch.tensor(frames, device=dst[0].device)
+    planes = []
+    for p, t in enumerate(dst):
+        h = t.shape[1]
+        k = max(1, int(h * share))
+        rows = np.arange(h) if k >= h else np.sort(rng.choice(h, size=k, replace=False))
+        part = t.index_select(0, fi).index_select(1, torch.tensor(rows, device=t.device))
+        if part.dtype == torch.int16:  # 9..16-bit samples live in int16 tensors: back to their unsigned values
+            part = part.to(torch.int32) & 0xFFFF
+        part = part.to(torch.float32).contiguous()
+        host = torch.empty(part.shape, dtype=part.dtype, pin_memory=True)  # through pinned memory, as every transfer here
+        host.copy_(part)
+        np.save(os.path.join(out_dir, f"plane{p}.npy"), host.numpy())
+        planes.append({"name": f"plane{p}", "shape": list(part.shape), "rows": "all" if k >= h else f"{k} of {h}, seeded"})
+    return {"dir": out_dir, "frames": frames, "planes": planes}
+
+
 def spawn_ranks(args) -> int:
     """`--gpus N` without a launcher: run the N ranks as children of this process, which has not touched the
     GPU (no torch.cuda call, no HIP library loaded) and never will -- a process that has initialised the GPU
@@ -294,11 +333,19 @@ def main():
     ap.add_argument("--workload", default="2160p-Y8", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="frames per step and per GPU (0 = auto)")
     ap.add_argument("--mode", default="auto", choices=["auto", "pool", "fused"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true", help="skip the comparison with the pool path (knock-out builds of tools/ab_bench.sh only: the line then says so)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: the comparison with the pool path, the single-frame "
+                         "latency and the CPU baseline (a plain run only sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the single-frame and CPU baseline legs")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the comparison with the pool path (knock-out builds of tools/ab_bench.sh only: the line then says so)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/plane<p>.npy (float32; a fixed, seeded "
+                         "sample of the frames and rows of a batch larger than 64 MB)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(spawn_ranks(args))
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
@@ -416,8 +463,14 @@ def main():
     # timed launches wrote are recomputed by a SECOND context on the three-kernel pool path over the HBM-resident pool
     # (sn_pool_kernels.hip: other kernels, other data layout, the semantic reference of the sweeps on the GPU) and must
     # be byte-equal; a mismatch is an error, not a note.  What both compute: /root/reference/src/SangNom2.cpp:332-397.
+    # A plain run (no --full) leaves this leg out and says so.
     verified = None
-    if rank == 0 and args.no_verify:
+    dumped = None
+    if rank == 0 and args.dump_outputs:  # what the last timed step wrote to `dst`
+        dumped = dump_outputs(torch, args.dump_outputs, dst, batch)
+    if rank == 0 and not args.full:
+        verified = {"ok": None, "frames": 0, "against": "nothing (plain run: --full verifies)"}
+    elif rank == 0 and args.no_verify:
         verified = {"ok": None, "frames": 0, "against": "nothing (--no-verify)"}
     elif rank == 0:
         verified = verify_against_pool_path(torch, SangNom2, clip, dev_index, stream, kw, src, dst, batch, batch, args.mode)
@@ -479,7 +532,9 @@ def main():
                          "kernel_ms_per_launch": round(launch_ms, 4),
                          "algorithmic_bytes_per_launch": alg_bytes, "valu": valu},
         }
-        if world == 1 and not args.no_cpu_baseline:  # (the profiling passes run with --no-cpu-baseline: the hot path only)
+        if dumped is not None:
+            out["dumped"] = dumped
+        if world == 1 and args.full and not args.no_cpu_baseline:  # (the profiling passes run with --no-cpu-baseline: the hot path only)
             # the other end of the scale: ONE frame per launch (what a synchronous GetFrame sees), device time per frame;
             # auto mode cuts such a launch into row bands where the planes allow it
             one_s, one_d = [t[:1] for t in src], [t[:1] for t in dst]
@@ -500,7 +555,7 @@ def main():
         # idle for ~10 s, which is what a utilisation sampler sees most of the run
         out["gpu_active_s"] = round(gpu_active_ms / 1e3, 4)
         out["gpu_window_s"] = round(time.perf_counter() - gpu_t0, 3)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(fmt, w, h, kw)
         print(json.dumps(out), flush=True)
     flt.close()

@@ -10,7 +10,7 @@ for i in 1 2 3; do
     for v in $libs; do
         cp "$v" "$lib"
         printf "%s " "$v"
-        python3 bench.py --no-cpu-baseline --steps 8 --warmup 2 "$@" 2>/dev/null | tail -1 |
+        python3 bench.py --full --no-cpu-baseline --steps 8 --warmup 2 "$@" 2>/dev/null | tail -1 |
             python3 -c "import sys, json; d = json.loads(sys.stdin.read()); print(d['config']['frame'], d['frames_per_s'])"
     done
 done

@@ -10,7 +10,7 @@ for wl in $wls; do
     for v in $libs; do
         cp "$v" "$lib"
         printf "%s %s " "$wl" "$v"
-        python3 bench.py --no-cpu-baseline --steps 6 --warmup 2 --workload $wl 2>/dev/null | tail -1 |
+        python3 bench.py --full --no-cpu-baseline --steps 6 --warmup 2 --workload $wl 2>/dev/null | tail -1 |
             python3 -c "import sys, json; d = json.loads(sys.stdin.read()); print(d['frames_per_s'], d['roofline']['frac'])"
     done
   done

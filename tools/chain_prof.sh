@@ -6,7 +6,7 @@ lib=avisynth_sangnom2_amd/libsangnom_hip.so
 out=gpurun_out/chain_$2
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-args="--workload 480p-YUV420P8 --steps 5 --warmup 2 --no-cpu-baseline"
+args="--workload 480p-YUV420P8 --steps 5 --warmup 2 --full --no-cpu-baseline"
 rm -rf $out/stats $out/pmc
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py $args > $out/stats.log 2>&1
 find $out/stats -name '*kernel_stats.csv' -exec cp {} $out/kernel_stats.csv \;

@@ -14,8 +14,8 @@ mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 steps=5; warm=2
 for wl in $wls; do
-    args="--workload $wl --steps $steps --warmup $warm --no-cpu-baseline"
-    python3 bench.py --workload $wl --no-cpu-baseline > "$out/bench_$wl.json" 2> "$out/bench_$wl.err"
+    args="--workload $wl --steps $steps --warmup $warm --full --no-cpu-baseline"
+    python3 bench.py --workload $wl --full --no-cpu-baseline > "$out/bench_$wl.json" 2> "$out/bench_$wl.err"
     frames=$(python3 -c "import json,sys; print(json.loads(open('$out/bench_$wl.json').read().strip().splitlines()[-1])['config']['frames_per_step_per_gpu'])")
     rm -rf "$out/stats"
     rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -- python3 bench.py $args > "$out/stats_$wl.log" 2>&1
