@@ -24,6 +24,9 @@ struct Line {
     unsigned FB[PXL];  // F | B << 8 in each 16-bit half (both are 8-bit values)
     __device__ __forceinline__ unsigned F(int j) const { return FB[j] & kByte; }
     __device__ __forceinline__ unsigned B(int j) const { return pk_lshr8(FB[j]); }  // F < 256: one packed shift, no mask
+    // [lo j, lo j+1, hi j, hi j+1] of F / of B: one byte permute
+    __device__ __forceinline__ unsigned F2(int j) const { return __builtin_amdgcn_perm(FB[j + 1], FB[j], 0x06020400u); }
+    __device__ __forceinline__ unsigned B2(int j) const { return __builtin_amdgcn_perm(FB[j + 1], FB[j], 0x07030501u); }
 };
 // The same with F and B in registers of their own: eight registers more per line, no extraction per use.  For the
 // sweeps whose stage 3 runs in the byte domain: there a line in this form only serves stage 1, two of them are live,
@@ -33,6 +36,8 @@ struct WideLine {
     unsigned Fv[PXL], Bv[PXL];
     __device__ __forceinline__ unsigned F(int j) const { return Fv[j]; }
     __device__ __forceinline__ unsigned B(int j) const { return Bv[j]; }
+    __device__ __forceinline__ unsigned F2(int j) const { return Fv[j] | (Fv[j + 1] << 8); }
+    __device__ __forceinline__ unsigned B2(int j) const { return Bv[j] | (Bv[j + 1] << 8); }
 };
 
 struct RawHalf {  // left dword, own 8 bytes, right dword of one strip
@@ -87,6 +92,21 @@ __device__ __forceinline__ Raw clamp_edges(Raw q, const LaneRole& role)
     return q;
 }
 
+// a + b + c with a wave-uniform c (an SGPR operand: the encoding has no literal)
+__device__ __forceinline__ unsigned add3_s(unsigned a, unsigned b, unsigned c)
+{
+    unsigned r;
+    asm("v_add3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(c));
+    return r;
+}
+// 4a + b as ONE instruction (left to itself the compiler splits these sums into two-operand adds and shifts)
+__device__ __forceinline__ unsigned lshl2_add(unsigned a, unsigned b)
+{
+    unsigned r;
+    asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
 // q: after clamp_edges()
 template <class LineT>
 __device__ __forceinline__ void unpack(LineT& L, const Raw& q)
@@ -101,25 +121,25 @@ __device__ __forceinline__ void unpack(LineT& L, const Raw& q)
         L.P[3 + k] = pair_byte(q.h[1].m0, q.h[0].m0, k);
         L.P[7 + k] = pair_byte(q.h[1].m1, q.h[0].m1, k);
     }
-    // F = ((4a + 5b - c) >> 3) mod 256, B = ((4c + 5b - a) >> 3) mod 256 with a bias of 2048 per half
-    unsigned Q4[PXL + 2], M[PXL + 2];  // positions 2 .. PXL+3
+    // F = ((4a + 5b - c) >> 3) mod 256, B = ((4c + 5b - a) >> 3) mod 256 (a, b, c = P[j + 2 .. j + 4]), computed 32 times
+    // over with a bias of 2048 per half: X = 32 (4 (a + b + 512) + (b - c)) for F and 32 (4 (b + c + 512) + (b - a)) for
+    // B -- the pair sum of B at j is that of F at j + 1, and X is one v_lshl_add_u32 of a pair sum and a difference.  The
+    // value then sits in bits 8..15 of each half, and one byte permute extracts it (no shift and mask).  32 (x + 2048) is
+    // in [57 376, 138 976]: the low half carries at most 2 into the high half, whose own value is a multiple of 32, so its
+    // bits 8..15 stay its own; differences may borrow from the high half, and the sums return it (32-bit adds are exact
+    // modulo 2^32).
+    unsigned Q[PXL + 2];  // 32 P[i + 2]
 #pragma unroll
-    for (int i = 0; i < PXL + 2; ++i) {
-        const unsigned p = L.P[i + 2];
-        const unsigned p2 = p + p;
-        Q4[i] = p2 + p2;
-        M[i] = 0x08000800u - p;
-    }
+    for (int i = 0; i < PXL + 2; ++i) Q[i] = L.P[i + 2] << 5;
 #pragma unroll
     for (int j = 0; j < PXL; ++j) {
-        const unsigned q5 = Q4[j + 1] + L.P[j + 3];
-        const unsigned f = ((Q4[j] + q5 + M[j + 2]) >> 3) & kByte;
+        const unsigned xf = lshl2_add(add3_s(Q[j], Q[j + 1], 0x40004000u), Q[j + 1] - Q[j + 2]);      // 4 (a + b) + (b - c)
+        const unsigned xb = lshl2_add(add3_s(Q[j + 1], Q[j + 2], 0x40004000u), Q[j + 1] - Q[j]);      // 4 (b + c) + (b - a)
         if constexpr (std::is_same<LineT, WideLine>::value) {
-            L.Fv[j] = f;
-            L.Bv[j] = ((Q4[j + 2] + q5 + M[j]) >> 3) & kByte;
+            L.Fv[j] = __builtin_amdgcn_perm(0u, xf, 0x0c030c01u);
+            L.Bv[j] = __builtin_amdgcn_perm(0u, xb, 0x0c030c01u);
         } else {
-            const unsigned b = ((Q4[j + 2] + q5 + M[j]) << 5) & 0xff00ff00u;  // (x >> 3 & 255) << 8
-            L.FB[j] = f | b;
+            L.FB[j] = __builtin_amdgcn_perm(xb, xf, 0x07030501u);  // F | B << 8 in each half
         }
     }
 }
@@ -184,8 +204,8 @@ __device__ __forceinline__ void make_raw(RawLine& R, const Raw& q, const LineT& 
     // F[j] = [lo strip, 0, hi strip, 0]: pixels j, j+1 side by side, then the four of a strip into one dword
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
-        const unsigned f01 = L.F(4 * g + 0) | (L.F(4 * g + 1) << 8), f23 = L.F(4 * g + 2) | (L.F(4 * g + 3) << 8);  // [lo0 lo1 hi0 hi1]
-        const unsigned b01 = L.B(4 * g + 0) | (L.B(4 * g + 1) << 8), b23 = L.B(4 * g + 2) | (L.B(4 * g + 3) << 8);
+        const unsigned f01 = L.F2(4 * g), f23 = L.F2(4 * g + 2);  // [lo0 lo1 hi0 hi1]
+        const unsigned b01 = L.B2(4 * g), b23 = L.B2(4 * g + 2);
         R.F[0][g] = __builtin_amdgcn_perm(f23, f01, 0x05040100u);
         R.F[1][g] = __builtin_amdgcn_perm(f23, f01, 0x07060302u);
         R.B[0][g] = __builtin_amdgcn_perm(b23, b01, 0x05040100u);
@@ -221,28 +241,42 @@ constexpr unsigned rank_of()
     return code[BUF] * 0x00010001u;
 }
 
-// The 7-tap box over S with the line buffer's clamps (SangNom2.cpp:144-150), the same instructions in every wave:
-//   * column 0 is lane 0 of the first strip, and lane 0 has no left neighbour: its DPP move keeps the `old` operand,
-//     S[0] -- the clamp.  (Lane 0 of every other strip is the outermost ghost lane, whose value is wrong by design.)
-//   * the last column sits in some lane of the last strip: a select per right-hand tap there (RCLAMP; every wave runs it
-//     unless SN_RCLAMP_BRANCH asks for a wave-uniform branch around it).
+// The 7-tap box over S with the line buffer's clamps (SangNom2.cpp:144-150), the same instructions in every wave.
+// It starts at window 3, which holds only the lane's own pixels, and walks outwards, so that every neighbour tap enters
+// exactly one instruction and that instruction is the DPP form of an operation the walk needs anyway:
+//   left:  Bx[j] = Bx[j+1] + (L - S[j+4]) + z      L - S[j+4] = v_sub_u32_dpp (wave_shr:1, lane 0 reads 0)
+//   right: Bx[j] = Bx[j-1] + (R & ~m) + (m S7 - S[j-4])        R & ~m = v_and_b32_dpp (wave_shl:1, lane 63 reads 0)
+//   * column 0 is lane 0 of the first strip, and lane 0 has no left neighbour: its tap reads 0 and z = S[0] there (the
+//     clamp; z = 0 elsewhere).  Lane 0 of every other strip is the outermost ghost lane, whose value is wrong by design:
+//     its tap reads 0.
+//   * the last column sits in some lane of the last strip: m = last_mask selects S[PXL-1] for the right-hand taps there
+//     (RCLAMP; every wave runs it unless SN_RCLAMP_BRANCH asks for a wave-uniform branch around it).
+// 22 instructions per buffer step (3 + 2 for windows 3 and 4, 7 left, 10 right); the box that started at window 0 took
+// 29 (each left tap in two sums, a move to preset every DPP `old`).  All sums stay below 2^16 per half; the differences
+// may borrow across the halves, which the later adds return (32-bit arithmetic is exact modulo 2^32).
 // Round 2 branched on "this wave holds an image edge" around two whole variants of the box: the edge waves paid 29
 // instructions per buffer instead of 20, the branch cut every buffer step into three scheduling regions, and the seam
 // refresh made every wave wait for the slowest (knocking the edge variant out -- wrong at the edges -- ran 12 % faster).
 template <bool RCLAMP>
 __device__ __forceinline__ void box7(const unsigned (&S)[PXL], unsigned (&Bx)[PXL], const LaneRole& role)
 {
-    unsigned L[3], R[3];
+    Bx[3] = add3(add3(add3(S[0], S[1], S[2]), S[3], S[4]), S[5], S[6]);
+    Bx[4] = Bx[3] - S[0] + S[PXL - 1];
+    const unsigned z = S[0] & role.first_mask;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        L[k] = dpp_from_left_or(S[0], S[PXL - 3 + k]);
-        R[k] = dpp_from_right(S[k]);
-        if constexpr (RCLAMP) R[k] = bfi(role.last_mask, S[PXL - 1], R[k]);  // clamp to column w-1
+    for (int j = 2; j >= 0; --j) Bx[j] = add3(Bx[j + 1], dpp_from_left(S[j + 5]) - S[j + 4], z);
+    if constexpr (RCLAMP) {
+        // ~m as an opaque value (one per kernel once hoisted): left with `x & ~m` the compiler may pick v_bitop3_b32, which
+        // has no DPP form, and keep a separate DPP move
+        unsigned keep = ~role.last_mask;
+        asm("" : "+v"(keep));
+        const unsigned m7 = S[PXL - 1] & role.last_mask;
+#pragma unroll
+        for (int j = 5; j < PXL; ++j) Bx[j] = add3(Bx[j - 1], dpp_from_right(S[j - 5]) & keep, m7 - S[j - 4]);
+    } else {
+#pragma unroll
+        for (int j = 5; j < PXL; ++j) Bx[j] = Bx[j - 1] - S[j - 4] + dpp_from_right(S[j - 5]);
     }
-    auto X = [&](int i) -> unsigned { return i < 0 ? L[i + 3] : i >= PXL ? R[i - PXL] : S[i]; };
-    Bx[0] = S[0] + S[1] + S[2] + S[3] + X(-1) + X(-2) + X(-3);
-#pragma unroll
-    for (int j = 0; j + 1 < PXL; ++j) Bx[j + 1] = Bx[j] - X(j - 3) + X(j + 4);
 }
 #ifndef SN_RCLAMP_BRANCH
 #define SN_RCLAMP_BRANCH 0
