@@ -347,23 +347,25 @@ __device__ __forceinline__ Out row_step(unsigned (&A)[reg_buffers(MODE)][PXL], c
     return o;
 }
 
-// LDS mailbox, receiver-ready: word [refresh parity][wave W][side][slot][i] is what ghost lane
-// `slot` on that side of wave W loads into packed A register i, so receiving costs no shuffling.  Inside the
-// plane the publisher stores its registers whole; at the wrap seam a half is stored on its own (16-bit store):
-//   left ghosts  (lanes 0, 1)   of wave W: both halves <- wave W-1 lanes 60, 61 (same half), except that the hi
-//                                          half of wave 0 (strip NW) <- wave NW-1 lanes 60, 61 lo half (strip NW-1)
-//   right ghosts (lanes 62, 63) of wave W: both halves <- wave W+1 lanes 2, 3 (same half), except that the lo
-//                                          half of wave NW-1 (strip NW-1) <- wave 0 lanes 2, 3 hi half (strip NW)
+// LDS mailbox: word [refresh parity][wave W][side][slot][i] is packed A register i of the seam lane that ghost lane
+// `slot` on that side of wave W mirrors.  Every publisher stores its registers whole (16 bytes per store, the same in
+// every wave, so no wave publishes longer than the others); the receiver picks the half it needs:
+//   left ghosts  (lanes 0, 1)   of wave W: <- wave W-1 lanes 60, 61, each half from the same half, except that the hi
+//                                          half of wave 0 (strip NW) <- wave NW-1's lo half (strip NW-1)
+//   right ghosts (lanes 62, 63) of wave W: <- wave W+1 lanes 2, 3, each half from the same half, except that the lo
+//                                          half of wave NW-1 (strip NW-1) <- wave 0's hi half (strip NW)
+// (the waves wrap round: wave NW-1 publishes its right seam to wave 0, wave 0 its left seam to wave NW-1).  ONE v_perm_b32
+// per register merges the word into a ghost lane, with a per-lane byte selector fixed before the sweep (ghost_sel).
 // The pool-coupled modes park six buffers' state in LDS and have room for ONE copy of the mailbox only: there a second
 // barrier (before publishing) makes sure every wave has taken the previous refresh out of it.  The other modes keep two
 // copies, alternating, and meet once per refresh.
 __host__ __device__ constexpr int mailbox_copies(int) { return 2; }  // (round 2: one copy and a second barrier where six buffers' state lived in LDS)
 template <int NW, int COPIES>
-struct Mailbox {  // [copy][wave 0..NW-1][side][slot][72][2 halves] 16-bit entries in dynamic LDS
-    unsigned short* h;
-    __device__ __forceinline__ unsigned short* at(int par, int wave, int side, int slot) const
+struct Mailbox {  // [copy][wave 0..NW-1][side][slot][72] packed words in dynamic LDS
+    unsigned* w;
+    __device__ __forceinline__ unsigned* at(int par, int wave, int side, int slot) const
     {
-        return h + (((((COPIES > 1 ? par : 0) * NW + wave) * 2 + side) * GH + slot) * (kBuffers * PXL)) * 2;
+        return w + ((((COPIES > 1 ? par : 0) * NW + wave) * 2 + side) * GH + slot) * (kBuffers * PXL);
     }
 };
 
@@ -371,6 +373,10 @@ __host__ __device__ constexpr int lds_bytes(int nw, int mode)
 {
     return (parked_line_slots(mode) + (kBuffers - reg_buffers(mode)) * 2) * 16 * nw * 64 + mailbox_copies(mode) * nw * 2 * GH * kBuffers * PXL * 4;
 }
+
+// Modes whose non-band sweep runs in blocks of K rows (see rows() in the kernel).  kPadded lives at the register limit
+// and spills in that form, so it keeps rows on their own, two per loop trip.
+__host__ __device__ constexpr bool block_rows(int mode) { return mode != kPadded; }
 
 template <int NW, int MODE, bool BAND>
 __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args a)
@@ -387,7 +393,7 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args 
     parked.v = reinterpret_cast<uint4*>(lds_raw + sub * lds_bytes(NW, MODE));
     parked.a = parked.v + parked_line_slots(MODE) * NW * 64;
     Mailbox<NW, mailbox_copies(MODE)> mb;
-    mb.h = reinterpret_cast<unsigned short*>(parked.a + (kBuffers - kRegBuffers) * 2 * NW * 64);
+    mb.w = reinterpret_cast<unsigned*>(parked.a + (kBuffers - kRegBuffers) * 2 * NW * 64);
     const int wave = tid >> 6;
     const int lane = tid & 63;
     const int nvw = a.nvw;
@@ -606,28 +612,94 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args 
     int out_row = dst_line + a.dst_pitch + (r0 - 1) * dst_step;
     src_next += src_step;
 
-    // Seam exchange roles.  Lanes 60, 61 are the right seam lanes and lanes 2, 3 the left seam
-    // lanes of BOTH virtual wavefronts of this wave, so they publish whole packed registers; the
-    // ghost lanes (0, 1 and 62, 63) take one half from each of two published registers.
+    // Seam exchange roles.  Lanes 60, 61 are the right seam lanes and lanes 2, 3 the left seam lanes of BOTH virtual
+    // wavefronts of this wave: they publish whole packed registers (see Mailbox).  The ghost lanes (0, 1 and 62, 63)
+    // merge each published word with ONE byte permute: bytes 4..7 of the selector's input are the mailbox word, 0..3 the
+    // lane's own register.  Per half: a ghost takes the word's same half -- or, at the wrap seam, its other half -- and
+    // a half that is not a live ghost keeps its own value.
     const bool pub_right = lane >= 64 - 2 * GH && lane < 64 - GH;
     const bool pub_left = lane >= GH && lane < 2 * GH;
     const bool recv_left = lane < GH;         // left ghosts of both strips
     const bool recv_right = lane >= 64 - GH;  // right ghosts of both strips
-    const unsigned ghost_mask = (ghost[0] && live[0] ? kLo : 0u) | (ghost[1] && live[1] ? kHi : 0u);
+    const unsigned ghost_sel = ((ghost[0] && live[0]) ? (recv_right && wave == NW - 1 ? 0x0706u : 0x0504u) : 0x0100u) |
+                               ((ghost[1] && live[1]) ? (recv_left && wave == 0 ? 0x0504u : 0x0706u) : 0x0302u) << 16;
     const int slot = recv_left ? lane : recv_right ? lane - (64 - GH) : pub_right ? lane - (64 - 2 * GH) : lane - GH;
+
+#ifdef SN_ROW_TIMING
+    unsigned long long rt_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rt_last = __builtin_amdgcn_s_memtime();
+#endif
+    // the refresh at the start of a block of K rows: one barrier, then the ghosts take the mailbox copy `par`
+    auto refresh = [&](int par) __attribute__((always_inline)) {
+#ifndef SN_X_NO_SEAM_BARRIER
+        __syncthreads();
+#endif
+        SN_RT(2);  // [2] the seam barrier
+        if (recv_left || recv_right) {
+            const unsigned* from = mb.at(par, wave, recv_left ? 0 : 1, slot);
+            auto merge = [&](int b, unsigned (&Ab)[PXL]) {
+#pragma unroll
+                for (int j = 0; j < PXL; ++j) Ab[j] = __builtin_amdgcn_perm(from[b * PXL + j], Ab[j], ghost_sel);
+            };
+#pragma unroll
+            for (int b = 0; b < kRegBuffers; ++b) merge(b, A[b]);
+#pragma unroll
+            for (int b = kRegBuffers; b < kBuffers; ++b) {
+                unsigned t[PXL];
+                load_A(parked, tid, b, t);
+                merge(b, t);
+                store_A(parked, tid, b, t);
+            }
+        }
+    };
+    // ... and the publish at its end, into the other copy: the seam lanes' registers whole, 18 16-byte stores in every wave
+    auto publish = [&](int wpar) __attribute__((always_inline)) {
+        if constexpr (mailbox_copies(MODE) == 1) __syncthreads();  // the previous refresh has been taken out
+        if (pub_right || pub_left) {
+            uint4* to = reinterpret_cast<uint4*>(pub_right ? mb.at(wpar, wave < NW - 1 ? wave + 1 : 0, 0, slot)
+                                                           : mb.at(wpar, wave > 0 ? wave - 1 : NW - 1, 1, slot));
+            auto send = [&](int b, const unsigned (&Ab)[PXL]) {
+                to[b * 2 + 0] = make_uint4(Ab[0], Ab[1], Ab[2], Ab[3]);
+                to[b * 2 + 1] = make_uint4(Ab[4], Ab[5], Ab[6], Ab[7]);
+            };
+#pragma unroll
+            for (int b = 0; b < kRegBuffers; ++b) send(b, A[b]);
+#pragma unroll
+            for (int b = kRegBuffers; b < kBuffers; ++b) {
+                unsigned t[PXL];
+                load_A(parked, tid, b, t);
+                send(b, t);
+            }
+        }
+    };
+
+    // Where a row sits.  A row on its own (POS < 0) decides refresh, publish, turn and LDS slots from its number; row POS
+    // of a block of K rows (the first row r with (r - 1) % K == 0) refreshes first if it is row 0 and the block asks for
+    // it, publishes last if it is row K - 1, and takes the rest from the block.
+    struct Blk {
+        int par;        // mailbox copy the block's refresh reads (its publish writes the other one)
+        bool refresh;   // the block starts with a refresh (not the sweep's first block)
+        int sl[3];      // LDS line slots (r - 1) % 3, r % 3, (r + 1) % 3 of the block's first row r
+    };
+    // Workgroups of eight waves take turns by the row within the block (TurnTaking::kLadder), the others by time slices
+    // or not at all (turn_shift_for), so only eight-wave kernels set a priority in every row of a block.
+    constexpr bool kLadderRows = NW * group_of(NW) == 8;
 
     // One pool row r: n = K[r], nn = K[r+1] (S1: the pair exists), c = K[r-1] parked (S3: the row has an
     // interpolated line).
     TurnTaking turns;
     turns.init(a.turn_shift);
-#ifdef SN_ROW_TIMING
-    unsigned long long rt_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rt_last = __builtin_amdgcn_s_memtime();
-#endif
-    auto step = [&](int r, LineOf<MODE>& n, LineOf<MODE>& nn, auto s1_tag, auto s3_tag, auto store_tag) __attribute__((always_inline)) {
+    auto step = [&](int r, LineOf<MODE>& n, LineOf<MODE>& nn, auto s1_tag, auto s3_tag, auto store_tag, auto pos_tag,
+                    const Blk& bk) __attribute__((always_inline)) {
         constexpr bool HAS_NEXT = decltype(s1_tag)::value;
         constexpr bool S3 = decltype(s3_tag)::value;
         constexpr bool STORE = decltype(store_tag)::value;
-        turns.update((r - 1) % K);
+        constexpr int POS = decltype(pos_tag)::value;
+        if constexpr (POS < 0) turns.update((r - 1) % K);
+        else if constexpr (POS == 0) turns.update(0);  // the time slices' clock is read once per block
+        else if constexpr (kLadderRows) turns.update(POS);
+        const int slot_c = POS < 0 ? (r - 1) % 3 : bk.sl[POS % 3];
+        const int slot_n = POS < 0 ? r % 3 : bk.sl[(POS + 1) % 3];
+        const int slot_nn = POS < 0 ? (r + 1) % 3 : bk.sl[(POS + 2) % 3];
         SN_RT(6);
         Raw qnext = qn;
         if constexpr (HAS_NEXT) {
@@ -639,7 +711,7 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args 
             unpack(nn, fq);
             RawLine R;
             make_raw(R, fq, nn);
-            park_raw(parked, tid, (r + 1) % 3, R);  // K[r + 1]: n of the next row, c of the one after
+            park_raw(parked, tid, slot_nn, R);  // K[r + 1]: n of the next row, c of the one after
             keep(dst_keep, qn, !BAND || (r + 1 >= ra && r < rb));
             dst_keep += dst_step;
         }
@@ -647,36 +719,18 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args 
             if (r + 2 <= nr) qnext = load_raw(src_next);  // prefetch K[r+2]
             src_next += src_step;
         }
-        const int par = (r / K) & 1;
         SN_RT(1);  // [1] unpack, windows, park, kept-line store, prefetch issue
-        if (r > r0 && (r - 1) % K == 0) {
-#ifndef SN_X_NO_SEAM_BARRIER
-            __syncthreads();
-#endif
-            SN_RT(2);  // [2] the seam barrier
-            if (recv_left || recv_right) {
-                const unsigned* from = reinterpret_cast<const unsigned*>(mb.at(par, wave, recv_left ? 0 : 1, slot));
-                auto merge = [&](int b, unsigned (&Ab)[PXL]) {
-#pragma unroll
-                    for (int j = 0; j < PXL; ++j) Ab[j] = bfi(ghost_mask, from[b * PXL + j], Ab[j]);
-                };
-#pragma unroll
-                for (int b = 0; b < kRegBuffers; ++b) merge(b, A[b]);
-#pragma unroll
-                for (int b = kRegBuffers; b < kBuffers; ++b) {
-                    unsigned t[PXL];
-                    load_A(parked, tid, b, t);
-                    merge(b, t);
-                    store_A(parked, tid, b, t);
-                }
-            }
+        if constexpr (POS < 0) {
+            if (r > r0 && (r - 1) % K == 0) refresh((r / K) & 1);
+        } else if constexpr (POS == 0) {
+            if (bk.refresh) refresh(bk.par);
         }
         RowCtx rc;
         rc.r = r;
         rc.vin_lo = rc.vin_hi = rc.vout = rc.vout_hi = kOutOfRange;
         rc.any_out = false;
-        rc.slot_c = (r - 1) % 3;
-        rc.slot_n = r % 3;
+        rc.slot_c = slot_c;
+        rc.slot_n = slot_n;
         if constexpr (chroma_mode(MODE)) {
             const bool row_in = r + 1 <= a.rows_in;
             rc.vin_lo = (row_in && in_cone(r + 1, a.cone_in, 0)) ? io.v_lo : kOutOfRange;
@@ -693,55 +747,10 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args 
         if constexpr (S3) put(out_row, o);  // stored at once: nothing is carried into the next row
         SN_RT(4);  // [4] nine buffer steps + stage 3 + output store
         out_row += dst_step;
-        if (r < sweep) {
-            if (r % K == 0) {
-                if constexpr (mailbox_copies(MODE) == 1) __syncthreads();  // the previous refresh has been taken out
-                const int wpar = ((r + 1) / K) & 1;
-                if (pub_right || pub_left) {
-                    // Inside the plane both halves of a seam register go to the same ghost lane of the neighbouring
-                    // wave (see Mailbox), i.e. the register is published whole, 16 bytes per store.  Only at the
-                    // wrap seam (strip NW-1 | strip NW) a half crosses over into the other half of its receiver
-                    // and is written on its own; halves at the image edge have no receiver at all.
-                    const bool whole = pub_right ? wave < NW - 1 : wave > 0;
-                    if (whole) {
-                        uint4* to = reinterpret_cast<uint4*>(pub_right ? mb.at(wpar, wave + 1, 0, slot) : mb.at(wpar, wave - 1, 1, slot));
-                        auto send = [&](int b, const unsigned (&Ab)[PXL]) {
-                            to[b * 2 + 0] = make_uint4(Ab[0], Ab[1], Ab[2], Ab[3]);
-                            to[b * 2 + 1] = make_uint4(Ab[4], Ab[5], Ab[6], Ab[7]);
-                        };
-#pragma unroll
-                        for (int b = 0; b < kRegBuffers; ++b) send(b, A[b]);
-#pragma unroll
-                        for (int b = kRegBuffers; b < kBuffers; ++b) {
-                            unsigned t[PXL];
-                            load_A(parked, tid, b, t);
-                            send(b, t);
-                        }
-                    } else {
-                        // wave NW-1, right seam lanes: low half (strip NW-1) -> high half of wave 0's left ghosts;
-                        // wave 0, left seam lanes: high half (strip NW) -> low half of wave NW-1's right ghosts
-                        // (two branches with the half fixed at compile time: the high half goes out with ds_write_b16_d16_hi, no
-                        // shift -- a per-lane shift amount cost 72 v_lshrrev per publish in the two waves the others wait for)
-                        auto send_half = [&](unsigned short* to, auto hi_tag) {
-                            constexpr bool HI = decltype(hi_tag)::value;
-                            auto send = [&](int b, const unsigned (&Ab)[PXL]) {
-#pragma unroll
-                                for (int j = 0; j < PXL; ++j) to[(b * PXL + j) * 2] = HI ? (unsigned short)(Ab[j] >> 16) : (unsigned short)Ab[j];
-                            };
-#pragma unroll
-                            for (int b = 0; b < kRegBuffers; ++b) send(b, A[b]);
-#pragma unroll
-                            for (int b = kRegBuffers; b < kBuffers; ++b) {
-                                unsigned t[PXL];
-                                load_A(parked, tid, b, t);
-                                send(b, t);
-                            }
-                        };
-                        if (pub_right) send_half(mb.at(wpar, 0, 0, slot) + 1, std::integral_constant<bool, false>{});
-                        else send_half(mb.at(wpar, NW - 1, 1, slot), std::integral_constant<bool, true>{});
-                    }
-                }
-            }
+        if constexpr (POS < 0) {
+            if (r < sweep && r % K == 0) publish(((r + 1) / K) & 1);
+        } else if constexpr (POS == K - 1) {
+            publish(bk.par ^ 1);  // a block lies below the sweep's last row (see rows())
         }
         qn = qnext;
         SN_RT(5);  // [5] publish (every fifth row)
@@ -751,6 +760,8 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args 
     };
     using T = std::integral_constant<bool, true>;
     using F = std::integral_constant<bool, false>;
+    using Own = std::integral_constant<int, -1>;  // a row on its own
+    const Blk alone{};
 
     // L1 = K[r] (n), L0 is reused for K[r+1] (nn); c lives in LDS.  Rows 1 .. nr-1 have a following line
     // pair, row nr does not (its next costs are zero or stale), rows beyond nr (kChroma only) have no
@@ -778,43 +789,71 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args 
         using ST = std::integral_constant<bool, MODE == kLumaSpill>;
         int r = r0;
         for (; r < ra; ++r) {
-            step(r, L1, L0, T{}, F{}, F{});
+            step(r, L1, L0, T{}, F{}, F{}, Own{}, alone);
             L1 = L0;
         }
         leave_state(0);
         const int own_next = rb < nr ? rb + 1 : nr;
         for (; r < own_next; ++r) {
-            step(r, L1, L0, T{}, T{}, ST{});
+            step(r, L1, L0, T{}, T{}, ST{}, Own{}, alone);
             L1 = L0;
         }
-        if (rb == nr) step(nr, L1, L0, F{}, T{}, ST{});
+        if (rb == nr) step(nr, L1, L0, F{}, T{}, ST{}, Own{}, alone);
         if (rb < last) leave_state(1);
     } else {
-        // Rows [from, to) with a following line pair: two rows per trip with the roles of the two line registers swapped,
-        // so that no row ends in a copy of a line; afterwards L1 is K[to] again.
+        // Rows [from, to) with a following line pair, in blocks of K rows on the absolute row grid: the refresh at the
+        // start of a block, the publish at its end, one turn per block, no per-row test for either.  Rows of a partial
+        // block (a split row, the plane's last rows) run on their own.  A block is five rows with the roles of the two
+        // line registers swapped from row to row and ONE copy of a line at its end (ten rows per trip would double a
+        // loop body that is already some 30 KB); afterwards L1 is K[to] again.
+        static_assert(K == 5, "a block is written out for five rows");
         auto rows = [&](int from, int to, auto store_tag) __attribute__((always_inline)) {
+            auto alone_rows = [&](int& r, int end) __attribute__((always_inline)) {
+                for (; r < end; ++r) {
+                    step(r, L1, L0, T{}, T{}, store_tag, Own{}, alone);
+                    L1 = L0;
+                }
+            };
             int r = from;
-            for (; r + 1 < to; r += 2) {
-                step(r, L1, L0, T{}, T{}, store_tag);
-                step(r + 1, L0, L1, T{}, T{}, store_tag);
+            if constexpr (!block_rows(MODE)) {
+                // two rows per trip with the roles of the two line registers swapped, so that no row ends in a copy of a line
+                for (; r + 1 < to; r += 2) {
+                    step(r, L1, L0, T{}, T{}, store_tag, Own{}, alone);
+                    step(r + 1, L0, L1, T{}, T{}, store_tag, Own{}, alone);
+                }
+                alone_rows(r, to);
+                return;
             }
-            if (r < to) {
-                step(r, L1, L0, T{}, T{}, store_tag);
+            const int head = from + (K - (from - 1) % K) % K;  // the first block's first row
+            alone_rows(r, head < to ? head : to);
+            for (; r + K <= to; r += K) {
+                Blk bk;
+                bk.par = ((r - 1) / K) & 1;
+                bk.refresh = r > r0;
+                bk.sl[0] = (r - 1) % 3;
+                bk.sl[1] = r % 3;
+                bk.sl[2] = (r + 1) % 3;
+                step(r + 0, L1, L0, T{}, T{}, store_tag, std::integral_constant<int, 0>{}, bk);
+                step(r + 1, L0, L1, T{}, T{}, store_tag, std::integral_constant<int, 1>{}, bk);
+                step(r + 2, L1, L0, T{}, T{}, store_tag, std::integral_constant<int, 2>{}, bk);
+                step(r + 3, L0, L1, T{}, T{}, store_tag, std::integral_constant<int, 3>{}, bk);
+                step(r + 4, L1, L0, T{}, T{}, store_tag, std::integral_constant<int, 4>{}, bk);
                 L1 = L0;
             }
+            alone_rows(r, to);
         };
         if constexpr (MODE == kLumaSpill) {
             // the rows whose smoothed values a chroma pass can see first, with the hand-off; the rest of the plane without
             const int split = a.rows_out + 1 < nr ? a.rows_out + 1 : nr;
             rows(1, split, T{});
             rows(split, nr, F{});
-            if (nr >= 1) step(nr, L1, L0, F{}, T{}, T{});
+            if (nr >= 1) step(nr, L1, L0, F{}, T{}, T{}, Own{}, alone);
         } else {
             using ST = std::integral_constant<bool, MODE == kChroma>;
             rows(1, nr, ST{});
-            if (nr >= 1) step(nr, L1, L0, F{}, T{}, ST{});
+            if (nr >= 1) step(nr, L1, L0, F{}, T{}, ST{}, Own{}, alone);
             if constexpr (chroma_mode(MODE)) {
-                for (int r = nr + 1; r <= last; ++r) step(r, L1, L0, F{}, F{}, ST{});
+                for (int r = nr + 1; r <= last; ++r) step(r, L1, L0, F{}, F{}, ST{}, Own{}, alone);
             }
         }
     }
