@@ -64,7 +64,8 @@ struct LaneRole {
     unsigned last_mask;  // 0xffff (shifted) in the half that owns column w-1 of the sweep
     unsigned line_last_mask;  // ... that owns the last column of the source lines (kChroma: region_w - 1)
     unsigned inside_mask;     // kChroma: halves whose columns lie inside the chroma region
-    unsigned key_mask;        // 0x0ff00ff0 in a VGPR (operand of the and-or that forms the ladder keys)
+    unsigned key_mask;        // 0x0ff0 in each live half, 0 in the others (operand of the and-or that forms the ladder
+                              // keys; zero keeps S zero where the half is not live, see box7)
 };
 
 // byte k of the lo word -> bits 0..7, byte k of the hi word -> bits 16..23
@@ -242,49 +243,40 @@ constexpr unsigned rank_of()
 }
 
 // The 7-tap box over S with the line buffer's clamps (SangNom2.cpp:144-150), the same instructions in every wave.
-// It starts at window 3, which holds only the lane's own pixels, and walks outwards, so that every neighbour tap enters
-// exactly one instruction and that instruction is the DPP form of an operation the walk needs anyway:
+// Windows 3 and 4 hold only the lane's own pixels and share S[1..6]: with P = S1 + S2 + S3 and Q = S4 + S5 + S6 they are
+// P + Q + S0 and P + Q + S7.  From there the box walks outwards, so that every neighbour tap enters exactly one
+// instruction and that instruction is the DPP form of an operation the walk needs anyway -- the same form on both sides:
 //   left:  Bx[j] = Bx[j+1] + (L - S[j+4]) + z      L - S[j+4] = v_sub_u32_dpp (wave_shr:1, lane 0 reads 0)
-//   right: Bx[j] = Bx[j-1] + (R & ~m) + (m S7 - S[j-4])        R & ~m = v_and_b32_dpp (wave_shl:1, lane 63 reads 0)
+//   right: Bx[j] = Bx[j-1] + (R - S[j-4]) + m      R - S[j-4] = v_sub_u32_dpp (wave_shl:1, lane 63 reads 0)
 //   * column 0 is lane 0 of the first strip, and lane 0 has no left neighbour: its tap reads 0 and z = S[0] there (the
 //     clamp; z = 0 elsewhere).  Lane 0 of every other strip is the outermost ghost lane, whose value is wrong by design:
 //     its tap reads 0.
-//   * the last column sits in some lane of the last strip: m = last_mask selects S[PXL-1] for the right-hand taps there
-//     (RCLAMP; every wave runs it unless SN_RCLAMP_BRANCH asks for a wave-uniform branch around it).
-// 22 instructions per buffer step (3 + 2 for windows 3 and 4, 7 left, 10 right); the box that started at window 0 took
-// 29 (each left tap in two sums, a move to preset every DPP `old`).  All sums stay below 2^16 per half; the differences
-// may borrow across the halves, which the later adds return (32-bit arithmetic is exact modulo 2^32).
+//   * column w - 1 sits in some lane of the last strip, and its right-hand tap must read 0 too, so that m = S[PXL-1]
+//     there (m = 0 elsewhere) adds the clamp.  It does, by an invariant of both 8-bit kernels: S is ZERO in every half
+//     that is not live.  Every fused width is a multiple of 32, so w - 1 is pixel 7 of its lane, and that lane is 3 mod 4
+//     in its strip (kFirst = 62, kInner = 60); the last strip has no right ghosts, so the lane after it is lane 64 (the
+//     DPP reads 0) or a half that is not live.  There the lines, the previous pass's rows and the luma pass's rows all
+//     load from an out-of-range voffset (zeros: every cost and every stale value is 0), and key_mask = 0 makes the key
+//     the bare rank code, so O = key >> 4 = 0 and A' = O + costs = 0 in every row: S = A + costs stays 0.  (The class-S
+//     waves of the one-sweep chroma kernel, which form no keys, mask O the same way.)  Before this the right walk paid
+//     for the clamp in every wave: R & ~m as a v_and_b32_dpp, and m S7 - S[j-4] apart, three instructions per window.
+// 18 instructions per buffer step (4 for windows 3 and 4, 1 + 6 left, 1 + 6 right); 22 before, and the box that started
+// at window 0 took 29 (each left tap in two sums, a move to preset every DPP `old`).  All sums stay below 2^16 per half;
+// the differences may borrow across the halves, which the later adds return (32-bit arithmetic is exact modulo 2^32).
 // Round 2 branched on "this wave holds an image edge" around two whole variants of the box: the edge waves paid 29
 // instructions per buffer instead of 20, the branch cut every buffer step into three scheduling regions, and the seam
 // refresh made every wave wait for the slowest (knocking the edge variant out -- wrong at the edges -- ran 12 % faster).
-template <bool RCLAMP>
 __device__ __forceinline__ void box7(const unsigned (&S)[PXL], unsigned (&Bx)[PXL], const LaneRole& role)
 {
-    Bx[3] = add3(add3(add3(S[0], S[1], S[2]), S[3], S[4]), S[5], S[6]);
-    Bx[4] = Bx[3] - S[0] + S[PXL - 1];
+    const unsigned p = add3(S[1], S[2], S[3]), q = add3(S[4], S[5], S[6]);
+    Bx[3] = add3(p, q, S[0]);
+    Bx[4] = add3(p, q, S[PXL - 1]);
     const unsigned z = S[0] & role.first_mask;
 #pragma unroll
     for (int j = 2; j >= 0; --j) Bx[j] = add3(Bx[j + 1], dpp_from_left(S[j + 5]) - S[j + 4], z);
-    if constexpr (RCLAMP) {
-        // ~m as an opaque value (one per kernel once hoisted): left with `x & ~m` the compiler may pick v_bitop3_b32, which
-        // has no DPP form, and keep a separate DPP move
-        unsigned keep = ~role.last_mask;
-        asm("" : "+v"(keep));
-        const unsigned m7 = S[PXL - 1] & role.last_mask;
+    const unsigned m = S[PXL - 1] & role.last_mask;
 #pragma unroll
-        for (int j = 5; j < PXL; ++j) Bx[j] = add3(Bx[j - 1], dpp_from_right(S[j - 5]) & keep, m7 - S[j - 4]);
-    } else {
-#pragma unroll
-        for (int j = 5; j < PXL; ++j) Bx[j] = Bx[j - 1] - S[j - 4] + dpp_from_right(S[j - 5]);
-    }
-}
-#ifndef SN_RCLAMP_BRANCH
-#define SN_RCLAMP_BRANCH 0
-#endif
-__device__ __forceinline__ void box7_any(const unsigned (&S)[PXL], unsigned (&Bx)[PXL], const LaneRole& role)
-{
-    if (SN_RCLAMP_BRANCH && !role.edge_wave) box7<false>(S, Bx, role);
-    else box7<true>(S, Bx, role);
+    for (int j = 5; j < PXL; ++j) Bx[j] = add3(Bx[j - 1], dpp_from_right(S[j - 5]) - S[j - 4], m);
 }
 
 // A RawLine parked in LDS for the two rows that use it: five uint4 per thread and line, `nthreads` apart (each thread

@@ -123,7 +123,7 @@ __device__ __forceinline__ u32x2 own_bytes(const RawHalf& h, bool first)
 // One cost buffer of one step in a wave that holds chroma columns.
 // STALE: some lanes re-smooth stale values (class RS, and the masked steps of both region classes).
 // MASKED: the first kSkew and the last kSkew + 1 steps (see Step).
-template <int BUF, bool STALE, bool MASKED, bool PARK, bool RC>
+template <int BUF, bool STALE, bool MASKED, bool PARK>
 __device__ __forceinline__ void region_buffer_step(unsigned (&A)[PXL], unsigned (&kmin)[PXL], const WideLine& n, const WideLine& nn, const Ctx& cx,
                                                    const Step& st, const u32x2& ld)
 {
@@ -164,7 +164,7 @@ __device__ __forceinline__ void region_buffer_step(unsigned (&A)[PXL], unsigned 
     }
 #pragma unroll
     for (int j = 0; j < PXL; ++j) S[j] = add3(A[j], U[j], V[j]);
-    box7<RC>(S, Bx, cx.role);  // RC: this wave holds the pool's last column (the select of the right-hand clamp)
+    box7(S, Bx, cx.role);
     unsigned O[PXL];
 #pragma unroll
     for (int j = 0; j < PXL; ++j) {
@@ -192,7 +192,7 @@ __device__ __forceinline__ u32x2 issue_stale(const Ctx& cx, int b, int row, int 
 }
 
 // The nine buffers and stage 3 of one step of a region wave; returns the interpolated bytes of both passes.
-template <bool STALE, bool MASKED, bool PARK, bool RC>
+template <bool STALE, bool MASKED, bool PARK>
 __device__ __forceinline__ Out region_row(unsigned (&A)[kBuffers][PXL], const WideLine& n, const WideLine& nn, const Ctx& cx, const Step& st, unsigned thr_key,
                                           u32x2 (&ahead)[kBuffers])
 {
@@ -208,7 +208,7 @@ __device__ __forceinline__ Out region_row(unsigned (&A)[kBuffers][PXL], const Wi
             __builtin_amdgcn_sched_barrier(0);  // (the refill must not be hoisted above the read of the same registers' previous content)
             ahead[B] = issue_stale(cx, B, st.s + 2, st.vin2);
         }
-        region_buffer_step<B, STALE, MASKED, PARK, RC>(A[B], kmin, n, nn, cx, st, ld);
+        region_buffer_step<B, STALE, MASKED, PARK>(A[B], kmin, n, nn, cx, st, ld);
         if constexpr (!STALE) __builtin_amdgcn_sched_barrier(0);
     };
     run(std::integral_constant<int, 0>{});
@@ -238,7 +238,7 @@ __device__ __forceinline__ Out region_row(unsigned (&A)[kBuffers][PXL], const Wi
 }
 
 // One cost buffer of one step in a wave right of the region (class S): D = the luma pass's row | last step's O << 16.
-template <int BUF, bool RC>
+template <int BUF>
 __device__ __forceinline__ void stale_buffer_step(unsigned (&A)[PXL], unsigned (&Oprev)[PXL], const LaneRole& role, const u32x2& ld, unsigned omask,
                                                   unsigned sel)
 {
@@ -248,7 +248,7 @@ __device__ __forceinline__ void stale_buffer_step(unsigned (&A)[PXL], unsigned (
         D[j] = __builtin_amdgcn_perm(Oprev[j], j < 4 ? ld.x : ld.y, sel + (unsigned)(j & 3));  // sel: 0x0c040c00, or 0x0c0c0c00 (no U row behind)
         S[j] = A[j] + D[j];
     }
-    box7<RC>(S, Bx, role);
+    box7(S, Bx, role);
 #pragma unroll
     for (int j = 0; j < PXL; ++j) {
         const unsigned O = pk_lshr4(Bx[j]) & omask;  // (sum / 16) wraps to uint8_t, SangNom2.cpp:152
@@ -260,7 +260,7 @@ __device__ __forceinline__ void stale_buffer_step(unsigned (&A)[PXL], unsigned (
 // The sweep of one wave of class CLS.  Each class is a function of its own (sweep_entry, not inlined into the kernel): one
 // function holding all three made the register allocator spill a line of the plain steps to scratch, and a scratch reload
 // waits for every load issued before it -- the prefetched lines, the luma pass's rows -- i.e. for HBM, in every row.
-template <int NW, int CLS, bool RC>
+template <int NW, int CLS>
 __device__ __forceinline__ void sweep(const Args& a)
 {
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -290,7 +290,7 @@ __device__ __forceinline__ void sweep(const Args& a)
     cx.role.last_mask = live && gl == a.nl - 1 ? kAll : 0u;
     cx.role.line_last_mask = chroma && x0 + PXL == a.region_w ? kAll : 0u;
     cx.role.inside_mask = chroma ? kAll : 0u;
-    cx.role.key_mask = 0x0ff00ff0u;
+    cx.role.key_mask = live ? 0x0ff00ff0u : 0u;  // S stays zero in lanes that are not live (box7)
     cx.role.edge_wave = __builtin_amdgcn_readfirstlane(__any((int)(cx.role.first_mask | cx.role.last_mask | cx.role.line_last_mask)) ? 1 : 0) != 0;
 
     for (int p = 0; p < 2; ++p) {
@@ -376,6 +376,7 @@ __device__ __forceinline__ void sweep(const Args& a)
             init(std::integral_constant<int, 8>{});
         }
         const int first_col = (wave == 0 ? 0 : kFirst + kInner * (wave - 1) - GH) * PXL;  // of lane 0 (a ghost lane)
+        const unsigned o_live = live ? kAll : 0u;
         for (int s = 1; s <= last_step; ++s) {
             // out of both passes' cones for good (they coincide at a step: row s + 1 with six extra columns, row s - 1 without)
             if (first_col >= cone_w + 3 * (nr - s) + 9) return;  // (a finished wave no longer counts at the barriers)
@@ -394,7 +395,8 @@ __device__ __forceinline__ void sweep(const Args& a)
                 }
             }
             const int vin2 = luma_row(s + 2);
-            const unsigned omask = s <= kSkew ? 0x000000ffu : 0x00ff00ffu;  // the V half starts from zero: A'[hi] = D
+            // the V half starts from zero: A'[hi] = D; lanes that are not live keep O, and with it S, at zero (box7)
+            const unsigned omask = (s <= kSkew ? 0x000000ffu : 0x00ff00ffu) & o_live;
             // V's row s - 2 takes U's row s - 1 -- unless that row does not exist (4:2:2: the pool ends with the chroma planes' last
             // row, so V's last row adds nothing, as its pass of the reference finds nothing below it: SangNom2.cpp:126-159)
             const unsigned sel = s - 1 <= a.sweep_u ? 0x0c040c00u : 0x0c0c0c00u;
@@ -403,7 +405,7 @@ __device__ __forceinline__ void sweep(const Args& a)
                 const u32x2 ld = ahead[B];  // row s + 1, fetched a whole step ago
                 __builtin_amdgcn_sched_barrier(0);
                 ahead[B] = issue_stale(cx, B, s + 2, vin2);
-                stale_buffer_step<B, RC>(A[B], Oprev[B], cx.role, ld, omask, sel);
+                stale_buffer_step<B>(A[B], Oprev[B], cx.role, ld, omask, sel);
             };
             run(std::integral_constant<int, 0>{});
             run(std::integral_constant<int, 1>{});
@@ -558,7 +560,7 @@ __device__ __forceinline__ void sweep(const Args& a)
             st.amask = ru == nr + 1 ? kHi : kAll;  // U's last row: its half of A keeps O alone, which is what V's last row needs
             st.from_a = rv == nr;
         }
-        const Out o = region_row<STALE, MASKED, CLS == kRS, RC>(A, n, nn, cx, st, thr_key, ahead);
+        const Out o = region_row<STALE, MASKED, CLS == kRS>(A, n, nn, cx, st, thr_key, ahead);
         {
             const int ru = s, rv = s - kSkew;
             u32x2 lo, hi;
@@ -627,7 +629,7 @@ __device__ __forceinline__ void sweep(const Args& a)
 // (an argument of a device function travels in vector registers and the compiler must take it for divergent: every word of
 // the argument block goes through v_readfirstlane once, so that in the sweep rows, pitches and pointers are scalars again --
 // as they are in a kernel that reads its own argument segment)
-template <int NW, int CLS, bool RC>
+template <int NW, int CLS>
 __device__ __attribute__((noinline)) void sweep_entry(const Args* from)
 {
     static_assert(sizeof(Args) % 4 == 0, "Args is copied word by word");
@@ -638,7 +640,7 @@ __device__ __attribute__((noinline)) void sweep_entry(const Args* from)
     for (int i = 0; i < kWords; ++i) words[i] = (uint32_t)__builtin_amdgcn_readfirstlane((int)in[i]);
     Args a;
     __builtin_memcpy(&a, words, sizeof a);
-    sweep<NW, CLS, RC>(a);
+    sweep<NW, CLS>(a);
 }
 
 template <int NW>
@@ -649,18 +651,10 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused_u8_uv(Args a)
     const int gl = wave == 0 ? lane : kFirst + kInner * (wave - 1) + (lane - GH);
     const bool live = gl < a.nl, chroma = live && gl * PXL < a.region_w, stale = live && !chroma;
     const int cls = __builtin_amdgcn_readfirstlane(__any((int)chroma) ? (__any((int)stale) ? (int)kRS : (int)kR) : (int)kS);
-    // ... and whether it holds the pool's last column: only there the box needs its right-hand clamp (a wave-uniform choice of
-    // the whole function, never a branch inside a buffer step)
-    const bool rc = __builtin_amdgcn_readfirstlane(__any((int)(live && gl == a.nl - 1)) ? 1 : 0) != 0;
-    if (cls == kS) {
-        if (rc) sweep_entry<NW, kS, true>(&a);
-        else sweep_entry<NW, kS, false>(&a);
-    } else if (cls == kR) {
-        sweep_entry<NW, kR, false>(&a);  // (the last column is never chroma: region_w < w)
-    } else {
-        if (rc) sweep_entry<NW, kRS, true>(&a);
-        else sweep_entry<NW, kRS, false>(&a);
-    }
+    // (the box is the same in every wave, the pool's last column included: one function per class)
+    if (cls == kS) sweep_entry<NW, kS>(&a);
+    else if (cls == kR) sweep_entry<NW, kR>(&a);
+    else sweep_entry<NW, kRS>(&a);
 }
 
 }  // namespace uv

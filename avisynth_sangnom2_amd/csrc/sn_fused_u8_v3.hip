@@ -18,7 +18,8 @@
 //     so what counts is the NUMBER of instructions, and each of these forms replaces two to four simple ones;
 //   * the +-3 horizontal taps of the box come from the neighbouring lanes with DPP wave_shr:1 / wave_shl:1 (one move
 //     serves both strips).  Column 0 is lane 0 of the first strip and has no left neighbour: its DPP move keeps the `old`
-//     operand, S[0] -- loadPixel's clamp (SangNom2.cpp:25-34) for free; the last column takes one select per right-hand tap.
+//     operand, S[0] -- loadPixel's clamp (SangNom2.cpp:25-34) for free; the last column's neighbour reads zero too (S is
+//     zero in every half that is not live) and its clamp is one masked S[7] per buffer step (box7).
 //     The same box in every wave: no branch inside a buffer step;
 //   * the first / last GH lanes of a strip are ghost lanes that recompute the neighbouring strip's 16 columns.  A ghost
 //     zone stays exact in its innermost 3 pixels for floor(16 / 3) = 5 rows (the missing outer neighbour corrupts 3 more
@@ -157,7 +158,7 @@ __device__ __forceinline__ void buffer_step(unsigned (&A)[PXL], unsigned (&kmin)
             V[j] = pk_sub_sat(y, x);
             S[j] = add3(A[j], U[j], V[j]);
         }
-        box7_any(S, Bx, role);
+        box7(S, Bx, role);
 #pragma unroll
         for (int j = 0; j < PXL; ++j) {
             const unsigned key = and_or(Bx[j], role.key_mask, rank_of<BUF, MODE>());
@@ -187,7 +188,7 @@ __device__ __forceinline__ void buffer_step(unsigned (&A)[PXL], unsigned (&kmin)
                 C[j] = cost<BUF>(n, nn, j);
                 S[j] = add3(A[j], C[j], D[j]);
             }
-            box7_any(S, Bx, role);
+            box7(S, Bx, role);
 #pragma unroll
             for (int j = 0; j < PXL; ++j) {
                 const unsigned key = and_or(Bx[j], role.key_mask, rank_of<BUF, MODE>());
@@ -207,7 +208,7 @@ __device__ __forceinline__ void buffer_step(unsigned (&A)[PXL], unsigned (&kmin)
     }
 #pragma unroll
     for (int j = 0; j < PXL; ++j) S[j] = A[j] + D[j];
-    box7_any(S, Bx, role);
+    box7(S, Bx, role);
 #pragma unroll
     for (int j = 0; j < PXL; ++j) {
         // key = (sum / 16 mod 256) << 4 | rank in ONE v_and_or_b32; the rank (< 16) falls off the PACKED shift that
@@ -407,7 +408,7 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args 
     role.last_mask = 0;
     role.line_last_mask = 0;
     role.inside_mask = 0;
-    role.key_mask = 0x0ff00ff0u;
+    role.key_mask = 0;  // 0x0ff00ff0 in live halves, 0 in the others: S stays zero there (box7)
     const int line_w = has_region(MODE) ? a.region_w : a.w;  // width of the source / destination plane
     bool line_live[2], line_real[2];
 #pragma unroll
@@ -428,6 +429,7 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args 
         x0[h] = gl * PXL;
         line_live[h] = live[h] && x0[h] < line_w;
         line_real[h] = real[h] && x0[h] < line_w;
+        if (live[h]) role.key_mask |= h ? 0x0ff00000u : 0x00000ff0u;
         if (live[h] && gl == 0) role.first_mask |= h ? kHi : kLo;
         if (live[h] && gl == a.nl - 1) role.last_mask |= h ? kHi : kLo;
         if (line_live[h] && x0[h] + PXL == line_w) role.line_last_mask |= h ? kHi : kLo;
@@ -510,8 +512,10 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args 
         }
         // a pool row is [chunk kind][thread][8 bytes]: the chunks of one kind lie side by side, so the lanes inside the
         // cone write and read whole cache lines (interleaved with the other kind every line was half useful)
-        io.v_lo = c_lo * (NW * 64 * 8) + t_lo * 8;
-        io.v_hi = c_hi * (NW * 64 * 8) + t_hi * 8;
+        // (a half that is not live reads nothing: behind the last strip's last column a strip that does not exist may
+        // still lie inside the cone, and S must stay zero there, see box7)
+        io.v_lo = live[0] ? c_lo * (NW * 64 * 8) + t_lo * 8 : kOutOfRange;
+        io.v_hi = live[1] ? c_hi * (NW * 64 * 8) + t_hi * 8 : kOutOfRange;
         io.v_out_lo = real[0] ? (linear ? x0[0] : tid * 8) : kOutOfRange;
         io.v_out_hi = real[1] ? (linear ? x0[1] : NW * 64 * 8 + tid * 8) : kOutOfRange;
     }

@@ -188,6 +188,16 @@ KIND(min_u16, O_MINU16) KIND(sub_u16, O_SUBU16) KIND(lshl_b16, O_LSHLB16) KIND(n
 KIND(ashr, O_ASHR) KIND(subrev, O_SUBREV) KIND(max_i16, O_MAXI16) KIND(cndmask_vcc, O_CNDV) KIND(mul_lo_u16, O_MULLO16)
 KIND(add_f16, O_ADDF16) KIND(mul_f32, O_MULF) KIND(fmac_f32, O_FMAC) KIND(max_f32, O_MAXF) KIND(cvt_f32_ubyte0, O_CVTU8)
 KIND(add_literal, O_ADDLIT) KIND(and_literal, O_ANDLIT) KIND(add_e64_sgpr, O_ADDE64) KIND(add_sgpr, O_ADDSG)
+// gfx950's packed three-operand IEEE minimum on f16 halves: the ladder's key minimum could fold two buffers' keys into one
+// instruction (keys < 0x1000 are non-negative f16 bit patterns, ordered like unsigned integers while denormals are kept)
+#define O_PKMIN3F16(n) "v_pk_minimum3_f16 v" STR(n) ", v" STR(n) ", v18, v19"
+KIND(pk_minimum3_f16, O_PKMIN3F16)
+// the sweep's mix with its key minimum as v_pk_minimum3_f16 in place of v_pk_min_u16
+#define SW32M X8(O_PKMAX(10), O_PKMIN3F16(11), O_SUB(12), O_ADD(13), O_ADD(14), O_SUB(15), O_AND(16), O_LSHR(17)) \
+              X8(O_ADD(10), O_OR(11), O_PKMIN3F16(12), O_AND(13), O_LSHR(14), O_ADDDPP(15), O_ADD3(16), O_AND(17)) \
+              X8(O_PKMAX(10), O_PKMIN3F16(11), O_SUB(12), O_ADD(13), O_ANDOR(14), O_AND(15), O_LSHR(16), O_OR(17)) \
+              X8(O_ADD(10), O_AND(11), O_BFI(12), O_MUL24(13), O_LSHR(14), O_ADDDPP(15), O_ADD(16), O_AND(17))
+DEFK(sweepmix_min3f16, SW32M SW32M SW32M SW32M)
 
 typedef void (*kern_t)(unsigned long long*, int);
 struct Entry {
@@ -216,6 +226,7 @@ int main(int argc, char** argv)
         E3(mul_lo_u16) E3(add_f16) E3(mul_f32) E3(fmac_f32) E3(max_f32) E3(cvt_f32_ubyte0) E3(add_literal) E3(and_literal)
         E3(add_e64_sgpr) E3(add_sgpr)
         {"mix 6 fast 2 salu", k_mix_f6salu2_ind},
+        E3(pk_minimum3_f16) {"sweep mix, pk_minimum3_f16 for pk_min", k_sweepmix_min3f16},
     };
     // arguments: [--waves 1,2,4] [--iters N] [--rounds R] substrings of the names to run
     std::vector<int> wlist = {1, 2, 3, 4, 8};
