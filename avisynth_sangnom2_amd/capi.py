@@ -27,7 +27,11 @@ EXPORTS = (
     "sn_pin_host_buffer", "sn_unpin_host_buffer", "sn_submit_host_to", "sn_debug_set_bands",
     "sn_create_with_policy", "sn_get_policy", "sn_set_policy", "sn_aa_create_with_policy",
     "sn_debug_raise_chain_fault",
+    "sn_create_ex", "sn_aa_create_ex", "sn_get_arithmetic",
 )
+
+# sn_options.arithmetic: which of the reference's two code paths a context reproduces (sangnom_hip.h)
+SN_ARITH_CXX, SN_ARITH_SSE2 = 0, 1
 
 SN_SMALL_AUTO, SN_SMALL_SWEEP = 0, 1
 # What a filter object asks for when its caller says nothing (all zeros = the library's defaults).  The test suite
@@ -46,6 +50,20 @@ class SnConfig(ctypes.Structure):
 class SnPolicy(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("struct_size", "small_launches", "chain", "copy_threads", "scratch_budget_mb", "chroma_sweeps")] + [
         ("reserved", ctypes.c_int32 * 2)]
+
+
+class SnOptions(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_int32), ("arithmetic", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6)]
+
+
+def options(arithmetic: int = SN_ARITH_CXX) -> "SnOptions":
+    return SnOptions(struct_size=ctypes.sizeof(SnOptions), arithmetic=int(arithmetic))
+
+
+def arithmetic_of_opt(opt: int) -> int:
+    """The script argument `opt`: 1 asks for the reference's SSE2 arithmetic; 0 and -1 are its C++ arithmetic (this
+    library's default -- upstream's own -1 means SSE2 on x86-64)."""
+    return SN_ARITH_SSE2 if opt == 1 else SN_ARITH_CXX
 
 
 def policy(**over) -> "SnPolicy":
@@ -110,6 +128,9 @@ def load():
     L.sn_validate.argtypes = [ctypes.POINTER(SnConfig), ctypes.c_char_p, ctypes.c_size_t]
     L.sn_create.argtypes = [ctypes.POINTER(SnConfig), ctypes.POINTER(vp)]
     L.sn_create_with_policy.argtypes = [ctypes.POINTER(SnConfig), ctypes.POINTER(SnPolicy), ctypes.POINTER(vp)]
+    L.sn_create_ex.argtypes = [ctypes.POINTER(SnConfig), ctypes.POINTER(SnPolicy), ctypes.POINTER(SnOptions), ctypes.POINTER(vp)]
+    L.sn_aa_create_ex.argtypes = [ctypes.POINTER(SnConfig), ctypes.POINTER(SnPolicy), ctypes.POINTER(SnOptions), ctypes.POINTER(vp)]
+    L.sn_get_arithmetic.argtypes = [vp]
     L.sn_get_policy.argtypes = [vp, ctypes.POINTER(SnPolicy)]
     L.sn_set_policy.argtypes = [vp, ctypes.POINTER(SnPolicy)]
     L.sn_aa_create_with_policy.argtypes = [ctypes.POINTER(SnConfig), ctypes.POINTER(SnPolicy), ctypes.POINTER(vp)]

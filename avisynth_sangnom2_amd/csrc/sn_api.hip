@@ -40,6 +40,13 @@ struct Context {
     bool process[3] = {true, true, true};
     bool history_free = false;
     bool use_fused = false;
+    int arith = SN_ARITH_CXX;  // sn_options.arithmetic, fixed for the context's life
+    // SN_ARITH_SSE2 on integer samples: the saturating instances of the pool kernels (float has one arithmetic)
+    bool saturating() const { return arith == SN_ARITH_SSE2 && cfg.bytes_per_sample < 4; }
+    // ... and which sweeps have such instances: 8-bit planes on their own (plain, padded and row-band sweeps of
+    // sn_fused_u8_v3.hip).  Not the pool-coupled sweeps of subsampled chroma, nor the 16-bit sweep: those clips run on
+    // the pool kernels in this arithmetic
+    bool saturating_sweeps() const { return cfg.bytes_per_sample == 1 && (isolated || !sn::fused_needs_pools(cfg)); }
 
     PoolArgs pool{};  // allocated on first use when the fused kernels serve the configuration
 
@@ -467,6 +474,31 @@ static int create_impl(const sn_config* cfg, Context* c)
             eligible = eligible && c->plane_fused[p];
         }
     }
+    if (c->arith == SN_ARITH_SSE2) {
+        // The reference's SSE2 stage drivers read one vector to the left of the last full one, so its output is defined
+        // for planes of at least two vectors (src/SangNom2_SSE2.cpp:705-715): 32 / 16 / 8 samples.  Every processed plane.
+        const int least = 32 / cfg->bytes_per_sample;
+        for (int p = 0; p < c->nplanes(); ++p)
+            if ((cfg->dh || c->process[p]) && c->plane_w(p) < least)
+                return sn::fail(c, SN_ERR_UNSUPPORTED,
+                                "SN_ARITH_SSE2: plane %d is %d samples wide; the reference's SSE2 path is defined from %d samples (two vectors) on",
+                                p, c->plane_w(p), least);
+    }
+    if (c->saturating()) {
+        // Only the 8-bit sweeps of planes on their own have instances of this arithmetic; every other integer plane runs
+        // on the pool kernels, and the context says so (sn_info.fused_eligible = 0).  DESIGN.md 4.5.
+        if (!c->saturating_sweeps()) {
+            if (cfg->mode == SN_MODE_FUSED)
+                return sn::fail(c, SN_ERR_UNSUPPORTED,
+                                "SN_MODE_FUSED requested but in SN_ARITH_SSE2 only 8-bit planes on their own have fused sweeps; "
+                                "this clip (%s) runs on the pool path in that mode",
+                                cfg->bytes_per_sample == 2 ? "9..16-bit samples" : "subsampled chroma sharing the luma pool");
+            eligible = false;
+            for (int p = 0; p < 3; ++p) c->plane_fused[p] = c->plane_padded[p] = false;
+        }
+        c->pool.arith = SN_ARITH_SSE2;
+        for (int p = 0; p < 3; ++p) c->plane_pool[p].arith = SN_ARITH_SSE2;
+    }
     if (cfg->mode == SN_MODE_FUSED && !eligible)
         return sn::fail(c, SN_ERR_UNSUPPORTED, "SN_MODE_FUSED requested but this configuration is not eligible");
     c->use_fused = eligible && cfg->mode != SN_MODE_POOL;
@@ -565,7 +597,19 @@ static const char* policy_text(const sn_policy* p)
 
 int sn_create(const sn_config* cfg, sn_context** out) { return sn_create_with_policy(cfg, nullptr, out); }
 
-int sn_create_with_policy(const sn_config* cfg, const sn_policy* policy, sn_context** out)
+int sn_create_with_policy(const sn_config* cfg, const sn_policy* policy, sn_context** out) { return sn_create_ex(cfg, policy, nullptr, out); }
+
+static const char* options_text(const sn_options* o)
+{
+    if (!o) return nullptr;
+    if (o->struct_size != (int32_t)sizeof(sn_options)) return "sn_options.struct_size mismatch";
+    if (o->arithmetic != SN_ARITH_CXX && o->arithmetic != SN_ARITH_SSE2) return "sn_options.arithmetic must be SN_ARITH_CXX or SN_ARITH_SSE2";
+    for (int32_t r : o->reserved)
+        if (r != 0) return "sn_options.reserved must be zero";
+    return nullptr;
+}
+
+int sn_create_ex(const sn_config* cfg, const sn_policy* policy, const sn_options* options, sn_context** out)
 {
     if (!cfg || !out) return sn::fail(nullptr, SN_ERR_INVALID_ARG, "cfg / out is NULL");
     *out = nullptr;
@@ -573,8 +617,10 @@ int sn_create_with_policy(const sn_config* cfg, const sn_policy* policy, sn_cont
     int rc = sn_validate(cfg, msg, sizeof msg);
     if (rc != SN_OK) return rc;  // g_last_error already holds the text
     if (const char* t = policy_text(policy)) return sn::fail(nullptr, SN_ERR_INVALID_ARG, "%s", t);
+    if (const char* t = options_text(options)) return sn::fail(nullptr, SN_ERR_INVALID_ARG, "%s", t);
     Context* c = new (std::nothrow) Context();
     if (!c) return sn::fail(nullptr, SN_ERR_INVALID_ARG, "out of host memory");
+    if (options) c->arith = options->arithmetic;
     if (policy) c->policy = *policy;
     c->policy.struct_size = (int32_t)sizeof(sn_policy);
     rc = create_impl(cfg, c);
@@ -900,6 +946,7 @@ static int run_group(Context* c, hipStream_t st, int slot0, int n, const void* c
         a.offset = offset;
         a.dh = c->cfg.dh;
         a.enabled = (c->cfg.dh || c->process[p]) ? 1 : 0;
+        a.arith = c->saturating() ? SN_ARITH_SSE2 : SN_ARITH_CXX;
         fused[p] = a.enabled && (c->isolated ? c->plane_fused[p] : c->use_fused) && sn::fused_layout_ok(a);
     }
     bool all_fused = true;
@@ -1921,6 +1968,12 @@ void* sn_get_stream(sn_context* h)
     return c ? reinterpret_cast<void*>(c->stream) : nullptr;
 }
 
+int sn_get_arithmetic(sn_context* h)
+{
+    Context* c = reinterpret_cast<Context*>(h);
+    return c ? c->arith : -1;
+}
+
 int sn_get_info(sn_context* h, sn_info* info)
 {
     Context* c = reinterpret_cast<Context*>(h);
@@ -1931,7 +1984,9 @@ int sn_get_info(sn_context* h, sn_info* info)
     info->pool_stride = c->stride_e;
     info->pool_rows = c->bh + 1;
     info->fused_eligible = sn::fused_eligible(c->cfg) ? 1 : 0;
-    if (c->isolated) {
+    if (c->saturating() && !c->saturating_sweeps()) {
+        info->fused_eligible = 0;  // sweeps without SN_ARITH_SSE2 instances: the pool path serves every plane
+    } else if (c->isolated) {
         info->fused_eligible = 1;
         for (int p = 0; p < c->nplanes(); ++p)
             if ((c->cfg.dh || c->process[p]) && !sn::fused_plane_eligible(c->cfg.bytes_per_sample, c->plane_w(p)) &&
@@ -2068,7 +2123,9 @@ void sn_aa_destroy(sn_aa_context* a)
 
 int sn_aa_create(const sn_config* cfg, sn_aa_context** out) { return sn_aa_create_with_policy(cfg, nullptr, out); }
 
-int sn_aa_create_with_policy(const sn_config* cfg, const sn_policy* policy, sn_aa_context** out)
+int sn_aa_create_with_policy(const sn_config* cfg, const sn_policy* policy, sn_aa_context** out) { return sn_aa_create_ex(cfg, policy, nullptr, out); }
+
+int sn_aa_create_ex(const sn_config* cfg, const sn_policy* policy, const sn_options* options, sn_aa_context** out)
 {
     auto fail_aa = [](sn_aa_context* a, int code, const std::string& msg) {
         g_aa_error = msg;
@@ -2090,13 +2147,13 @@ int sn_aa_create_with_policy(const sn_config* cfg, const sn_policy* policy, sn_a
     c1.max_batch = 1;
     c1.mode = SN_MODE_AUTO;
     c1.stream = nullptr;
-    int rc = sn_create_with_policy(&c1, policy, &a->first);
+    int rc = sn_create_ex(&c1, policy, options, &a->first);
     if (rc != SN_OK) return fail_aa(a, rc, sn_last_error(nullptr));
     sn_config c2 = *cfg;
     c2.max_batch = 1;
     c2.mode = SN_MODE_AUTO;
     c2.stream = sn_get_stream(a->first);
-    rc = sn_create_with_policy(&c2, policy, &a->second);
+    rc = sn_create_ex(&c2, policy, options, &a->second);
     if (rc != SN_OK) return fail_aa(a, rc, sn_last_error(nullptr));
     a->stream = reinterpret_cast<hipStream_t>(sn_get_stream(a->first));
     a->planes = cfg->num_planes < 3 ? cfg->num_planes : 3;

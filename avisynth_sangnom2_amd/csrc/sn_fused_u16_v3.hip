@@ -1075,6 +1075,7 @@ void fused_u16_pool_unpack(const uint32_t* raw, int sweep_w, int rows, uint16_t*
 
 hipError_t launch_fused_u16_v3(hipStream_t st, const PlaneArgs& p, double threshold, int nframes, const FusedPool* pool)
 {
+    if (p.arith != SN_ARITH_CXX) return hipErrorInvalidValue;  // this sweep has the C++ arithmetic only: an error, never wrapping pixels in SN_ARITH_SSE2
     v3c::Args a{};
     a.src = p.src;
     a.dst = p.dst;

@@ -108,8 +108,22 @@ __device__ __forceinline__ unsigned lshl2_add(unsigned a, unsigned b)
     return r;
 }
 
-// q: after clamp_edges()
-template <class LineT>
+// The SangNom value of the SSE2 arithmetic (SN_ARITH_SSE2, sn_pixel.h PxA) on packed pairs: 4a + 5b - c in clean 16-bit
+// halves, a LOGICAL >> 3, an unsigned minimum against 255 -- as _mm_srli_epi16 + _mm_packus_epi16 give it
+// (src/SangNom2_SSE2.cpp:446-516): a negative half is at least 0x1fe0 after the shift, so the one minimum covers it and
+// the values above 255 alike.  The borrows the default form lets travel between the halves (below) would be wrong here:
+// every operation is a packed 16-bit one.
+__device__ __forceinline__ unsigned sg_sat(unsigned a, unsigned b, unsigned c)
+{
+    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+    const u16x2 va = __builtin_bit_cast(u16x2, a), vb = __builtin_bit_cast(u16x2, b), vc = __builtin_bit_cast(u16x2, c);
+    const u16x2 five = {5, 5}, lim = {255, 255};
+    const u16x2 s = (u16x2)((u16x2)(va << 2) + vb * five - vc) >> 3;
+    return __builtin_bit_cast(unsigned, __builtin_elementwise_min(s, lim));
+}
+
+// q: after clamp_edges().  ARITH: SN_ARITH_* (0: the reference's C++ arithmetic)
+template <class LineT, int ARITH = 0>
 __device__ __forceinline__ void unpack(LineT& L, const Raw& q)
 {
 #pragma unroll
@@ -122,7 +136,20 @@ __device__ __forceinline__ void unpack(LineT& L, const Raw& q)
         L.P[3 + k] = pair_byte(q.h[1].m0, q.h[0].m0, k);
         L.P[7 + k] = pair_byte(q.h[1].m1, q.h[0].m1, k);
     }
-    // F = ((4a + 5b - c) >> 3) mod 256, B = ((4c + 5b - a) >> 3) mod 256 (a, b, c = P[j + 2 .. j + 4]), computed 32 times
+    if constexpr (ARITH == 1) {  // the SSE2 arithmetic: F and B saturate (sg_sat), nothing of the form below applies
+#pragma unroll
+        for (int j = 0; j < PXL; ++j) {
+            const unsigned f = sg_sat(L.P[j + 2], L.P[j + 3], L.P[j + 4]), b = sg_sat(L.P[j + 4], L.P[j + 3], L.P[j + 2]);
+            if constexpr (std::is_same<LineT, WideLine>::value) {
+                L.Fv[j] = f;
+                L.Bv[j] = b;
+            } else {
+                L.FB[j] = f | (b << 8);  // F | B << 8 in each half
+            }
+        }
+        return;
+    }
+    // The C++ arithmetic: F = ((4a + 5b - c) >> 3) mod 256, B = ((4c + 5b - a) >> 3) mod 256 (a, b, c = P[j + 2 .. j + 4]), computed 32 times
     // over with a bias of 2048 per half: X = 32 (4 (a + b + 512) + (b - c)) for F and 32 (4 (b + c + 512) + (b - a)) for
     // B -- the pair sum of B at j is that of F at j + 1, and X is one v_lshl_add_u32 of a pair sum and a difference.  The
     // value then sits in bits 8..15 of each half, and one byte permute extracts it (no shift and mask).  32 (x + 2048) is
@@ -266,6 +293,17 @@ constexpr unsigned rank_of()
 // Round 2 branched on "this wave holds an image edge" around two whole variants of the box: the edge waves paid 29
 // instructions per buffer instead of 20, the branch cut every buffer step into three scheduling regions, and the seam
 // refresh made every wave wait for the slowest (knocking the edge variant out -- wrong at the edges -- ran 12 % faster).
+// In the SSE2 arithmetic the window sum saturates: min(sum >> 4, 255) (src/SangNom2_SSE2.cpp:748-761).  The key is
+// (Bx & 0x0ff00ff0) | rank, so a half of 4096 or more has to become 4095, whose bits 4..11 are 255: ONE v_pk_min_u16 in
+// front of the v_and_or (Bx holds the true sums, below 2^16 per half: the borrows have been returned by then).  A
+// minimum never turns a zero half into something else, so S stays zero in every half that is not live.
+template <int ARITH>
+__device__ __forceinline__ unsigned box_sat(unsigned bx)
+{
+    if constexpr (ARITH == 1) return pk_min(bx, 0x0fff0fffu);
+    return bx;
+}
+
 __device__ __forceinline__ void box7(const unsigned (&S)[PXL], unsigned (&Bx)[PXL], const LaneRole& role)
 {
     const unsigned p = add3(S[1], S[2], S[3]), q = add3(S[4], S[5], S[6]);

@@ -674,6 +674,7 @@ bool fused_uv_ok(int sweep_w, int region_w, int nk_c, int bh)
 hipError_t launch_fused_u8_uv(hipStream_t st, const PlaneArgs& pu, const PlaneArgs& pv, double thr_u, double thr_v, int nframes, const FusedPool& pool)
 {
     using namespace v3c;
+    if (pu.arith != SN_ARITH_CXX || pv.arith != SN_ARITH_CXX) return hipErrorInvalidValue;  // the C++ arithmetic only (see launch_fused_u16_v3)
     uv::Args a{};
     const PlaneArgs* pp[2] = {&pu, &pv};
     for (int p = 0; p < 2; ++p) {

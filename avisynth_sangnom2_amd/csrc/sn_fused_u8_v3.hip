@@ -139,7 +139,7 @@ using LineOf = typename std::conditional<wide_lines(MODE), WideLine, Line>::type
 // S1: the costs of row r+1 come from the lines (n, nn); otherwise they are zero (kPlain /
 // kLumaSpill: row bh is never written) or the previous pass's values (kChroma).
 // STORE: the smoothed row goes to pool_out (lanes / rows that keep nothing carry an out-of-range voffset).
-template <int BUF, int MODE, bool S1, bool STORE>
+template <int BUF, int MODE, bool S1, bool STORE, int ARITH = 0>
 __device__ __forceinline__ void buffer_step(unsigned (&A)[PXL], unsigned (&kmin)[PXL], const LineOf<MODE>& n, const LineOf<MODE>& nn,
                                             const LaneRole& role, const PoolIO& io, const RowCtx& rc,
                                             PoolIO::RawPair& stale)
@@ -161,7 +161,7 @@ __device__ __forceinline__ void buffer_step(unsigned (&A)[PXL], unsigned (&kmin)
         box7(S, Bx, role);
 #pragma unroll
         for (int j = 0; j < PXL; ++j) {
-            const unsigned key = and_or(Bx[j], role.key_mask, rank_of<BUF, MODE>());
+            const unsigned key = and_or(box_sat<ARITH>(Bx[j]), role.key_mask, rank_of<BUF, MODE>());
             O[j] = pk_lshr4(key);
             A[j] = add3(O[j], U[j], V[j]);
             kmin[j] = pk_min(kmin[j], key);
@@ -191,7 +191,7 @@ __device__ __forceinline__ void buffer_step(unsigned (&A)[PXL], unsigned (&kmin)
             box7(S, Bx, role);
 #pragma unroll
             for (int j = 0; j < PXL; ++j) {
-                const unsigned key = and_or(Bx[j], role.key_mask, rank_of<BUF, MODE>());
+                const unsigned key = and_or(box_sat<ARITH>(Bx[j]), role.key_mask, rank_of<BUF, MODE>());
                 O[j] = pk_lshr4(key);
                 A[j] = add3(O[j], C[j], D[j]);
                 kmin[j] = pk_min(kmin[j], key);
@@ -214,7 +214,7 @@ __device__ __forceinline__ void buffer_step(unsigned (&A)[PXL], unsigned (&kmin)
         // key = (sum / 16 mod 256) << 4 | rank in ONE v_and_or_b32; the rank (< 16) falls off the PACKED shift that
         // yields O (a 32-bit shift would push the high half's rank into the low half).  Every VALU instruction of this
         // stream costs the same issue slot (profiles/r3_ubench_valu_table.txt), so what counts is their NUMBER.
-        const unsigned key = and_or(Bx[j], role.key_mask, rank_of<BUF, MODE>());
+        const unsigned key = and_or(box_sat<ARITH>(Bx[j]), role.key_mask, rank_of<BUF, MODE>());
         O[j] = pk_lshr4(key);        // (sum / 16) wraps to uint8_t, SangNom2.cpp:152
         A[j] = O[j] + D[j];          // O + D[r+1]
         kmin[j] = pk_min(kmin[j], key);
@@ -280,7 +280,7 @@ __device__ __forceinline__ void unpark_raw(const Parked<NT, RB>& pk, int tid, in
 }
 
 // S3: the row has an interpolated line (stage 3); kChroma sweeps one extra row without one.
-template <int MODE, bool S1, bool S3, bool STORE, int NT>
+template <int MODE, bool S1, bool S3, bool STORE, int NT, int ARITH = 0>
 __device__ __forceinline__ Out row_step(unsigned (&A)[reg_buffers(MODE)][PXL], const Parked<NT, reg_buffers(MODE)>& pk, int tid, const LineOf<MODE>& n,
                                         const LineOf<MODE>& nn, const LaneRole& role, unsigned thr_key, const PoolIO& io,
                                         const RowCtx& rc)
@@ -299,11 +299,11 @@ __device__ __forceinline__ Out row_step(unsigned (&A)[reg_buffers(MODE)][PXL], c
         constexpr int B = decltype(buf)::value;
         PoolIO::RawPair& st = (B & 1) ? st1 : st0;
         if constexpr (B < reg_buffers(MODE)) {
-            buffer_step<B, MODE, S1, STORE>(A[B], kmin, n, nn, role, io, rc, st);
+            buffer_step<B, MODE, S1, STORE, ARITH>(A[B], kmin, n, nn, role, io, rc, st);
         } else {
             unsigned t[PXL];
             load_A(pk, tid, B, t);
-            buffer_step<B, MODE, S1, STORE>(t, kmin, n, nn, role, io, rc, st);
+            buffer_step<B, MODE, S1, STORE, ARITH>(t, kmin, n, nn, role, io, rc, st);
             store_A(pk, tid, B, t);
         }
     };
@@ -379,7 +379,7 @@ __host__ __device__ constexpr int lds_bytes(int nw, int mode)
 // and spills in that form, so it keeps rows on their own, two per loop trip.
 __host__ __device__ constexpr bool block_rows(int mode) { return mode != kPadded; }
 
-template <int NW, int MODE, bool BAND>
+template <int NW, int MODE, bool BAND, int ARITH = 0>
 __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args a)
 {
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -561,8 +561,8 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args 
     if (nk > 1) keep(dst_line + r0 * dst_step, q1, r0 == ra && r0 <= nr);
     {
         const Raw f0 = clamp_edges(q0, role), f1 = clamp_edges(q1, role);
-        unpack(L0, f0);
-        unpack(L1, f1);
+        unpack<LineOf<MODE>, ARITH>(L0, f0);
+        unpack<LineOf<MODE>, ARITH>(L1, f1);
         RawLine R;
         make_raw(R, f0, L0);
         park_raw(parked, tid, (r0 - 1) % 3, R);  // K[r0 - 1]: c of row r0
@@ -712,7 +712,7 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args 
             asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
             SN_RT(0);  // [0] the wait for the prefetched line
 #endif
-            unpack(nn, fq);
+            unpack<LineOf<MODE>, ARITH>(nn, fq);
             RawLine R;
             make_raw(R, fq, nn);
             park_raw(parked, tid, slot_nn, R);  // K[r + 1]: n of the next row, c of the one after
@@ -747,7 +747,7 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args 
             rc.any_out = __builtin_amdgcn_readfirstlane(__any((rc.vout != kOutOfRange) | (rc.vout_hi != kOutOfRange)) ? 1 : 0) != 0;
         }
         SN_RT(3);  // [3] ghost refresh (every fifth row) and row set-up
-        const Out o = row_step<MODE, HAS_NEXT, S3, STORE>(A, parked, tid, n, nn, role, thr_key, io, rc);
+        const Out o = row_step<MODE, HAS_NEXT, S3, STORE, NW * 64, ARITH>(A, parked, tid, n, nn, role, thr_key, io, rc);
         if constexpr (S3) put(out_row, o);  // stored at once: nothing is carried into the next row
         SN_RT(4);  // [4] nine buffer steps + stage 3 + output store
         out_row += dst_step;
@@ -880,7 +880,7 @@ static int virtual_waves_for(int nl) { return strips_for(nl); }
 // This file is compiled twice (csrc/Makefile).  The sweeps of planes on their own (kPlain, kPadded) go into an object
 // of their own, built with -mllvm -amdgpu-sched-strategy=max-ilp: +1.7 % on them, but that scheduler makes the
 // pool-coupled modes (which live at the register limit) spill, so those keep the default one.
-template <int MODE, bool BAND = false>
+template <int MODE, bool BAND = false, int ARITH = 0>
 static hipError_t launch_mode(hipStream_t st, const v3::Args& a, int nframes)
 {
     const int g = v3c::group_of(a.nw);
@@ -889,9 +889,9 @@ static hipError_t launch_mode(hipStream_t st, const v3::Args& a, int nframes)
 #define SN_LAUNCH(NW)                                                                                              \
     case NW:                                                                                                       \
         if (lds > 64 * 1024)                                                                                       \
-            e = hipFuncSetAttribute((const void*)v3::k_fused_u8_v3<NW, MODE, BAND>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
+            e = hipFuncSetAttribute((const void*)v3::k_fused_u8_v3<NW, MODE, BAND, ARITH>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
         if (e == hipSuccess)                                                                                       \
-            hipLaunchKernelGGL((v3::k_fused_u8_v3<NW, MODE, BAND>), dim3((nframes + g - 1) / g, BAND ? a.nbands : 1), dim3(NW * g * 64), lds, st, a); \
+            hipLaunchKernelGGL((v3::k_fused_u8_v3<NW, MODE, BAND, ARITH>), dim3((nframes + g - 1) / g, BAND ? a.nbands : 1), dim3(NW * g * 64), lds, st, a); \
         break;
     switch (a.nw) {
         SN_LAUNCH(1) SN_LAUNCH(2) SN_LAUNCH(3) SN_LAUNCH(4) SN_LAUNCH(5) SN_LAUNCH(6) SN_LAUNCH(7) SN_LAUNCH(8)
@@ -917,6 +917,10 @@ extern "C" __attribute__((visibility("default"))) int sn_debug_row_cycles(unsign
 #ifdef SN_TU_PLAIN
 hipError_t launch_fused_u8_v3_plain(hipStream_t st, const v3c::Args& a, int nframes, int mode)
 {
+    if (a.arith == SN_ARITH_SSE2) {  // the saturating instances (planes on their own are the sweeps that have them)
+        if (a.nbands > 1) return mode == v3::kPlain ? launch_mode<v3::kPlain, true, 1>(st, a, nframes) : hipErrorInvalidValue;
+        return mode == v3::kPadded ? launch_mode<v3::kPadded, false, 1>(st, a, nframes) : launch_mode<v3::kPlain, false, 1>(st, a, nframes);
+    }
     if (a.nbands > 1) return mode == v3::kPlain ? launch_mode<v3::kPlain, true>(st, a, nframes) : hipErrorInvalidValue;  // only planes on their own are cut
     return mode == v3::kPadded ? launch_mode<v3::kPadded>(st, a, nframes) : launch_mode<v3::kPlain>(st, a, nframes);
 }
@@ -981,6 +985,7 @@ hipError_t launch_fused_u8_v3(hipStream_t st, const PlaneArgs& p, double thresho
 
     a.turn_shift = v3c::turn_shift_for(a.nk, a.nw * v3c::group_of(a.nw), 1);
     a.nframes = nframes;
+    a.arith = p.arith;
     if (!pool) return launch_fused_u8_v3_plain(st, a, nframes, v3::kPlain);
     if (pool->nbands > 1) {
         a.band_rows = pool->band_rows;
@@ -991,6 +996,7 @@ hipError_t launch_fused_u8_v3(hipStream_t st, const PlaneArgs& p, double thresho
         a.band_reset = pool->band_reset;
     }
     if (pool->mode == v3::kPlain) return launch_fused_u8_v3_plain(st, a, nframes, v3::kPlain);
+    if (a.arith != SN_ARITH_CXX && pool->mode != v3::kPadded) return hipErrorInvalidValue;  // the pool-coupled sweeps have no such instances
     a.pool_in = pool->pool_in;
     a.pool_out = pool->pool_out;
     a.pool_frame_stride = pool->frame_stride;

@@ -27,6 +27,7 @@ struct PlaneArgs {
     int32_t enabled;           // processPlane[i] || dh
     const int32_t* guard;      // pool-path kernels: when set, frame f is worked on only if guard[f] != 0 (sn_band.hip)
     int32_t guard_single;      // ... 1: ONE word decides for every frame of the launch (guard[0]; the redo of a chain that timed out)
+    int32_t arith = 0;         // SN_ARITH_*: read by the 8-bit sweeps of planes on their own (the pool kernels take PoolArgs::arith)
 };
 
 // Scratch pool geometry (src/SangNom2.cpp:287-288,305-310), in elements of T.
@@ -40,6 +41,7 @@ struct PoolArgs {
     int32_t rows;              // stage 2 stops before this pool row (0 = bh: the whole pool, as the reference does)
     int32_t slot_step = 0;     // k_prepare / k_finalize: frame f uses slot (slot0 + f * slot_step) % slot_mod
     int32_t slot_mod = 0;      // (0 / 0: slot0 + f)
+    int32_t arith = 0;         // SN_ARITH_*: which instances of the integer kernels run (sn_pixel.h, PxA); float ignores it
 };
 
 // Stage 2 of a history-carrying clip as a chain of passes (one per processed plane and frame, in the reference's

@@ -80,7 +80,7 @@ hipError_t launch_assemble(hipStream_t st, const PlaneArgs& p, int bytes, int nf
 // Shared tap loader: the 14 edge-clamped taps and the four SangNom values of one pixel pair
 // (loadPixel + calculateSangNom, SangNom2.cpp:25-34,60-72,84-103).
 // ------------------------------------------------------------------------------------------------
-template <class T>
+template <class T, int A = 0>
 struct Taps {
     using W = typename Px<T>::W;
     W c[7], n[7];  // index k+3 for tap k = -3..3
@@ -94,10 +94,10 @@ struct Taps {
             c[k + 3] = (W)cl[q];
             n[k + 3] = (W)nl[q];
         }
-        f1 = Px<T>::sg(c[2], c[3], c[4]);
-        f2 = Px<T>::sg(n[4], n[3], n[2]);
-        b1 = Px<T>::sg(c[4], c[3], c[2]);
-        b2 = Px<T>::sg(n[2], n[3], n[4]);
+        f1 = PxA<T, A>::sg(c[2], c[3], c[4]);
+        f2 = PxA<T, A>::sg(n[4], n[3], n[2]);
+        b1 = PxA<T, A>::sg(c[4], c[3], c[2]);
+        b2 = PxA<T, A>::sg(n[2], n[3], n[4]);
     }
 };
 
@@ -110,10 +110,10 @@ __device__ __forceinline__ int64_t slot_of(const PoolArgs& pool, int slot0, int 
     return pool.slot_mod ? s % pool.slot_mod : s;
 }
 
-template <class T>
+template <class T, int A>
 __global__ void __launch_bounds__(256) k_prepare(PlaneArgs p, PoolArgs pool, int slot0)
 {
-    using P = Px<T>;
+    using P = PxA<T, A>;
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     const int y = blockIdx.y;
     const int f = blockIdx.z;
@@ -122,7 +122,7 @@ __global__ void __launch_bounds__(256) k_prepare(PlaneArgs p, PoolArgs pool, int
     const uint8_t* plane = p.dst + (int64_t)f * p.dst_frame_stride;
     const T* cl = reinterpret_cast<const T*>(plane + (int64_t)(p.offset + 2 * y) * p.dst_pitch);
     const T* nl = reinterpret_cast<const T*>(plane + (int64_t)(p.offset + 2 * y + 2) * p.dst_pitch);
-    Taps<T> t;
+    Taps<T, A> t;
     t.load(cl, nl, x, p.w);
     T* pb = reinterpret_cast<T*>(pool.base + slot_of(pool, slot0, f) * pool.slot_bytes);
     const size_t bufsz = (size_t)pool.stride_e * (pool.bh + 1);
@@ -152,10 +152,10 @@ struct alignas(NC * sizeof(T)) SampleVec {
     T v[NC];
 };
 
-template <class T, int NC>
+template <class T, int NC, int A>
 __global__ void __launch_bounds__(kSmoothThreads) k_smooth(PoolArgs pool, int slot0)
 {
-    using P = Px<T>;
+    using P = PxA<T, A>;
     using W = typename P::W;
     using Vec = SampleVec<T, NC>;
     extern __shared__ __align__(16) unsigned char smem[];
@@ -218,6 +218,7 @@ __global__ void __launch_bounds__(kSmoothThreads) k_smooth(PoolArgs pool, int sl
 // the odd-aligned pairs the box needs come from v_alignbit, the box slides (two instructions per further pair), the
 // neighbours' sums arrive as two 8-byte LDS reads instead of six 4-byte ones.  45 vector instructions per 8 columns and
 // row against 79 per 4: stage 2 of one 2160p pool 830 -> 454 us.
+template <int A>
 __global__ void __launch_bounds__(kSmoothThreads) k_smooth_u8x2(PoolArgs pool, int slot0)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -282,7 +283,7 @@ __global__ void __launch_bounds__(kSmoothThreads) k_smooth_u8x2(PoolArgs pool, i
         Row o;
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-            o.v[m] = (T >> 4) & 0x00ff00ffu;  // (sum / 16) wraps to uint8_t, SangNom2.cpp:152; integer sums: any order
+            o.v[m] = box8<A>(T);  // sum / 16 narrowed to uint8_t as the arithmetic A does (sn_pixel.h: wraps, SangNom2.cpp:152, or saturates); integer sums: any order
             if (m < 3) T = (T - O[m] - E[1 + m]) + (E[4 + m] + O[m + 4]);
         }
         uint2 q;
@@ -312,6 +313,7 @@ __global__ void __launch_bounds__(kSmoothThreads) k_smooth_u8x2(PoolArgs pool, i
 // mailbox -- one barrier every five rows instead of one per row, no LDS on the row's critical path.  Waves drift by
 // up to four rows between barriers, and the rows are smoothed IN PLACE: a lane fetches pool row r + 2 + kAhead while it
 // works on row r, i.e. before the wave that owns those columns (at most four rows ahead) can have overwritten it.
+template <int A>
 __global__ void __launch_bounds__(kSmoothThreads) k_smooth_u8_strips(PoolArgs pool, int slot0)
 {
     using namespace v3c;
@@ -391,7 +393,7 @@ __global__ void __launch_bounds__(kSmoothThreads) k_smooth_u8_strips(PoolArgs po
         Row o;
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-            o.v[m] = (T >> 4) & 0x00ff00ffu;  // (sum / 16) wraps to uint8_t, SangNom2.cpp:152; integer sums: any order
+            o.v[m] = box8<A>(T);  // sum / 16 narrowed to uint8_t as the arithmetic A does (sn_pixel.h: wraps, SangNom2.cpp:152, or saturates); integer sums: any order
             if (m < 3) T = (T - O[m] - E[1 + m]) + (E[4 + m] + O[m + 4]);
         }
         if (real) {
@@ -500,7 +502,7 @@ constexpr int kChainLag = 3;
 // Round 3: TWO passes per wave.  A 32-bit register holds column x of one pass in its low half and column x of the pass
 // that follows it in the chain (three blocks behind) in its high half -- the packing of the fused 8-bit sweeps, with two
 // passes where those have two strips -- so one instruction stream smooths a row of each: eight packed registers per lane,
-// three-row sums, DPP for the neighbours, a sliding box, `(sum >> 4) & 0x00ff00ff`.  76 instructions per lane and round
+// three-row sums, DPP for the neighbours, a sliding box, `(sum >> 4) & 0x00ff00ff` (box8<A>).  76 instructions per lane and round
 // row for sixteen columns where the one-pass body took 75 for eight; the workgroup is bound by what its CU issues, so the
 // chain runs twice as fast.  The halves are at different rows of different pool slots: each has its own pointers, fetch
 // ring, fresh-row count, and its loads, stores, ghost refresh and first-rows round are masked per half.  The mailbox is
@@ -550,7 +552,7 @@ __device__ unsigned long long sn_chain_cycles[6];
 #endif
 // THREADS: the launch bound.  The workgroups of a spread chain and short chains (a frame's two or three passes) have eight
 // waves at most and 256 registers each; a long chain on one workgroup per buffer has sixteen waves and 128.
-template <bool GROUPED, int THREADS>
+template <bool GROUPED, int THREADS, int A>
 __global__ void __launch_bounds__(THREADS) k_smooth_u8_chain(PoolArgs pool, ChainArgs ch, int nw, int lanes, int pass_rounds,
                                                                     int cycle)
 {
@@ -769,8 +771,8 @@ __global__ void __launch_bounds__(THREADS) k_smooth_u8_chain(PoolArgs pool, Chai
                 unsigned T4 = ((X[4] + X[5]) + (X[6] + X[7])) + ((X[8] + X[9]) + X[10]);
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    o.v[c] = (T >> 4) & 0x00ff00ffu;  // (sum / 16) wraps to uint8_t, SangNom2.cpp:152; integer sums: any order
-                    o.v[4 + c] = (T4 >> 4) & 0x00ff00ffu;
+                    o.v[c] = box8<A>(T);  // sum / 16 narrowed to uint8_t as the arithmetic A does (sn_pixel.h: wraps, SangNom2.cpp:152, or saturates); integer sums: any order
+                    o.v[4 + c] = box8<A>(T4);
                     if (c < 3) {
                         T = (T - X[c]) + X[c + 7];
                         T4 = (T4 - X[4 + c]) + X[c + 11];
@@ -779,7 +781,7 @@ __global__ void __launch_bounds__(THREADS) k_smooth_u8_chain(PoolArgs pool, Chai
             } else {  // sixteen waves: bound by what the CU issues, three instructions fewer
 #pragma unroll
                 for (int c = 0; c < 8; ++c) {
-                    o.v[c] = (T >> 4) & 0x00ff00ffu;
+                    o.v[c] = box8<A>(T);
                     if (c < 7) T = (T - X[c]) + X[c + 7];
                 }
             }
@@ -859,7 +861,7 @@ extern "C" __attribute__((visibility("default"))) int sn_debug_chain_cycles(unsi
 // workgroups per buffer as k_smooth_u8_chain<true> -- with one pass per wave a workgroup of sixteen waves only holds
 // 16 / nw passes, so here the workgroups ADD slots (up to the sixteen the lag of three rounds can use) before they
 // shorten the rounds.
-template <bool GROUPED>
+template <bool GROUPED, int A>
 __global__ void __launch_bounds__(kSmoothThreads) k_smooth_u16_chain(PoolArgs pool, ChainArgs ch, int nw, int lanes, int pass_rounds,
                                                                     int cycle)
 {
@@ -982,7 +984,7 @@ __global__ void __launch_bounds__(kSmoothThreads) k_smooth_u16_chain(PoolArgs po
                 Row o;
 #pragma unroll
                 for (int m = 0; m < 8; ++m) {
-                    o.v[m] = (T >> 4) & 0xffffu;
+                    o.v[m] = box16<A>(T);
                     if (m < 7) T = (T - X[m]) + X[m + 7];
                 }
                 {
@@ -1166,6 +1168,7 @@ __global__ void __launch_bounds__(kSmoothThreads) k_smooth_f32_chain(PoolArgs po
 // bits), a sliding box (two instructions per further column instead of three three-operand adds), one 16-byte row
 // access and two 16-byte LDS reads per thread and row: 55 vector instructions per 8 columns against 79 per 4
 // (one 2160p pool 830 -> 613 us).
+template <int A>
 __global__ void __launch_bounds__(kSmoothThreads) k_smooth_u16x8(PoolArgs pool, int slot0)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -1225,7 +1228,7 @@ __global__ void __launch_bounds__(kSmoothThreads) k_smooth_u16x8(PoolArgs pool, 
         Row o;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            o.v[k] = (T >> 4) & 0xffffu;  // (sum / 16) wraps to uint16_t, SangNom2.cpp:152; integer sums: any order
+            o.v[k] = box16<A>(T);  // sum / 16 narrowed to uint16_t as the arithmetic A does (sn_pixel.h: wraps, SangNom2.cpp:152, or saturates); integer sums: any order
             if (k < 7) T = (T - X[k]) + X[k + 7];
         }
         uint4 q;
@@ -1252,6 +1255,7 @@ __global__ void __launch_bounds__(kSmoothThreads) k_smooth_u16x8(PoolArgs pool, 
 
 // 9..16-bit pools of 512 columns and more in strips, as k_smooth_u8_strips: 60 lanes x 8 columns per wave, one 32-bit
 // sum per register, the three sums on either side over DPP, ghost lanes refreshed from the mailbox every K rows.
+template <int A>
 __global__ void __launch_bounds__(kSmoothThreads) k_smooth_u16_strips(PoolArgs pool, int slot0)
 {
     using namespace v3c;
@@ -1328,7 +1332,7 @@ __global__ void __launch_bounds__(kSmoothThreads) k_smooth_u16_strips(PoolArgs p
         Row o;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            o.v[k] = (T >> 4) & 0xffffu;  // (sum / 16) wraps to uint16_t, SangNom2.cpp:152; integer sums: any order
+            o.v[k] = box16<A>(T);  // sum / 16 narrowed to uint16_t as the arithmetic A does (sn_pixel.h: wraps, SangNom2.cpp:152, or saturates); integer sums: any order
             if (k < 7) T = (T - X[k]) + X[k + 7];
         }
         if (real) {
@@ -1566,10 +1570,10 @@ __global__ void __launch_bounds__(kSmoothThreads) k_smooth_f32_strips(PoolArgs p
     }
 }
 
-template <class T, int NC>
+template <class T, int NC, int A>
 __global__ void __launch_bounds__(kSmoothThreads) k_smooth_strided(PoolArgs pool, int slot0)
 {
-    using P = Px<T>;
+    using P = PxA<T, A>;
     using W = typename P::W;
     extern __shared__ __align__(16) unsigned char smem[];
     const int se = pool.stride_e;
@@ -1634,11 +1638,11 @@ __global__ void __launch_bounds__(kSmoothThreads) k_smooth_strided(PoolArgs pool
 // ------------------------------------------------------------------------------------------------
 // Stage 3: finalizePlane_c, SangNom2.cpp:161-257.  One thread per interpolated pixel.
 // ------------------------------------------------------------------------------------------------
-template <class T>
+template <class T, int A>
 __global__ void __launch_bounds__(256)
 k_finalize(PlaneArgs p, PoolArgs pool, int slot0, typename Px<T>::W thr)
 {
-    using P = Px<T>;
+    using P = PxA<T, A>;
     using W = typename P::W;
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     const int y = blockIdx.y;
@@ -1649,7 +1653,7 @@ k_finalize(PlaneArgs p, PoolArgs pool, int slot0, typename Px<T>::W thr)
     const T* cl = reinterpret_cast<const T*>(plane + (int64_t)(p.offset + 2 * y) * p.dst_pitch);
     const T* nl = reinterpret_cast<const T*>(plane + (int64_t)(p.offset + 2 * y + 2) * p.dst_pitch);
     T* ol = reinterpret_cast<T*>(plane + (int64_t)(p.offset + 2 * y + 1) * p.dst_pitch);
-    Taps<T> t;
+    Taps<T, A> t;
     t.load(cl, nl, x, p.w);
     const T* pb = reinterpret_cast<const T*>(pool.base + slot_of(pool, slot0, f) * pool.slot_bytes);
     const size_t bufsz = (size_t)pool.stride_e * (pool.bh + 1);
@@ -1673,7 +1677,7 @@ k_finalize(PlaneArgs p, PoolArgs pool, int slot0, typename Px<T>::W thr)
     ol[x] = (T)r;
 }
 
-template <class T>
+template <class T, int A>
 static hipError_t launch_pool_plane_t(hipStream_t st, const PlaneArgs& p, const PoolArgs& pool,
                                       double threshold, int nframes, int slot0)
 {
@@ -1681,27 +1685,27 @@ static hipError_t launch_pool_plane_t(hipStream_t st, const PlaneArgs& p, const 
     const int nr = p.h_out / 2 - 1;
     if (nr > 0) {
         dim3 grid((p.w + 255) / 256, nr, nframes), block(256);
-        hipLaunchKernelGGL(k_prepare<T>, grid, block, 0, st, p, pool, slot0);
+        hipLaunchKernelGGL((k_prepare<T, A>), grid, block, 0, st, p, pool, slot0);
     }
     if (std::is_same<T, uint8_t>::value && pool.bh > 1 && pool.stride_e >= 512 && v3c::strips_for(pool.stride_e / 8) <= kSmoothThreads / 64) {
         const int nw = v3c::strips_for(pool.stride_e / 8);
         const size_t lds = (size_t)2 * nw * 2 * v3c::GH * 4 * sizeof(unsigned);
-        hipLaunchKernelGGL(k_smooth_u8_strips, dim3(kBuffers, nframes), dim3(nw * 64), lds, st, pool, slot0);
+        hipLaunchKernelGGL(k_smooth_u8_strips<A>, dim3(kBuffers, nframes), dim3(nw * 64), lds, st, pool, slot0);
     } else if (std::is_same<T, uint8_t>::value && pool.bh > 1 && pool.stride_e >= 256 && pool.stride_e <= 8 * kSmoothThreads) {
         const int threads = ((pool.stride_e / 8) + 63) / 64 * 64;
         const size_t lds = (size_t)2 * (pool.stride_e / 8) * sizeof(uint4);
-        hipLaunchKernelGGL(k_smooth_u8x2, dim3(kBuffers, nframes), dim3(threads), lds, st, pool, slot0);
+        hipLaunchKernelGGL(k_smooth_u8x2<A>, dim3(kBuffers, nframes), dim3(threads), lds, st, pool, slot0);
     } else if (std::is_same<T, uint16_t>::value && pool.bh > 1 && pool.stride_e >= 512 && v3c::strips_for(pool.stride_e / 8) <= kSmoothThreads / 64) {
         const int nw = v3c::strips_for(pool.stride_e / 8);
         const size_t lds = (size_t)2 * nw * 2 * v3c::GH * 8 * sizeof(unsigned);
-        hipLaunchKernelGGL(k_smooth_u16_strips, dim3(kBuffers, nframes), dim3(nw * 64), lds, st, pool, slot0);
+        hipLaunchKernelGGL(k_smooth_u16_strips<A>, dim3(kBuffers, nframes), dim3(nw * 64), lds, st, pool, slot0);
     } else if (std::is_same<T, uint16_t>::value && pool.bh > 1 && pool.stride_e >= 256 && pool.stride_e <= 8 * kSmoothThreads) {
         const int threads = ((pool.stride_e / 8) + 63) / 64 * 64;
         const size_t lds = (size_t)2 * 2 * (pool.stride_e / 8) * sizeof(uint4);
         hipError_t e = hipSuccess;
-        if (lds > 48 * 1024) e = hipFuncSetAttribute((const void*)k_smooth_u16x8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (lds > 48 * 1024) e = hipFuncSetAttribute((const void*)k_smooth_u16x8<A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_smooth_u16x8, dim3(kBuffers, nframes), dim3(threads), lds, st, pool, slot0);
+        hipLaunchKernelGGL(k_smooth_u16x8<A>, dim3(kBuffers, nframes), dim3(threads), lds, st, pool, slot0);
     } else if (std::is_same<T, float>::value && pool.bh > 1 && pool.stride_e >= 512 && v3c::strips_for(pool.stride_e / 8) <= kSmoothThreads / 64 &&
                nframes <= 8) {
         // launches of more frames are bound by HBM, where the ghost lanes' second fetch of the seam columns costs more
@@ -1729,12 +1733,12 @@ static hipError_t launch_pool_plane_t(hipStream_t st, const PlaneArgs& p, const 
 #define SN_SMOOTH(NC)                                                                              \
     do {                                                                                           \
         if (lds > 48 * 1024)                                                                       \
-            e = hipFuncSetAttribute((const void*)k_smooth<T, NC>,                                  \
+            e = hipFuncSetAttribute((const void*)k_smooth<T, NC, A>,                                  \
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);         \
-        if (e == hipSuccess) hipLaunchKernelGGL((k_smooth<T, NC>), grid, block, lds, st, pool, slot0); \
+        if (e == hipSuccess) hipLaunchKernelGGL((k_smooth<T, NC, A>), grid, block, lds, st, pool, slot0); \
     } while (0)
         if (nc <= 1) {
-            if (e == hipSuccess) hipLaunchKernelGGL((k_smooth_strided<T, 1>), grid, dim3(kSmoothThreads), lds, st, pool, slot0);
+            if (e == hipSuccess) hipLaunchKernelGGL((k_smooth_strided<T, 1, A>), grid, dim3(kSmoothThreads), lds, st, pool, slot0);
         } else if (nc <= 2) SN_SMOOTH(2);
         else if (nc <= 4) SN_SMOOTH(4);
         else SN_SMOOTH(8);
@@ -1745,7 +1749,7 @@ static hipError_t launch_pool_plane_t(hipStream_t st, const PlaneArgs& p, const 
         dim3 grid((p.w + 255) / 256, nr, nframes), block(256);
         W thr;
         if constexpr (sizeof(T) == 4) thr = (float)threshold; else thr = (W)threshold;
-        hipLaunchKernelGGL(k_finalize<T>, grid, block, 0, st, p, pool, slot0, thr);
+        hipLaunchKernelGGL((k_finalize<T, A>), grid, block, 0, st, p, pool, slot0, thr);
     }
     return hipGetLastError();
 }
@@ -1759,15 +1763,15 @@ int pool_chain_lanes(int bytes, int stride_e)
     return nw <= kSmoothThreads / 128 ? kSmoothThreads / 64 / nw : 0;                     // at least two passes in flight
 }
 
-template <class T>
+template <class T, int A>
 static hipError_t launch_pool_prepare_t(hipStream_t st, const PlaneArgs& p, const PoolArgs& pool, int nframes, int slot0)
 {
     const int nr = p.h_out / 2 - 1;
-    if (nr > 0) hipLaunchKernelGGL(k_prepare<T>, dim3((p.w + 255) / 256, nr, nframes), dim3(256), 0, st, p, pool, slot0);
+    if (nr > 0) hipLaunchKernelGGL((k_prepare<T, A>), dim3((p.w + 255) / 256, nr, nframes), dim3(256), 0, st, p, pool, slot0);
     return hipGetLastError();
 }
 
-template <class T>
+template <class T, int A>
 static hipError_t launch_pool_finalize_t(hipStream_t st, const PlaneArgs& p, const PoolArgs& pool, double threshold, int nframes,
                                          int slot0)
 {
@@ -1775,16 +1779,16 @@ static hipError_t launch_pool_finalize_t(hipStream_t st, const PlaneArgs& p, con
     const int nr = p.h_out / 2 - 1;
     W thr;
     if constexpr (sizeof(T) == 4) thr = (float)threshold; else thr = (W)threshold;
-    if (nr > 0) hipLaunchKernelGGL(k_finalize<T>, dim3((p.w + 255) / 256, nr, nframes), dim3(256), 0, st, p, pool, slot0, thr);
+    if (nr > 0) hipLaunchKernelGGL((k_finalize<T, A>), dim3((p.w + 255) / 256, nr, nframes), dim3(256), 0, st, p, pool, slot0, thr);
     return hipGetLastError();
 }
 
 hipError_t launch_pool_prepare(hipStream_t st, const PlaneArgs& p, const PoolArgs& pool, int bytes, int nframes, int slot0)
 {
     switch (bytes) {
-    case 1: return launch_pool_prepare_t<uint8_t>(st, p, pool, nframes, slot0);
-    case 2: return launch_pool_prepare_t<uint16_t>(st, p, pool, nframes, slot0);
-    case 4: return launch_pool_prepare_t<float>(st, p, pool, nframes, slot0);
+    case 1: return pool.arith ? launch_pool_prepare_t<uint8_t, 1>(st, p, pool, nframes, slot0) : launch_pool_prepare_t<uint8_t, 0>(st, p, pool, nframes, slot0);
+    case 2: return pool.arith ? launch_pool_prepare_t<uint16_t, 1>(st, p, pool, nframes, slot0) : launch_pool_prepare_t<uint16_t, 0>(st, p, pool, nframes, slot0);
+    case 4: return launch_pool_prepare_t<float, 0>(st, p, pool, nframes, slot0);  // float: one arithmetic
     }
     return hipErrorInvalidValue;
 }
@@ -1793,9 +1797,9 @@ hipError_t launch_pool_finalize(hipStream_t st, const PlaneArgs& p, const PoolAr
                                 int slot0)
 {
     switch (bytes) {
-    case 1: return launch_pool_finalize_t<uint8_t>(st, p, pool, threshold, nframes, slot0);
-    case 2: return launch_pool_finalize_t<uint16_t>(st, p, pool, threshold, nframes, slot0);
-    case 4: return launch_pool_finalize_t<float>(st, p, pool, threshold, nframes, slot0);
+    case 1: return pool.arith ? launch_pool_finalize_t<uint8_t, 1>(st, p, pool, threshold, nframes, slot0) : launch_pool_finalize_t<uint8_t, 0>(st, p, pool, threshold, nframes, slot0);
+    case 2: return pool.arith ? launch_pool_finalize_t<uint16_t, 1>(st, p, pool, threshold, nframes, slot0) : launch_pool_finalize_t<uint16_t, 0>(st, p, pool, threshold, nframes, slot0);
+    case 4: return launch_pool_finalize_t<float, 0>(st, p, pool, threshold, nframes, slot0);
     }
     return hipErrorInvalidValue;
 }
@@ -1855,20 +1859,16 @@ hipError_t launch_pool_chain(hipStream_t st, const PoolArgs& pool, const ChainAr
     const int sets = bytes == 1 ? lanes / 2 : lanes;  // sets of nw waves (8-bit: a set carries two passes)
     const size_t lds = (size_t)sets * 2 * nw * 2 * v3c::GH * 8 * sizeof(unsigned);
     const dim3 grid(kBuffers * groups, nchains), block(sets * nw * 64);
-    if (bytes == 4 && groups > 1)
-        hipLaunchKernelGGL(k_smooth_f32_chain<true>, grid, block, lds, st, pool, chain, nw, lanes, pass_rounds, cycle);
-    else if (bytes == 4)
-        hipLaunchKernelGGL(k_smooth_f32_chain<false>, grid, block, lds, st, pool, chain, nw, lanes, pass_rounds, cycle);
-    else if (bytes == 2 && groups > 1)
-        hipLaunchKernelGGL(k_smooth_u16_chain<true>, grid, block, lds, st, pool, chain, nw, lanes, pass_rounds, cycle);
-    else if (bytes == 2)
-        hipLaunchKernelGGL(k_smooth_u16_chain<false>, grid, block, lds, st, pool, chain, nw, lanes, pass_rounds, cycle);
-    else if (groups > 1)
-        hipLaunchKernelGGL((k_smooth_u8_chain<true, kChain8Threads / 2>), grid, block, lds, st, pool, chain, nw, lanes, pass_rounds, cycle);
-    else if ((int)block.x <= kChain8Threads / 2)
-        hipLaunchKernelGGL((k_smooth_u8_chain<false, kChain8Threads / 2>), grid, block, lds, st, pool, chain, nw, lanes, pass_rounds, cycle);
-    else
-        hipLaunchKernelGGL((k_smooth_u8_chain<false, kChain8Threads>), grid, block, lds, st, pool, chain, nw, lanes, pass_rounds, cycle);
+    const bool sat = pool.arith != 0;  // SN_ARITH_SSE2: the saturating box (integer types only)
+#define SN_CHAIN(K) hipLaunchKernelGGL(K, grid, block, lds, st, pool, chain, nw, lanes, pass_rounds, cycle)
+    if (bytes == 4 && groups > 1) SN_CHAIN(k_smooth_f32_chain<true>);
+    else if (bytes == 4) SN_CHAIN(k_smooth_f32_chain<false>);
+    else if (bytes == 2 && groups > 1) { if (sat) SN_CHAIN((k_smooth_u16_chain<true, 1>)); else SN_CHAIN((k_smooth_u16_chain<true, 0>)); }
+    else if (bytes == 2) { if (sat) SN_CHAIN((k_smooth_u16_chain<false, 1>)); else SN_CHAIN((k_smooth_u16_chain<false, 0>)); }
+    else if (groups > 1) { if (sat) SN_CHAIN((k_smooth_u8_chain<true, kChain8Threads / 2, 1>)); else SN_CHAIN((k_smooth_u8_chain<true, kChain8Threads / 2, 0>)); }
+    else if ((int)block.x <= kChain8Threads / 2) { if (sat) SN_CHAIN((k_smooth_u8_chain<false, kChain8Threads / 2, 1>)); else SN_CHAIN((k_smooth_u8_chain<false, kChain8Threads / 2, 0>)); }
+    else { if (sat) SN_CHAIN((k_smooth_u8_chain<false, kChain8Threads, 1>)); else SN_CHAIN((k_smooth_u8_chain<false, kChain8Threads, 0>)); }
+#undef SN_CHAIN
     return hipGetLastError();
 }
 
@@ -1876,9 +1876,9 @@ hipError_t launch_pool_plane(hipStream_t st, const PlaneArgs& p, const PoolArgs&
                              double threshold, int nframes, int slot0)
 {
     switch (bytes) {
-    case 1: return launch_pool_plane_t<uint8_t>(st, p, pool, threshold, nframes, slot0);
-    case 2: return launch_pool_plane_t<uint16_t>(st, p, pool, threshold, nframes, slot0);
-    default: return launch_pool_plane_t<float>(st, p, pool, threshold, nframes, slot0);
+    case 1: return pool.arith ? launch_pool_plane_t<uint8_t, 1>(st, p, pool, threshold, nframes, slot0) : launch_pool_plane_t<uint8_t, 0>(st, p, pool, threshold, nframes, slot0);
+    case 2: return pool.arith ? launch_pool_plane_t<uint16_t, 1>(st, p, pool, threshold, nframes, slot0) : launch_pool_plane_t<uint16_t, 0>(st, p, pool, threshold, nframes, slot0);
+    default: return launch_pool_plane_t<float, 0>(st, p, pool, threshold, nframes, slot0);  // float: one arithmetic
     }
 }
 

@@ -68,7 +68,8 @@ class SangNom2:
                  host_depth: int = 0, isolated_planes: bool = False, fresh_pool: bool = False,
                  small_launches: int | None = None, chain: int | None = None, copy_threads: int | None = None,
                  scratch_budget_mb: int | None = None, chroma_sweeps: int | None = None):
-        # `threads` is a dummy in the reference (README.md:40-41); `opt` picks its CPU code path.
+        # `threads` is a dummy in the reference (README.md:40-41); `opt` picks its CPU code path, and with it the
+        # arithmetic: opt=1 reproduces its SSE2 path (SN_ARITH_SSE2), opt=0 and opt=-1 its C++ path.
         if opt < -1 or opt > 1:
             raise SangNomError(capi.SN_ERR_CONFIG, "SangNom2: opt must be between -1..2.")  # sic, SangNom2.cpp:420
         self.clip = clip
@@ -87,7 +88,9 @@ class SangNom2:
         # at most that many workgroups per cost buffer
         pol = capi.policy(small_launches=small_launches, chain=chain, copy_threads=copy_threads, scratch_budget_mb=scratch_budget_mb,
                           chroma_sweeps=chroma_sweeps)
-        rc = self._lib.sn_create_with_policy(ctypes.byref(cfg), ctypes.byref(pol), ctypes.byref(self._h))
+        self.arithmetic = capi.arithmetic_of_opt(opt)
+        opts = capi.options(self.arithmetic)
+        rc = self._lib.sn_create_ex(ctypes.byref(cfg), ctypes.byref(pol), ctypes.byref(opts), ctypes.byref(self._h))
         if rc != capi.SN_OK:
             self._h = None
             raise SangNomError(rc, self._lib.sn_last_error(None).decode())
@@ -348,7 +351,9 @@ class SangNomAAHost:
     SangNomAA (host/sangnom2_avs_plugin.cpp) binds."""
 
     def __init__(self, clip: ClipFormat, order: int = 1, aa: int = 48, aac: int = 0, luma: bool = True, chroma: bool = True,
-                 device: int = 0, isolated_planes: bool = False, fresh_pool: bool = False, **policy_kw):
+                 device: int = 0, isolated_planes: bool = False, fresh_pool: bool = False, opt: int = -1, **policy_kw):
+        if opt < -1 or opt > 1:
+            raise SangNomError(capi.SN_ERR_CONFIG, "SangNom2: opt must be between -1..2.")  # sic, SangNom2.cpp:420
         self.clip = clip
         self._lib = capi.load()
         cfg = capi.SnConfig(
@@ -358,7 +363,8 @@ class SangNomAAHost:
             isolated_planes=int(isolated_planes), fresh_pool=int(fresh_pool), stream=None)
         self._h = ctypes.c_void_p()
         pol = capi.policy(**{k: policy_kw.get(k) for k in ("small_launches", "chain", "copy_threads", "scratch_budget_mb")})
-        rc = self._lib.sn_aa_create_with_policy(ctypes.byref(cfg), ctypes.byref(pol), ctypes.byref(self._h))
+        opts = capi.options(capi.arithmetic_of_opt(opt))
+        rc = self._lib.sn_aa_create_ex(ctypes.byref(cfg), ctypes.byref(pol), ctypes.byref(opts), ctypes.byref(self._h))
         if rc != capi.SN_OK:
             self._h = None
             raise SangNomError(rc, self._lib.sn_aa_last_error(None).decode())

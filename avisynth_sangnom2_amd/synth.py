@@ -8,6 +8,8 @@ Patterns:
   checker  hard 0/max checker ((x//5 + y//3) & 1)  (maximises wrap in stage 2)
   sine     smooth diagonal sinusoid (typical anti-aliasing input)
   edges    noise-modulated slanted edges (exercises every direction of the ladder)
+  checker2 hard 0/max checker of 2x2 blocks, shifted by the seed   } on these the reference's SSE2 path (saturating)
+  noise01  every sample 0 or max, at random                         } and its C++ path (wrapping) differ most
 """
 from __future__ import annotations
 
@@ -39,7 +41,11 @@ def plane(h: int, w: int, bytes: int = 1, bits: int = 8, pattern: str = "noise",
         if bytes == 4:
             return ((r >> np.uint64(40)).astype(np.float32) * np.float32(1.0 / (1 << 24))).astype(np.float32)
         return (r % np.uint64(maxv + 1)).astype({1: np.uint8, 2: np.uint16}[bytes])
-    if pattern == "checker":
+    if pattern == "noise01":
+        return (((r >> np.uint64(33)) & np.uint64(1)).astype(np.float64) * maxv).astype({1: np.uint8, 2: np.uint16, 4: np.float32}[bytes])
+    if pattern == "checker2":
+        v = (((x // 2 + y // 2 + seed) & 1) * maxv)
+    elif pattern == "checker":
         v = (((x // 5 + y // 3) & 1) * maxv)
     elif pattern == "sine":
         v = (0.5 + 0.5 * np.sin((x * 0.043 + y * 0.071) + seed)) * maxv

@@ -33,7 +33,7 @@ struct Args {  // SangNom2(clip, order, aa, aac, threads, dh, luma, chroma, opt)
     bool dh = false;
     bool luma = true;
     bool chroma = true;
-    int opt = -1;     // the reference's CPU code-path switch; validated, otherwise unused
+    int opt = -1;     // the reference's CPU code-path switch: 1 = its SSE2 arithmetic (SN_ARITH_SSE2), 0 and -1 = its C++ arithmetic
     int device = 0;   // HIP device ordinal (not a script argument)
     int lookahead = -1;  // frames in flight behind GetFrame; -1: $SANGNOM_LOOKAHEAD or 1 (synchronous)
     bool isolated = false;  // extension: every plane filtered as a Y clip of its own (sn_config.isolated_planes)
@@ -91,7 +91,10 @@ public:
         c.fresh_pool = a.fresh ? 1 : 0;
         sn_policy pol = a.policy;
         pol.struct_size = (int32_t)sizeof pol;
-        const int rc = sn_create_with_policy(&c, &pol, &ctx_);
+        sn_options opts{};
+        opts.struct_size = (int32_t)sizeof opts;
+        opts.arithmetic = a.opt == 1 ? SN_ARITH_SSE2 : SN_ARITH_CXX;
+        const int rc = sn_create_ex(&c, &pol, &opts, &ctx_);
         if (rc != SN_OK) env->ThrowError("%s: %s", name, sn_last_error(nullptr));
         if (a.dh) Host::SetHeight(vi_, Host::Height(vi_) * 2);  // src/SangNom2.cpp:284-285
         planes_ = c.num_planes;
@@ -260,7 +263,10 @@ public:
         c.fresh_pool = a.fresh ? 1 : 0;
         sn_policy pol = a.policy;
         pol.struct_size = (int32_t)sizeof pol;
-        if (sn_aa_create_with_policy(&c, &pol, &ctx_) != SN_OK) env->ThrowError("%s: %s", name, sn_aa_last_error(nullptr));
+        sn_options opts{};
+        opts.struct_size = (int32_t)sizeof opts;
+        opts.arithmetic = a.opt == 1 ? SN_ARITH_SSE2 : SN_ARITH_CXX;
+        if (sn_aa_create_ex(&c, &pol, &opts, &ctx_) != SN_OK) env->ThrowError("%s: %s", name, sn_aa_last_error(nullptr));
         planes_ = c.num_planes;
         alpha_ = Host::NumComponents(vi_) == 4;
     }

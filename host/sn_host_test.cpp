@@ -8,6 +8,7 @@
 // planes = 4 in the header is a YUVA clip: the fourth plane is luma-sized and passed through.
 // in.bin : 14 x int32 {w,h,bytes,bits,planes,subw,subh,order,aa,aac,dh,luma,chroma,nframes}, then per
 //          frame: int32 parity + the planes, tightly packed.
+// SN_HOST_TEST_OPT=<-1|0|1> in the environment of this TEST program is the script argument `opt` (default -1).
 // out.bin: per frame the output planes, tightly packed.  On a constructor error: exit code 3 and
 //          the message on stdout.
 #include <cstdio>
@@ -66,6 +67,7 @@ int main(int argc, char** argv)
     // the test clips are small: SN_HOST_TEST_SWEEPS=1 (read by this TEST program, the library reads no environment) asks
     // for the whole-plane sweeps instead of the small-launch paths
     if (const char* e = getenv("SN_HOST_TEST_SWEEPS")) a.policy.small_launches = atoi(e) ? SN_SMALL_SWEEP : SN_SMALL_AUTO;
+    if (const char* e = getenv("SN_HOST_TEST_OPT")) a.opt = atoi(e);
     const bool aa_idiom = argc > 3 && strcmp(argv[3], "aa") == 0;
     if (argc > 3 && !aa_idiom) a.lookahead = atoi(argv[3]);
     std::vector<int> order;

@@ -19,6 +19,8 @@
  * Results are bit-exact to the reference's opt=0 path for 8..16-bit integer formats and for
  * 32-bit float, under the conventions that make the reference's output defined
  * (zero-filled scratch pool, one context == one filter instance, frames in call order).
+ * With sn_options.arithmetic = SN_ARITH_SSE2 (sn_create_ex) they are bit-exact to its opt=1 path
+ * instead -- what its default opt=-1 computes on every x86-64 host.
  *
  * There is NO CPU fallback: every entry point that computes needs a HIP device and fails with
  * SN_ERR_NO_DEVICE / SN_ERR_HIP otherwise.
@@ -116,6 +118,31 @@ typedef struct sn_policy {
     int32_t reserved[2];        /* zero                                                                            */
 } sn_policy;
 
+/* What a context computes (sn_create_ex), as opposed to how (sn_policy).  Fixed for the context's life.
+ * The reference has two code paths that do not give the same pixels for integer samples: its C++ path (opt=0)
+ * wraps modulo 2^(8 sizeof T) in two narrowing steps where its SSE2 path (opt=1, and opt=-1 on every x86-64 host)
+ * saturates to the container's maximum MAXT (255; 65535 for every 9..16-bit depth):
+ *   the SangNom value (4 p1 + 5 p2 - p3) >> 3    SSE2: MAXT if the sum is negative or the value exceeds MAXT
+ *                                                (src/SangNom2_SSE2.cpp:446-516, used by stages 1 and 3)
+ *   the box of stage 2, sum / 16                 SSE2: min(sum >> 4, MAXT)   (src/SangNom2_SSE2.cpp:748-761)
+ * Everything else, and all of float, is the same.  SN_ARITH_CXX is this library's default and what sn_create /
+ * sn_create_with_policy give.  Which kernels run in SN_ARITH_SSE2: 8-bit planes on their own (Y8, 4:4:4, isolated_planes,
+ * fresh_pool) have fused sweeps in this arithmetic and are served as in the default one (sn_info.fused_eligible = 1,
+ * SN_MODE_FUSED accepted); 8-bit clips whose subsampled chroma shares the luma pool (4:2:0, 4:2:2) and every 9..16-bit
+ * clip run on the pool path -- the sweeps they use by default have no instances of this arithmetic, so
+ * sn_info.fused_eligible is 0 and SN_MODE_FUSED fails at creation; float clips run as ever.  Every processed plane
+ * must be at least two SSE2 vectors wide -- 32 / 16 / 8 samples for 8-bit / 16-bit / float, where the reference's SSE2
+ * path reads outside the row below that -- else SN_ERR_UNSUPPORTED. */
+enum {
+    SN_ARITH_CXX = 0,   /* the reference's opt=0                                              */
+    SN_ARITH_SSE2 = 1   /* the reference's opt=1 (its default on x86-64)                      */
+};
+typedef struct sn_options {
+    int32_t struct_size;   /* = sizeof(sn_options)                                           */
+    int32_t arithmetic;    /* SN_ARITH_*                                                     */
+    int32_t reserved[6];   /* zero                                                           */
+} sn_options;
+
 /* Geometry and counters of a live context. */
 typedef struct sn_info {
     int32_t struct_size;
@@ -154,6 +181,10 @@ int sn_validate(const sn_config* cfg, char* msg, size_t msg_len);
  * device pool (zero-filled), stream.  Runs sn_validate first. */
 int sn_create(const sn_config* cfg, sn_context** out);
 int sn_create_with_policy(const sn_config* cfg, const sn_policy* policy /* NULL = defaults */, sn_context** out);
+/* ... with options (NULL, or arithmetic = SN_ARITH_CXX: exactly sn_create_with_policy). */
+int sn_create_ex(const sn_config* cfg, const sn_policy* policy /* NULL = defaults */, const sn_options* options /* NULL = defaults */,
+                 sn_context** out);
+int sn_get_arithmetic(sn_context* ctx); /* SN_ARITH_* of a live context; -1 for NULL */
 void sn_destroy(sn_context* ctx);
 
 /* The policy in force / a new one (small_launches, chain, copy_threads and chroma_sweeps may change during a context's life; the
@@ -251,6 +282,7 @@ int sn_turn_device(sn_context* ctx, int32_t direction, int32_t nframes, const vo
 typedef struct sn_aa_context sn_aa_context;
 int sn_aa_create(const sn_config* cfg, sn_aa_context** out);
 int sn_aa_create_with_policy(const sn_config* cfg, const sn_policy* policy /* NULL = defaults; both passes */, sn_aa_context** out);
+int sn_aa_create_ex(const sn_config* cfg, const sn_policy* policy, const sn_options* options /* both passes */, sn_aa_context** out);
 int sn_aa_process_host(sn_aa_context* ctx, const void* const src[3], const int32_t src_pitch[3], void* const dst[3],
                        const int32_t dst_pitch[3], int32_t parity);
 const char* sn_aa_last_error(const sn_aa_context* ctx); /* ctx == NULL: last failed sn_aa_create on this thread */

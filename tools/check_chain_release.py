@@ -47,6 +47,9 @@ def kernels(text):
     return found
 
 
+# GROUPED instances per kernel template: the integer kernels exist in both arithmetics (SN_ARITH_CXX, SN_ARITH_SSE2), float in one
+EXPECTED = {"k_smooth_u8_chain": 2, "k_smooth_u16_chain": 2, "k_smooth_f32_chain": 1}
+
 VMEM = ("buffer_", "global_", "flat_", "scratch_")
 
 
@@ -70,18 +73,25 @@ def uncovered(code):
 def main():
     path = sys.argv[1] if len(sys.argv) > 1 else disassemble()
     ks = kernels(open(path).read())
-    if len(ks) < 3:
-        print("expected the three grouped chain kernels, found", sorted(ks))
+    # one line per kernel template: its instances (launch bounds, SN_ARITH_* arithmetic) are checked one by one and reported together
+    families, rc = {}, 0
+    for name in sorted(ks):
+        m = re.match(r"_ZN2sn\d+(k_smooth_\w+?_chain)ILb1E", name)
+        if not m:
+            print("a grouped chain kernel whose name this tool cannot read:", name)
+            return 1
+        families.setdefault(m.group(1), []).append(name)
+    found = {f: len(n) for f, n in families.items()}
+    if found != EXPECTED:
+        print("expected the grouped chain instances", EXPECTED, "and found", found, "::", sorted(ks))
         return 1
-    rc = 0
-    for name, code in sorted(ks.items()):
-        bars = sum(1 for c in code if c.startswith("s_barrier"))
-        bad = uncovered(code)
-        loop_bad = bad  # (these kernels have ONE barrier, at the head of the round loop; any other must be covered too)
-        print(f"{name}: {bars} s_barrier, {len(loop_bad)} without a preceding s_waitcnt vmcnt(0)")
-        for i, ctx in loop_bad:
+    for family, names in sorted(families.items()):
+        bars = sum(1 for n in names for c in ks[n] if c.startswith("s_barrier"))
+        bad = [(n, i, ctx) for n in names for i, ctx in uncovered(ks[n])]  # (these kernels have ONE barrier, at the head of the round loop; any other must be covered too)
+        print(f"{family}<true>, {len(names)} instance(s): {bars} s_barrier, {len(bad)} without a preceding s_waitcnt vmcnt(0)")
+        for n, i, ctx in bad:
             rc = 1
-            print("   at instruction", i, "::", " | ".join(ctx))
+            print("   ", n, "at instruction", i, "::", " | ".join(ctx))
     return rc
 
 
