@@ -28,6 +28,8 @@ EXPORTS = (
     "sn_create_with_policy", "sn_get_policy", "sn_set_policy", "sn_aa_create_with_policy",
     "sn_debug_raise_chain_fault",
     "sn_create_ex", "sn_aa_create_ex", "sn_get_arithmetic",
+    "sn_aa_process_device_strided", "sn_aa_synchronize", "sn_aa_get_stream", "sn_aa_get_info",
+    "sn_aa_host_slots", "sn_aa_submit_host", "sn_aa_collect_host",
 )
 
 # sn_options.arithmetic: which of the reference's two code paths a context reproduces (sangnom_hip.h)
@@ -162,5 +164,13 @@ def load():
     L.sn_aa_last_error.restype = ctypes.c_char_p
     L.sn_aa_destroy.argtypes = [vp]
     L.sn_aa_destroy.restype = None
+    L.sn_aa_process_device_strided.argtypes = [vp, i32, p3v, p3l, p3i, p3v, p3l, p3i, p3i]
+    L.sn_aa_synchronize.argtypes = [vp]
+    L.sn_aa_get_stream.argtypes = [vp]
+    L.sn_aa_get_stream.restype = vp
+    L.sn_aa_get_info.argtypes = [vp, i32, ctypes.POINTER(SnInfo)]
+    L.sn_aa_host_slots.argtypes = [vp]
+    L.sn_aa_submit_host.argtypes = [vp, p3v, p3i, i32, ctypes.POINTER(i32)]
+    L.sn_aa_collect_host.argtypes = [vp, i32, p3v, p3i]
     _lib = L
     return L

@@ -39,6 +39,7 @@ struct Context {
     float aaf[3] = {0, 0, 0};
     bool process[3] = {true, true, true};
     bool history_free = false;
+    bool copies_elsewhere = false;  // a pass of sn_aa_*: planes that are not processed are copied by that call, once
     bool use_fused = false;
     int arith = SN_ARITH_CXX;  // sn_options.arithmetic, fixed for the context's life
     // SN_ARITH_SSE2 on integer samples: the saturating instances of the pool kernels (float has one arithmetic)
@@ -946,6 +947,7 @@ static int run_group(Context* c, hipStream_t st, int slot0, int n, const void* c
         a.offset = offset;
         a.dh = c->cfg.dh;
         a.enabled = (c->cfg.dh || c->process[p]) ? 1 : 0;
+        a.copied_elsewhere = c->copies_elsewhere ? 1 : 0;
         a.arith = c->saturating() ? SN_ARITH_SSE2 : SN_ARITH_CXX;
         fused[p] = a.enabled && (c->isolated ? c->plane_fused[p] : c->use_fused) && sn::fused_layout_ok(a);
     }
@@ -1381,6 +1383,7 @@ static int run_chain(Context* c, hipStream_t st, int n, const void* const src[3]
         a.offset = offset;
         a.dh = c->cfg.dh;
         a.enabled = (c->cfg.dh || c->process[p]) ? 1 : 0;
+        a.copied_elsewhere = c->copies_elsewhere ? 1 : 0;
         SN_HIP(c, sn::launch_assemble(st, a, B, n));
     }
     sn::PoolArgs ring = c->pool;
@@ -2083,21 +2086,50 @@ int sn_debug_read_coupled_rows(sn_context* h, int32_t which, void* host_dst, siz
 }
 
 // ---- the anti-aliasing idiom as one call -------------------------------------------------------
+// Two filter instances (the turned clip, the clip) on ONE stream and the turn kernel between them.  A batch runs in
+// chunks of as many frames as the intermediates hold: turn the chunk, first pass over it, turn back, second pass, so
+// that each instance sees its frames in order.  Host frames go through groups of frame slots: upload on one stream, the
+// device work of every group on the call's stream (in submission order, which is what a history-carrying pass needs),
+// download on a third; events order the three, nothing waits inside a kernel.
 struct sn_aa_context {
     sn_config cfg{};
     sn_context* first = nullptr;   // the turned clip
     sn_context* second = nullptr;  // the clip itself, on first's stream
     hipStream_t stream = nullptr;
+    hipStream_t up = nullptr, down = nullptr;  // host frames: H2D / D2H (created with the first group of slots)
     int planes = 1;
+    int max_batch = 1;
+    bool process[3] = {true, true, true};
     int w[3] = {0, 0, 0}, h[3] = {0, 0, 0};  // clip geometry per plane
     int pitch[3] = {0, 0, 0}, tpitch[3] = {0, 0, 0};
-    uint8_t* d_src[3] = {nullptr, nullptr, nullptr};  // clip geometry
-    uint8_t* d_t1[3] = {nullptr, nullptr, nullptr};   // turned: input of the first pass
+    int64_t cbytes[3] = {0, 0, 0}, tbytes[3] = {0, 0, 0};  // one frame of a plane: clip geometry / turned
+    int cap = 0;                                       // frames the intermediates hold (a chunk)
+    uint8_t* d_t1[3] = {nullptr, nullptr, nullptr};   // turned: input of the first pass (only its kept lines are written)
     uint8_t* d_u1[3] = {nullptr, nullptr, nullptr};   // turned: its output
-    uint8_t* d_t2[3] = {nullptr, nullptr, nullptr};   // clip geometry: input of the second pass
-    uint8_t* d_out[3] = {nullptr, nullptr, nullptr};
-    uint8_t* h_src[3] = {nullptr, nullptr, nullptr};  // pinned staging for planes the caller holds in pageable memory
-    uint8_t* h_dst[3] = {nullptr, nullptr, nullptr};
+    uint8_t* d_t2[3] = {nullptr, nullptr, nullptr};   // clip geometry: input of the second pass (kept lines only)
+    // host frames: `per_group` slots form a group whose frames one batch works on; the ring's groups, then one group of
+    // one slot for the synchronous call
+    struct Slot {
+        uint8_t state = Context::kFree;
+        int32_t parity = 1;
+        void* out[3] = {nullptr, nullptr, nullptr};  // pinned destination planes named before the launch: written from the device
+        int32_t out_pitch[3] = {0, 0, 0};
+        bool copied[3] = {false, false, false};      // a plane that is not processed and already lies in its destination
+    };
+    struct Group {
+        int n = 0;
+        uint8_t* d_src[3] = {nullptr, nullptr, nullptr};
+        uint8_t* d_out[3] = {nullptr, nullptr, nullptr};
+        uint8_t* h_src[3] = {nullptr, nullptr, nullptr};  // pinned staging for planes the caller holds in pageable memory
+        uint8_t* h_dst[3] = {nullptr, nullptr, nullptr};
+        hipEvent_t arrived = nullptr, swept = nullptr, done = nullptr;
+        int lo = 0, hi = 0;  // slots [lo, hi) are staged and not yet launched
+        std::vector<Slot> slot;
+    };
+    std::vector<Group> groups;  // [0, ring_groups): the ring; [ring_groups]: the synchronous call's
+    int depth = 0, per_group = 1, ring_groups = 0, ring_next = 0;
+    bool ring_ready = false;
+    Copier* copier = nullptr;  // the first context's
     std::string err;
 };
 
@@ -2105,19 +2137,79 @@ static thread_local std::string g_aa_error;
 
 const char* sn_aa_last_error(const sn_aa_context* a) { return a ? a->err.c_str() : g_aa_error.c_str(); }
 
+static int aa_fail(sn_aa_context* a, int code, const std::string& m)
+{
+    if (a) a->err = m;
+    else g_aa_error = m;
+    return code;
+}
+
+#define SN_AA_HIP(call)                                                                                          \
+    do {                                                                                                         \
+        hipError_t e_ = (call);                                                                                  \
+        if (e_ != hipSuccess) return aa_fail(a, SN_ERR_HIP, std::string(#call " failed: ") + hipGetErrorString(e_)); \
+    } while (0)
+#define SN_AA_SN(ctx, call)                                            \
+    do {                                                               \
+        const int rc_ = (call);                                        \
+        if (rc_ != SN_OK) return aa_fail(a, rc_, sn_last_error(ctx));  \
+    } while (0)
+
+static void aa_free_group(sn_aa_context::Group& g)
+{
+    for (int p = 0; p < 3; ++p) {
+        for (uint8_t* q : {g.d_src[p], g.d_out[p]})
+            if (q) (void)hipFree(q);
+        for (uint8_t* q : {g.h_src[p], g.h_dst[p]})
+            if (q) (void)hipHostFree(q);
+    }
+    for (hipEvent_t e : {g.arrived, g.swept, g.done})
+        if (e) (void)hipEventDestroy(e);
+}
+
+// The intermediates for chunks of `frames` frames, or of what the scratch budget holds (a batch beyond that is walked in
+// more chunks).  At creation for cfg.max_batch; the ring asks again for a group's frames when it is first used.
+static int aa_ensure_intermediates(sn_aa_context* a, int frames)
+{
+    if (frames <= a->cap) return SN_OK;
+    int64_t per_frame = 0;
+    for (int p = 0; p < a->planes; ++p)
+        if (a->process[p]) per_frame += 2 * a->tbytes[p] + a->cbytes[p];
+    const int64_t fit = per_frame > 0 ? scratch_budget(reinterpret_cast<Context*>(a->first)) / per_frame : frames;
+    const int cap = (int)(fit < 1 ? 1 : fit < frames ? fit : frames);
+    if (cap <= a->cap) return SN_OK;
+    SN_AA_HIP(hipStreamSynchronize(a->stream));
+    for (int p = 0; p < a->planes; ++p) {
+        if (!a->process[p]) continue;  // copied from source to destination: no turn, no pass, no intermediate
+        const size_t nb[3] = {(size_t)a->tbytes[p] * cap, (size_t)a->tbytes[p] * cap, (size_t)a->cbytes[p] * cap};
+        uint8_t** q[3] = {&a->d_t1[p], &a->d_u1[p], &a->d_t2[p]};
+        for (int k = 0; k < 3; ++k) {
+            if (*q[k]) SN_AA_HIP(hipFree(*q[k]));
+            *q[k] = nullptr;
+            SN_AA_HIP(hipMalloc(reinterpret_cast<void**>(q[k]), nb[k]));
+            // the turns write only the lines the next pass keeps: a pass that read another line would read this pattern
+            SN_AA_HIP(hipMemsetAsync(*q[k], 0xA5, nb[k], a->stream));
+        }
+    }
+    SN_AA_HIP(hipStreamSynchronize(a->stream));
+    a->cap = cap;
+    return SN_OK;
+}
+
 void sn_aa_destroy(sn_aa_context* a)
 {
     if (!a) return;
     (void)hipSetDevice(a->cfg.device);
-    if (a->stream) (void)hipStreamSynchronize(a->stream);
+    for (hipStream_t st : {a->up, a->stream, a->down})  // frames in flight: in the order their work was queued
+        if (st) (void)hipStreamSynchronize(st);
     if (a->second) sn_destroy(a->second);
-    if (a->first) sn_destroy(a->first);  // owns the stream
+    if (a->first) sn_destroy(a->first);  // owns the stream unless the caller gave one
     for (int p = 0; p < 3; ++p)
-        for (uint8_t* q : {a->d_src[p], a->d_t1[p], a->d_u1[p], a->d_t2[p], a->d_out[p]})
+        for (uint8_t* q : {a->d_t1[p], a->d_u1[p], a->d_t2[p]})
             if (q) (void)hipFree(q);
-    for (int p = 0; p < 3; ++p)
-        for (uint8_t* q : {a->h_src[p], a->h_dst[p]})
-            if (q) (void)hipHostFree(q);
+    for (auto& g : a->groups) aa_free_group(g);
+    for (hipStream_t st : {a->up, a->down})
+        if (st) (void)hipStreamDestroy(st);
     delete a;
 }
 
@@ -2136,109 +2228,339 @@ int sn_aa_create_ex(const sn_config* cfg, const sn_policy* policy, const sn_opti
     *out = nullptr;
     if (cfg->struct_size != (int32_t)sizeof(sn_config)) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_config.struct_size mismatch");
     if (cfg->dh) return fail_aa(nullptr, SN_ERR_UNSUPPORTED, "sn_aa_create: dh is not part of the anti-aliasing idiom");
+    if (cfg->max_batch < 0) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "max_batch must be >= 0");
+    if (cfg->host_depth < 0 || cfg->host_depth > 256) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "host_depth must be 0..256");
     sn_aa_context* a = new (std::nothrow) sn_aa_context();
     if (!a) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "out of host memory");
     a->cfg = *cfg;
+    a->max_batch = cfg->max_batch > 1 ? cfg->max_batch : 1;
+    // the ring: two groups, so that one group uploads while the other is worked on; a group's frames are one batch
+    a->depth = cfg->host_depth > 0 ? cfg->host_depth : 4;
+    a->ring_groups = a->depth < 2 ? 1 : 2;
+    a->per_group = a->depth / a->ring_groups;
+    a->depth = a->ring_groups * a->per_group;
+    const int inner_batch = a->max_batch > a->per_group ? a->max_batch : a->per_group;
     sn_config c1 = *cfg;  // TurnLeft: width <-> height, the chroma subsampling turns with it
     c1.width = cfg->height;
     c1.height = cfg->width;
     c1.sub_w = cfg->sub_h;
     c1.sub_h = cfg->sub_w;
-    c1.max_batch = 1;
+    c1.max_batch = inner_batch;
     c1.mode = SN_MODE_AUTO;
-    c1.stream = nullptr;
     int rc = sn_create_ex(&c1, policy, options, &a->first);
     if (rc != SN_OK) return fail_aa(a, rc, sn_last_error(nullptr));
     sn_config c2 = *cfg;
-    c2.max_batch = 1;
+    c2.max_batch = inner_batch;
     c2.mode = SN_MODE_AUTO;
     c2.stream = sn_get_stream(a->first);
     rc = sn_create_ex(&c2, policy, options, &a->second);
     if (rc != SN_OK) return fail_aa(a, rc, sn_last_error(nullptr));
-    a->stream = reinterpret_cast<hipStream_t>(sn_get_stream(a->first));
+    Context* f1 = reinterpret_cast<Context*>(a->first);
+    f1->copies_elsewhere = reinterpret_cast<Context*>(a->second)->copies_elsewhere = true;
+    a->stream = f1->stream;
     a->planes = cfg->num_planes < 3 ? cfg->num_planes : 3;
     const int B = cfg->bytes_per_sample;
     for (int p = 0; p < a->planes; ++p) {
+        a->process[p] = f1->process[p];
         a->w[p] = p ? cfg->width >> cfg->sub_w : cfg->width;
         a->h[p] = p ? cfg->height >> cfg->sub_h : cfg->height;
         a->pitch[p] = (a->w[p] * B + 255) & ~255;
         a->tpitch[p] = (a->h[p] * B + 255) & ~255;
-        const size_t clip_bytes = (size_t)a->pitch[p] * a->h[p], turned_bytes = (size_t)a->tpitch[p] * a->w[p];
-        for (uint8_t** q : {&a->d_src[p], &a->d_t2[p], &a->d_out[p]})
-            if (hipMalloc(reinterpret_cast<void**>(q), clip_bytes) != hipSuccess) return fail_aa(a, SN_ERR_HIP, "hipMalloc failed (sn_aa_create)");
-        for (uint8_t** q : {&a->h_src[p], &a->h_dst[p]})
-            if (hipHostMalloc(reinterpret_cast<void**>(q), clip_bytes, hipHostMallocDefault) != hipSuccess) return fail_aa(a, SN_ERR_HIP, "hipHostMalloc failed (sn_aa_create)");
-        for (uint8_t** q : {&a->d_t1[p], &a->d_u1[p]})
-            if (hipMalloc(reinterpret_cast<void**>(q), turned_bytes) != hipSuccess) return fail_aa(a, SN_ERR_HIP, "hipMalloc failed (sn_aa_create)");
+        a->cbytes[p] = (int64_t)a->pitch[p] * a->h[p];
+        a->tbytes[p] = (int64_t)a->tpitch[p] * a->w[p];
     }
+    if (int rc2 = aa_ensure_intermediates(a, a->max_batch)) return fail_aa(a, rc2, a->err);
     *out = a;
     return SN_OK;
 }
 
+// Frames [0, n) of a strided device batch through both passes, on the call's stream.
+static int aa_run(sn_aa_context* a, int n, const void* const src[3], const int64_t sfs[3], const int32_t sp[3], void* const dst[3],
+                  const int64_t dfs[3], const int32_t dp[3], const int32_t* parity)
+{
+    Context* c1 = reinterpret_cast<Context*>(a->first);
+    Context* c2 = reinterpret_cast<Context*>(a->second);
+    const int B = a->cfg.bytes_per_sample;
+    hipStream_t st = a->stream;
+    // planes that are not processed are never touched by the passes (copies_elsewhere): their pointers only have to be there
+    const void* s1[3] = {src[0], src[1], src[2]};
+    void* d1[3] = {dst[0], dst[1], dst[2]};
+    const void* s2[3] = {src[0], src[1], src[2]};
+    for (int p = 0; p < a->planes; ++p)
+        if (a->process[p]) s1[p] = a->d_t1[p], d1[p] = a->d_u1[p], s2[p] = a->d_t2[p];
+    for (int f0 = 0; f0 < n; f0 += a->cap) {
+        const int m = n - f0 < a->cap ? n - f0 : a->cap;
+        const int32_t* par = parity ? parity + f0 : nullptr;
+        // a turn writes the lines its pass keeps: one launch per run of frames with the same field offset, as run_batch cuts them
+        auto turns = [&](int right) -> int {
+            for (int g0 = 0; g0 < m;) {
+                const int off = field_offset(c1, par ? par[g0] : 1);
+                int g1 = g0 + 1;
+                while (g1 < m && field_offset(c1, par ? par[g1] : 1) == off) ++g1;
+                for (int p = 0; p < a->planes; ++p) {
+                    if (!a->process[p]) continue;
+                    if (!right)  // TurnLeft: the clip's plane -> h wide, w high
+                        SN_AA_HIP(sn::launch_turn(st, B, 0, g1 - g0, static_cast<const uint8_t*>(src[p]) + (int64_t)(f0 + g0) * sfs[p], sfs[p], sp[p],
+                                                  a->w[p], a->h[p], a->d_t1[p] + g0 * a->tbytes[p], a->tbytes[p], a->tpitch[p], off));
+                    else  // TurnRight of the first pass's output
+                        SN_AA_HIP(sn::launch_turn(st, B, 1, g1 - g0, a->d_u1[p] + g0 * a->tbytes[p], a->tbytes[p], a->tpitch[p], a->h[p], a->w[p],
+                                                  a->d_t2[p] + g0 * a->cbytes[p], a->cbytes[p], a->pitch[p], off));
+                }
+                g0 = g1;
+            }
+            return SN_OK;
+        };
+        if (int rc = turns(0)) return rc;
+        SN_AA_SN(a->first, run_batch(c1, st, 0, m, s1, a->tbytes, a->tpitch, d1, a->tbytes, a->tpitch, par));
+        if (int rc = turns(1)) return rc;
+        void* d2[3] = {nullptr, nullptr, nullptr};
+        for (int p = 0; p < a->planes; ++p) d2[p] = static_cast<uint8_t*>(dst[p]) + (int64_t)f0 * dfs[p];
+        SN_AA_SN(a->second, run_batch(c2, st, 0, m, s2, a->cbytes, a->pitch, d2, dfs, dp, par));
+    }
+    return SN_OK;
+}
+
+int sn_aa_process_device_strided(sn_aa_context* a, int32_t nframes, const void* const src[3], const int64_t sfs[3], const int32_t sp[3],
+                                 void* const dst[3], const int64_t dfs[3], const int32_t dp[3], const int32_t* parity)
+{
+    if (!a) return aa_fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    if (nframes < 0 || nframes > a->max_batch)
+        return aa_fail(a, SN_ERR_INVALID_ARG, "nframes " + std::to_string(nframes) + " outside 0..max_batch (" + std::to_string(a->max_batch) + ")");
+    if (!src || !sfs || !sp || !dst || !dfs || !dp) return aa_fail(a, SN_ERR_INVALID_ARG, "plane / stride array is NULL");
+    const int B = a->cfg.bytes_per_sample;
+    for (int p = 0; p < a->planes; ++p) {
+        if (!src[p] || !dst[p] || sp[p] < a->w[p] * B || dp[p] < a->w[p] * B)
+            return aa_fail(a, SN_ERR_INVALID_ARG, "plane pointer is NULL or pitch smaller than the row");
+        if (sp[p] % B || dp[p] % B || sfs[p] % B || dfs[p] % B || (uintptr_t)src[p] % B || (uintptr_t)dst[p] % B)
+            return aa_fail(a, SN_ERR_INVALID_ARG, "plane pointer / pitch / frame stride not aligned to the sample size");
+    }
+    if (nframes == 0) return SN_OK;
+    SN_AA_HIP(hipSetDevice(a->cfg.device));
+    // a plane that is not processed: source to destination, once; no turn and no pass
+    for (int p = 0; p < a->planes; ++p) {
+        if (a->process[p]) continue;
+        for (int f = 0; f < nframes; ++f)
+            SN_AA_HIP(hipMemcpy2DAsync(static_cast<uint8_t*>(dst[p]) + f * dfs[p], (size_t)dp[p], static_cast<const uint8_t*>(src[p]) + f * sfs[p],
+                                       (size_t)sp[p], (size_t)a->w[p] * B, a->h[p], hipMemcpyDeviceToDevice, a->stream));
+    }
+    return aa_run(a, nframes, src, sfs, sp, dst, dfs, dp, parity);
+}
+
+int sn_aa_synchronize(sn_aa_context* a)
+{
+    if (!a) return aa_fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    SN_AA_HIP(hipSetDevice(a->cfg.device));
+    SN_AA_SN(a->first, sn_synchronize(a->first));  // the call's stream, and what a chain may have to report
+    SN_AA_SN(a->second, sn_synchronize(a->second));
+    if (a->down) SN_AA_HIP(hipStreamSynchronize(a->down));
+    return SN_OK;
+}
+
+void* sn_aa_get_stream(sn_aa_context* a) { return a ? reinterpret_cast<void*>(a->stream) : nullptr; }
+
+int sn_aa_get_info(sn_aa_context* a, int32_t pass, sn_info* info)
+{
+    if (!a) return aa_fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    if (pass != 0 && pass != 1) return aa_fail(a, SN_ERR_INVALID_ARG, "pass must be 0 (the turned clip) or 1 (the clip)");
+    sn_context* c = pass ? a->second : a->first;
+    SN_AA_SN(c, sn_get_info(c, info));
+    return SN_OK;
+}
+
+// -- host frames ------------------------------------------------------------------------------------------------
+static int aa_ensure_group(sn_aa_context* a, int gi, int n)
+{
+    if (!a->up) {
+        SN_AA_HIP(hipStreamCreateWithFlags(&a->up, hipStreamNonBlocking));
+        SN_AA_HIP(hipStreamCreateWithFlags(&a->down, hipStreamNonBlocking));
+        a->groups.resize((size_t)a->ring_groups + 1);
+        ensure_copier(reinterpret_cast<Context*>(a->first));
+        a->copier = reinterpret_cast<Context*>(a->first)->copier;  // the first pass's copy threads (it never uses them itself here)
+    }
+    sn_aa_context::Group& g = a->groups[(size_t)gi];
+    if (g.n) return SN_OK;
+    for (int p = 0; p < a->planes; ++p) {
+        const size_t nb = (size_t)a->cbytes[p] * n;
+        // a plane that is not processed never visits the device: its staging carries it from submission to collection
+        SN_AA_HIP(hipHostMalloc(reinterpret_cast<void**>(&g.h_src[p]), nb, hipHostMallocDefault));
+        if (!a->process[p]) continue;
+        SN_AA_HIP(hipHostMalloc(reinterpret_cast<void**>(&g.h_dst[p]), nb, hipHostMallocDefault));
+        SN_AA_HIP(hipMalloc(reinterpret_cast<void**>(&g.d_src[p]), nb));
+        SN_AA_HIP(hipMalloc(reinterpret_cast<void**>(&g.d_out[p]), nb));
+    }
+    for (hipEvent_t* e : {&g.arrived, &g.swept, &g.done}) SN_AA_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    g.slot.assign((size_t)n, sn_aa_context::Slot{});
+    g.n = n;
+    return SN_OK;
+}
+
+static int aa_ensure_ring(sn_aa_context* a)
+{
+    if (a->ring_ready) return SN_OK;
+    for (int gi = 0; gi < a->ring_groups; ++gi)
+        if (int rc = aa_ensure_group(a, gi, a->per_group)) return rc;
+    if (int rc = aa_ensure_intermediates(a, a->per_group)) return rc;
+    SN_AA_SN(a->first, prepare_small_launch_scratch(reinterpret_cast<Context*>(a->first)));
+    SN_AA_SN(a->second, prepare_small_launch_scratch(reinterpret_cast<Context*>(a->second)));
+    a->ring_ready = true;
+    return SN_OK;
+}
+
+static int aa_check_host_planes(sn_aa_context* a, const void* const ptr[3], const int32_t pitch[3])
+{
+    if (!ptr || !pitch) return aa_fail(a, SN_ERR_INVALID_ARG, "plane array is NULL");
+    for (int p = 0; p < a->planes; ++p)
+        if (!ptr[p] || pitch[p] < a->w[p] * a->cfg.bytes_per_sample)
+            return aa_fail(a, SN_ERR_INVALID_ARG, "plane pointer is NULL or pitch smaller than the row");
+    return SN_OK;
+}
+
+// Slot k of group g takes a frame: pageable planes into the pinned staging (the copy threads), then H2D; pinned ones are
+// DMA'd as they lie.  With the destination at hand (the synchronous call) a plane that is not processed goes there at once.
+static int aa_stage(sn_aa_context* a, sn_aa_context::Group& g, int k, const void* const src[3], const int32_t sp[3], void* const dst[3],
+                    const int32_t dp[3], int32_t parity)
+{
+    const int B = a->cfg.bytes_per_sample;
+    sn_aa_context::Slot sl{};
+    sl.parity = parity;
+    Copier::Job jobs[3];
+    int nj = 0;
+    bool direct[3] = {false, false, false};
+    for (int p = 0; p < a->planes; ++p) {
+        if (!a->process[p]) {  // host to host, once where the destination is known
+            sl.copied[p] = dst != nullptr;
+            jobs[nj++] = {dst ? static_cast<uint8_t*>(dst[p]) : g.h_src[p] + k * a->cbytes[p], static_cast<const uint8_t*>(src[p]),
+                          dst ? dp[p] : a->pitch[p], sp[p], a->w[p] * B, a->h[p]};
+            continue;
+        }
+        direct[p] = sn::plane_is_pinned(src[p], sp[p], a->w[p] * B, a->h[p]);
+        if (!direct[p]) jobs[nj++] = {g.h_src[p] + k * a->cbytes[p], static_cast<const uint8_t*>(src[p]), a->pitch[p], sp[p], a->w[p] * B, a->h[p]};
+        if (dst && sn::plane_is_pinned(dst[p], dp[p], a->w[p] * B, a->h[p])) sl.out[p] = dst[p], sl.out_pitch[p] = dp[p];
+    }
+    if (nj) a->copier->run(jobs, nj);
+    for (int p = 0; p < a->planes; ++p) {
+        if (!a->process[p]) continue;
+        SN_AA_HIP(hipMemcpy2DAsync(g.d_src[p] + k * a->cbytes[p], a->pitch[p], direct[p] ? src[p] : g.h_src[p] + k * a->cbytes[p],
+                                   direct[p] ? (size_t)sp[p] : (size_t)a->pitch[p], (size_t)a->w[p] * B, a->h[p], hipMemcpyHostToDevice, a->up));
+    }
+    sl.state = Context::kStaged;
+    g.slot[(size_t)k] = sl;
+    g.hi = k + 1;
+    return SN_OK;
+}
+
+// The staged slots [lo, hi) of a group: one batch on the call's stream behind their uploads, their downloads behind it.
+static int aa_launch(sn_aa_context* a, sn_aa_context::Group& g)
+{
+    const int n = g.hi - g.lo;
+    if (n <= 0) return SN_OK;
+    const int B = a->cfg.bytes_per_sample;
+    SN_AA_HIP(hipEventRecord(g.arrived, a->up));
+    SN_AA_HIP(hipStreamWaitEvent(a->stream, g.arrived, 0));
+    const void* s3[3] = {nullptr, nullptr, nullptr};
+    void* d3[3] = {nullptr, nullptr, nullptr};
+    std::vector<int32_t> par((size_t)n);
+    for (int k = 0; k < n; ++k) par[(size_t)k] = g.slot[(size_t)(g.lo + k)].parity;
+    bool any = false;
+    for (int p = 0; p < a->planes; ++p) {
+        any = any || a->process[p];
+        s3[p] = a->process[p] ? g.d_src[p] + g.lo * a->cbytes[p] : g.h_src[p];  // (not processed: never read on the device)
+        d3[p] = a->process[p] ? g.d_out[p] + g.lo * a->cbytes[p] : g.h_src[p];
+    }
+    if (any)
+        if (int rc = aa_run(a, n, s3, a->cbytes, a->pitch, d3, a->cbytes, a->pitch, par.data())) return rc;
+    SN_AA_HIP(hipEventRecord(g.swept, a->stream));
+    SN_AA_HIP(hipStreamWaitEvent(a->down, g.swept, 0));
+    for (int k = g.lo; k < g.hi; ++k) {
+        sn_aa_context::Slot& sl = g.slot[(size_t)k];
+        for (int p = 0; p < a->planes; ++p) {
+            if (!a->process[p]) continue;
+            SN_AA_HIP(hipMemcpy2DAsync(sl.out[p] ? sl.out[p] : g.h_dst[p] + k * a->cbytes[p], sl.out[p] ? (size_t)sl.out_pitch[p] : (size_t)a->pitch[p],
+                                       g.d_out[p] + k * a->cbytes[p], a->pitch[p], (size_t)a->w[p] * B, a->h[p], hipMemcpyDeviceToHost, a->down));
+        }
+        sl.state = Context::kInFlight;
+    }
+    SN_AA_HIP(hipEventRecord(g.done, a->down));
+    g.lo = g.hi;
+    return SN_OK;
+}
+
+int sn_aa_host_slots(sn_aa_context* a)
+{
+    if (!a) return 0;
+    if (hipSetDevice(a->cfg.device) != hipSuccess || aa_ensure_ring(a) != SN_OK) return 0;
+    return a->depth;
+}
+
+int sn_aa_submit_host(sn_aa_context* a, const void* const src[3], const int32_t sp[3], int32_t parity, int32_t* slot_out)
+{
+    if (!a) return aa_fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    if (!slot_out) return aa_fail(a, SN_ERR_INVALID_ARG, "slot pointer is NULL");
+    if (int rc = aa_check_host_planes(a, src, sp)) return rc;
+    SN_AA_HIP(hipSetDevice(a->cfg.device));
+    if (int rc = aa_ensure_ring(a)) return rc;
+    const int slot = a->ring_next, gi = slot / a->per_group, k = slot % a->per_group;
+    sn_aa_context::Group& g = a->groups[(size_t)gi];
+    if (g.slot[(size_t)k].state != Context::kFree)
+        return aa_fail(a, SN_ERR_BUSY, "all " + std::to_string(a->depth) + " host slots are in flight: collect slot " + std::to_string(slot) + " first");
+    if (k == 0) g.lo = g.hi = 0;  // the ring came round to this group again
+    if (int rc = aa_stage(a, g, k, src, sp, nullptr, nullptr, parity)) return rc;
+    a->ring_next = (slot + 1) % a->depth;
+    *slot_out = slot;
+    return g.hi == g.n ? aa_launch(a, g) : SN_OK;
+}
+
+// Waits for slot k of group g and brings its planes into the caller's.
+static int aa_finish(sn_aa_context* a, sn_aa_context::Group& g, int k, void* const dst[3], const int32_t dp[3])
+{
+    const int B = a->cfg.bytes_per_sample;
+    sn_aa_context::Slot& sl = g.slot[(size_t)k];
+    if (sl.state == Context::kStaged)  // its group is not full yet: run what is staged
+        if (int rc = aa_launch(a, g)) return rc;
+    SN_AA_HIP(hipEventSynchronize(g.done));
+    SN_AA_SN(a->first, chain_fault(reinterpret_cast<Context*>(a->first)));
+    SN_AA_SN(a->second, chain_fault(reinterpret_cast<Context*>(a->second)));
+    Copier::Job jobs[3];
+    int nj = 0;
+    for (int p = 0; p < a->planes; ++p) {
+        if (a->process[p] ? sl.out[p] == dst[p] : sl.copied[p]) continue;  // already there
+        const uint8_t* from = (a->process[p] ? g.h_dst[p] : g.h_src[p]) + k * a->cbytes[p];
+        jobs[nj++] = {static_cast<uint8_t*>(dst[p]), from, dp[p], a->pitch[p], a->w[p] * B, a->h[p]};
+    }
+    if (nj) a->copier->run(jobs, nj);
+    sl = sn_aa_context::Slot{};
+    return SN_OK;
+}
+
+int sn_aa_collect_host(sn_aa_context* a, int32_t slot, void* const dst[3], const int32_t dp[3])
+{
+    if (!a) return aa_fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    if (!a->ring_ready || slot < 0 || slot >= a->depth || a->groups[(size_t)(slot / a->per_group)].slot[(size_t)(slot % a->per_group)].state == Context::kFree)
+        return aa_fail(a, SN_ERR_INVALID_ARG, "slot " + std::to_string(slot) + " holds no frame");
+    if (int rc = aa_check_host_planes(a, dst, dp)) return rc;
+    SN_AA_HIP(hipSetDevice(a->cfg.device));
+    return aa_finish(a, a->groups[(size_t)(slot / a->per_group)], slot % a->per_group, dst, dp);
+}
+
+// The one-frame case: a slot of its own (so that frames in the ring stay where they are), staged, run and collected at once.
 int sn_aa_process_host(sn_aa_context* a, const void* const src[3], const int32_t sp[3], void* const dst[3], const int32_t dp[3],
                        int32_t parity)
 {
     if (!a) return sn::fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
-    auto bad = [&](int code, const std::string& m) { a->err = m; return code; };
-    if (!src || !sp || !dst || !dp) return bad(SN_ERR_INVALID_ARG, "plane array is NULL");
-    const int B = a->cfg.bytes_per_sample;
-    for (int p = 0; p < a->planes; ++p)
-        if (!src[p] || !dst[p] || sp[p] < a->w[p] * B || dp[p] < a->w[p] * B) return bad(SN_ERR_INVALID_ARG, "plane pointer is NULL or pitch smaller than the row");
-#define SN_AA_HIP(call)                                                                                      \
-    do {                                                                                                     \
-        hipError_t e_ = (call);                                                                              \
-        if (e_ != hipSuccess) return bad(SN_ERR_HIP, std::string(#call " failed: ") + hipGetErrorString(e_)); \
-    } while (0)
-#define SN_AA_SN(ctx, call)                                                 \
-    do {                                                                    \
-        const int rc_ = (call);                                             \
-        if (rc_ != SN_OK) return bad(rc_, sn_last_error(ctx));              \
-    } while (0)
+    if (!src || !sp || !dst || !dp) return aa_fail(a, SN_ERR_INVALID_ARG, "plane array is NULL");
+    if (int rc = aa_check_host_planes(a, src, sp)) return rc;
+    if (int rc = aa_check_host_planes(a, dst, dp)) return rc;
     SN_AA_HIP(hipSetDevice(a->cfg.device));
     SN_AA_SN(a->first, prepare_small_launch_scratch(reinterpret_cast<Context*>(a->first)));
     SN_AA_SN(a->second, prepare_small_launch_scratch(reinterpret_cast<Context*>(a->second)));
-    // planes in pageable memory go through the context's pinned staging (the runtime never sees a pageable pointer, see
-    // sn_process_host); planes inside memory the caller pinned are DMA'd as they lie
-    for (int p = 0; p < a->planes; ++p) {
-        const void* from = src[p];
-        size_t from_pitch = (size_t)sp[p];
-        if (!sn::plane_is_pinned(src[p], sp[p], a->w[p] * B, a->h[p])) {
-            for (int y = 0; y < a->h[p]; ++y)
-                memcpy(a->h_src[p] + (size_t)y * a->pitch[p], static_cast<const uint8_t*>(src[p]) + (size_t)y * sp[p], (size_t)a->w[p] * B);
-            from = a->h_src[p];
-            from_pitch = (size_t)a->pitch[p];
-        }
-        SN_AA_HIP(hipMemcpy2DAsync(a->d_src[p], a->pitch[p], from, from_pitch, (size_t)a->w[p] * B, a->h[p], hipMemcpyHostToDevice, a->stream));
-    }
-    for (int p = 0; p < a->planes; ++p)  // TurnLeft
-        SN_AA_SN(a->first, sn_turn_device(a->first, -1, 1, a->d_src[p], 0, a->pitch[p], a->w[p], a->h[p], a->d_t1[p], 0, a->tpitch[p]));
-    {
-        const void* s3[3] = {a->d_t1[0], a->d_t1[1], a->d_t1[2]};
-        void* d3[3] = {a->d_u1[0], a->d_u1[1], a->d_u1[2]};
-        SN_AA_SN(a->first, sn_process_device(a->first, s3, a->tpitch, d3, a->tpitch, parity));
-    }
-    for (int p = 0; p < a->planes; ++p)  // TurnRight: the turned plane is h wide and w high
-        SN_AA_SN(a->first, sn_turn_device(a->first, +1, 1, a->d_u1[p], 0, a->tpitch[p], a->h[p], a->w[p], a->d_t2[p], 0, a->pitch[p]));
-    {
-        const void* s3[3] = {a->d_t2[0], a->d_t2[1], a->d_t2[2]};
-        void* d3[3] = {a->d_out[0], a->d_out[1], a->d_out[2]};
-        SN_AA_SN(a->second, sn_process_device(a->second, s3, a->pitch, d3, a->pitch, parity));
-    }
-    bool staged[3] = {false, false, false};
-    for (int p = 0; p < a->planes; ++p) {
-        staged[p] = !sn::plane_is_pinned(dst[p], dp[p], a->w[p] * B, a->h[p]);
-        SN_AA_HIP(hipMemcpy2DAsync(staged[p] ? a->h_dst[p] : dst[p], staged[p] ? (size_t)a->pitch[p] : (size_t)dp[p], a->d_out[p], a->pitch[p],
-                                   (size_t)a->w[p] * B, a->h[p], hipMemcpyDeviceToHost, a->stream));
-    }
-    SN_AA_HIP(hipStreamSynchronize(a->stream));
-    for (int p = 0; p < a->planes; ++p)
-        if (staged[p])
-            for (int y = 0; y < a->h[p]; ++y)
-                memcpy(static_cast<uint8_t*>(dst[p]) + (size_t)y * dp[p], a->h_dst[p] + (size_t)y * a->pitch[p], (size_t)a->w[p] * B);
+    if (int rc = aa_ensure_group(a, a->ring_groups, 1)) return rc;
+    sn_aa_context::Group& g = a->groups[(size_t)a->ring_groups];
+    g.lo = g.hi = 0;
+    if (int rc = aa_stage(a, g, 0, src, sp, dst, dp, parity)) return rc;
+    return aa_finish(a, g, 0, dst, dp);
+}
 #undef SN_AA_HIP
 #undef SN_AA_SN
-    return SN_OK;
-}
 
 }  // extern "C"
 #pragma GCC visibility pop

@@ -28,6 +28,7 @@ struct PlaneArgs {
     const int32_t* guard;      // pool-path kernels: when set, frame f is worked on only if guard[f] != 0 (sn_band.hip)
     int32_t guard_single;      // ... 1: ONE word decides for every frame of the launch (guard[0]; the redo of a chain that timed out)
     int32_t arith = 0;         // SN_ARITH_*: read by the 8-bit sweeps of planes on their own (the pool kernels take PoolArgs::arith)
+    int32_t copied_elsewhere = 0;  // a plane that is not enabled is copied by the caller (sn_aa_*): launch_assemble leaves it alone
 };
 
 // Scratch pool geometry (src/SangNom2.cpp:287-288,305-310), in elements of T.
@@ -64,9 +65,10 @@ struct ChainArgs {
 
 struct Context;
 
-// sn_turn.hip: quarter turn of a plane (right = clockwise), for device-resident anti-aliasing pipelines
+// sn_turn.hip: quarter turn of a plane (right = clockwise), for device-resident anti-aliasing pipelines;
+// line_parity 0 / 1: only the destination lines of that parity are written, < 0: all of them
 hipError_t launch_turn(hipStream_t s, int bytes, int right, int nframes, const uint8_t* src, int64_t src_frame_stride, int src_pitch, int w,
-                       int h, uint8_t* dst, int64_t dst_frame_stride, int dst_pitch);
+                       int h, uint8_t* dst, int64_t dst_frame_stride, int dst_pitch, int line_parity = -1);
 
 // sn_pool_kernels.hip: the three-kernel path over the HBM-resident pool (every format).
 hipError_t launch_assemble(hipStream_t s, const PlaneArgs& p, int bytes, int nframes);

@@ -56,6 +56,7 @@ __global__ void __launch_bounds__(256) k_assemble(PlaneArgs p, int row_bytes)
 
 hipError_t launch_assemble(hipStream_t st, const PlaneArgs& p, int bytes, int nframes)
 {
+    if (!p.enabled && p.copied_elsewhere) return hipSuccess;
     const int row_bytes = p.w * bytes;
     auto aligned = [&](int a) {
         return ((uintptr_t)p.src % a == 0) && ((uintptr_t)p.dst % a == 0) && (p.src_pitch % a == 0) &&

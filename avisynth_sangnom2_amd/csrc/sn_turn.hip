@@ -7,6 +7,9 @@
 //   left (anti-clockwise):  dst[y'][x'] = src[x'][W-1-y']
 // 64 x 64 sample tiles go through LDS so that both the reads and the writes are row-contiguous; HBM-bound:
 // 2 x W x H x B bytes per plane.
+// Field form (line_parity 0 / 1): only the destination lines of that parity are written -- the lines the SangNom2 pass
+// that follows keeps, the only ones it reads.  A destination line is a source column, so a tile still reads whole source
+// rows but writes 32 of its 64 lines: 1.5 x W x H x B bytes.  The other lines of the destination are left as they were.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -18,7 +21,7 @@ constexpr int kTile = 64;
 
 template <class T>
 __global__ void __launch_bounds__(256) k_turn(const uint8_t* src, int64_t sfs, int spitch, int w, int h, uint8_t* dst, int64_t dfs, int dpitch,
-                                             int right, int dword_ok)
+                                             int right, int dword_ok, int line_parity)
 {
     constexpr int P = 4 / (int)sizeof(T);  // samples per dword
     constexpr int RD = kTile / P;          // dwords per tile row
@@ -37,8 +40,11 @@ __global__ void __launch_bounds__(256) k_turn(const uint8_t* src, int64_t sfs, i
             tile32[r][q] = reinterpret_cast<const uint32_t*>(s + (int64_t)(y0 + r) * spitch)[x0 / P + q];
         }
         __syncthreads();
-        for (int i = threadIdx.x; i < kTile * RD; i += 256) {
-            const int r = i / RD, q = i % RD;  // r: source column inside the tile = destination row; q: dword of that row
+        // destination line of tile column r: x0 + r (right) or w - 1 - x0 - r (left); the field form takes every other column
+        const int rstep = line_parity < 0 ? 1 : 2;
+        const int r0 = line_parity < 0 ? 0 : ((right ? x0 : w - 1 - x0) ^ line_parity) & 1;
+        for (int i = threadIdx.x; i < kTile / rstep * RD; i += 256) {
+            const int r = r0 + rstep * (i / RD), q = i % RD;  // r: source column inside the tile = destination row; q: dword of that row
             uint32_t v = 0;
 #pragma unroll
             for (int j = 0; j < P; ++j) {
@@ -68,12 +74,13 @@ __global__ void __launch_bounds__(256) k_turn(const uint8_t* src, int64_t sfs, i
         if (sy >= h) continue;
         const int dx = right ? h - 1 - sy : sy;
         const int dy = right ? sx : w - 1 - sx;
+        if (line_parity >= 0 && ((dy ^ line_parity) & 1)) continue;
         reinterpret_cast<T*>(d + (int64_t)dy * dpitch)[dx] = tile[sy - y0][r];
     }
 }
 
 hipError_t launch_turn(hipStream_t st, int bytes, int right, int nframes, const uint8_t* src, int64_t sfs, int spitch, int w, int h, uint8_t* dst,
-                       int64_t dfs, int dpitch)
+                       int64_t dfs, int dpitch, int line_parity)
 {
     if (nframes <= 0 || w <= 0 || h <= 0) return hipSuccess;
     dim3 grid((w + kTile - 1) / kTile, (h + kTile - 1) / kTile, nframes), block(256);
@@ -83,9 +90,9 @@ hipError_t launch_turn(hipStream_t st, int bytes, int right, int nframes, const 
                              ? 1
                              : 0;
     switch (bytes) {
-    case 1: hipLaunchKernelGGL(k_turn<uint8_t>, grid, block, 0, st, src, sfs, spitch, w, h, dst, dfs, dpitch, right, dword_ok); break;
-    case 2: hipLaunchKernelGGL(k_turn<uint16_t>, grid, block, 0, st, src, sfs, spitch, w, h, dst, dfs, dpitch, right, dword_ok); break;
-    default: hipLaunchKernelGGL(k_turn<uint32_t>, grid, block, 0, st, src, sfs, spitch, w, h, dst, dfs, dpitch, right, dword_ok); break;
+    case 1: hipLaunchKernelGGL(k_turn<uint8_t>, grid, block, 0, st, src, sfs, spitch, w, h, dst, dfs, dpitch, right, dword_ok, line_parity); break;
+    case 2: hipLaunchKernelGGL(k_turn<uint16_t>, grid, block, 0, st, src, sfs, spitch, w, h, dst, dfs, dpitch, right, dword_ok, line_parity); break;
+    default: hipLaunchKernelGGL(k_turn<uint32_t>, grid, block, 0, st, src, sfs, spitch, w, h, dst, dfs, dpitch, right, dword_ok, line_parity); break;
     }
     return hipGetLastError();
 }

@@ -297,84 +297,48 @@ def SangNom(clip: ClipFormat, order: int = 1, aa: int = 48, opt: int = -1, **kw)
     return SangNom2(clip, order=(2, 1, 0)[order], aa=aa, aac=0, opt=opt, **kw)
 
 
-class SangNomAA:
-    """The anti-aliasing idiom TurnLeft().SangNom2(...).TurnRight().SangNom2(...) with the frames kept on the
-    device between the two passes: two filter instances -- one for the turned clip, one for the
-    clip itself -- on one stream, and the library's turn kernel in between.  Not a function of the reference; the
-    result is what that script gives with it."""
-
-    def __init__(self, clip: ClipFormat, max_batch: int = 1, device: int = 0, **kw):
-        self.clip = clip
-        turned = ClipFormat(width=clip.height, height=clip.width, bytes=clip.bytes, bits=clip.bits, planes=clip.planes,
-                            subw=clip.subh, subh=clip.subw)
-        self.first = SangNom2(turned, max_batch=max_batch, device=device, **kw)
-        self.second = SangNom2(clip, max_batch=max_batch, device=device, stream=self.first.stream_handle(), **kw)
-        self._tmp = None
-
-    def close(self):
-        self.second.close()
-        self.first.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def process_batch(self, src, dst, parity=None):
-        """src[p], dst[p]: torch tensors [N, H_p, W_p] on the device.  Asynchronous on the instances' stream."""
-        import torch
-        n = self.first.nplanes
-        N = src[0].shape[0]
-        if self._tmp is None or self._tmp[0][0].shape[0] != N:
-            mk = lambda shape, like: torch.empty((N,) + tuple(shape), dtype=like.dtype, device=like.device)
-            self._tmp = ([mk(self.first.plane_shape_in(p), src[p]) for p in range(n)],
-                         [mk(self.first.plane_shape_out(p), src[p]) for p in range(n)],
-                         [mk(self.second.plane_shape_in(p), src[p]) for p in range(n)])
-            # the buffers were allocated on torch's current stream; the library runs on its own
-            torch.cuda.current_stream().synchronize()
-        t1, u1, t2 = self._tmp
-        for p in range(n):
-            self.first.turn(src[p], t1[p], -1)
-        self.first.process_batch(t1, u1, parity)
-        for p in range(n):
-            self.first.turn(u1[p], t2[p], +1)
-        return self.second.process_batch(t2, dst, parity)
-
-    def synchronize(self):
-        self.second.synchronize()
-
-
-class SangNomAAHost:
-    """The same idiom through the C ABI's one-call entry point (sn_aa_create / sn_aa_process_host): host planes in,
-    host planes out, the frame stays on the device between the two passes.  This is what the plugin function
-    SangNomAA (host/sangnom2_avs_plugin.cpp) binds."""
+class _AAContext:
+    """An sn_aa_context: the anti-aliasing idiom TurnLeft().SangNom2(...).TurnRight().SangNom2(...) as one call of the
+    library.  Not a function of the reference; the result is what that script gives with it."""
 
     def __init__(self, clip: ClipFormat, order: int = 1, aa: int = 48, aac: int = 0, luma: bool = True, chroma: bool = True,
-                 device: int = 0, isolated_planes: bool = False, fresh_pool: bool = False, opt: int = -1, **policy_kw):
+                 device: int = 0, isolated_planes: bool = False, fresh_pool: bool = False, opt: int = -1, max_batch: int = 1,
+                 host_depth: int = 0, stream: int | None = None, **policy_kw):
         if opt < -1 or opt > 1:
             raise SangNomError(capi.SN_ERR_CONFIG, "SangNom2: opt must be between -1..2.")  # sic, SangNom2.cpp:420
         self.clip = clip
+        self.max_batch = max_batch
         self._lib = capi.load()
         cfg = capi.SnConfig(
             struct_size=ctypes.sizeof(capi.SnConfig), width=clip.width, height=clip.height, bytes_per_sample=clip.bytes,
             bits_per_sample=clip.bits, num_planes=clip.planes, sub_w=clip.subw, sub_h=clip.subh, order=order, aa=aa, aac=aac,
-            dh=0, luma=int(luma), chroma=int(chroma), device=device, max_batch=1, mode=capi.SN_MODE_AUTO, host_depth=0,
-            isolated_planes=int(isolated_planes), fresh_pool=int(fresh_pool), stream=None)
+            dh=0, luma=int(luma), chroma=int(chroma), device=device, max_batch=max_batch, mode=capi.SN_MODE_AUTO, host_depth=host_depth,
+            isolated_planes=int(isolated_planes), fresh_pool=int(fresh_pool), stream=stream)
         self._h = ctypes.c_void_p()
-        pol = capi.policy(**{k: policy_kw.get(k) for k in ("small_launches", "chain", "copy_threads", "scratch_budget_mb")})
+        pol = capi.policy(**{k: policy_kw.get(k) for k in ("small_launches", "chain", "copy_threads", "scratch_budget_mb", "chroma_sweeps")})
         opts = capi.options(capi.arithmetic_of_opt(opt))
         rc = self._lib.sn_aa_create_ex(ctypes.byref(cfg), ctypes.byref(pol), ctypes.byref(opts), ctypes.byref(self._h))
         if rc != capi.SN_OK:
             self._h = None
             raise SangNomError(rc, self._lib.sn_aa_last_error(None).decode())
 
+    @property
+    def nplanes(self) -> int:
+        return min(self.clip.planes, 3)
+
+    def plane_shape(self, p: int):
+        return (self.clip.height >> (self.clip.subh if p else 0), self.clip.width >> (self.clip.subw if p else 0))
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.sn_aa_destroy(self._h)
             self._h = None
 
-    __del__ = close
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
     def __enter__(self):
         return self
@@ -382,16 +346,87 @@ class SangNomAAHost:
     def __exit__(self, *a):
         self.close()
 
-    def get_frame(self, src, parity: int = 1):
-        n = min(self.clip.planes, 3)
-        dst = [np.zeros_like(src[p]) for p in range(n)]
-        sp, dp = (ctypes.c_void_p * 3)(), (ctypes.c_void_p * 3)()
-        spi, dpi = (ctypes.c_int32 * 3)(), (ctypes.c_int32 * 3)()
-        for p in range(n):
-            if src[p].dtype != self.clip.dtype or src[p].strides[1] != self.clip.bytes:
-                raise ValueError("planes must be x-contiguous arrays of the clip's sample type")
-            sp[p], dp[p], spi[p], dpi[p] = src[p].ctypes.data, dst[p].ctypes.data, src[p].strides[0], dst[p].strides[0]
-        rc = self._lib.sn_aa_process_host(self._h, sp, spi, dp, dpi, int(parity))
+    def _check(self, rc: int):
         if rc != capi.SN_OK:
             raise SangNomError(rc, self._lib.sn_aa_last_error(self._h).decode())
+
+    def synchronize(self):
+        self._check(self._lib.sn_aa_synchronize(self._h))
+
+    def stream_handle(self) -> int:
+        return self._lib.sn_aa_get_stream(self._h)
+
+    def info(self, pass_: int) -> capi.SnInfo:
+        """sn_get_info of one of the two filter instances: 0 the turned clip's, 1 the clip's."""
+        i = capi.SnInfo(struct_size=ctypes.sizeof(capi.SnInfo))
+        self._check(self._lib.sn_aa_get_info(self._h, int(pass_), ctypes.byref(i)))
+        return i
+
+
+class SangNomAA(_AAContext):
+    """The idiom on device-resident batches (sn_aa_process_device_strided): the frames stay on the device between the
+    two passes."""
+
+    def __init__(self, clip: ClipFormat, max_batch: int = 1, device: int = 0, **kw):
+        super().__init__(clip, max_batch=max_batch, device=device, **kw)
+
+    def process_batch(self, src, dst, parity=None):
+        """src[p], dst[p]: torch tensors [N, H_p, W_p] on the device.  Asynchronous on the call's stream."""
+        n, B = self.nplanes, self.clip.bytes
+        N = src[0].shape[0]
+        sp, dp = (ctypes.c_void_p * 3)(), (ctypes.c_void_p * 3)()
+        spi, dpi = (ctypes.c_int32 * 3)(), (ctypes.c_int32 * 3)()
+        sfs, dfs = (ctypes.c_int64 * 3)(), (ctypes.c_int64 * 3)()
+        for p in range(n):
+            s, d = src[p], dst[p]
+            if tuple(s.shape) != (N,) + self.plane_shape(p) or tuple(d.shape) != (N,) + self.plane_shape(p):
+                raise ValueError(f"plane {p}: bad shape {tuple(s.shape)} -> {tuple(d.shape)}")
+            if s.stride(2) != 1 or d.stride(2) != 1 or s.element_size() != B or d.element_size() != B:
+                raise ValueError("planes must be x-contiguous tensors of the clip's sample type")
+            if not s.is_cuda or not d.is_cuda:
+                raise ValueError("process_batch needs device-resident tensors (SangNomAAHost takes host planes)")
+            sp[p], dp[p] = s.data_ptr(), d.data_ptr()
+            spi[p], dpi[p] = s.stride(1) * B, d.stride(1) * B
+            sfs[p], dfs[p] = s.stride(0) * B, d.stride(0) * B
+        par = None if parity is None else (ctypes.c_int32 * N)(*[int(x) for x in parity])
+        self._check(self._lib.sn_aa_process_device_strided(self._h, N, sp, sfs, spi, dp, dfs, dpi, par))
+        return dst
+
+
+class SangNomAAHost(_AAContext):
+    """The idiom on host planes (sn_aa_process_host; sn_aa_submit_host / sn_aa_collect_host for look-ahead): the frame
+    crosses PCIe once each way.  This is what the plugin function SangNomAA (host/sangnom2_avs_plugin.cpp) binds."""
+
+    def _plane_args(self, planes):
+        ptr, pitch = (ctypes.c_void_p * 3)(), (ctypes.c_int32 * 3)()
+        for p in range(self.nplanes):
+            a = planes[p]
+            if a.dtype != self.clip.dtype or a.strides[1] != self.clip.bytes:
+                raise ValueError("planes must be x-contiguous arrays of the clip's sample type")
+            ptr[p], pitch[p] = a.ctypes.data, a.strides[0]
+        return ptr, pitch
+
+    def get_frame(self, src, parity: int = 1):
+        dst = [np.zeros_like(src[p]) for p in range(self.nplanes)]
+        sp, spi = self._plane_args(src)
+        dp, dpi = self._plane_args(dst)
+        self._check(self._lib.sn_aa_process_host(self._h, sp, spi, dp, dpi, int(parity)))
+        return dst
+
+    def slots(self) -> int:
+        return self._lib.sn_aa_host_slots(self._h)
+
+    def submit(self, src, parity: int = 1) -> int:
+        """Queue one host frame on the ring; returns its slot (SangNomError with code SN_ERR_BUSY when the ring is full)."""
+        sp, spi = self._plane_args(src)
+        slot = ctypes.c_int32(-1)
+        self._check(self._lib.sn_aa_submit_host(self._h, sp, spi, int(parity), ctypes.byref(slot)))
+        return slot.value
+
+    def collect(self, slot: int, dst=None):
+        """Wait for the frame in `slot`; returns its planes."""
+        if dst is None:
+            dst = [np.zeros(self.plane_shape(p), dtype=self.clip.dtype) for p in range(self.nplanes)]
+        dp, dpi = self._plane_args(dst)
+        self._check(self._lib.sn_aa_collect_host(self._h, int(slot), dp, dpi))
         return dst

@@ -116,6 +116,12 @@ AVSValue __cdecl Create_SangNomAA(AVSValue args, void*, IScriptEnvironment* env)
     a.aa = args[2].AsInt(48);
     a.aac = args[3].AsInt(0);
     a.device = args[4].AsInt(0);
+    a.luma = args[5].AsBool(true);
+    a.chroma = args[6].AsBool(true);
+    a.opt = args[7].AsInt(-1);
+    a.isolated = args[8].AsBool(false);
+    a.fresh = args[9].AsBool(false);
+    a.lookahead = args[10].AsInt(-1);
     return new SangNomAA(args[0].AsClip(), a, env);
 }
 
@@ -139,7 +145,7 @@ extern "C" __declspec(dllexport) const char* __stdcall AvisynthPluginInit3(IScri
     env->AddFunction("SangNom", "c[order]i[aa]i[opt]i", Create_SangNom, 0);                                        // :482
     env->AddFunction("SangNom2HIP", "c[order]i[aa]i[aac]i[threads]i[dh]b[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i[device]i",
                      Create_SangNom2HIP, 0);
-    env->AddFunction("SangNomAA", "c[order]i[aa]i[aac]i[device]i", Create_SangNomAA, 0);
+    env->AddFunction("SangNomAA", "c[order]i[aa]i[aac]i[device]i[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i", Create_SangNomAA, 0);
     return "SangNom2";
 }
 #endif  // SN_HAVE_AVISYNTH

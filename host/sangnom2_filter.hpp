@@ -226,6 +226,8 @@ private:
 // aa, aac) as one filter over sn_aa_process_host -- the frame crosses PCIe once each way instead of four times
 // (README.md:3 of the reference: "mainly used in anti-aliasing scripts").  Same checks and messages
 // as SangNom2 for the clip itself; the turned clip must pass them as well (e.g. an even WIDTH).
+// Args::lookahead works as in Filter, over sn_aa_submit_host / sn_aa_collect_host, and only when BOTH passes are
+// history-free (sn_aa_get_info); otherwise GetFrame stays synchronous, for the reason given in Filter's constructor.
 template <class Host>
 class AAFilter {
 public:
@@ -259,6 +261,12 @@ public:
         c.chroma = a.chroma;
         c.device = a.device;
         c.max_batch = 1;
+        int la = a.lookahead;
+        if (la < 0) {
+            const char* e = std::getenv("SANGNOM_LOOKAHEAD");
+            la = e ? std::atoi(e) : 1;
+        }
+        c.host_depth = std::max(1, std::min(la, 256));
         c.isolated_planes = a.isolated ? 1 : 0;
         c.fresh_pool = a.fresh ? 1 : 0;
         sn_policy pol = a.policy;
@@ -269,15 +277,26 @@ public:
         if (sn_aa_create_ex(&c, &pol, &opts, &ctx_) != SN_OK) env->ThrowError("%s: %s", name, sn_aa_last_error(nullptr));
         planes_ = c.num_planes;
         alpha_ = Host::NumComponents(vi_) == 4;
+        num_frames_ = Host::NumFrames(vi_);
+        sn_info i0{}, i1{};
+        i0.struct_size = i1.struct_size = (int32_t)sizeof i0;
+        const bool ahead = c.host_depth > 1 && sn_aa_get_info(ctx_, 0, &i0) == SN_OK && sn_aa_get_info(ctx_, 1, &i1) == SN_OK &&
+                           i0.history_free && i1.history_free;
+        slots_ = ahead ? sn_aa_host_slots(ctx_) : 1;
     }
     AAFilter(const AAFilter&) = delete;
     AAFilter& operator=(const AAFilter&) = delete;
-    ~AAFilter() { sn_aa_destroy(ctx_); }
+    ~AAFilter()
+    {
+        inflight_.clear();  // frames still in the ring are dropped with the context
+        sn_aa_destroy(ctx_);
+    }
 
     const Info& GetInfo() const { return vi_; }
 
     FramePtr GetFrame(int n, Env* env)
     {
+        if (slots_ > 1) return GetFrameAhead(n, env);
         FramePtr src = Host::GetFrame(child_, n, env);
         FramePtr dst = Host::NewFrame(env, vi_, src);
         const void* sp[3] = {nullptr, nullptr, nullptr};
@@ -291,15 +310,70 @@ public:
         }
         const int parity = args_.order == 0 ? (Host::GetParity(child_, n) ? 1 : 0) : 1;
         if (sn_aa_process_host(ctx_, sp, spitch, dp, dpitch, parity) != SN_OK) env->ThrowError("SangNomAA: %s", sn_aa_last_error(ctx_));
-        if (alpha_) {  // passed through (see Filter::CopyAlpha)
-            const size_t row = (size_t)Host::Width(vi_) * Host::ComponentSize(vi_);
-            for (int y = 0; y < Host::Height(vi_); ++y)
-                std::memcpy(Host::WritePtr(dst, 3) + (size_t)y * Host::Pitch(dst, 3), Host::ReadPtr(src, 3) + (size_t)y * Host::Pitch(src, 3), row);
-        }
+        CopyAlpha(src, dst);
         return dst;
     }
 
 private:
+    struct Pending {
+        int n;
+        FramePtr src, dst;  // src is held until the slot is collected (pinned planes are read by the device as they lie)
+        int32_t slot;
+    };
+
+    void CopyAlpha(const FramePtr& src, const FramePtr& dst) const  // passed through (see Filter::CopyAlpha)
+    {
+        if (!alpha_) return;
+        const size_t row = (size_t)Host::Width(vi_) * Host::ComponentSize(vi_);
+        for (int y = 0; y < Host::Height(vi_); ++y)
+            std::memcpy(Host::WritePtr(dst, 3) + (size_t)y * Host::Pitch(dst, 3), Host::ReadPtr(src, 3) + (size_t)y * Host::Pitch(src, 3), row);
+    }
+
+    FramePtr Collect(Env* env)
+    {
+        Pending p = inflight_.front();
+        inflight_.pop_front();
+        void* dp[3] = {nullptr, nullptr, nullptr};
+        int32_t dpitch[3] = {0, 0, 0};
+        for (int i = 0; i < planes_; ++i) {
+            dp[i] = Host::WritePtr(p.dst, i);
+            dpitch[i] = Host::Pitch(p.dst, i);
+        }
+        if (sn_aa_collect_host(ctx_, p.slot, dp, dpitch) != SN_OK) env->ThrowError("SangNomAA: %s", sn_aa_last_error(ctx_));
+        return p.dst;
+    }
+
+    // Filter::GetFrameAhead over the anti-aliasing call's ring: a request out of sequence drains it and starts over
+    FramePtr GetFrameAhead(int n, Env* env)
+    {
+        if (inflight_.empty() || inflight_.front().n != n) {
+            while (!inflight_.empty()) Collect(env);
+            next_ = n;
+        }
+        while ((int)inflight_.size() < slots_ && next_ < num_frames_) {
+            Pending p;
+            p.n = next_++;
+            p.src = Host::GetFrame(child_, p.n, env);
+            p.dst = Host::NewFrame(env, vi_, p.src);
+            const void* sp[3] = {nullptr, nullptr, nullptr};
+            int32_t spitch[3] = {0, 0, 0};
+            for (int i = 0; i < planes_; ++i) {
+                sp[i] = Host::ReadPtr(p.src, i);
+                spitch[i] = Host::Pitch(p.src, i);
+            }
+            const int parity = args_.order == 0 ? (Host::GetParity(child_, p.n) ? 1 : 0) : 1;
+            if (sn_aa_submit_host(ctx_, sp, spitch, parity, &p.slot) != SN_OK) env->ThrowError("SangNomAA: %s", sn_aa_last_error(ctx_));
+            CopyAlpha(p.src, p.dst);
+            inflight_.push_back(p);
+        }
+        if (inflight_.empty()) env->ThrowError("SangNomAA: frame %d is outside the clip", n);
+        return Collect(env);
+    }
+
+    std::deque<Pending> inflight_;
+    int next_ = 0;
+    int num_frames_ = 0;
+    int slots_ = 1;
     ClipPtr child_;
     Args args_;
     Info vi_{};

@@ -2,13 +2,15 @@
 // engine drives the reference plugin: build a source clip, construct SangNom2(clip, ...), request
 // frames with GetFrame(n).  tests/test_host_adapter.py feeds it frames and compares the output with
 // the oracle.
-//   sn_host_test <in.bin> <out.bin> [lookahead | aa [first-frame-order...]]
-// lookahead > 1 runs GetFrame over the host ring; "aa" constructs SangNomAA (sangnom::AAFilter) instead of SangNom2;
+//   sn_host_test <in.bin> <out.bin> [lookahead | aa | aa:<lookahead> [first-frame-order...]]
+// lookahead > 1 runs GetFrame over the host ring; "aa" constructs SangNomAA (sangnom::AAFilter) instead of SangNom2,
+// "aa:<N>" with look-ahead N;
 // the optional list gives the order in which frames are requested (default 0 .. nframes-1), e.g. to exercise a seek.
 // planes = 4 in the header is a YUVA clip: the fourth plane is luma-sized and passed through.
 // in.bin : 14 x int32 {w,h,bytes,bits,planes,subw,subh,order,aa,aac,dh,luma,chroma,nframes}, then per
 //          frame: int32 parity + the planes, tightly packed.
-// SN_HOST_TEST_OPT=<-1|0|1> in the environment of this TEST program is the script argument `opt` (default -1).
+// SN_HOST_TEST_OPT=<-1|0|1> in the environment of this TEST program is the script argument `opt` (default -1),
+// SN_HOST_TEST_FRESH=1 sets Args::fresh.
 // out.bin: per frame the output planes, tightly packed.  On a constructor error: exit code 3 and
 //          the message on stdout.
 #include <cstdio>
@@ -68,7 +70,9 @@ int main(int argc, char** argv)
     // for the whole-plane sweeps instead of the small-launch paths
     if (const char* e = getenv("SN_HOST_TEST_SWEEPS")) a.policy.small_launches = atoi(e) ? SN_SMALL_SWEEP : SN_SMALL_AUTO;
     if (const char* e = getenv("SN_HOST_TEST_OPT")) a.opt = atoi(e);
-    const bool aa_idiom = argc > 3 && strcmp(argv[3], "aa") == 0;
+    if (const char* e = getenv("SN_HOST_TEST_FRESH")) a.fresh = atoi(e) != 0;
+    const bool aa_idiom = argc > 3 && strncmp(argv[3], "aa", 2) == 0 && (argv[3][2] == 0 || argv[3][2] == ':');
+    if (aa_idiom && argv[3][2] == ':') a.lookahead = atoi(argv[3] + 3);
     if (argc > 3 && !aa_idiom) a.lookahead = atoi(argv[3]);
     std::vector<int> order;
     for (int i = 4; i < argc; ++i) order.push_back(atoi(argv[i]));

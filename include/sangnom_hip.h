@@ -274,8 +274,10 @@ int sn_turn_device(sn_context* ctx, int32_t direction, int32_t nframes, const vo
  * host planes (README.md:3 of the reference: "mainly used in anti-aliasing scripts"): the frame
  * crosses PCIe once each way and stays on the device between the two passes (two filter instances -- one for the
  * turned clip, one for the clip itself -- on one stream, sn_turn_device in between).  `cfg` describes the clip
- * (dh must be 0; luma / chroma / isolated_planes / fresh_pool / device apply to both passes; max_batch, mode, stream and
- * host_depth are ignored); the turned clip must pass the reference's checks too (sn_aa_create reports the first
+ * (dh must be 0; luma / chroma / isolated_planes / fresh_pool / device apply to both passes; max_batch >= 1: frames one
+ * sn_aa_process_device_strided call may carry; host_depth: slots of the host ring, 0 = 4, allocated when
+ * sn_aa_submit_host is first called; stream: the stream of the call's device work, NULL = one of its own; mode is
+ * ignored: both passes run SN_MODE_AUTO); the turned clip must pass the reference's checks too (sn_aa_create reports the first
  * pass's message otherwise).  The result is what that script gives with the reference: two instances, so for widths
  * or heights that are not a multiple of 32 each pass carries its own pool history from frame to frame.  Not a
  * function of the reference; host/sangnom2_avs_plugin.cpp registers it as SangNomAA. */
@@ -286,7 +288,31 @@ int sn_aa_create_ex(const sn_config* cfg, const sn_policy* policy, const sn_opti
 int sn_aa_process_host(sn_aa_context* ctx, const void* const src[3], const int32_t src_pitch[3], void* const dst[3],
                        const int32_t dst_pitch[3], int32_t parity);
 const char* sn_aa_last_error(const sn_aa_context* ctx); /* ctx == NULL: last failed sn_aa_create on this thread */
-void sn_aa_destroy(sn_aa_context* ctx);
+void sn_aa_destroy(sn_aa_context* ctx); /* waits for frames still in flight */
+
+/* The same idiom on `nframes` (<= cfg.max_batch) device-resident frames, laid out as for sn_process_device_strided;
+ * asynchronous on the call's stream.  Frame f of the result is what nframes calls of sn_aa_process_host give in order
+ * (each pass sees its frames in order, so history-carrying clips are the script's).  The frames are walked in chunks:
+ * turn, first pass, turn back, second pass; the intermediates are allocated at creation and count against
+ * sn_policy.scratch_budget_mb, a batch beyond what fits takes more chunks.  A turn writes only the lines the following
+ * pass keeps; a plane that is not processed (luma / chroma = 0) is copied from src to dst once. */
+int sn_aa_process_device_strided(sn_aa_context* ctx, int32_t nframes, const void* const src[3], const int64_t src_frame_stride[3],
+                                 const int32_t src_pitch[3], void* const dst[3], const int64_t dst_frame_stride[3],
+                                 const int32_t dst_pitch[3], const int32_t* parity /* NULL = all 1 */);
+/* Waits for everything the context has queued (device batches and host frames in flight). */
+int sn_aa_synchronize(sn_aa_context* ctx);
+/* The hipStream_t of the call's device work (cfg.stream if one was given); NULL for a NULL context. */
+void* sn_aa_get_stream(sn_aa_context* ctx);
+/* sn_get_info of one of the two filter instances: pass 0 is the turned clip's, pass 1 the clip's. */
+int sn_aa_get_info(sn_aa_context* ctx, int32_t pass, sn_info* info);
+/* The host ring of the anti-aliasing call, with the contract of sn_host_slots / sn_submit_host / sn_collect_host: slots
+ * are taken round-robin, SN_ERR_BUSY when the next slot has not been collected, and collecting in submission order never
+ * waits for a later frame.  Upload, device work and download of different frames overlap; the device work runs in
+ * submission order.  Planes inside memory pinned with sn_pin_host_buffer are transferred as they lie (keep them until
+ * the slot is collected), others are staged.  sn_aa_host_slots returns the number of slots (<= 0 on failure). */
+int sn_aa_host_slots(sn_aa_context* ctx);
+int sn_aa_submit_host(sn_aa_context* ctx, const void* const src[3], const int32_t src_pitch[3], int32_t parity, int32_t* slot);
+int sn_aa_collect_host(sn_aa_context* ctx, int32_t slot, void* const dst[3], const int32_t dst_pitch[3]);
 
 int sn_synchronize(sn_context* ctx);
 void* sn_get_stream(sn_context* ctx); /* the hipStream_t the context launches on */

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Device-resident rate of the anti-aliasing idiom TurnLeft().SangNom2().TurnRight().SangNom2() (SangNomAA) and of
-the turn kernel alone.  usage: python tools/aa_bench.py [--frames 512] [--fresh 1]"""
+the turn kernel alone; with --host, frames from pageable host memory: the synchronous call (SangNomAAHost.get_frame)
+against the ring at --depth.
+usage: python tools/aa_bench.py [--frames 512] [--fresh 1] [--fmt Y8] [--size 3840x2160] [--host [--depth 8]]"""
 import argparse
 import json
 import os
@@ -10,7 +12,47 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from avisynth_sangnom2_amd import SangNom2, SangNomAA, clip_format  # noqa: E402
+import numpy as np  # noqa: E402
+
+from avisynth_sangnom2_amd import SangNom2, SangNomAA, SangNomAAHost, clip_format  # noqa: E402
+
+
+def host_rates(clip, a):
+    """Frames from pageable host memory, every result collected into pageable memory: frames/s of the synchronous call and
+    of the ring with as many frames in flight as it holds.  A whole frame crosses PCIe each way."""
+    rng = np.random.default_rng(1)
+    n = min(a.frames, 64)
+    shapes = [(clip.height >> (clip.subh if p else 0), clip.width >> (clip.subw if p else 0)) for p in range(clip.planes)]
+    frames = [[rng.integers(0, 256, s, dtype=np.uint8) for s in shapes] for _ in range(8)]
+    out = {"clip": f"{clip.width}x{clip.height} planes {clip.planes}", "host_frames": n, "fresh_pool": bool(a.fresh),
+           "pcie_bytes_per_frame_each_way": sum(s[0] * s[1] for s in shapes) * clip.bytes}
+    with SangNomAAHost(clip, aac=48 if clip.planes > 1 else 0, fresh_pool=bool(a.fresh)) as flt:
+        for i in range(3):
+            flt.get_frame(frames[i])
+        t0 = time.perf_counter()
+        for i in range(n):
+            flt.get_frame(frames[i % 8])
+        out["sync_fps"] = round(n / (time.perf_counter() - t0), 1)
+    if not hasattr(SangNomAAHost, "submit"):
+        return out
+    with SangNomAAHost(clip, aac=48 if clip.planes > 1 else 0, fresh_pool=bool(a.fresh), host_depth=a.depth) as flt:
+        slots = flt.slots()
+        dst = [np.zeros(s, np.uint8) for s in shapes]
+
+        def run(count):
+            pending, f, done = [], 0, 0
+            while done < count:
+                while f < count and len(pending) < slots:
+                    pending.append(flt.submit(frames[f % 8]))
+                    f += 1
+                flt.collect(pending.pop(0), dst)
+                done += 1
+        run(2 * slots)
+        t0 = time.perf_counter()
+        run(n)
+        out["ring_fps"] = round(n / (time.perf_counter() - t0), 1)
+        out["ring_slots"] = slots
+    return out
 
 
 def main():
@@ -19,15 +61,23 @@ def main():
     ap.add_argument("--fresh", type=int, default=1)
     ap.add_argument("--fmt", default="Y8")
     ap.add_argument("--size", default="3840x2160")
+    ap.add_argument("--host", action="store_true", help="frames from host memory: the synchronous call against the ring")
+    ap.add_argument("--depth", type=int, default=8, help="--host: slots of the ring")
     a = ap.parse_args()
     w, h = [int(x) for x in a.size.split("x")]
     clip = clip_format(a.fmt, w, h)
+    if clip.bytes != 1:
+        sys.exit("aa_bench: 8-bit formats only")
+    if a.host:
+        print(json.dumps(host_rates(clip, a)))
+        return
     dev = torch.device("cuda:0")
     N = a.frames
-    src = [torch.randint(0, 256, (N, h, w), device=dev, dtype=torch.uint8)]
-    dst = [torch.empty_like(src[0])]
+    src = [torch.randint(0, 256, (N, h >> (clip.subh if p else 0), w >> (clip.subw if p else 0)), device=dev, dtype=torch.uint8)
+           for p in range(clip.planes)]
+    dst = [torch.empty_like(s) for s in src]
     out = {"clip": f"{a.fmt} {w}x{h}", "frames": N, "fresh_pool": bool(a.fresh)}
-    with SangNomAA(clip, max_batch=N, fresh_pool=bool(a.fresh)) as aa:
+    with SangNomAA(clip, max_batch=N, fresh_pool=bool(a.fresh), aac=48 if clip.planes > 1 else 0) as aa:
         torch.cuda.synchronize()
         for _ in range(2):
             aa.process_batch(src, dst)
