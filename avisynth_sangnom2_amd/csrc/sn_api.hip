@@ -2091,6 +2091,9 @@ int sn_debug_read_coupled_rows(sn_context* h, int32_t which, void* host_dst, siz
 // that each instance sees its frames in order.  Host frames go through groups of frame slots: upload on one stream, the
 // device work of every group on the call's stream (in submission order, which is what a history-carrying pass needs),
 // download on a third; events order the three, nothing waits inside a kernel.
+// With cfg.dh both passes double the height: the idiom enlarges by two in both directions.  The first pass's output is
+// then twice as high as the turned clip, the second pass's input twice as wide as the clip and its output (the
+// destination) twice as wide and twice as high; without dh every one of these geometries is the clip's or the turned one.
 struct sn_aa_context {
     sn_config cfg{};
     sn_context* first = nullptr;   // the turned clip
@@ -2103,10 +2106,16 @@ struct sn_aa_context {
     int w[3] = {0, 0, 0}, h[3] = {0, 0, 0};  // clip geometry per plane
     int pitch[3] = {0, 0, 0}, tpitch[3] = {0, 0, 0};
     int64_t cbytes[3] = {0, 0, 0}, tbytes[3] = {0, 0, 0};  // one frame of a plane: clip geometry / turned
+    int ow[3] = {0, 0, 0}, oh[3] = {0, 0, 0};              // the destination's geometry per plane (dh: 2w x 2h)
+    int opitch[3] = {0, 0, 0};
+    int64_t obytes[3] = {0, 0, 0};
+    int64_t u1bytes[3] = {0, 0, 0};                        // the first pass's output: tpitch x ow lines
+    int t2pitch[3] = {0, 0, 0};                            // the second pass's input: ow wide, h high
+    int64_t t2bytes[3] = {0, 0, 0};
     int cap = 0;                                       // frames the intermediates hold (a chunk)
-    uint8_t* d_t1[3] = {nullptr, nullptr, nullptr};   // turned: input of the first pass (only its kept lines are written)
-    uint8_t* d_u1[3] = {nullptr, nullptr, nullptr};   // turned: its output
-    uint8_t* d_t2[3] = {nullptr, nullptr, nullptr};   // clip geometry: input of the second pass (kept lines only)
+    uint8_t* d_t1[3] = {nullptr, nullptr, nullptr};   // turned: input of the first pass (only its kept lines are written; dh: every line)
+    uint8_t* d_u1[3] = {nullptr, nullptr, nullptr};   // turned: its output (dh: twice as high)
+    uint8_t* d_t2[3] = {nullptr, nullptr, nullptr};   // turned back: input of the second pass (kept lines only; dh: every line, twice as wide)
     // host frames: `per_group` slots form a group whose frames one batch works on; the ring's groups, then one group of
     // one slot for the synchronous call
     struct Slot {
@@ -2174,14 +2183,14 @@ static int aa_ensure_intermediates(sn_aa_context* a, int frames)
     if (frames <= a->cap) return SN_OK;
     int64_t per_frame = 0;
     for (int p = 0; p < a->planes; ++p)
-        if (a->process[p]) per_frame += 2 * a->tbytes[p] + a->cbytes[p];
+        if (a->process[p]) per_frame += a->tbytes[p] + a->u1bytes[p] + a->t2bytes[p];
     const int64_t fit = per_frame > 0 ? scratch_budget(reinterpret_cast<Context*>(a->first)) / per_frame : frames;
     const int cap = (int)(fit < 1 ? 1 : fit < frames ? fit : frames);
     if (cap <= a->cap) return SN_OK;
     SN_AA_HIP(hipStreamSynchronize(a->stream));
     for (int p = 0; p < a->planes; ++p) {
         if (!a->process[p]) continue;  // copied from source to destination: no turn, no pass, no intermediate
-        const size_t nb[3] = {(size_t)a->tbytes[p] * cap, (size_t)a->tbytes[p] * cap, (size_t)a->cbytes[p] * cap};
+        const size_t nb[3] = {(size_t)a->tbytes[p] * cap, (size_t)a->u1bytes[p] * cap, (size_t)a->t2bytes[p] * cap};
         uint8_t** q[3] = {&a->d_t1[p], &a->d_u1[p], &a->d_t2[p]};
         for (int k = 0; k < 3; ++k) {
             if (*q[k]) SN_AA_HIP(hipFree(*q[k]));
@@ -2227,7 +2236,6 @@ int sn_aa_create_ex(const sn_config* cfg, const sn_policy* policy, const sn_opti
     if (!cfg || !out) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "cfg / out is NULL");
     *out = nullptr;
     if (cfg->struct_size != (int32_t)sizeof(sn_config)) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_config.struct_size mismatch");
-    if (cfg->dh) return fail_aa(nullptr, SN_ERR_UNSUPPORTED, "sn_aa_create: dh is not part of the anti-aliasing idiom");
     if (cfg->max_batch < 0) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "max_batch must be >= 0");
     if (cfg->host_depth < 0 || cfg->host_depth > 256) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "host_depth must be 0..256");
     sn_aa_context* a = new (std::nothrow) sn_aa_context();
@@ -2249,7 +2257,12 @@ int sn_aa_create_ex(const sn_config* cfg, const sn_policy* policy, const sn_opti
     c1.mode = SN_MODE_AUTO;
     int rc = sn_create_ex(&c1, policy, options, &a->first);
     if (rc != SN_OK) return fail_aa(a, rc, sn_last_error(nullptr));
-    sn_config c2 = *cfg;
+    sn_config c2 = *cfg;  // TurnRight of the first pass's output: with dh that is twice as wide as the clip
+    if (cfg->dh) {
+        if (cfg->width > INT32_MAX / 2)  // what the second pass's own check would say, had 2W fitted its field
+            return fail_aa(a, SN_ERR_UNSUPPORTED, "width " + std::to_string(2 * (int64_t)cfg->width) + " exceeds the supported maximum of 8192");
+        c2.width = 2 * cfg->width;
+    }
     c2.max_batch = inner_batch;
     c2.mode = SN_MODE_AUTO;
     c2.stream = sn_get_stream(a->first);
@@ -2261,13 +2274,20 @@ int sn_aa_create_ex(const sn_config* cfg, const sn_policy* policy, const sn_opti
     a->planes = cfg->num_planes < 3 ? cfg->num_planes : 3;
     const int B = cfg->bytes_per_sample;
     for (int p = 0; p < a->planes; ++p) {
-        a->process[p] = f1->process[p];
+        a->process[p] = cfg->dh || f1->process[p];  // dh forces every plane, as in the reference (SangNom2.cpp:361-366)
         a->w[p] = p ? cfg->width >> cfg->sub_w : cfg->width;
         a->h[p] = p ? cfg->height >> cfg->sub_h : cfg->height;
         a->pitch[p] = (a->w[p] * B + 255) & ~255;
         a->tpitch[p] = (a->h[p] * B + 255) & ~255;
         a->cbytes[p] = (int64_t)a->pitch[p] * a->h[p];
         a->tbytes[p] = (int64_t)a->tpitch[p] * a->w[p];
+        a->ow[p] = cfg->dh ? (p ? c2.width >> cfg->sub_w : c2.width) : a->w[p];
+        a->oh[p] = cfg->dh ? 2 * a->h[p] : a->h[p];
+        a->opitch[p] = (a->ow[p] * B + 255) & ~255;
+        a->obytes[p] = (int64_t)a->opitch[p] * a->oh[p];
+        a->u1bytes[p] = (int64_t)a->tpitch[p] * a->ow[p];
+        a->t2pitch[p] = a->opitch[p];
+        a->t2bytes[p] = (int64_t)a->t2pitch[p] * a->h[p];
     }
     if (int rc2 = aa_ensure_intermediates(a, a->max_batch)) return fail_aa(a, rc2, a->err);
     *out = a;
@@ -2291,8 +2311,20 @@ static int aa_run(sn_aa_context* a, int n, const void* const src[3], const int64
     for (int f0 = 0; f0 < n; f0 += a->cap) {
         const int m = n - f0 < a->cap ? n - f0 : a->cap;
         const int32_t* par = parity ? parity + f0 : nullptr;
-        // a turn writes the lines its pass keeps: one launch per run of frames with the same field offset, as run_batch cuts them
+        // a turn writes the lines its pass keeps: one launch per run of frames with the same field offset, as run_batch cuts them;
+        // a dh pass reads every line of its source: the whole form, one launch for the chunk
         auto turns = [&](int right) -> int {
+            if (a->cfg.dh) {
+                for (int p = 0; p < a->planes; ++p) {  // dh forces every plane
+                    if (!right)
+                        SN_AA_HIP(sn::launch_turn(st, B, 0, m, static_cast<const uint8_t*>(src[p]) + (int64_t)f0 * sfs[p], sfs[p], sp[p], a->w[p], a->h[p],
+                                                  a->d_t1[p], a->tbytes[p], a->tpitch[p], -1));
+                    else
+                        SN_AA_HIP(sn::launch_turn(st, B, 1, m, a->d_u1[p], a->u1bytes[p], a->tpitch[p], a->h[p], a->ow[p], a->d_t2[p], a->t2bytes[p],
+                                                  a->t2pitch[p], -1));
+                }
+                return SN_OK;
+            }
             for (int g0 = 0; g0 < m;) {
                 const int off = field_offset(c1, par ? par[g0] : 1);
                 int g1 = g0 + 1;
@@ -2303,19 +2335,19 @@ static int aa_run(sn_aa_context* a, int n, const void* const src[3], const int64
                         SN_AA_HIP(sn::launch_turn(st, B, 0, g1 - g0, static_cast<const uint8_t*>(src[p]) + (int64_t)(f0 + g0) * sfs[p], sfs[p], sp[p],
                                                   a->w[p], a->h[p], a->d_t1[p] + g0 * a->tbytes[p], a->tbytes[p], a->tpitch[p], off));
                     else  // TurnRight of the first pass's output
-                        SN_AA_HIP(sn::launch_turn(st, B, 1, g1 - g0, a->d_u1[p] + g0 * a->tbytes[p], a->tbytes[p], a->tpitch[p], a->h[p], a->w[p],
-                                                  a->d_t2[p] + g0 * a->cbytes[p], a->cbytes[p], a->pitch[p], off));
+                        SN_AA_HIP(sn::launch_turn(st, B, 1, g1 - g0, a->d_u1[p] + g0 * a->u1bytes[p], a->u1bytes[p], a->tpitch[p], a->h[p], a->ow[p],
+                                                  a->d_t2[p] + g0 * a->t2bytes[p], a->t2bytes[p], a->t2pitch[p], off));
                 }
                 g0 = g1;
             }
             return SN_OK;
         };
         if (int rc = turns(0)) return rc;
-        SN_AA_SN(a->first, run_batch(c1, st, 0, m, s1, a->tbytes, a->tpitch, d1, a->tbytes, a->tpitch, par));
+        SN_AA_SN(a->first, run_batch(c1, st, 0, m, s1, a->tbytes, a->tpitch, d1, a->u1bytes, a->tpitch, par));
         if (int rc = turns(1)) return rc;
         void* d2[3] = {nullptr, nullptr, nullptr};
         for (int p = 0; p < a->planes; ++p) d2[p] = static_cast<uint8_t*>(dst[p]) + (int64_t)f0 * dfs[p];
-        SN_AA_SN(a->second, run_batch(c2, st, 0, m, s2, a->cbytes, a->pitch, d2, dfs, dp, par));
+        SN_AA_SN(a->second, run_batch(c2, st, 0, m, s2, a->t2bytes, a->t2pitch, d2, dfs, dp, par));
     }
     return SN_OK;
 }
@@ -2329,7 +2361,7 @@ int sn_aa_process_device_strided(sn_aa_context* a, int32_t nframes, const void* 
     if (!src || !sfs || !sp || !dst || !dfs || !dp) return aa_fail(a, SN_ERR_INVALID_ARG, "plane / stride array is NULL");
     const int B = a->cfg.bytes_per_sample;
     for (int p = 0; p < a->planes; ++p) {
-        if (!src[p] || !dst[p] || sp[p] < a->w[p] * B || dp[p] < a->w[p] * B)
+        if (!src[p] || !dst[p] || sp[p] < a->w[p] * B || dp[p] < a->ow[p] * B)
             return aa_fail(a, SN_ERR_INVALID_ARG, "plane pointer is NULL or pitch smaller than the row");
         if (sp[p] % B || dp[p] % B || sfs[p] % B || dfs[p] % B || (uintptr_t)src[p] % B || (uintptr_t)dst[p] % B)
             return aa_fail(a, SN_ERR_INVALID_ARG, "plane pointer / pitch / frame stride not aligned to the sample size");
@@ -2380,13 +2412,13 @@ static int aa_ensure_group(sn_aa_context* a, int gi, int n)
     sn_aa_context::Group& g = a->groups[(size_t)gi];
     if (g.n) return SN_OK;
     for (int p = 0; p < a->planes; ++p) {
-        const size_t nb = (size_t)a->cbytes[p] * n;
+        const size_t nb = (size_t)a->cbytes[p] * n, onb = (size_t)a->obytes[p] * n;
         // a plane that is not processed never visits the device: its staging carries it from submission to collection
         SN_AA_HIP(hipHostMalloc(reinterpret_cast<void**>(&g.h_src[p]), nb, hipHostMallocDefault));
         if (!a->process[p]) continue;
-        SN_AA_HIP(hipHostMalloc(reinterpret_cast<void**>(&g.h_dst[p]), nb, hipHostMallocDefault));
+        SN_AA_HIP(hipHostMalloc(reinterpret_cast<void**>(&g.h_dst[p]), onb, hipHostMallocDefault));
         SN_AA_HIP(hipMalloc(reinterpret_cast<void**>(&g.d_src[p]), nb));
-        SN_AA_HIP(hipMalloc(reinterpret_cast<void**>(&g.d_out[p]), nb));
+        SN_AA_HIP(hipMalloc(reinterpret_cast<void**>(&g.d_out[p]), onb));
     }
     for (hipEvent_t* e : {&g.arrived, &g.swept, &g.done}) SN_AA_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
     g.slot.assign((size_t)n, sn_aa_context::Slot{});
@@ -2406,11 +2438,11 @@ static int aa_ensure_ring(sn_aa_context* a)
     return SN_OK;
 }
 
-static int aa_check_host_planes(sn_aa_context* a, const void* const ptr[3], const int32_t pitch[3])
+static int aa_check_host_planes(sn_aa_context* a, const void* const ptr[3], const int32_t pitch[3], bool out = false)
 {
     if (!ptr || !pitch) return aa_fail(a, SN_ERR_INVALID_ARG, "plane array is NULL");
     for (int p = 0; p < a->planes; ++p)
-        if (!ptr[p] || pitch[p] < a->w[p] * a->cfg.bytes_per_sample)
+        if (!ptr[p] || pitch[p] < (out ? a->ow[p] : a->w[p]) * a->cfg.bytes_per_sample)
             return aa_fail(a, SN_ERR_INVALID_ARG, "plane pointer is NULL or pitch smaller than the row");
     return SN_OK;
 }
@@ -2435,7 +2467,7 @@ static int aa_stage(sn_aa_context* a, sn_aa_context::Group& g, int k, const void
         }
         direct[p] = sn::plane_is_pinned(src[p], sp[p], a->w[p] * B, a->h[p]);
         if (!direct[p]) jobs[nj++] = {g.h_src[p] + k * a->cbytes[p], static_cast<const uint8_t*>(src[p]), a->pitch[p], sp[p], a->w[p] * B, a->h[p]};
-        if (dst && sn::plane_is_pinned(dst[p], dp[p], a->w[p] * B, a->h[p])) sl.out[p] = dst[p], sl.out_pitch[p] = dp[p];
+        if (dst && sn::plane_is_pinned(dst[p], dp[p], a->ow[p] * B, a->oh[p])) sl.out[p] = dst[p], sl.out_pitch[p] = dp[p];
     }
     if (nj) a->copier->run(jobs, nj);
     for (int p = 0; p < a->planes; ++p) {
@@ -2465,18 +2497,18 @@ static int aa_launch(sn_aa_context* a, sn_aa_context::Group& g)
     for (int p = 0; p < a->planes; ++p) {
         any = any || a->process[p];
         s3[p] = a->process[p] ? g.d_src[p] + g.lo * a->cbytes[p] : g.h_src[p];  // (not processed: never read on the device)
-        d3[p] = a->process[p] ? g.d_out[p] + g.lo * a->cbytes[p] : g.h_src[p];
+        d3[p] = a->process[p] ? g.d_out[p] + g.lo * a->obytes[p] : g.h_src[p];
     }
     if (any)
-        if (int rc = aa_run(a, n, s3, a->cbytes, a->pitch, d3, a->cbytes, a->pitch, par.data())) return rc;
+        if (int rc = aa_run(a, n, s3, a->cbytes, a->pitch, d3, a->obytes, a->opitch, par.data())) return rc;
     SN_AA_HIP(hipEventRecord(g.swept, a->stream));
     SN_AA_HIP(hipStreamWaitEvent(a->down, g.swept, 0));
     for (int k = g.lo; k < g.hi; ++k) {
         sn_aa_context::Slot& sl = g.slot[(size_t)k];
         for (int p = 0; p < a->planes; ++p) {
             if (!a->process[p]) continue;
-            SN_AA_HIP(hipMemcpy2DAsync(sl.out[p] ? sl.out[p] : g.h_dst[p] + k * a->cbytes[p], sl.out[p] ? (size_t)sl.out_pitch[p] : (size_t)a->pitch[p],
-                                       g.d_out[p] + k * a->cbytes[p], a->pitch[p], (size_t)a->w[p] * B, a->h[p], hipMemcpyDeviceToHost, a->down));
+            SN_AA_HIP(hipMemcpy2DAsync(sl.out[p] ? sl.out[p] : g.h_dst[p] + k * a->obytes[p], sl.out[p] ? (size_t)sl.out_pitch[p] : (size_t)a->opitch[p],
+                                       g.d_out[p] + k * a->obytes[p], a->opitch[p], (size_t)a->ow[p] * B, a->oh[p], hipMemcpyDeviceToHost, a->down));
         }
         sl.state = Context::kInFlight;
     }
@@ -2524,8 +2556,11 @@ static int aa_finish(sn_aa_context* a, sn_aa_context::Group& g, int k, void* con
     int nj = 0;
     for (int p = 0; p < a->planes; ++p) {
         if (a->process[p] ? sl.out[p] == dst[p] : sl.copied[p]) continue;  // already there
-        const uint8_t* from = (a->process[p] ? g.h_dst[p] : g.h_src[p]) + k * a->cbytes[p];
-        jobs[nj++] = {static_cast<uint8_t*>(dst[p]), from, dp[p], a->pitch[p], a->w[p] * B, a->h[p]};
+        // (a plane that is not processed has the clip's geometry on both sides: there is none with dh)
+        if (a->process[p])
+            jobs[nj++] = {static_cast<uint8_t*>(dst[p]), g.h_dst[p] + k * a->obytes[p], dp[p], a->opitch[p], a->ow[p] * B, a->oh[p]};
+        else
+            jobs[nj++] = {static_cast<uint8_t*>(dst[p]), g.h_src[p] + k * a->cbytes[p], dp[p], a->pitch[p], a->w[p] * B, a->h[p]};
     }
     if (nj) a->copier->run(jobs, nj);
     sl = sn_aa_context::Slot{};
@@ -2537,7 +2572,7 @@ int sn_aa_collect_host(sn_aa_context* a, int32_t slot, void* const dst[3], const
     if (!a) return aa_fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
     if (!a->ring_ready || slot < 0 || slot >= a->depth || a->groups[(size_t)(slot / a->per_group)].slot[(size_t)(slot % a->per_group)].state == Context::kFree)
         return aa_fail(a, SN_ERR_INVALID_ARG, "slot " + std::to_string(slot) + " holds no frame");
-    if (int rc = aa_check_host_planes(a, dst, dp)) return rc;
+    if (int rc = aa_check_host_planes(a, dst, dp, true)) return rc;
     SN_AA_HIP(hipSetDevice(a->cfg.device));
     return aa_finish(a, a->groups[(size_t)(slot / a->per_group)], slot % a->per_group, dst, dp);
 }
@@ -2549,7 +2584,7 @@ int sn_aa_process_host(sn_aa_context* a, const void* const src[3], const int32_t
     if (!a) return sn::fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
     if (!src || !sp || !dst || !dp) return aa_fail(a, SN_ERR_INVALID_ARG, "plane array is NULL");
     if (int rc = aa_check_host_planes(a, src, sp)) return rc;
-    if (int rc = aa_check_host_planes(a, dst, dp)) return rc;
+    if (int rc = aa_check_host_planes(a, dst, dp, true)) return rc;
     SN_AA_HIP(hipSetDevice(a->cfg.device));
     SN_AA_SN(a->first, prepare_small_launch_scratch(reinterpret_cast<Context*>(a->first)));
     SN_AA_SN(a->second, prepare_small_launch_scratch(reinterpret_cast<Context*>(a->second)));

@@ -299,20 +299,23 @@ def SangNom(clip: ClipFormat, order: int = 1, aa: int = 48, opt: int = -1, **kw)
 
 class _AAContext:
     """An sn_aa_context: the anti-aliasing idiom TurnLeft().SangNom2(...).TurnRight().SangNom2(...) as one call of the
-    library.  Not a function of the reference; the result is what that script gives with it."""
+    library.  Not a function of the reference; the result is what that script gives with it.
+    dh=True: both passes with dh=true, enlargement by two in both directions; every plane is processed (luma / chroma are
+    ignored, as in the reference) and every destination plane is twice as wide and twice as high as its source plane."""
 
     def __init__(self, clip: ClipFormat, order: int = 1, aa: int = 48, aac: int = 0, luma: bool = True, chroma: bool = True,
                  device: int = 0, isolated_planes: bool = False, fresh_pool: bool = False, opt: int = -1, max_batch: int = 1,
-                 host_depth: int = 0, stream: int | None = None, **policy_kw):
+                 host_depth: int = 0, stream: int | None = None, dh: bool = False, **policy_kw):
         if opt < -1 or opt > 1:
             raise SangNomError(capi.SN_ERR_CONFIG, "SangNom2: opt must be between -1..2.")  # sic, SangNom2.cpp:420
         self.clip = clip
+        self.dh = bool(dh)
         self.max_batch = max_batch
         self._lib = capi.load()
         cfg = capi.SnConfig(
             struct_size=ctypes.sizeof(capi.SnConfig), width=clip.width, height=clip.height, bytes_per_sample=clip.bytes,
             bits_per_sample=clip.bits, num_planes=clip.planes, sub_w=clip.subw, sub_h=clip.subh, order=order, aa=aa, aac=aac,
-            dh=0, luma=int(luma), chroma=int(chroma), device=device, max_batch=max_batch, mode=capi.SN_MODE_AUTO, host_depth=host_depth,
+            dh=int(self.dh), luma=int(luma), chroma=int(chroma), device=device, max_batch=max_batch, mode=capi.SN_MODE_AUTO, host_depth=host_depth,
             isolated_planes=int(isolated_planes), fresh_pool=int(fresh_pool), stream=stream)
         self._h = ctypes.c_void_p()
         pol = capi.policy(**{k: policy_kw.get(k) for k in ("small_launches", "chain", "copy_threads", "scratch_budget_mb", "chroma_sweeps")})
@@ -328,6 +331,10 @@ class _AAContext:
 
     def plane_shape(self, p: int):
         return (self.clip.height >> (self.clip.subh if p else 0), self.clip.width >> (self.clip.subw if p else 0))
+
+    def plane_shape_out(self, p: int):
+        h, w = self.plane_shape(p)
+        return (2 * h, 2 * w) if self.dh else (h, w)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -371,7 +378,8 @@ class SangNomAA(_AAContext):
         super().__init__(clip, max_batch=max_batch, device=device, **kw)
 
     def process_batch(self, src, dst, parity=None):
-        """src[p], dst[p]: torch tensors [N, H_p, W_p] on the device.  Asynchronous on the call's stream."""
+        """src[p], dst[p]: torch tensors [N, H_p, W_p] on the device (dh: dst[p] is [N, 2 H_p, 2 W_p]).  Asynchronous on
+        the call's stream."""
         n, B = self.nplanes, self.clip.bytes
         N = src[0].shape[0]
         sp, dp = (ctypes.c_void_p * 3)(), (ctypes.c_void_p * 3)()
@@ -379,7 +387,7 @@ class SangNomAA(_AAContext):
         sfs, dfs = (ctypes.c_int64 * 3)(), (ctypes.c_int64 * 3)()
         for p in range(n):
             s, d = src[p], dst[p]
-            if tuple(s.shape) != (N,) + self.plane_shape(p) or tuple(d.shape) != (N,) + self.plane_shape(p):
+            if tuple(s.shape) != (N,) + self.plane_shape(p) or tuple(d.shape) != (N,) + self.plane_shape_out(p):
                 raise ValueError(f"plane {p}: bad shape {tuple(s.shape)} -> {tuple(d.shape)}")
             if s.stride(2) != 1 or d.stride(2) != 1 or s.element_size() != B or d.element_size() != B:
                 raise ValueError("planes must be x-contiguous tensors of the clip's sample type")
@@ -397,19 +405,22 @@ class SangNomAAHost(_AAContext):
     """The idiom on host planes (sn_aa_process_host; sn_aa_submit_host / sn_aa_collect_host for look-ahead): the frame
     crosses PCIe once each way.  This is what the plugin function SangNomAA (host/sangnom2_avs_plugin.cpp) binds."""
 
-    def _plane_args(self, planes):
+    def _plane_args(self, planes, shape_of=None):
         ptr, pitch = (ctypes.c_void_p * 3)(), (ctypes.c_int32 * 3)()
         for p in range(self.nplanes):
             a = planes[p]
             if a.dtype != self.clip.dtype or a.strides[1] != self.clip.bytes:
                 raise ValueError("planes must be x-contiguous arrays of the clip's sample type")
+            if shape_of is not None and a.shape != shape_of(p):
+                raise ValueError(f"plane {p}: shape {a.shape}, expected {shape_of(p)}")
             ptr[p], pitch[p] = a.ctypes.data, a.strides[0]
         return ptr, pitch
 
-    def get_frame(self, src, parity: int = 1):
-        dst = [np.zeros_like(src[p]) for p in range(self.nplanes)]
-        sp, spi = self._plane_args(src)
-        dp, dpi = self._plane_args(dst)
+    def get_frame(self, src, parity: int = 1, dst=None):
+        sp, spi = self._plane_args(src, self.plane_shape if self.dh else None)
+        if dst is None:
+            dst = [np.zeros(self.plane_shape_out(p), dtype=self.clip.dtype) if self.dh else np.zeros_like(src[p]) for p in range(self.nplanes)]
+        dp, dpi = self._plane_args(dst, self.plane_shape_out if self.dh else None)
         self._check(self._lib.sn_aa_process_host(self._h, sp, spi, dp, dpi, int(parity)))
         return dst
 
@@ -418,7 +429,7 @@ class SangNomAAHost(_AAContext):
 
     def submit(self, src, parity: int = 1) -> int:
         """Queue one host frame on the ring; returns its slot (SangNomError with code SN_ERR_BUSY when the ring is full)."""
-        sp, spi = self._plane_args(src)
+        sp, spi = self._plane_args(src, self.plane_shape if self.dh else None)
         slot = ctypes.c_int32(-1)
         self._check(self._lib.sn_aa_submit_host(self._h, sp, spi, int(parity), ctypes.byref(slot)))
         return slot.value
@@ -426,7 +437,7 @@ class SangNomAAHost(_AAContext):
     def collect(self, slot: int, dst=None):
         """Wait for the frame in `slot`; returns its planes."""
         if dst is None:
-            dst = [np.zeros(self.plane_shape(p), dtype=self.clip.dtype) for p in range(self.nplanes)]
-        dp, dpi = self._plane_args(dst)
+            dst = [np.zeros(self.plane_shape_out(p), dtype=self.clip.dtype) for p in range(self.nplanes)]
+        dp, dpi = self._plane_args(dst, self.plane_shape_out if self.dh else None)
         self._check(self._lib.sn_aa_collect_host(self._h, int(slot), dp, dpi))
         return dst

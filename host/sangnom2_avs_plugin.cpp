@@ -27,6 +27,7 @@ struct AvsHost {
     static Info GetInfo(const ClipPtr& c) { return c->GetVideoInfo(); }
     static int Width(const Info& v) { return v.width; }
     static int Height(const Info& v) { return v.height; }
+    static void SetWidth(Info& v, int w) { v.width = w; }
     static void SetHeight(Info& v, int h) { v.height = h; }
     static int ComponentSize(const Info& v) { return v.ComponentSize(); }
     static int BitsPerComponent(const Info& v) { return v.BitsPerComponent(); }
@@ -99,12 +100,16 @@ AVSValue __cdecl Create_SangNom2HIP(AVSValue args, void*, IScriptEnvironment* en
 }
 
 // SangNomAA(clip, order, aa, aac): TurnLeft().SangNom2(order, aa, aac).TurnRight().SangNom2(order, aa, aac) with the frame
-// staying on the device between the passes (sangnom::AAFilter).
+// staying on the device between the passes (sangnom::AAFilter).  dh=true: both passes with dh=true, the clip comes out
+// twice as wide and twice as high.
 class SangNomAA : public GenericVideoFilter {
     sangnom::AAFilter<AvsHost> impl_;
 
 public:
-    SangNomAA(PClip child, const sangnom::Args& a, IScriptEnvironment* env) : GenericVideoFilter(child), impl_(child, a, env, "SangNomAA") {}
+    SangNomAA(PClip child, const sangnom::Args& a, IScriptEnvironment* env) : GenericVideoFilter(child), impl_(child, a, env, "SangNomAA")
+    {
+        vi = impl_.GetInfo();
+    }
     PVideoFrame __stdcall GetFrame(int n, IScriptEnvironment* env) override { return impl_.GetFrame(n, env); }
     int __stdcall SetCacheHints(int cachehints, int) override { return cachehints == CACHE_GET_MTMODE ? MT_MULTI_INSTANCE : 0; }
 };
@@ -122,6 +127,7 @@ AVSValue __cdecl Create_SangNomAA(AVSValue args, void*, IScriptEnvironment* env)
     a.isolated = args[8].AsBool(false);
     a.fresh = args[9].AsBool(false);
     a.lookahead = args[10].AsInt(-1);
+    a.dh = args[11].AsBool(false);
     return new SangNomAA(args[0].AsClip(), a, env);
 }
 
@@ -145,7 +151,7 @@ extern "C" __declspec(dllexport) const char* __stdcall AvisynthPluginInit3(IScri
     env->AddFunction("SangNom", "c[order]i[aa]i[opt]i", Create_SangNom, 0);                                        // :482
     env->AddFunction("SangNom2HIP", "c[order]i[aa]i[aac]i[threads]i[dh]b[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i[device]i",
                      Create_SangNom2HIP, 0);
-    env->AddFunction("SangNomAA", "c[order]i[aa]i[aac]i[device]i[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i", Create_SangNomAA, 0);
+    env->AddFunction("SangNomAA", "c[order]i[aa]i[aac]i[device]i[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i[dh]b", Create_SangNomAA, 0);
     return "SangNom2";
 }
 #endif  // SN_HAVE_AVISYNTH

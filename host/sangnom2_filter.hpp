@@ -228,6 +228,9 @@ private:
 // as SangNom2 for the clip itself; the turned clip must pass them as well (e.g. an even WIDTH).
 // Args::lookahead works as in Filter, over sn_aa_submit_host / sn_aa_collect_host, and only when BOTH passes are
 // history-free (sn_aa_get_info); otherwise GetFrame stays synchronous, for the reason given in Filter's constructor.
+// With Args::dh both passes run with dh=true: TurnLeft().SangNom2(dh=true).TurnRight().SangNom2(dh=true), enlargement by
+// two in both directions.  The filter's clip is then twice as wide and twice as high, every plane is processed (luma /
+// chroma are ignored, as in the reference), and the alpha of a YUVA clip fills a 2 x 2 block per source sample.
 template <class Host>
 class AAFilter {
 public:
@@ -257,6 +260,7 @@ public:
         c.order = a.order;
         c.aa = a.aa;
         c.aac = a.aac;
+        c.dh = a.dh;
         c.luma = a.luma;
         c.chroma = a.chroma;
         c.device = a.device;
@@ -275,6 +279,10 @@ public:
         opts.struct_size = (int32_t)sizeof opts;
         opts.arithmetic = a.opt == 1 ? SN_ARITH_SSE2 : SN_ARITH_CXX;
         if (sn_aa_create_ex(&c, &pol, &opts, &ctx_) != SN_OK) env->ThrowError("%s: %s", name, sn_aa_last_error(nullptr));
+        if (a.dh) {  // each pass doubles the height of what it is given: the clip comes out twice as wide and twice as high
+            Host::SetWidth(vi_, Host::Width(vi_) * 2);
+            Host::SetHeight(vi_, Host::Height(vi_) * 2);
+        }
         planes_ = c.num_planes;
         alpha_ = Host::NumComponents(vi_) == 4;
         num_frames_ = Host::NumFrames(vi_);
@@ -324,9 +332,21 @@ private:
     void CopyAlpha(const FramePtr& src, const FramePtr& dst) const  // passed through (see Filter::CopyAlpha)
     {
         if (!alpha_) return;
-        const size_t row = (size_t)Host::Width(vi_) * Host::ComponentSize(vi_);
-        for (int y = 0; y < Host::Height(vi_); ++y)
-            std::memcpy(Host::WritePtr(dst, 3) + (size_t)y * Host::Pitch(dst, 3), Host::ReadPtr(src, 3) + (size_t)y * Host::Pitch(src, 3), row);
+        const size_t B = (size_t)Host::ComponentSize(vi_);
+        const size_t row = (size_t)Host::Width(vi_) * B;
+        if (!args_.dh) {
+            for (int y = 0; y < Host::Height(vi_); ++y)
+                std::memcpy(Host::WritePtr(dst, 3) + (size_t)y * Host::Pitch(dst, 3), Host::ReadPtr(src, 3) + (size_t)y * Host::Pitch(src, 3), row);
+            return;
+        }
+        // dh: every source sample fills a 2 x 2 block (Filter::CopyAlpha repeats lines; here the samples of a line as well)
+        const int w_out = Host::Width(vi_);
+        for (int y = 0; y < Host::Height(vi_); y += 2) {
+            const uint8_t* s = Host::ReadPtr(src, 3) + (size_t)(y / 2) * Host::Pitch(src, 3);
+            uint8_t* d = Host::WritePtr(dst, 3) + (size_t)y * Host::Pitch(dst, 3);
+            for (int x = 0; x < w_out; ++x) std::memcpy(d + (size_t)x * B, s + (size_t)(x / 2) * B, B);
+            std::memcpy(d + Host::Pitch(dst, 3), d, row);
+        }
     }
 
     FramePtr Collect(Env* env)

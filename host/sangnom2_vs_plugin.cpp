@@ -4,6 +4,9 @@
 // offers the same filter to VapourSynth scripts through the C ABI of include/sangnom_hip.h:
 //     core.sangnomhip.SangNom(clip, order=1, dh=False, aa=48, aac=0, luma=True, chroma=True,
 //                             isolated=False, fresh=False)
+//     core.sangnomhip.SangNomAA(clip, order=1, aa=48, aac=0, luma=True, chroma=True, isolated=False, fresh=False, dh=False)
+// SangNomAA is the anti-aliasing idiom (a quarter turn, SangNom, the turn back, SangNom) as one call of the library
+// (sn_aa_process_host); with dh=True both passes double the height: the clip comes out twice as wide and twice as high.
 // It needs the VapourSynth SDK header VapourSynth4.h, a third-party file that is not part of this repository or
 // of the build image: without it this file compiles to nothing, so it has NOT been compiled or run here
 // (INTEGRATION.md says so).  With the SDK:  make -C host VS_INCLUDE_DIR=<dir of VapourSynth4.h>.
@@ -27,6 +30,7 @@ struct SangNomData {
     VSNode* node = nullptr;
     VSVideoInfo vi{};
     sn_context* ctx = nullptr;
+    sn_aa_context* aa = nullptr;  // SangNomAA: the anti-aliasing call instead of one filter instance
     int planes = 1;
     int order = 1;
     std::mutex mtx;  // one context == one filter instance: frames go through it one at a time, in request order
@@ -63,8 +67,10 @@ const VSFrame* VS_CC sangnomGetFrame(int n, int activationReason, void* instance
     int rc;
     {
         std::lock_guard<std::mutex> lk(d->mtx);
-        rc = sn_process_host(d->ctx, sp, spitch, dp, dpitch, parity);
-        if (rc != SN_OK) vsapi->setFilterError((std::string("SangNom: ") + sn_last_error(d->ctx)).c_str(), frameCtx);
+        rc = d->aa ? sn_aa_process_host(d->aa, sp, spitch, dp, dpitch, parity) : sn_process_host(d->ctx, sp, spitch, dp, dpitch, parity);
+        if (rc != SN_OK)
+            vsapi->setFilterError((std::string(d->aa ? "SangNomAA: " : "SangNom: ") + (d->aa ? sn_aa_last_error(d->aa) : sn_last_error(d->ctx))).c_str(),
+                                  frameCtx);
     }
     vsapi->freeFrame(src);
     if (rc != SN_OK) {
@@ -78,12 +84,15 @@ void VS_CC sangnomFree(void* instanceData, VSCore*, const VSAPI* vsapi)
 {
     SangNomData* d = static_cast<SangNomData*>(instanceData);
     vsapi->freeNode(d->node);
-    sn_destroy(d->ctx);
+    if (d->aa) sn_aa_destroy(d->aa);
+    else sn_destroy(d->ctx);
     delete d;
 }
 
-void VS_CC sangnomCreate(const VSMap* in, VSMap* out, void*, VSCore* core, const VSAPI* vsapi)
+void VS_CC sangnomCreate(const VSMap* in, VSMap* out, void* userData, VSCore* core, const VSAPI* vsapi)
 {
+    const bool aa = userData != nullptr;  // registered as SangNomAA
+    const std::string name = aa ? "SangNomAA: " : "SangNom: ";
     SangNomData* d = new SangNomData;
     int err = 0;
     d->node = vsapi->mapGetNode(in, "clip", 0, &err);
@@ -94,7 +103,7 @@ void VS_CC sangnomCreate(const VSMap* in, VSMap* out, void*, VSCore* core, const
         return e ? def : (int)v;
     };
     auto fail = [&](const std::string& msg) {
-        vsapi->mapSetError(out, ("SangNom: " + msg).c_str());
+        vsapi->mapSetError(out, (name + msg).c_str());
         vsapi->freeNode(d->node);
         delete d;
     };
@@ -119,16 +128,19 @@ void VS_CC sangnomCreate(const VSMap* in, VSMap* out, void*, VSCore* core, const
     c.fresh_pool = geti("fresh", 0) != 0;
     c.max_batch = 1;
     c.mode = SN_MODE_AUTO;
+    auto bare = [](const char* m) { return std::string(m + (std::string(m).rfind("SangNom2: ", 0) == 0 ? 10 : 0)); };  // the reference's prefix
     char msg[256];
-    if (sn_validate(&c, msg, sizeof msg) != SN_OK) return fail(msg + (std::string(msg).rfind("SangNom2: ", 0) == 0 ? 10 : 0));
-    if (sn_create(&c, &d->ctx) != SN_OK) return fail(sn_last_error(nullptr));
+    if (sn_validate(&c, msg, sizeof msg) != SN_OK) return fail(bare(msg));
+    // SangNomAA: the turned clip and, with dh, the clip twice as wide are validated by the creation itself
+    if (aa ? sn_aa_create(&c, &d->aa) != SN_OK : sn_create(&c, &d->ctx) != SN_OK) return fail(bare(aa ? sn_aa_last_error(nullptr) : sn_last_error(nullptr)));
     d->planes = c.num_planes;
     if (c.dh) d->vi.height *= 2;
+    if (c.dh && aa) d->vi.width *= 2;  // both passes double the height of what they are given
     // The context keeps the reference's per-instance state (scratch pool, frame order), so frames are served one at
     // a time in request order: fmFrameState.  With fresh=True every frame is independent, but the context is still
     // not re-entrant (one stream, one staging area), hence the mutex above rather than a parallel mode.
     VSFilterDependency deps[] = {{d->node, rpStrictSpatial}};
-    vsapi->createVideoFilter(out, "SangNom", &d->vi, sangnomGetFrame, sangnomFree, fmFrameState, deps, 1, d, core);
+    vsapi->createVideoFilter(out, aa ? "SangNomAA" : "SangNom", &d->vi, sangnomGetFrame, sangnomFree, fmFrameState, deps, 1, d, core);
 }
 
 }  // namespace
@@ -140,5 +152,9 @@ VS_EXTERNAL_API(void) VapourSynthPluginInit2(VSPlugin* plugin, const VSPLUGINAPI
     vspapi->registerFunction("SangNom",
                              "clip:vnode;order:int:opt;dh:int:opt;aa:int:opt;aac:int:opt;luma:int:opt;chroma:int:opt;isolated:int:opt;fresh:int:opt;",
                              "clip:vnode;", sangnomCreate, nullptr, plugin);
+    static int aa_tag = 1;
+    vspapi->registerFunction("SangNomAA",
+                             "clip:vnode;order:int:opt;aa:int:opt;aac:int:opt;luma:int:opt;chroma:int:opt;isolated:int:opt;fresh:int:opt;dh:int:opt;",
+                             "clip:vnode;", sangnomCreate, &aa_tag, plugin);
 }
 #endif  // SN_HAVE_VAPOURSYNTH

@@ -91,6 +91,7 @@ struct TestHost {
     static Info GetInfo(const ClipPtr& c) { return c->GetInfo(); }
     static int Width(const Info& v) { return v.width; }
     static int Height(const Info& v) { return v.height; }
+    static void SetWidth(Info& v, int w) { v.width = w; }
     static void SetHeight(Info& v, int h) { v.height = h; }
     static int ComponentSize(const Info& v) { return v.component_size; }
     static int BitsPerComponent(const Info& v) { return v.bits_per_component; }

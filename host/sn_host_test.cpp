@@ -4,14 +4,15 @@
 // the oracle.
 //   sn_host_test <in.bin> <out.bin> [lookahead | aa | aa:<lookahead> [first-frame-order...]]
 // lookahead > 1 runs GetFrame over the host ring; "aa" constructs SangNomAA (sangnom::AAFilter) instead of SangNom2,
-// "aa:<N>" with look-ahead N;
+// "aa:<N>" with look-ahead N; the header's dh word reaches either filter (SangNomAA with dh: frames twice as wide and
+// twice as high);
 // the optional list gives the order in which frames are requested (default 0 .. nframes-1), e.g. to exercise a seek.
 // planes = 4 in the header is a YUVA clip: the fourth plane is luma-sized and passed through.
 // in.bin : 14 x int32 {w,h,bytes,bits,planes,subw,subh,order,aa,aac,dh,luma,chroma,nframes}, then per
 //          frame: int32 parity + the planes, tightly packed.
 // SN_HOST_TEST_OPT=<-1|0|1> in the environment of this TEST program is the script argument `opt` (default -1),
 // SN_HOST_TEST_FRESH=1 sets Args::fresh.
-// out.bin: per frame the output planes, tightly packed.  On a constructor error: exit code 3 and
+// out.bin: per frame the output planes in the filter's own geometry (its GetInfo()), tightly packed.  On a constructor error: exit code 3 and
 //          the message on stdout.
 #include <cstdio>
 #include <cstdlib>
@@ -95,17 +96,17 @@ int main(int argc, char** argv)
     try {
         FILE* out = fopen(argv[2], "wb");
         if (!out) return 2;
-        auto dump = [&](const FramePtr& d) {
-            for (int p = 0; p < clip->vi.num_components; ++p)
-                for (int y = 0; y < d->Height(p); ++y)
-                    fwrite(d->Ptr(p) + (size_t)y * d->Pitch(p), 1, d->RowSize(p), out);
+        auto dump = [&](const FramePtr& d, const ClipInfo& vi) {  // vi: the filter's clip info
+            for (int p = 0; p < vi.num_components; ++p)
+                for (int y = 0; y < vi.PlaneHeight(p); ++y)
+                    fwrite(d->Ptr(p) + (size_t)y * d->Pitch(p), 1, (size_t)vi.PlaneWidth(p) * vi.component_size, out);
         };
         if (aa_idiom) {
             sangnom::AAFilter<TestHost> flt(clip, a, &env);
-            for (int n : order) dump(flt.GetFrame(n, &env));
+            for (int n : order) dump(flt.GetFrame(n, &env), flt.GetInfo());
         } else {
             sangnom::Filter<TestHost> flt(clip, a, &env);
-            for (int n : order) dump(flt.GetFrame(n, &env));
+            for (int n : order) dump(flt.GetFrame(n, &env), flt.GetInfo());
         }
         fclose(out);
     } catch (const Error& e) {

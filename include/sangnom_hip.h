@@ -274,13 +274,27 @@ int sn_turn_device(sn_context* ctx, int32_t direction, int32_t nframes, const vo
  * host planes (README.md:3 of the reference: "mainly used in anti-aliasing scripts"): the frame
  * crosses PCIe once each way and stays on the device between the two passes (two filter instances -- one for the
  * turned clip, one for the clip itself -- on one stream, sn_turn_device in between).  `cfg` describes the clip
- * (dh must be 0; luma / chroma / isolated_planes / fresh_pool / device apply to both passes; max_batch >= 1: frames one
+ * (dh: see below; luma / chroma / isolated_planes / fresh_pool / device apply to both passes; max_batch >= 1: frames one
  * sn_aa_process_device_strided call may carry; host_depth: slots of the host ring, 0 = 4, allocated when
  * sn_aa_submit_host is first called; stream: the stream of the call's device work, NULL = one of its own; mode is
  * ignored: both passes run SN_MODE_AUTO); the turned clip must pass the reference's checks too (sn_aa_create reports the first
  * pass's message otherwise).  The result is what that script gives with the reference: two instances, so for widths
  * or heights that are not a multiple of 32 each pass carries its own pool history from frame to frame.  Not a
- * function of the reference; host/sangnom2_avs_plugin.cpp registers it as SangNomAA. */
+ * function of the reference; host/sangnom2_avs_plugin.cpp registers it as SangNomAA.
+ *
+ * With cfg.dh = 1 the call is TurnLeft().SangNom2(order, aa, aac, dh=true).TurnRight().SangNom2(order, aa, aac, dh=true):
+ * enlargement by two in both directions, the SangNom counterpart of nnedi3_rpow2(2).  cfg.width / cfg.height and every
+ * src plane, pitch and frame stride still describe the input clip; every dst plane is twice as wide and twice as high as
+ * its source plane (dst pitch >= 2 * plane width * bytes_per_sample).  As in the reference, dh forces every plane through
+ * both passes: luma and chroma are ignored.  The first instance filters the turned clip (height x width in, height x
+ * 2 width out), the second one a clip of 2 width x height (sn_aa_get_info(ctx, 1): out_height = 2 height, pool_stride =
+ * roundup(2 width, 32)); each is validated as SangNom2 validates it, the turned clip first (an odd width: "SangNom2:
+ * height must be even."), and 2 width is held against the width limit.  The first pass carries history when height is
+ * not a multiple of 32, the second when 2 width is not.  Both passes read every line of their source, so the turns are
+ * whole turns, and the intermediates per processed plane and frame are the turned source, the first pass's output
+ * (twice that) and the second pass's input (twice that again, up to pitch rounding): five plane sizes against three
+ * without dh, counted against sn_policy.scratch_budget_mb in the same way.  On the host path a whole source frame goes
+ * up and a frame four times its size comes down; nothing of it can be copied on the host. */
 typedef struct sn_aa_context sn_aa_context;
 int sn_aa_create(const sn_config* cfg, sn_aa_context** out);
 int sn_aa_create_with_policy(const sn_config* cfg, const sn_policy* policy /* NULL = defaults; both passes */, sn_aa_context** out);
@@ -295,7 +309,8 @@ void sn_aa_destroy(sn_aa_context* ctx); /* waits for frames still in flight */
  * (each pass sees its frames in order, so history-carrying clips are the script's).  The frames are walked in chunks:
  * turn, first pass, turn back, second pass; the intermediates are allocated at creation and count against
  * sn_policy.scratch_budget_mb, a batch beyond what fits takes more chunks.  A turn writes only the lines the following
- * pass keeps; a plane that is not processed (luma / chroma = 0) is copied from src to dst once. */
+ * pass keeps (with dh: every line); a plane that is not processed (luma / chroma = 0, never with dh) is copied from src
+ * to dst once. */
 int sn_aa_process_device_strided(sn_aa_context* ctx, int32_t nframes, const void* const src[3], const int64_t src_frame_stride[3],
                                  const int32_t src_pitch[3], void* const dst[3], const int64_t dst_frame_stride[3],
                                  const int32_t dst_pitch[3], const int32_t* parity /* NULL = all 1 */);

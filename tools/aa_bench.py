@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Device-resident rate of the anti-aliasing idiom TurnLeft().SangNom2().TurnRight().SangNom2() (SangNomAA) and of
 the turn kernel alone; with --host, frames from pageable host memory: the synchronous call (SangNomAAHost.get_frame)
-against the ring at --depth.
-usage: python tools/aa_bench.py [--frames 512] [--fresh 1] [--fmt Y8] [--size 3840x2160] [--host [--depth 8]]"""
+against the ring at --depth.  --dh: the enlargement form (both passes with dh=true, destinations twice as wide and twice
+as high); --dh --composed: the same idiom composed by hand from two SangNom2(dh=True) contexts and SangNom2.turn on one
+stream, the way a caller had to build it before the call took dh.
+usage: python tools/aa_bench.py [--frames 512] [--fresh 1] [--fmt Y8] [--size 3840x2160] [--dh [--composed]] [--host [--depth 8]]"""
 import argparse
 import json
 import os
@@ -14,7 +16,7 @@ import torch  # noqa: E402
 
 import numpy as np  # noqa: E402
 
-from avisynth_sangnom2_amd import SangNom2, SangNomAA, SangNomAAHost, clip_format  # noqa: E402
+from avisynth_sangnom2_amd import ClipFormat, SangNom2, SangNomAA, SangNomAAHost, clip_format  # noqa: E402
 
 
 def host_rates(clip, a):
@@ -24,9 +26,16 @@ def host_rates(clip, a):
     n = min(a.frames, 64)
     shapes = [(clip.height >> (clip.subh if p else 0), clip.width >> (clip.subw if p else 0)) for p in range(clip.planes)]
     frames = [[rng.integers(0, 256, s, dtype=np.uint8) for s in shapes] for _ in range(8)]
-    out = {"clip": f"{clip.width}x{clip.height} planes {clip.planes}", "host_frames": n, "fresh_pool": bool(a.fresh),
-           "pcie_bytes_per_frame_each_way": sum(s[0] * s[1] for s in shapes) * clip.bytes}
-    with SangNomAAHost(clip, aac=48 if clip.planes > 1 else 0, fresh_pool=bool(a.fresh)) as flt:
+    out = {"clip": f"{clip.width}x{clip.height} planes {clip.planes}", "host_frames": n, "fresh_pool": bool(a.fresh)}
+    up = sum(s[0] * s[1] for s in shapes) * clip.bytes
+    if a.dh:
+        out["dh"] = True
+        out["pcie_bytes_per_frame_up"], out["pcie_bytes_per_frame_down"] = up, 4 * up
+    else:
+        out["pcie_bytes_per_frame_each_way"] = up
+    dh_kw = dict(dh=True) if a.dh else {}
+    oshapes = [(2 * s[0], 2 * s[1]) if a.dh else s for s in shapes]
+    with SangNomAAHost(clip, aac=48 if clip.planes > 1 else 0, fresh_pool=bool(a.fresh), **dh_kw) as flt:
         for i in range(3):
             flt.get_frame(frames[i])
         t0 = time.perf_counter()
@@ -35,9 +44,9 @@ def host_rates(clip, a):
         out["sync_fps"] = round(n / (time.perf_counter() - t0), 1)
     if not hasattr(SangNomAAHost, "submit"):
         return out
-    with SangNomAAHost(clip, aac=48 if clip.planes > 1 else 0, fresh_pool=bool(a.fresh), host_depth=a.depth) as flt:
+    with SangNomAAHost(clip, aac=48 if clip.planes > 1 else 0, fresh_pool=bool(a.fresh), host_depth=a.depth, **dh_kw) as flt:
         slots = flt.slots()
-        dst = [np.zeros(s, np.uint8) for s in shapes]
+        dst = [np.zeros(s, np.uint8) for s in oshapes]
 
         def run(count):
             pending, f, done = [], 0, 0
@@ -55,6 +64,37 @@ def host_rates(clip, a):
     return out
 
 
+def composed_dh_rate(clip, a, src, dst):
+    """The dh idiom from two SangNom2(dh=True) contexts and SangNom2.turn on one stream: frames/s, device-resident."""
+    N, dev = a.frames, src[0].device
+    turned = ClipFormat(width=clip.height, height=clip.width, bytes=clip.bytes, bits=clip.bits, planes=clip.planes, subw=clip.subh, subh=clip.subw)
+    wide = ClipFormat(width=2 * clip.width, height=clip.height, bytes=clip.bytes, bits=clip.bits, planes=clip.planes, subw=clip.subw, subh=clip.subh)
+    kw = dict(max_batch=N, fresh_pool=bool(a.fresh), aac=48 if clip.planes > 1 else 0, dh=True)
+    with SangNom2(turned, **kw) as first, SangNom2(wide, stream=first.stream_handle(), **kw) as second:
+        hw = [tuple(s.shape[1:]) for s in src]
+        t1 = [torch.empty((N, w_, h_), device=dev, dtype=torch.uint8) for h_, w_ in hw]
+        u1 = [torch.empty((N, 2 * w_, h_), device=dev, dtype=torch.uint8) for h_, w_ in hw]
+        t2 = [torch.empty((N, h_, 2 * w_), device=dev, dtype=torch.uint8) for h_, w_ in hw]
+        torch.cuda.synchronize()
+
+        def once():
+            for p in range(clip.planes):
+                first.turn(src[p], t1[p], -1)
+            first.process_batch(t1, u1)
+            for p in range(clip.planes):
+                first.turn(u1[p], t2[p], +1)
+            second.process_batch(t2, dst)
+        for _ in range(2):
+            once()
+        second.synchronize()
+        reps = 5
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            once()
+        second.synchronize()
+        return round(N * reps / (time.perf_counter() - t0), 1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=512)
@@ -63,11 +103,15 @@ def main():
     ap.add_argument("--size", default="3840x2160")
     ap.add_argument("--host", action="store_true", help="frames from host memory: the synchronous call against the ring")
     ap.add_argument("--depth", type=int, default=8, help="--host: slots of the ring")
+    ap.add_argument("--dh", action="store_true", help="both passes with dh=true: enlargement by two in both directions")
+    ap.add_argument("--composed", action="store_true", help="--dh, device-resident: two SangNom2(dh=True) contexts and SangNom2.turn by hand")
     a = ap.parse_args()
     w, h = [int(x) for x in a.size.split("x")]
     clip = clip_format(a.fmt, w, h)
     if clip.bytes != 1:
         sys.exit("aa_bench: 8-bit formats only")
+    if a.composed and (not a.dh or a.host):
+        sys.exit("aa_bench: --composed goes with --dh, device-resident")
     if a.host:
         print(json.dumps(host_rates(clip, a)))
         return
@@ -75,9 +119,16 @@ def main():
     N = a.frames
     src = [torch.randint(0, 256, (N, h >> (clip.subh if p else 0), w >> (clip.subw if p else 0)), device=dev, dtype=torch.uint8)
            for p in range(clip.planes)]
-    dst = [torch.empty_like(s) for s in src]
+    k = 2 if a.dh else 1
+    dst = [torch.empty((N, k * s.shape[1], k * s.shape[2]), device=dev, dtype=torch.uint8) for s in src]
     out = {"clip": f"{a.fmt} {w}x{h}", "frames": N, "fresh_pool": bool(a.fresh)}
-    with SangNomAA(clip, max_batch=N, fresh_pool=bool(a.fresh), aac=48 if clip.planes > 1 else 0) as aa:
+    if a.dh:
+        out["dh"] = True
+    if a.composed:
+        out["composed_fps"] = composed_dh_rate(clip, a, src, dst)
+        print(json.dumps(out))
+        return
+    with SangNomAA(clip, max_batch=N, fresh_pool=bool(a.fresh), aac=48 if clip.planes > 1 else 0, **(dict(dh=True) if a.dh else {})) as aa:
         torch.cuda.synchronize()
         for _ in range(2):
             aa.process_batch(src, dst)
