@@ -93,18 +93,18 @@ __device__ __forceinline__ Raw clamp_edges(Raw q, const LaneRole& role)
     return q;
 }
 
-// a + b + c with a wave-uniform c (an SGPR operand: the encoding has no literal)
-__device__ __forceinline__ unsigned add3_s(unsigned a, unsigned b, unsigned c)
+// 32a + c with a wave-uniform c, and 4 (a + b): ONE instruction each (left to itself the compiler splits these sums into
+// two-operand adds and shifts)
+__device__ __forceinline__ unsigned lshl5_add_s(unsigned a, unsigned c)
 {
     unsigned r;
-    asm("v_add3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(c));
+    asm("v_lshl_add_u32 %0, %1, 5, %2" : "=v"(r) : "v"(a), "s"(c));
     return r;
 }
-// 4a + b as ONE instruction (left to itself the compiler splits these sums into two-operand adds and shifts)
-__device__ __forceinline__ unsigned lshl2_add(unsigned a, unsigned b)
+__device__ __forceinline__ unsigned add_lshl2(unsigned a, unsigned b)
 {
     unsigned r;
-    asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(r) : "v"(a), "v"(b));
+    asm("v_add_lshl_u32 %0, %1, %2, 2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
 
@@ -151,18 +151,27 @@ __device__ __forceinline__ void unpack(LineT& L, const Raw& q)
     }
     // The C++ arithmetic: F = ((4a + 5b - c) >> 3) mod 256, B = ((4c + 5b - a) >> 3) mod 256 (a, b, c = P[j + 2 .. j + 4]), computed 32 times
     // over with a bias of 2048 per half: X = 32 (4 (a + b + 512) + (b - c)) for F and 32 (4 (b + c + 512) + (b - a)) for
-    // B -- the pair sum of B at j is that of F at j + 1, and X is one v_lshl_add_u32 of a pair sum and a difference.  The
+    // B.  Neighbouring pixels share every term: with Q[i] = 32 P[i + 2] + 0x2000 per half (one v_lshl_add_u32, the bias
+    // in an SGPR), T[i] = 4 (Q[i] + Q[i + 1]) (one v_add_lshl_u32: the pair sum with its bias of 4 x 0x4000) and
+    // e[i] = Q[i] - Q[i + 1] (the bias cancels), F is T[j] + e[j + 1] and B is T[j + 1] - e[j] -- the pair sum of B at j
+    // is that of F at j + 1, and the difference of B at j + 1 is minus that of F at j.  44 instructions per line where a
+    // shift, a pair sum, a difference and a v_lshl_add per value took 51.  The
     // value then sits in bits 8..15 of each half, and one byte permute extracts it (no shift and mask).  32 (x + 2048) is
     // in [57 376, 138 976]: the low half carries at most 2 into the high half, whose own value is a multiple of 32, so its
     // bits 8..15 stay its own; differences may borrow from the high half, and the sums return it (32-bit adds are exact
     // modulo 2^32).
-    unsigned Q[PXL + 2];  // 32 P[i + 2]
+    unsigned Q[PXL + 2], T[PXL + 1], e[PXL + 1];
 #pragma unroll
-    for (int i = 0; i < PXL + 2; ++i) Q[i] = L.P[i + 2] << 5;
+    for (int i = 0; i < PXL + 2; ++i) Q[i] = lshl5_add_s(L.P[i + 2], 0x20002000u);
+#pragma unroll
+    for (int i = 0; i < PXL + 1; ++i) {
+        T[i] = add_lshl2(Q[i], Q[i + 1]);
+        e[i] = Q[i] - Q[i + 1];
+    }
 #pragma unroll
     for (int j = 0; j < PXL; ++j) {
-        const unsigned xf = lshl2_add(add3_s(Q[j], Q[j + 1], 0x40004000u), Q[j + 1] - Q[j + 2]);      // 4 (a + b) + (b - c)
-        const unsigned xb = lshl2_add(add3_s(Q[j + 1], Q[j + 2], 0x40004000u), Q[j + 1] - Q[j]);      // 4 (b + c) + (b - a)
+        const unsigned xf = T[j] + e[j + 1];  // 4 (a + b) + (b - c)
+        const unsigned xb = T[j + 1] - e[j];  // 4 (b + c) + (b - a)
         if constexpr (std::is_same<LineT, WideLine>::value) {
             L.Fv[j] = __builtin_amdgcn_perm(0u, xf, 0x0c030c01u);
             L.Bv[j] = __builtin_amdgcn_perm(0u, xb, 0x0c030c01u);

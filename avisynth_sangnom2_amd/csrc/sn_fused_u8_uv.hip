@@ -124,7 +124,7 @@ __device__ __forceinline__ u32x2 own_bytes(const RawHalf& h, bool first)
 // STALE: some lanes re-smooth stale values (class RS, and the masked steps of both region classes).
 // MASKED: the first kSkew and the last kSkew + 1 steps (see Step).
 template <int BUF, bool STALE, bool MASKED, bool PARK>
-__device__ __forceinline__ void region_buffer_step(unsigned (&A)[PXL], unsigned (&kmin)[PXL], const WideLine& n, const WideLine& nn, const Ctx& cx,
+__device__ __forceinline__ void region_buffer_step(unsigned (&A)[PXL], unsigned (&kmin)[PXL], unsigned (&held)[PXL], const WideLine& n, const WideLine& nn, const Ctx& cx,
                                                    const Step& st, const u32x2& ld)
 {
     unsigned U[PXL], V[PXL], S[PXL], Bx[PXL];
@@ -176,7 +176,7 @@ __device__ __forceinline__ void region_buffer_step(unsigned (&A)[PXL], unsigned 
         } else {
             A[j] = add3(O[j], U[j], V[j]);
         }
-        kmin[j] = pk_min(kmin[j], key);
+        fold_key<BUF>(kmin[j], held[j], key);
     }
     if constexpr (STALE) {
         if constexpr (PARK) {  // (class R runs this code only in its masked steps, without a park)
@@ -196,7 +196,7 @@ template <bool STALE, bool MASKED, bool PARK>
 __device__ __forceinline__ Out region_row(unsigned (&A)[kBuffers][PXL], const WideLine& n, const WideLine& nn, const Ctx& cx, const Step& st, unsigned thr_key,
                                           u32x2 (&ahead)[kBuffers])
 {
-    unsigned kmin[PXL];
+    unsigned kmin[PXL], held[PXL];  // held: an even buffer's keys until the next buffer folds them (fold_key)
 #pragma unroll
     for (int j = 0; j < PXL; ++j) kmin[j] = thr_key;
     // STALE: `ahead` holds the luma pass's row s + 1, fetched a whole step ago (a trip to HBM is longer than two buffer steps);
@@ -208,7 +208,7 @@ __device__ __forceinline__ Out region_row(unsigned (&A)[kBuffers][PXL], const Wi
             __builtin_amdgcn_sched_barrier(0);  // (the refill must not be hoisted above the read of the same registers' previous content)
             ahead[B] = issue_stale(cx, B, st.s + 2, st.vin2);
         }
-        region_buffer_step<B, STALE, MASKED, PARK>(A[B], kmin, n, nn, cx, st, ld);
+        region_buffer_step<B, STALE, MASKED, PARK>(A[B], kmin, held, n, nn, cx, st, ld);
         if constexpr (!STALE) __builtin_amdgcn_sched_barrier(0);
     };
     run(std::integral_constant<int, 0>{});

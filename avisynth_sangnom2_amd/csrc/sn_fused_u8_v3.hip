@@ -10,16 +10,22 @@
 //   * a lane owns 8 consecutive pixels of every row IN EACH OF TWO COLUMN STRIPS: every quantity of stages 1 and 2 fits
 //     13 bits, so a 32-bit register holds two pixels -- bits 0..15 strip `wave`, bits 16..31 strip `wave + NW` -- and one
 //     instruction serves both.  Per cost buffer only A[r] = O[r-1] + D[r] is kept (8 registers), all nine in VGPRs;
-//   * per buffer and register the row body is nine instructions: U = x -sat y, V = y -sat x (v_pk_sub_u16 clamp; the cost
-//     |x - y| = U + V is never formed), S = A + U + V (v_add3), the sliding box B[j+1] = B[j] - X[j-3] + X[j+4] (two plain
-//     adds), key = (B & 0x0ff00ff0) | code (v_and_or), O = key >> 4 as a PACKED shift (the code falls off both halves),
-//     A' = O + U + V (v_add3), kmin = min(kmin, key) (v_pk_min_u16).  On gfx950 every packed, DPP and three-operand form
-//     issues in the same 4-cycle class and one such form in eight drags a whole stream there (profiles/r3_ubench_valu_*),
-//     so what counts is the NUMBER of instructions, and each of these forms replaces two to four simple ones;
+//   * per buffer step (one cost buffer, the lane's eight packed registers): U = x -sat y, V = y -sat x (v_pk_sub_u16 clamp;
+//     the cost |x - y| = U + V is never formed) and S = A + U + V (v_add3), three per register; the 7-tap box in 18
+//     instructions for all eight windows (box7, sn_fused_u8_parts.h: windows 3 and 4 from two shared three-term sums, then
+//     one v_sub_u32_dpp and one v_add3 per window walking outwards on both sides); key = (B & 0x0ff00ff0) | code
+//     (v_and_or), O = key >> 4 as a PACKED shift (the code falls off both halves) and A' = O + U + V (v_add3), three per
+//     register; and the ladder's minimum over the keys, which takes TWO buffers' keys per instruction -- an even buffer
+//     hands its keys on, the odd one after it folds kmin = min(kmin, held, key) with v_pk_minimum3_f16 (keys are below
+//     0x1000 per half, where f16 patterns order like integers: pk_min3_keys, sn_fused_v3_common.h), the ninth buffer with
+//     v_pk_min_u16 -- five per register and row.  On gfx950 every packed, DPP and three-operand form issues in the same
+//     4-cycle class and one such form in eight drags a whole stream there (profiles/r3_ubench_valu_*), so what counts is
+//     the NUMBER of instructions, and each of these forms replaces two to four simple ones;
 //   * the +-3 horizontal taps of the box come from the neighbouring lanes with DPP wave_shr:1 / wave_shl:1 (one move
-//     serves both strips).  Column 0 is lane 0 of the first strip and has no left neighbour: its DPP move keeps the `old`
-//     operand, S[0] -- loadPixel's clamp (SangNom2.cpp:25-34) for free; the last column's neighbour reads zero too (S is
-//     zero in every half that is not live) and its clamp is one masked S[7] per buffer step (box7).
+//     serves both strips), each folded into the subtract that consumes it.  Column 0 is lane 0 of the first strip and has
+//     no left neighbour: its tap reads zero and loadPixel's clamp (SangNom2.cpp:25-34) is one masked S[0] per buffer step;
+//     the last column's neighbour reads zero too (S is zero in every half that is not live) and its clamp is one masked
+//     S[7] (box7).
 //     The same box in every wave: no branch inside a buffer step;
 //   * the first / last GH lanes of a strip are ghost lanes that recompute the neighbouring strip's 16 columns.  A ghost
 //     zone stays exact in its innermost 3 pixels for floor(16 / 3) = 5 rows (the missing outer neighbour corrupts 3 more
@@ -140,7 +146,7 @@ using LineOf = typename std::conditional<wide_lines(MODE), WideLine, Line>::type
 // kLumaSpill: row bh is never written) or the previous pass's values (kChroma).
 // STORE: the smoothed row goes to pool_out (lanes / rows that keep nothing carry an out-of-range voffset).
 template <int BUF, int MODE, bool S1, bool STORE, int ARITH = 0>
-__device__ __forceinline__ void buffer_step(unsigned (&A)[PXL], unsigned (&kmin)[PXL], const LineOf<MODE>& n, const LineOf<MODE>& nn,
+__device__ __forceinline__ void buffer_step(unsigned (&A)[PXL], unsigned (&kmin)[PXL], unsigned (&held)[PXL], const LineOf<MODE>& n, const LineOf<MODE>& nn,
                                             const LaneRole& role, const PoolIO& io, const RowCtx& rc,
                                             PoolIO::RawPair& stale)
 {
@@ -164,7 +170,7 @@ __device__ __forceinline__ void buffer_step(unsigned (&A)[PXL], unsigned (&kmin)
             const unsigned key = and_or(box_sat<ARITH>(Bx[j]), role.key_mask, rank_of<BUF, MODE>());
             O[j] = pk_lshr4(key);
             A[j] = add3(O[j], U[j], V[j]);
-            kmin[j] = pk_min(kmin[j], key);
+            fold_key<BUF>(kmin[j], held[j], key);
         }
         if constexpr (MODE == kLumaSpill && STORE) io.store(BUF, rc.r, rc.vout, rc.vout_hi, O);
         return;
@@ -194,7 +200,7 @@ __device__ __forceinline__ void buffer_step(unsigned (&A)[PXL], unsigned (&kmin)
                 const unsigned key = and_or(box_sat<ARITH>(Bx[j]), role.key_mask, rank_of<BUF, MODE>());
                 O[j] = pk_lshr4(key);
                 A[j] = add3(O[j], C[j], D[j]);
-                kmin[j] = pk_min(kmin[j], key);
+                fold_key<BUF>(kmin[j], held[j], key);
             }
             if constexpr (MODE != kChromaLast && STORE) io.store(BUF, rc.r, rc.vout, rc.vout_hi, O);
             return;
@@ -217,7 +223,7 @@ __device__ __forceinline__ void buffer_step(unsigned (&A)[PXL], unsigned (&kmin)
         const unsigned key = and_or(box_sat<ARITH>(Bx[j]), role.key_mask, rank_of<BUF, MODE>());
         O[j] = pk_lshr4(key);        // (sum / 16) wraps to uint8_t, SangNom2.cpp:152
         A[j] = O[j] + D[j];          // O + D[r+1]
-        kmin[j] = pk_min(kmin[j], key);
+        fold_key<BUF>(kmin[j], held[j], key);
     }
     // no branch around the packing (a branch inside the buffer steps costs more than it saves, see box7): rows past the
     // hand-off run a sweep without it (STORE), lanes that keep nothing let the range check drop their stores
@@ -285,7 +291,7 @@ __device__ __forceinline__ Out row_step(unsigned (&A)[reg_buffers(MODE)][PXL], c
                                         const LineOf<MODE>& nn, const LaneRole& role, unsigned thr_key, const PoolIO& io,
                                         const RowCtx& rc)
 {
-    unsigned kmin[PXL];
+    unsigned kmin[PXL], held[PXL];  // held: an even buffer's keys on their way to the next buffer's minimum (fold_key)
 #pragma unroll
     for (int j = 0; j < PXL; ++j) kmin[j] = thr_key;  // the `minBuf > aaf` arm: cost aaf + 1, rank 0
     // kChroma: the previous pass's row r+1 is fetched one buffer ahead of its use (HBM latency), and the
@@ -299,11 +305,11 @@ __device__ __forceinline__ Out row_step(unsigned (&A)[reg_buffers(MODE)][PXL], c
         constexpr int B = decltype(buf)::value;
         PoolIO::RawPair& st = (B & 1) ? st1 : st0;
         if constexpr (B < reg_buffers(MODE)) {
-            buffer_step<B, MODE, S1, STORE, ARITH>(A[B], kmin, n, nn, role, io, rc, st);
+            buffer_step<B, MODE, S1, STORE, ARITH>(A[B], kmin, held, n, nn, role, io, rc, st);
         } else {
             unsigned t[PXL];
             load_A(pk, tid, B, t);
-            buffer_step<B, MODE, S1, STORE, ARITH>(t, kmin, n, nn, role, io, rc, st);
+            buffer_step<B, MODE, S1, STORE, ARITH>(t, kmin, held, n, nn, role, io, rc, st);
             store_A(pk, tid, B, t);
         }
     };

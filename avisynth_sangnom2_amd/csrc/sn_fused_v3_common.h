@@ -185,6 +185,31 @@ __device__ __forceinline__ unsigned and_or_v(unsigned a, unsigned m, unsigned c)
     asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(m), "v"(c));
     return r;
 }
+// min(a, b, c) of ladder keys in both halves as ONE v_pk_minimum3_f16 (same issue class as v_pk_min_u16, which has no
+// three-input form).  A float minimum is the unsigned minimum of the bit patterns only because of what a key is:
+//   * key < 0x1000 per half -- (sum & 0x0ff0) | rank through LaneRole::key_mask (the bare rank, < 16, in a half that is
+//     not live), and the threshold key (thr + 1) << 4 with thr <= 168, at most 0x0a90.  So the sign bit and the
+//     exponent's top bit are clear: a non-negative finite f16, never a NaN or Inf pattern, no -0, and non-negative f16
+//     patterns order like the unsigned integers they are;
+//   * keys below 0x0400 are denormal patterns: the instruction must hand them on as they are.  Every 8-bit kernel runs
+//     with f16 denormals kept (csrc/Makefile: -fno-gpu-flush-denormals-to-zero, .amdhsa_float_denorm_mode_16_64 3).
+// A minimum returns one of its operands bit for bit, so the rank in the low nibble comes through.
+__device__ __forceinline__ unsigned pk_min3_keys(unsigned a, unsigned b, unsigned c)
+{
+    unsigned r;
+    asm("v_pk_minimum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+// One buffer's keys into the ladder's running minimum, five instructions per register and row where one per buffer took
+// nine: buffers 0, 2, 4, 6 hand their key on (`held`, live for one buffer step), buffers 1, 3, 5, 7 fold it with their
+// own, buffer 8 folds alone.
+template <int BUF>
+__device__ __forceinline__ void fold_key(unsigned& kmin, unsigned& held, unsigned key)
+{
+    if constexpr (BUF == kBuffers - 1) kmin = pk_min(kmin, key);
+    else if constexpr (BUF % 2 == 0) held = key;
+    else kmin = pk_min3_keys(kmin, held, key);
+}
 // |a - b| in both halves (values < 32768 per half)
 __device__ __forceinline__ unsigned pk_absdiff(unsigned a, unsigned b) { return pk_max(a, b) - pk_min(a, b); }
 // (m & x) | (~m & y): v_bfi_b32
