@@ -16,7 +16,10 @@
 //   * stage 3 cannot pack a rank into the value, so the sweep visits the buffers from the lowest rung of
 //     the reference's ladder to the highest (P0, P8, P1, P7, P2, P6, P3, P5, P4) and keeps
 //     (minimum, rank of the last buffer that was <= minimum): ties end on the higher rung, as :211-249.
-// Inputs are assumed finite, as the reference does (its min / == ladder has no NaN handling either).
+// What is promised about sample values (tests/test_float_values_gpu.py): the reference's bit patterns for every
+// finite input -- negative, out of [0, 1], denormal, -0.0, and beyond FLT_MAX / 4, where 4 * p1 overflows on its own -- and for
+// non-finite inputs wherever the reference writes a sample at all: its min / == ladder has no NaN handling, a NaN at the
+// minimum takes no arm and leaves the sample of the new frame as it was, and such samples are undefined here as well.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -74,16 +77,17 @@ struct LaneRole {
     unsigned first_mask, last_mask;  // all ones where first / last
 };
 
-// sum = ((p1 * 4 + p2 * 5) - p3) * 0.125; p1 * 4 is exact, so the fma rounds exactly like the reference's
-// multiply-then-add
+// sum = ((p1 * 4 + p2 * 5) - p3) * 0.125, every operation rounded on its own as in the reference (contraction is off).
+// p1 * 4 is exact only while it stays finite: beyond FLT_MAX / 4 the reference's product is an infinity, which an fma
+// (one rounding, of p1 * 4 + p2 * 5) would miss when p2 * 5 has the other sign -- so no fma here.
 __device__ __forceinline__ void sangnom_values(Line& L)
 {
 #pragma unroll
     for (int j = 0; j < PXL; ++j) {
         const float a = L.P[j + 2], b = L.P[j + 3], c = L.P[j + 4];
         const float q5 = b * 5.0f;
-        L.F[j] = (__builtin_fmaf(a, 4.0f, q5) - c) * 0.125f;
-        L.B[j] = (__builtin_fmaf(c, 4.0f, q5) - a) * 0.125f;
+        L.F[j] = ((a * 4.0f + q5) - c) * 0.125f;
+        L.B[j] = ((c * 4.0f + q5) - a) * 0.125f;
     }
 }
 
@@ -223,7 +227,8 @@ __host__ __device__ constexpr int visit(int i)
 }
 
 // kPadded: a plane narrower than its pool stride on a zero-filled pool (sn_config.fresh_pool): costs are zero in the padding
-// columns -- a multiplication by 1 or 0 (costs are finite and not negative, so that is exact).  Chroma modes: outside the
+// columns -- a multiplication by 1 or 0 (exact: by 1 for whatever the cost is, an infinity or a NaN included; by 0 only in lanes of
+// the padding, which load no samples and whose costs are zero already, so there is no inf * 0).  Chroma modes: outside the
 // chroma region the cost of the next row is what the previous pass left there (`stale`, fetched one buffer ahead).
 // How a wave of the region gets the previous pass's values in a row of a chroma mode (a wave runs whole loops of one kind):
 //   kQuiet   no lane takes one (a wave inside the region: three of the four of a 4:2:0 pass): no fetch -- even one whose every

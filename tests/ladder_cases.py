@@ -23,19 +23,34 @@ Y8_SHAPES = (("Y8", 64, 24, None), ("Y8", 992, 24, None), ("Y8", 4096, 16, None)
 YUV_SHAPES = (("YUV420P8", 64, 40, None), ("YUV420P8", 992, 40, None))
 
 
+# The same inputs at 9 .. 16 bits (test_u16_ladder_gpu.py): the constants scale with the threshold, 1 << (bits - 8), noise and
+# checker cover the depth's range, and the ramp wraps at the depth's modulus inside the plane.  "noise16" fills the 16-bit
+# container whatever the depth: samples above the depth's maximum, which the reference wraps modulo 65536 like any other.
+U16_PATTERNS = PATTERNS
+Y16_SHAPES = (("Y16", 64, 24, None), ("Y16", 544, 24, None), ("Y16", 1920, 16, None), ("Y16", 480, 200, (6, 0)), ("Y16", 480, 200, (6, 100)))
+YUV16_SHAPES = (("YUV420P16", 64, 40, None), ("YUV420P16", 1024, 40, None))
+ODD_DEPTHS = (9, 14, 15)
+ODD_DEPTH_SHAPES = ((64, 24), (544, 24))
+
+
 def frames(clip, pattern, n=NFRAMES, seed0=71):
+    scale = 1 << (clip.bits - 8)
+    top = (1 << clip.bits) - 1
     out = []
     for i in range(n):
         planes = synth.frame(clip, "noise", seed=seed0 + i)
         if pattern == "flat":  # every cost zero: all nine buffers tie at key = rank
-            planes = [np.full_like(p, 117 + 3 * i) for p in planes]
+            planes = [np.full_like(p, (117 + 3 * i) * scale) for p in planes]
         elif pattern == "near-flat":  # costs of 0 .. 2: keys far below 0x0400
-            planes = [(96 + p % 3).astype(p.dtype) for p in planes]
-        elif pattern == "checker2":  # two-pixel checker of 0 and 255: large sums, keys near 0x0ff0
+            planes = [(96 * scale + p % 3).astype(p.dtype) for p in planes]
+        elif pattern == "checker2":  # two-pixel checker of 0 and the maximum: large sums, keys near the top of the range
             planes = synth.frame(clip, "checker2", seed=seed0 + i)
-        elif pattern == "ramp":  # slope 1 along a row (wrapping at 256), one column further right per line: the diagonal
-            # buffers on either side of the matching one tie
-            planes = [((np.add.outer(np.arange(p.shape[0]), np.arange(p.shape[1])) + 5 * i) & 255).astype(p.dtype) for p in planes]
+        elif pattern == "ramp":  # slope 1 along a row (wrapping at 256, or at the depth's modulus a few columns in), one column
+            # further right per line: the diagonal buffers on either side of the matching one tie
+            start = 0 if clip.bits == 8 else top - 39
+            planes = [((np.add.outer(np.arange(p.shape[0]), np.arange(p.shape[1])) + 5 * i + start) & top).astype(p.dtype) for p in planes]
+        elif pattern == "noise16":
+            planes = [synth.plane(p.shape[0], p.shape[1], 2, 16, "noise", (seed0 + i) * 3 + k) for k, p in enumerate(planes)]
         elif pattern != "noise":
             raise ValueError(pattern)
         out.append(planes)

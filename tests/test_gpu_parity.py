@@ -13,6 +13,7 @@ import pytest
 from avisynth_sangnom2_amd import ClipFormat, SangNom, SangNom2, SangNomAA, SangNomAAHost, SangNomError, clip_format, synth
 from oracle.oracle import Oracle
 from oracle.sangnom_numpy import NumpySangNom
+from tests import float_cases as fc
 from tests.util import describe_diff, make_frames, oracle_cfg, same, to_host
 
 
@@ -1117,16 +1118,12 @@ def test_non_finite_float_samples_follow_the_reference_ladder(hip_lib, mode):
     ys, xs = rng.integers(0, 64, 40), rng.integers(0, 256, 40)
     vals = np.array([np.inf, -np.inf, np.nan, 3.0e38, -3.0e38], dtype=np.float32)
     plane[ys, xs] = vals[rng.integers(0, len(vals), 40)]
-    # pixels the reference writes: the same whatever the new frame held before
-    a = Oracle(oracle_cfg(clip)).process(src, dst=[np.zeros((64, 256), np.float32)])[0]
-    b = Oracle(oracle_cfg(clip)).process(src, dst=[np.full((64, 256), 7.0, np.float32)])[0]
-    written = (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
-    assert written.mean() > 0.7 and not written.all()
+    # pixels the reference writes: the same whatever the new frame held before (tests/float_cases.py, which
+    # test_float_values_gpu.py uses for the padded and coupled sweeps and the row bands)
+    want, written = fc.written_by_reference(clip, src)
     with SangNom2(clip, mode=mode) as flt:
         got = flt.get_frame(src)[0]
-    ok = (a.view(np.uint32) == got.view(np.uint32)) | (np.isnan(a) & np.isnan(got))
-    bad = np.argwhere(written & ~ok)
-    assert len(bad) == 0, f"{len(bad)} defined samples differ, first {bad[:4].tolist()}: {a[written & ~ok][:4]} vs {got[written & ~ok][:4]}"
+    fc.assert_defined_samples_match(want[0], written[0], got, mode)
 
 
 @pytest.mark.parametrize("fmt,w,h,kw", AA_CASES[:6], ids=[f"{c[0]}-{c[1]}x{c[2]}-{i}" for i, c in enumerate(AA_CASES[:6])])
