@@ -39,7 +39,8 @@ SN_SMALL_AUTO, SN_SMALL_SWEEP = 0, 1
 # What a filter object asks for when its caller says nothing (all zeros = the library's defaults).  The test suite
 # changes entries here (small clips would otherwise never reach the whole-plane sweeps); the library itself reads no
 # environment variable.
-POLICY_DEFAULTS = {"small_launches": SN_SMALL_AUTO, "chain": 0, "copy_threads": 0, "scratch_budget_mb": 0, "chroma_sweeps": 0}
+POLICY_DEFAULTS = {"small_launches": SN_SMALL_AUTO, "chain": 0, "copy_threads": 0, "scratch_budget_mb": 0, "chroma_sweeps": 0,
+                   "sse2_sweeps": 0}
 
 
 class SnConfig(ctypes.Structure):
@@ -50,8 +51,8 @@ class SnConfig(ctypes.Structure):
 
 
 class SnPolicy(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in ("struct_size", "small_launches", "chain", "copy_threads", "scratch_budget_mb", "chroma_sweeps")] + [
-        ("reserved", ctypes.c_int32 * 2)]
+    _fields_ = [(n, ctypes.c_int32) for n in ("struct_size", "small_launches", "chain", "copy_threads", "scratch_budget_mb", "chroma_sweeps",
+                                                 "sse2_sweeps")] + [("reserved", ctypes.c_int32 * 1)]
 
 
 class SnOptions(ctypes.Structure):

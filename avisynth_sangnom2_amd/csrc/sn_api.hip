@@ -44,10 +44,11 @@ struct Context {
     int arith = SN_ARITH_CXX;  // sn_options.arithmetic, fixed for the context's life
     // SN_ARITH_SSE2 on integer samples: the saturating instances of the pool kernels (float has one arithmetic)
     bool saturating() const { return arith == SN_ARITH_SSE2 && cfg.bytes_per_sample < 4; }
-    // ... and which sweeps have such instances: 8-bit planes on their own (plain, padded and row-band sweeps of
-    // sn_fused_u8_v3.hip).  Not the pool-coupled sweeps of subsampled chroma, nor the 16-bit sweep: those clips run on
-    // the pool kernels in this arithmetic
-    bool saturating_sweeps() const { return cfg.bytes_per_sample == 1 && (isolated || !sn::fused_needs_pools(cfg)); }
+    // ... and which sweeps it uses there.  Every sweep has such instances, but by default (sn_policy.sse2_sweeps = 0) a
+    // context keeps the kernels of the release that introduced the arithmetic: sweeps for 8-bit planes on their own
+    // (plain, padded and row-band sweeps of sn_fused_u8_v3.hip), the pool kernels for the pool-coupled sweeps of subsampled
+    // chroma and for 9..16-bit clips.  sse2_sweeps = 1: whatever has sweeps in the default arithmetic
+    bool saturating_sweeps() const { return policy.sse2_sweeps == 1 || (cfg.bytes_per_sample == 1 && (isolated || !sn::fused_needs_pools(cfg))); }
 
     PoolArgs pool{};  // allocated on first use when the fused kernels serve the configuration
 
@@ -486,8 +487,8 @@ static int create_impl(const sn_config* cfg, Context* c)
                                 p, c->plane_w(p), least);
     }
     if (c->saturating()) {
-        // Only the 8-bit sweeps of planes on their own have instances of this arithmetic; every other integer plane runs
-        // on the pool kernels, and the context says so (sn_info.fused_eligible = 0).  DESIGN.md 4.5.
+        // Without sn_policy.sse2_sweeps only the 8-bit sweeps of planes on their own run in this arithmetic; every other
+        // integer plane runs on the pool kernels, and the context says so (sn_info.fused_eligible = 0).  DESIGN.md 4.5.
         if (!c->saturating_sweeps()) {
             if (cfg->mode == SN_MODE_FUSED)
                 return sn::fail(c, SN_ERR_UNSUPPORTED,
@@ -593,6 +594,7 @@ static const char* policy_text(const sn_policy* p)
     if (p->copy_threads < 0 || p->copy_threads > 16) return "sn_policy.copy_threads must be 0..16";
     if (p->scratch_budget_mb < 0) return "sn_policy.scratch_budget_mb must not be negative";
     if (p->chroma_sweeps != 0 && p->chroma_sweeps != 1) return "sn_policy.chroma_sweeps must be 0 (U and V as one sweep) or 1 (a sweep each)";
+    if (p->sse2_sweeps != 0 && p->sse2_sweeps != 1) return "sn_policy.sse2_sweeps must be 0 (the kernels of the previous release) or 1 (sweeps wherever SN_ARITH_CXX has them)";
     return nullptr;
 }
 
@@ -1988,7 +1990,7 @@ int sn_get_info(sn_context* h, sn_info* info)
     info->pool_rows = c->bh + 1;
     info->fused_eligible = sn::fused_eligible(c->cfg) ? 1 : 0;
     if (c->saturating() && !c->saturating_sweeps()) {
-        info->fused_eligible = 0;  // sweeps without SN_ARITH_SSE2 instances: the pool path serves every plane
+        info->fused_eligible = 0;  // SN_ARITH_SSE2 without sn_policy.sse2_sweeps: the pool path serves every plane
     } else if (c->isolated) {
         info->fused_eligible = 1;
         for (int p = 0; p < c->nplanes(); ++p)
@@ -2046,6 +2048,7 @@ int sn_set_policy(sn_context* h, const sn_policy* policy)
     c->policy.chain = policy->chain;
     c->policy.copy_threads = policy->copy_threads;  // (a copier that already runs keeps its threads)
     c->policy.chroma_sweeps = policy->chroma_sweeps;
+    // (scratch_budget_mb and sse2_sweeps are read at creation only)
     return SN_OK;
 }
 

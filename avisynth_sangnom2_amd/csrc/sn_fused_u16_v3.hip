@@ -9,6 +9,11 @@
 //
 // Reference semantics: /root/reference/src/SangNom2.cpp:60-65 (wrap to uint16_t, arithmetic >> 3),
 // :74-124, :126-159 (sum / 16 wraps to uint16_t), :161-257, :361-391.
+//
+// ARITH (SN_ARITH_*, sn_pixel.h PxA<uint16_t, A>): 0 is the arithmetic above.  1 is the reference's SSE2 path, which
+// differs in two narrowing steps, both on 32-bit values here: the SangNom value is min((uint32_t)(4a + 5b - c) >> 3, 65535)
+// (unpack) and the box min(sum >> 4, 65535) (box_sat in front of every `& 0xffff0`).  Both stay 16-bit, so the packed forms
+// (F | B << 16, the pool's O pairs, the gather's halfwords) hold them as they hold the wrapped values.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -97,7 +102,17 @@ struct GatherLine {  // what park_gather() writes: 8 dwords of pixels, 4 of F pa
     unsigned d[8], f[4], b[4];
 };
 
-template <class LineT>
+// The window sum of the SSE2 arithmetic, in front of the mask that cuts O << 4 out of it: a sum of 2^20 or more (at most
+// 21 * 65535 < 2^21) becomes 0xfffff, whose bits 4..19 are 65535 = min(sum >> 4, 65535), src/SangNom2_SSE2.cpp:748-761.
+// One v_min_u32; the default arithmetic keeps the sum as it is (the mask wraps it).
+// (Written at each site as `if constexpr (ARITH == 1) box_sat(Bx)`: the default instances see the code they always had.)
+__device__ __forceinline__ void box_sat(unsigned (&Bx)[PXL])
+{
+#pragma unroll
+    for (int j = 0; j < PXL; ++j) Bx[j] = umin(Bx[j], 0xfffffu);
+}
+
+template <class LineT, int ARITH = 0>
 __device__ __forceinline__ void unpack(LineT& L, const Raw& q, const LaneRole& role, GatherLine* G = nullptr)
 {
     // dword i of (a, b) holds pixels x0 - 4 + 2i (low half) and x0 - 3 + 2i; the lane that owns column 0
@@ -124,9 +139,17 @@ __device__ __forceinline__ void unpack(LineT& L, const Raw& q, const LaneRole& r
 #pragma unroll
     for (int j = 0; j < PXL; ++j) {
         const unsigned a = L.P[j + 2], b = L.P[j + 3], c = L.P[j + 4];
-        const unsigned x5 = 4 * b + b + 0x80000u;
-        fv[j] = ((4 * a + x5 - c) >> 3) & kVal;
-        bv[j] = ((4 * c + x5 - a) >> 3) & kVal;
+        if constexpr (ARITH == 1) {
+            // the SSE2 arithmetic: no bias, a LOGICAL shift of the 32-bit sum (_mm_srli_epi32) and the unsigned-saturating
+            // pack -- a negative sum has its top bits set after the shift and saturates like a value above 65535
+            const unsigned x5 = 4 * b + b;
+            fv[j] = umin((4 * a + x5 - c) >> 3, kVal);
+            bv[j] = umin((4 * c + x5 - a) >> 3, kVal);
+        } else {
+            const unsigned x5 = 4 * b + b + 0x80000u;
+            fv[j] = ((4 * a + x5 - c) >> 3) & kVal;
+            bv[j] = ((4 * c + x5 - a) >> 3) & kVal;
+        }
         if constexpr (std::is_same<LineT, WideLine>::value) {
             L.Fv[j] = fv[j];
             L.Bv[j] = bv[j];
@@ -311,7 +334,7 @@ struct RowCtx {
 // FETCH (chroma modes): some lane of the wave takes the previous pass's value instead of a cost in this row.  A wave inside
 // the region (three of the four of a 4:2:0 pass) does not: its step is the one of a plane on its own -- v_sad_u16 accumulates,
 // D never exists -- and it fetches nothing (a fetch whose every lane is out of range is still a trip to the texture unit).
-template <int BUF, int MODE, bool S1, bool STORE, bool FETCH>
+template <int BUF, int MODE, bool S1, bool STORE, bool FETCH, int ARITH = 0>
 __device__ __forceinline__ void buffer_step(unsigned (&A)[PXL], unsigned (&kmin)[PXL], const LineOf<MODE>& n, const LineOf<MODE>& nn,
                                             const LaneRole& role, const PoolIO& io, const RowCtx& rc, const u32x4& stale)
 {
@@ -325,9 +348,10 @@ __device__ __forceinline__ void buffer_step(unsigned (&A)[PXL], unsigned (&kmin)
         } else {
             box7(S, Bx, role);
         }
+        if constexpr (ARITH == 1) box_sat(Bx);
 #pragma unroll
         for (int j = 0; j < PXL; ++j) {
-            const unsigned key = and_or(Bx[j], role.key_mask, rank_of<BUF, MODE>());  // (sum / 16 mod 65536) << 4 | rank
+            const unsigned key = and_or(Bx[j], role.key_mask, rank_of<BUF, MODE>());  // (sum / 16 mod 65536, or saturated) << 4 | rank
             O[j] = key >> 4;                                                     // SangNom2.cpp:152
             A[j] = S1 ? cost_acc<BUF>(n, nn, j, O[j]) : O[j];
             kmin[j] = umin(kmin[j], key);
@@ -339,6 +363,7 @@ __device__ __forceinline__ void buffer_step(unsigned (&A)[PXL], unsigned (&kmin)
 #pragma unroll
         for (int j = 0; j < PXL; ++j) S[j] = S1 ? cost_acc<BUF>(n, nn, j, A[j]) : A[j];
         box7(S, Bx, role);
+        if constexpr (ARITH == 1) box_sat(Bx);
 #pragma unroll
         for (int j = 0; j < PXL; ++j) {
             const unsigned t = Bx[j] & 0xffff0u;
@@ -369,10 +394,11 @@ __device__ __forceinline__ void buffer_step(unsigned (&A)[PXL], unsigned (&kmin)
 #pragma unroll
     for (int j = 0; j < PXL; ++j) S[j] = A[j] + D[j];
     box7(S, Bx, role);
+    if constexpr (ARITH == 1) box_sat(Bx);
 #pragma unroll
     for (int j = 0; j < PXL; ++j) {
         const unsigned t = Bx[j] & 0xffff0u;  // O << 4; shared by O and the key: three full-rate ops
-        O[j] = t >> 4;                        // (sum / 16) wraps to uint16_t, SangNom2.cpp:152
+        O[j] = t >> 4;                        // (sum / 16) wraps to uint16_t, SangNom2.cpp:152 (ARITH 1: saturated)
         A[j] = O[j] + D[j];
         kmin[j] = umin(kmin[j], t | rank_of<BUF, MODE>());
     }
@@ -381,7 +407,7 @@ __device__ __forceinline__ void buffer_step(unsigned (&A)[PXL], unsigned (&kmin)
 
 // A wave of a chroma sweep whose columns all lie outside the chroma region has no lines, no stage 1 and no stage 3: the
 // cost of the next row is what the previous pass left there, nothing else (see stale_wave_sweep).
-template <int BUF>
+template <int BUF, int ARITH = 0>
 __device__ __forceinline__ void stale_buffer_step(unsigned (&A)[PXL], const u32x4& stale, const LaneRole& role, const PoolIO& io, int r, int vout,
                                                   bool vout_any)
 {
@@ -390,9 +416,10 @@ __device__ __forceinline__ void stale_buffer_step(unsigned (&A)[PXL], const u32x
 #pragma unroll
     for (int j = 0; j < PXL; ++j) S[j] = A[j] + D[j];
     box7(S, Bx, role);
+    if constexpr (ARITH == 1) box_sat(Bx);
 #pragma unroll
     for (int j = 0; j < PXL; ++j) {
-        O[j] = (Bx[j] >> 4) & kVal;  // (sum / 16) wraps to uint16_t, SangNom2.cpp:152
+        O[j] = (Bx[j] >> 4) & kVal;  // (sum / 16) wraps to uint16_t, SangNom2.cpp:152 (ARITH 1: saturated)
         A[j] = O[j] + D[j];
     }
     if (vout_any) io.store(BUF, r, vout, O);
@@ -458,7 +485,7 @@ struct Out {
     u32x4 v;  // 8 interpolated 16-bit pixels
 };
 
-template <int MODE, bool S1, bool S3, bool STORE, bool FETCH, int NT>
+template <int MODE, bool S1, bool S3, bool STORE, bool FETCH, int NT, int ARITH = 0>
 __device__ __forceinline__ Out row_step(unsigned (&A)[reg_buffers(MODE)][PXL], const Parked<NT, reg_buffers(MODE)>& pk,
                                         int tid, const LineOf<MODE>& n, const LineOf<MODE>& nn, const LaneRole& role, unsigned thr_key,
                                         const PoolIO& io, const RowCtx& rc, StaleRing& st)
@@ -474,11 +501,11 @@ __device__ __forceinline__ Out row_step(unsigned (&A)[reg_buffers(MODE)][PXL], c
             else st.s[T % (kStaleAhead + 1)] = io.issue(T - kBuffers, rc.r + 2, rc.vin_next);
         }
         if constexpr (B < reg_buffers(MODE)) {
-            buffer_step<B, MODE, S1, STORE, FETCH>(A[B], kmin, n, nn, role, io, rc, st.s[B % (kStaleAhead + 1)]);
+            buffer_step<B, MODE, S1, STORE, FETCH, ARITH>(A[B], kmin, n, nn, role, io, rc, st.s[B % (kStaleAhead + 1)]);
         } else {
             unsigned t[PXL];
             pk.load_A(tid, B, t);
-            buffer_step<B, MODE, S1, STORE, FETCH>(t, kmin, n, nn, role, io, rc, st.s[B % (kStaleAhead + 1)]);
+            buffer_step<B, MODE, S1, STORE, FETCH, ARITH>(t, kmin, n, nn, role, io, rc, st.s[B % (kStaleAhead + 1)]);
             pk.store_A(tid, B, t);
         }
     };
@@ -566,7 +593,7 @@ __host__ __device__ constexpr int lds_bytes(int nw, int mode)
            + 2 * (nw + 1) * 2 * GH * kBuffers * PXL * 4;
 }
 
-template <int NW, int MODE, bool BAND>
+template <int NW, int MODE, bool BAND, int ARITH = 0>
 __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u16_v3(Args a)
 {
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -729,15 +756,15 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u16_v3(Args
                 }
                 const int vout = (r <= a.rows_out && in_cone(r, a.cone_out)) ? io.v_out : kOutOfRange;
                 const bool vout_any = __builtin_amdgcn_readfirstlane(__any(vout != kOutOfRange) ? 1 : 0) != 0;
-                stale_buffer_step<0>(As[0], cur[0], role, io, r, vout, vout_any);
-                stale_buffer_step<1>(As[1], cur[1], role, io, r, vout, vout_any);
-                stale_buffer_step<2>(As[2], cur[2], role, io, r, vout, vout_any);
-                stale_buffer_step<3>(As[3], cur[3], role, io, r, vout, vout_any);
-                stale_buffer_step<4>(As[4], cur[4], role, io, r, vout, vout_any);
-                stale_buffer_step<5>(As[5], cur[5], role, io, r, vout, vout_any);
-                stale_buffer_step<6>(As[6], cur[6], role, io, r, vout, vout_any);
-                stale_buffer_step<7>(As[7], cur[7], role, io, r, vout, vout_any);
-                stale_buffer_step<8>(As[8], cur[8], role, io, r, vout, vout_any);
+                stale_buffer_step<0, ARITH>(As[0], cur[0], role, io, r, vout, vout_any);
+                stale_buffer_step<1, ARITH>(As[1], cur[1], role, io, r, vout, vout_any);
+                stale_buffer_step<2, ARITH>(As[2], cur[2], role, io, r, vout, vout_any);
+                stale_buffer_step<3, ARITH>(As[3], cur[3], role, io, r, vout, vout_any);
+                stale_buffer_step<4, ARITH>(As[4], cur[4], role, io, r, vout, vout_any);
+                stale_buffer_step<5, ARITH>(As[5], cur[5], role, io, r, vout, vout_any);
+                stale_buffer_step<6, ARITH>(As[6], cur[6], role, io, r, vout, vout_any);
+                stale_buffer_step<7, ARITH>(As[7], cur[7], role, io, r, vout, vout_any);
+                stale_buffer_step<8, ARITH>(As[8], cur[8], role, io, r, vout, vout_any);
                 if (r < sweep && r % K == 0) {
                     if (pub_right || pub_left) {
                         unsigned* to = pub_right ? mb.at(((r + 1) / K) & 1, wave + 1, 0, slot) : mb.at(((r + 1) / K) & 1, wave - 1, 1, slot);
@@ -767,13 +794,13 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u16_v3(Args
     if (nk > 1) keep(dst_line + r0 * dst_step, q1, r0 == ra);
     if constexpr (gather_stage3(MODE)) {
         GatherLine G;
-        unpack(L0, q0, role, &G);
+        unpack<LineOf<MODE>, ARITH>(L0, q0, role, &G);
         parked.park_gather(tid, (r0 - 1) % 3, G);  // K[r0 - 1]: the upper line of row r0
-        unpack(L1, q1, role, &G);
+        unpack<LineOf<MODE>, ARITH>(L1, q1, role, &G);
         parked.park_gather(tid, r0 % 3, G);        // K[r0]: its lower line
     } else {
-        unpack(L0, q0, role);
-        unpack(L1, q1, role);
+        unpack<LineOf<MODE>, ARITH>(L0, q0, role);
+        unpack<LineOf<MODE>, ARITH>(L1, q1, role);
         parked.park(tid, L0);
     }
 
@@ -837,10 +864,10 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u16_v3(Args
         if constexpr (S1) {
             if constexpr (gather_stage3(MODE)) {
                 GatherLine G;
-                unpack(nn, qn, role, &G);  // waits for the line prefetched one row ago
+                unpack<LineOf<MODE>, ARITH>(nn, qn, role, &G);  // waits for the line prefetched one row ago
                 parked.park_gather(tid, (r + 1) % 3, G);  // K[r + 1]: lower line of the next row, upper line of the one after
             } else {
-                unpack(nn, qn, role);
+                unpack<LineOf<MODE>, ARITH>(nn, qn, role);
             }
             keep(dst_keep, qn, !BAND || (r + 1 >= ra && r < rb));
             dst_keep += dst_step;
@@ -886,7 +913,7 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u16_v3(Args
             rc.vout = (r <= a.rows_out && (!BAND || r >= ra) && in_cone(r, a.cone_out)) ? io.v_out : kOutOfRange;
             rc.any_out = __builtin_amdgcn_readfirstlane(__any(rc.vout != kOutOfRange) ? 1 : 0) != 0;
         }
-        pending = row_step<MODE, S1, S3, STORE, chroma_mode(MODE) && decltype(fetch_tag)::value>(A, parked, tid, n, nn, role, thr_key, io, rc, stale_ring);
+        pending = row_step<MODE, S1, S3, STORE, chroma_mode(MODE) && decltype(fetch_tag)::value, NT, ARITH>(A, parked, tid, n, nn, role, thr_key, io, rc, stale_ring);
         if constexpr (S1 && !gather_stage3(MODE)) parked.park(tid, n);  // n is the next row's c
         if (r < sweep && r % K == 0) {
             const int wpar = ((r + 1) / K) & 1;
@@ -1021,7 +1048,7 @@ namespace sn {
 namespace w16 {
 #endif
 
-template <int MODE, bool BAND = false>
+template <int MODE, bool BAND = false, int ARITH = 0>
 static hipError_t launch_mode(hipStream_t st, const Args& a, int nframes)
 {
     const int g = v3c::group_of(a.nw);
@@ -1030,9 +1057,9 @@ static hipError_t launch_mode(hipStream_t st, const Args& a, int nframes)
 #define SN_LAUNCH(NW)                                                                                              \
     case NW:                                                                                                       \
         if (lds > 64 * 1024)                                                                                       \
-            e = hipFuncSetAttribute((const void*)k_fused_u16_v3<NW, MODE, BAND>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
+            e = hipFuncSetAttribute((const void*)k_fused_u16_v3<NW, MODE, BAND, ARITH>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
         if (e == hipSuccess)                                                                                       \
-            hipLaunchKernelGGL((k_fused_u16_v3<NW, MODE, BAND>), dim3((nframes + g - 1) / g, BAND ? a.nbands : 1), dim3(NW * g * 64), lds, st, a); \
+            hipLaunchKernelGGL((k_fused_u16_v3<NW, MODE, BAND, ARITH>), dim3((nframes + g - 1) / g, BAND ? a.nbands : 1), dim3(NW * g * 64), lds, st, a); \
         break;
     switch (a.nw) {
         SN_LAUNCH(1) SN_LAUNCH(2) SN_LAUNCH(3) SN_LAUNCH(4) SN_LAUNCH(5) SN_LAUNCH(6) SN_LAUNCH(7) SN_LAUNCH(8)
@@ -1073,9 +1100,11 @@ void fused_u16_pool_unpack(const uint32_t* raw, int sweep_w, int rows, uint16_t*
         }
 }
 
+template <int ARITH>
+static hipError_t launch_arith(hipStream_t st, v3c::Args& a, const PlaneArgs& p, int nframes, const FusedPool* pool);
+
 hipError_t launch_fused_u16_v3(hipStream_t st, const PlaneArgs& p, double threshold, int nframes, const FusedPool* pool)
 {
-    if (p.arith != SN_ARITH_CXX) return hipErrorInvalidValue;  // this sweep has the C++ arithmetic only: an error, never wrapping pixels in SN_ARITH_SSE2
     v3c::Args a{};
     a.src = p.src;
     a.dst = p.dst;
@@ -1095,7 +1124,17 @@ hipError_t launch_fused_u16_v3(hipStream_t st, const PlaneArgs& p, double thresh
     a.nframes = nframes;
     a.src_bytes = (int)((int64_t)p.src_pitch * p.h_in);
     a.dst_bytes = (int)((int64_t)p.dst_pitch * p.h_out);
-    if (!pool) return w16::launch_mode<v3c::kPlain>(st, a, nframes);
+    a.arith = p.arith;
+    // every mode has an instance of either arithmetic; anything else is an error, never wrapping pixels in SN_ARITH_SSE2
+    if (p.arith == SN_ARITH_CXX) return launch_arith<0>(st, a, p, nframes, pool);
+    if (p.arith == SN_ARITH_SSE2) return launch_arith<1>(st, a, p, nframes, pool);
+    return hipErrorInvalidValue;
+}
+
+template <int ARITH>
+static hipError_t launch_arith(hipStream_t st, v3c::Args& a, const PlaneArgs& p, int nframes, const FusedPool* pool)
+{
+    if (!pool) return w16::launch_mode<v3c::kPlain, false, ARITH>(st, a, nframes);
     if (pool->nbands > 1) {
         a.band_rows = pool->band_rows;
         a.band_warm = pool->band_warm;
@@ -1103,10 +1142,10 @@ hipError_t launch_fused_u16_v3(hipStream_t st, const PlaneArgs& p, double thresh
         a.band_state = pool->band_state;
         a.band_flags = pool->band_flags;
         a.band_reset = pool->band_reset;
-        if (pool->mode == v3c::kPlain) return w16::launch_mode<v3c::kPlain, true>(st, a, nframes);
+        if (pool->mode == v3c::kPlain) return w16::launch_mode<v3c::kPlain, true, ARITH>(st, a, nframes);
         if (pool->mode != v3c::kLumaSpill) return hipErrorInvalidValue;  // of the pool-coupled sweeps only the luma one is cut
     }
-    if (pool->mode == v3c::kPlain) return w16::launch_mode<v3c::kPlain>(st, a, nframes);
+    if (pool->mode == v3c::kPlain) return w16::launch_mode<v3c::kPlain, false, ARITH>(st, a, nframes);
     a.pool_in = pool->pool_in;
     a.pool_out = pool->pool_out;
     a.pool_frame_stride = pool->frame_stride;
@@ -1120,11 +1159,11 @@ hipError_t launch_fused_u16_v3(hipStream_t st, const PlaneArgs& p, double thresh
     a.cone_in = pool->cone_in;
     a.cone_out = pool->cone_out;
     a.pool_row_bytes = pool->mode == v3c::kLumaSpill ? pool->pool_row_bytes : 0;
-    if (pool->mode == v3c::kLumaSpill && a.nbands > 1) return w16::launch_mode<v3c::kLumaSpill, true>(st, a, nframes);
-    if (pool->mode == v3c::kLumaSpill) return w16::launch_mode<v3c::kLumaSpill>(st, a, nframes);
-    if (pool->mode == v3c::kPadded) return w16::launch_mode<v3c::kPadded>(st, a, nframes);
-    if (!pool->pool_out) return w16::launch_mode<v3c::kChromaLast>(st, a, nframes);
-    return w16::launch_mode<v3c::kChroma>(st, a, nframes);
+    if (pool->mode == v3c::kLumaSpill && a.nbands > 1) return w16::launch_mode<v3c::kLumaSpill, true, ARITH>(st, a, nframes);
+    if (pool->mode == v3c::kLumaSpill) return w16::launch_mode<v3c::kLumaSpill, false, ARITH>(st, a, nframes);
+    if (pool->mode == v3c::kPadded) return w16::launch_mode<v3c::kPadded, false, ARITH>(st, a, nframes);
+    if (!pool->pool_out) return w16::launch_mode<v3c::kChromaLast, false, ARITH>(st, a, nframes);
+    return w16::launch_mode<v3c::kChroma, false, ARITH>(st, a, nframes);
 }
 
 }  // namespace sn

@@ -305,7 +305,9 @@ constexpr unsigned rank_of()
 // In the SSE2 arithmetic the window sum saturates: min(sum >> 4, 255) (src/SangNom2_SSE2.cpp:748-761).  The key is
 // (Bx & 0x0ff00ff0) | rank, so a half of 4096 or more has to become 4095, whose bits 4..11 are 255: ONE v_pk_min_u16 in
 // front of the v_and_or (Bx holds the true sums, below 2^16 per half: the borrows have been returned by then).  A
-// minimum never turns a zero half into something else, so S stays zero in every half that is not live.
+// minimum never turns a zero half into something else, so S stays zero in every half that is not live.  The bound holds
+// in the pool-coupled sweeps too: what they take from a pool is a saturated O of the previous pass, at most 255 like a
+// cost, and where a stale value enters the sum the cost beside it is zero -- S <= 3 * 255 and a window <= 5 355 per half.
 template <int ARITH>
 __device__ __forceinline__ unsigned box_sat(unsigned bx)
 {

@@ -123,7 +123,7 @@ __device__ __forceinline__ u32x2 own_bytes(const RawHalf& h, bool first)
 // One cost buffer of one step in a wave that holds chroma columns.
 // STALE: some lanes re-smooth stale values (class RS, and the masked steps of both region classes).
 // MASKED: the first kSkew and the last kSkew + 1 steps (see Step).
-template <int BUF, bool STALE, bool MASKED, bool PARK>
+template <int BUF, bool STALE, bool MASKED, bool PARK, int ARITH = 0>
 __device__ __forceinline__ void region_buffer_step(unsigned (&A)[PXL], unsigned (&kmin)[PXL], unsigned (&held)[PXL], const WideLine& n, const WideLine& nn, const Ctx& cx,
                                                    const Step& st, const u32x2& ld)
 {
@@ -168,7 +168,7 @@ __device__ __forceinline__ void region_buffer_step(unsigned (&A)[PXL], unsigned 
     unsigned O[PXL];
 #pragma unroll
     for (int j = 0; j < PXL; ++j) {
-        const unsigned key = and_or(Bx[j], cx.role.key_mask, rank_of<BUF, 0>());
+        const unsigned key = and_or(box_sat<ARITH>(Bx[j]), cx.role.key_mask, rank_of<BUF, 0>());  // (SN_ARITH_SSE2: U and V saturate alike, one packed minimum)
         O[j] = pk_lshr4(key);
         if constexpr (MASKED) {
             O[j] &= st.omask;
@@ -192,7 +192,7 @@ __device__ __forceinline__ u32x2 issue_stale(const Ctx& cx, int b, int row, int 
 }
 
 // The nine buffers and stage 3 of one step of a region wave; returns the interpolated bytes of both passes.
-template <bool STALE, bool MASKED, bool PARK>
+template <bool STALE, bool MASKED, bool PARK, int ARITH = 0>
 __device__ __forceinline__ Out region_row(unsigned (&A)[kBuffers][PXL], const WideLine& n, const WideLine& nn, const Ctx& cx, const Step& st, unsigned thr_key,
                                           u32x2 (&ahead)[kBuffers])
 {
@@ -208,7 +208,7 @@ __device__ __forceinline__ Out region_row(unsigned (&A)[kBuffers][PXL], const Wi
             __builtin_amdgcn_sched_barrier(0);  // (the refill must not be hoisted above the read of the same registers' previous content)
             ahead[B] = issue_stale(cx, B, st.s + 2, st.vin2);
         }
-        region_buffer_step<B, STALE, MASKED, PARK>(A[B], kmin, held, n, nn, cx, st, ld);
+        region_buffer_step<B, STALE, MASKED, PARK, ARITH>(A[B], kmin, held, n, nn, cx, st, ld);
         if constexpr (!STALE) __builtin_amdgcn_sched_barrier(0);
     };
     run(std::integral_constant<int, 0>{});
@@ -238,7 +238,7 @@ __device__ __forceinline__ Out region_row(unsigned (&A)[kBuffers][PXL], const Wi
 }
 
 // One cost buffer of one step in a wave right of the region (class S): D = the luma pass's row | last step's O << 16.
-template <int BUF>
+template <int BUF, int ARITH = 0>
 __device__ __forceinline__ void stale_buffer_step(unsigned (&A)[PXL], unsigned (&Oprev)[PXL], const LaneRole& role, const u32x2& ld, unsigned omask,
                                                   unsigned sel)
 {
@@ -251,7 +251,7 @@ __device__ __forceinline__ void stale_buffer_step(unsigned (&A)[PXL], unsigned (
     box7(S, Bx, role);
 #pragma unroll
     for (int j = 0; j < PXL; ++j) {
-        const unsigned O = pk_lshr4(Bx[j]) & omask;  // (sum / 16) wraps to uint8_t, SangNom2.cpp:152
+        const unsigned O = pk_lshr4(box_sat<ARITH>(Bx[j])) & omask;  // (sum / 16) wraps to uint8_t, SangNom2.cpp:152 (ARITH 1: saturates)
         A[j] = O + D[j];
         Oprev[j] = O;
     }
@@ -260,7 +260,7 @@ __device__ __forceinline__ void stale_buffer_step(unsigned (&A)[PXL], unsigned (
 // The sweep of one wave of class CLS.  Each class is a function of its own (sweep_entry, not inlined into the kernel): one
 // function holding all three made the register allocator spill a line of the plain steps to scratch, and a scratch reload
 // waits for every load issued before it -- the prefetched lines, the luma pass's rows -- i.e. for HBM, in every row.
-template <int NW, int CLS>
+template <int NW, int CLS, int ARITH>
 __device__ __forceinline__ void sweep(const Args& a)
 {
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -405,7 +405,7 @@ __device__ __forceinline__ void sweep(const Args& a)
                 const u32x2 ld = ahead[B];  // row s + 1, fetched a whole step ago
                 __builtin_amdgcn_sched_barrier(0);
                 ahead[B] = issue_stale(cx, B, s + 2, vin2);
-                stale_buffer_step<B>(A[B], Oprev[B], cx.role, ld, omask, sel);
+                stale_buffer_step<B, ARITH>(A[B], Oprev[B], cx.role, ld, omask, sel);
             };
             run(std::integral_constant<int, 0>{});
             run(std::integral_constant<int, 1>{});
@@ -469,8 +469,8 @@ __device__ __forceinline__ void sweep(const Args& a)
         if (a.offset == 1) keep(0, 0, q0, vstore);  // the line that cannot be interpolated, SangNom2.cpp:386-391
         keep(0, dst_line[0] + dst_step[0], q1, vstore);
         const Raw f0 = clamp_edges(q0, cx.role), f1 = clamp_edges(q1, cx.role);
-        unpack(L0, f0);
-        unpack(L1, f1);
+        unpack<WideLine, ARITH>(L0, f0);
+        unpack<WideLine, ARITH>(L1, f1);
         RawLine R;
         make_raw(R, f0, L0);
         park_raw_at(cx.lines + 0 * 5 * 64, 64, lane, R);  // K_U[0]: c of U's row 1
@@ -508,7 +508,7 @@ __device__ __forceinline__ void sweep(const Args& a)
         const int ku = s + 1, kv = s + 1 - kSkew;  // the kept lines this step takes in
         {
             const Raw fq = clamp_edges(qn, cx.role);
-            unpack(nn, fq);
+            unpack<WideLine, ARITH>(nn, fq);
             RawLine R;
             make_raw(R, fq, nn);
             park_raw_at(cx.lines + ((s + 1) % 3) * 5 * 64, 64, lane, R);
@@ -560,7 +560,7 @@ __device__ __forceinline__ void sweep(const Args& a)
             st.amask = ru == nr + 1 ? kHi : kAll;  // U's last row: its half of A keeps O alone, which is what V's last row needs
             st.from_a = rv == nr;
         }
-        const Out o = region_row<STALE, MASKED, CLS == kRS>(A, n, nn, cx, st, thr_key, ahead);
+        const Out o = region_row<STALE, MASKED, CLS == kRS, ARITH>(A, n, nn, cx, st, thr_key, ahead);
         {
             const int ru = s, rv = s - kSkew;
             u32x2 lo, hi;
@@ -629,7 +629,7 @@ __device__ __forceinline__ void sweep(const Args& a)
 // (an argument of a device function travels in vector registers and the compiler must take it for divergent: every word of
 // the argument block goes through v_readfirstlane once, so that in the sweep rows, pitches and pointers are scalars again --
 // as they are in a kernel that reads its own argument segment)
-template <int NW, int CLS>
+template <int NW, int CLS, int ARITH>
 __device__ __attribute__((noinline)) void sweep_entry(const Args* from)
 {
     static_assert(sizeof(Args) % 4 == 0, "Args is copied word by word");
@@ -640,10 +640,10 @@ __device__ __attribute__((noinline)) void sweep_entry(const Args* from)
     for (int i = 0; i < kWords; ++i) words[i] = (uint32_t)__builtin_amdgcn_readfirstlane((int)in[i]);
     Args a;
     __builtin_memcpy(&a, words, sizeof a);
-    sweep<NW, CLS>(a);
+    sweep<NW, CLS, ARITH>(a);
 }
 
-template <int NW>
+template <int NW, int ARITH = 0>
 __global__ void __launch_bounds__(NW * 64, 2) k_fused_u8_uv(Args a)
 {
     // the class of this wave, from its lanes' columns (ghost lanes included); the rest of the geometry is derived in sweep()
@@ -652,9 +652,9 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused_u8_uv(Args a)
     const bool live = gl < a.nl, chroma = live && gl * PXL < a.region_w, stale = live && !chroma;
     const int cls = __builtin_amdgcn_readfirstlane(__any((int)chroma) ? (__any((int)stale) ? (int)kRS : (int)kR) : (int)kS);
     // (the box is the same in every wave, the pool's last column included: one function per class)
-    if (cls == kS) sweep_entry<NW, kS>(&a);
-    else if (cls == kR) sweep_entry<NW, kR>(&a);
-    else sweep_entry<NW, kRS>(&a);
+    if (cls == kS) sweep_entry<NW, kS, ARITH>(&a);
+    else if (cls == kR) sweep_entry<NW, kR, ARITH>(&a);
+    else sweep_entry<NW, kRS, ARITH>(&a);
 }
 
 }  // namespace uv
@@ -674,7 +674,7 @@ bool fused_uv_ok(int sweep_w, int region_w, int nk_c, int bh)
 hipError_t launch_fused_u8_uv(hipStream_t st, const PlaneArgs& pu, const PlaneArgs& pv, double thr_u, double thr_v, int nframes, const FusedPool& pool)
 {
     using namespace v3c;
-    if (pu.arith != SN_ARITH_CXX || pv.arith != SN_ARITH_CXX) return hipErrorInvalidValue;  // the C++ arithmetic only (see launch_fused_u16_v3)
+    if (pu.arith != pv.arith || (pu.arith != SN_ARITH_CXX && pu.arith != SN_ARITH_SSE2)) return hipErrorInvalidValue;  // no instance: an error, never wrapping pixels
     uv::Args a{};
     const PlaneArgs* pp[2] = {&pu, &pv};
     for (int p = 0; p < 2; ++p) {
@@ -725,16 +725,22 @@ hipError_t launch_fused_u8_uv(hipStream_t st, const PlaneArgs& pu, const PlaneAr
     if (a.sweep_u != a.nk && a.sweep_u != a.nk - 1) return hipErrorInvalidValue;  // nr_c + 1, or nr_c where the pool has no row below (4:2:2)
     const int lds = uv::lds_bytes(nw, nreg, nrs);
     hipError_t e = hipSuccess;
+#define SN_LAUNCH_A(NW, ARITH)                                                                                         \
+    do {                                                                                                               \
+        if (lds > 64 * 1024) e = hipFuncSetAttribute((const void*)uv::k_fused_u8_uv<NW, ARITH>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
+        if (e == hipSuccess) hipLaunchKernelGGL((uv::k_fused_u8_uv<NW, ARITH>), dim3(nframes), dim3(NW * 64), lds, st, a); \
+    } while (0)
 #define SN_LAUNCH(NW)                                                                                                  \
     case NW:                                                                                                           \
-        if (lds > 64 * 1024) e = hipFuncSetAttribute((const void*)uv::k_fused_u8_uv<NW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
-        if (e == hipSuccess) hipLaunchKernelGGL((uv::k_fused_u8_uv<NW>), dim3(nframes), dim3(NW * 64), lds, st, a);    \
+        if (pu.arith == SN_ARITH_CXX) SN_LAUNCH_A(NW, 0);                                                              \
+        else SN_LAUNCH_A(NW, 1);                                                                                       \
         break;
     switch (nw) {
         SN_LAUNCH(1) SN_LAUNCH(2) SN_LAUNCH(3) SN_LAUNCH(4) SN_LAUNCH(5) SN_LAUNCH(6) SN_LAUNCH(7) SN_LAUNCH(8)
     default: return hipErrorInvalidValue;
     }
 #undef SN_LAUNCH
+#undef SN_LAUNCH_A
     if (e != hipSuccess) return e;
     return hipGetLastError();
 }

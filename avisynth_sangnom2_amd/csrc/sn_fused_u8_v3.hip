@@ -964,6 +964,20 @@ void fused_v3_pool_unpack(const uint32_t* raw, int sweep_w, int rows, uint8_t* o
             }
 }
 
+// The pool-coupled sweeps in the arithmetic ARITH (SN_ARITH_*).  What they take from a pool is a saturated O of the
+// previous pass (at most 255, like a cost), so the bounds next to box7 and box_sat hold with stale values in the sum.
+template <int ARITH>
+static hipError_t launch_coupled(hipStream_t st, const v3::Args& a, int nframes, const FusedPool& pool)
+{
+    if (a.nbands > 1) {  // of the pool-coupled sweeps only the luma one is cut (sn_fused_v3_common.h)
+        if (pool.mode != v3::kLumaSpill) return hipErrorInvalidValue;
+        return launch_mode<v3::kLumaSpill, true, ARITH>(st, a, nframes);
+    }
+    if (pool.mode == v3::kLumaSpill) return launch_mode<v3::kLumaSpill, false, ARITH>(st, a, nframes);
+    if (!pool.pool_out) return launch_mode<v3::kChromaLast, false, ARITH>(st, a, nframes);
+    return launch_mode<v3::kChroma, false, ARITH>(st, a, nframes);
+}
+
 // pool == nullptr: a plane on its own (kPlain).  Otherwise pool->mode selects kLumaSpill / kChroma and
 // pool->sweep_w is the luma width the sweep covers (p describes the plane being interpolated).
 hipError_t launch_fused_u8_v3(hipStream_t st, const PlaneArgs& p, double threshold, int nframes, const FusedPool* pool)
@@ -1002,7 +1016,7 @@ hipError_t launch_fused_u8_v3(hipStream_t st, const PlaneArgs& p, double thresho
         a.band_reset = pool->band_reset;
     }
     if (pool->mode == v3::kPlain) return launch_fused_u8_v3_plain(st, a, nframes, v3::kPlain);
-    if (a.arith != SN_ARITH_CXX && pool->mode != v3::kPadded) return hipErrorInvalidValue;  // the pool-coupled sweeps have no such instances
+    if (a.arith != SN_ARITH_CXX && a.arith != SN_ARITH_SSE2) return hipErrorInvalidValue;  // no instance: an error, never wrapping pixels
     a.pool_in = pool->pool_in;
     a.pool_out = pool->pool_out;
     a.pool_frame_stride = pool->frame_stride;
@@ -1017,13 +1031,7 @@ hipError_t launch_fused_u8_v3(hipStream_t st, const PlaneArgs& p, double thresho
     a.cone_out = pool->cone_out;
     if (pool->mode == v3::kPadded) return launch_fused_u8_v3_plain(st, a, nframes, v3::kPadded);
     a.pool_row_bytes = pool->mode == v3::kLumaSpill ? pool->pool_row_bytes : 0;
-    if (a.nbands > 1) {  // of the pool-coupled sweeps only the luma one is cut (sn_fused_v3_common.h)
-        if (pool->mode != v3::kLumaSpill) return hipErrorInvalidValue;
-        return launch_mode<v3::kLumaSpill, true>(st, a, nframes);
-    }
-    if (pool->mode == v3::kLumaSpill) return launch_mode<v3::kLumaSpill>(st, a, nframes);
-    if (!pool->pool_out) return launch_mode<v3::kChromaLast>(st, a, nframes);
-    return launch_mode<v3::kChroma>(st, a, nframes);
+    return a.arith == SN_ARITH_CXX ? launch_coupled<0>(st, a, nframes, *pool) : launch_coupled<1>(st, a, nframes, *pool);
 }
 
 #endif  // SN_TU_PLAIN

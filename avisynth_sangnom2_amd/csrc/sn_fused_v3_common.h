@@ -65,7 +65,7 @@ struct Args {
     uint32_t* band_state;     // [frame][band][warm, end][kBuffers * PXL][threads of the plane] state words, ghosts zeroed
     int32_t* band_flags;      // [frame]: set by the verification that follows (sn_band.hip)
     int32_t band_reset;       // this sweep clears band_flags first (the first plane of a frame)
-    int32_t arith;            // SN_ARITH_*: which instances the launcher picks (8-bit planes on their own have both)
+    int32_t arith;            // SN_ARITH_*: which instances the launcher picks (every integer sweep has both)
 };
 
 // The reference's nine buffers are sized for the luma plane and shared by all planes, so a

@@ -27,7 +27,7 @@ struct PlaneArgs {
     int32_t enabled;           // processPlane[i] || dh
     const int32_t* guard;      // pool-path kernels: when set, frame f is worked on only if guard[f] != 0 (sn_band.hip)
     int32_t guard_single;      // ... 1: ONE word decides for every frame of the launch (guard[0]; the redo of a chain that timed out)
-    int32_t arith = 0;         // SN_ARITH_*: read by the 8-bit sweeps of planes on their own (the pool kernels take PoolArgs::arith)
+    int32_t arith = 0;         // SN_ARITH_*: which instances of the fused sweeps run (the pool kernels take PoolArgs::arith)
     int32_t copied_elsewhere = 0;  // a plane that is not enabled is copied by the caller (sn_aa_*): launch_assemble leaves it alone
 };
 

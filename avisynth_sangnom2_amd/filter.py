@@ -67,7 +67,7 @@ class SangNom2:
                  device: int = 0, max_batch: int = 1, mode: str = "auto", stream: int | None = None,
                  host_depth: int = 0, isolated_planes: bool = False, fresh_pool: bool = False,
                  small_launches: int | None = None, chain: int | None = None, copy_threads: int | None = None,
-                 scratch_budget_mb: int | None = None, chroma_sweeps: int | None = None):
+                 scratch_budget_mb: int | None = None, chroma_sweeps: int | None = None, sse2_sweeps: int | None = None):
         # `threads` is a dummy in the reference (README.md:40-41); `opt` picks its CPU code path, and with it the
         # arithmetic: opt=1 reproduces its SSE2 path (SN_ARITH_SSE2), opt=0 and opt=-1 its C++ path.
         if opt < -1 or opt > 1:
@@ -85,9 +85,10 @@ class SangNom2:
         self.device = device
         self._h = ctypes.c_void_p()
         # scheduling only (sn_policy, sangnom_hip.h); None = capi.POLICY_DEFAULTS.  chain: 0 on, -1 off, 1 / 2 / 4 / 8 = on with
-        # at most that many workgroups per cost buffer
+        # at most that many workgroups per cost buffer.  sse2_sweeps (opt=1 only, read at creation): 1 = the sweeps serve every
+        # configuration they serve with opt=0, 0 = 9..16-bit and shared-pool 4:2:0 / 4:2:2 clips stay on the pool kernels
         pol = capi.policy(small_launches=small_launches, chain=chain, copy_threads=copy_threads, scratch_budget_mb=scratch_budget_mb,
-                          chroma_sweeps=chroma_sweeps)
+                          chroma_sweeps=chroma_sweeps, sse2_sweeps=sse2_sweeps)
         self.arithmetic = capi.arithmetic_of_opt(opt)
         opts = capi.options(self.arithmetic)
         rc = self._lib.sn_create_ex(ctypes.byref(cfg), ctypes.byref(pol), ctypes.byref(opts), ctypes.byref(self._h))
@@ -147,7 +148,8 @@ class SangNom2:
         return out
 
     def set_policy(self, **fields) -> None:
-        """Change the scheduling policy of the live context (sn_set_policy): small_launches, chain, copy_threads, chroma_sweeps."""
+        """Change the scheduling policy of the live context (sn_set_policy): small_launches, chain, copy_threads, chroma_sweeps
+        (scratch_budget_mb and sse2_sweeps are read at creation only)."""
         cur = capi.SnPolicy(struct_size=ctypes.sizeof(capi.SnPolicy))
         self._check(self._lib.sn_get_policy(self._h, ctypes.byref(cur)))
         for k, v in fields.items():
@@ -318,7 +320,7 @@ class _AAContext:
             dh=int(self.dh), luma=int(luma), chroma=int(chroma), device=device, max_batch=max_batch, mode=capi.SN_MODE_AUTO, host_depth=host_depth,
             isolated_planes=int(isolated_planes), fresh_pool=int(fresh_pool), stream=stream)
         self._h = ctypes.c_void_p()
-        pol = capi.policy(**{k: policy_kw.get(k) for k in ("small_launches", "chain", "copy_threads", "scratch_budget_mb", "chroma_sweeps")})
+        pol = capi.policy(**{k: policy_kw.get(k) for k in ("small_launches", "chain", "copy_threads", "scratch_budget_mb", "chroma_sweeps", "sse2_sweeps")})
         opts = capi.options(capi.arithmetic_of_opt(opt))
         rc = self._lib.sn_aa_create_ex(ctypes.byref(cfg), ctypes.byref(pol), ctypes.byref(opts), ctypes.byref(self._h))
         if rc != capi.SN_OK:

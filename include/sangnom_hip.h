@@ -115,7 +115,13 @@ typedef struct sn_policy {
     int32_t chroma_sweeps;      /* 8-bit 4:2:0 clips in the sweeps: 0 = U and V as ONE sweep where the geometry allows *
                                  * (sn_fused_u8_uv.hip: the U -> V hand-off stays in registers), 1 = one sweep per      *
                                  * chroma plane with a hand-off pool between them (rounds 1-3).  May change any time   */
-    int32_t reserved[2];        /* zero                                                                            */
+    int32_t sse2_sweeps;        /* SN_ARITH_SSE2 contexts only (no effect otherwise): 0 = the kernels of the release   *
+                                 * that introduced the arithmetic -- sweeps for 8-bit planes on their own, the pool    *
+                                 * kernels for 9..16-bit clips and for 8-bit clips whose subsampled chroma shares the   *
+                                 * luma pool; 1 = sweeps for every configuration that has them in SN_ARITH_CXX (same    *
+                                 * pixels, several times faster).  Read at creation only (sn_set_policy ignores it).    *
+                                 * Took the place of reserved[0]: a caller who zeroes the reserved words gets 0         */
+    int32_t reserved[1];        /* zero                                                                            */
 } sn_policy;
 
 /* What a context computes (sn_create_ex), as opposed to how (sn_policy).  Fixed for the context's life.
@@ -126,11 +132,13 @@ typedef struct sn_policy {
  *                                                (src/SangNom2_SSE2.cpp:446-516, used by stages 1 and 3)
  *   the box of stage 2, sum / 16                 SSE2: min(sum >> 4, MAXT)   (src/SangNom2_SSE2.cpp:748-761)
  * Everything else, and all of float, is the same.  SN_ARITH_CXX is this library's default and what sn_create /
- * sn_create_with_policy give.  Which kernels run in SN_ARITH_SSE2: 8-bit planes on their own (Y8, 4:4:4, isolated_planes,
- * fresh_pool) have fused sweeps in this arithmetic and are served as in the default one (sn_info.fused_eligible = 1,
- * SN_MODE_FUSED accepted); 8-bit clips whose subsampled chroma shares the luma pool (4:2:0, 4:2:2) and every 9..16-bit
- * clip run on the pool path -- the sweeps they use by default have no instances of this arithmetic, so
- * sn_info.fused_eligible is 0 and SN_MODE_FUSED fails at creation; float clips run as ever.  Every processed plane
+ * sn_create_with_policy give.  Which kernels run in SN_ARITH_SSE2: every fused sweep has instances of this arithmetic
+ * (8-bit, 8-bit U and V as one sweep, 9..16-bit; plain, padded, row bands and the pool-coupled sweeps of 4:2:0 / 4:2:2),
+ * and sn_policy.sse2_sweeps says which a context uses.  With 0, the default, 8-bit planes on their own (Y8, 4:4:4,
+ * isolated_planes, fresh_pool) are served by the sweeps as in the default arithmetic (sn_info.fused_eligible = 1,
+ * SN_MODE_FUSED accepted), while 8-bit clips whose subsampled chroma shares the luma pool (4:2:0, 4:2:2) and every
+ * 9..16-bit clip run on the pool path: sn_info.fused_eligible is 0 and SN_MODE_FUSED fails at creation.  With 1 every
+ * configuration is served as in SN_ARITH_CXX.  Float clips run as ever.  Every processed plane
  * must be at least two SSE2 vectors wide -- 32 / 16 / 8 samples for 8-bit / 16-bit / float, where the reference's SSE2
  * path reads outside the row below that -- else SN_ERR_UNSUPPORTED. */
 enum {

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Randomised parity run on the GPU: random formats, sizes, arguments, extension flags and frame sequences through
-the C ABI (host frames, device batches and the host ring) against oracle instances.  usage: python tools/fuzz.py [--seconds 120] [--seed 1]"""
+the C ABI (host frames, device batches and the host ring) against oracle instances.  A quarter of the integer
+configurations run with opt=1 (the SSE2 arithmetic, against tests/sse2_model.py), and those draw sn_policy.sse2_sweeps too.
+usage: python tools/fuzz.py [--seconds 120] [--seed 1]"""
 import argparse
 import os
 import random
@@ -12,6 +14,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from avisynth_sangnom2_amd import ClipFormat, SangNom2, clip_format, synth  # noqa: E402
 from oracle.oracle import Config, Oracle  # noqa: E402
+from tests import sse2_model as sm  # noqa: E402
 from tests.util import to_host  # noqa: E402
 
 FORMATS = ["Y8", "Y8", "Y8", "Y10", "Y16", "Y32", "YUV420P8", "YUV420P8", "YUV420P16", "YUV422P8", "YUV444P8", "YUV444PS", "YUV420PS"]
@@ -19,6 +22,15 @@ FORMATS = ["Y8", "Y8", "Y8", "Y10", "Y16", "Y32", "YUV420P8", "YUV420P8", "YUV42
 
 def cfg_of(clip, **kw):
     return Config(width=clip.width, height=clip.height, bytes=clip.bytes, bits=clip.bits, planes=clip.planes, subw=clip.subw, subh=clip.subh, **kw)
+
+
+def reference(clip, opt, **kw):
+    """process(planes, parity) of one reference instance: the C oracle (opt=0) or the numpy model of the SSE2 path (opt=1)."""
+    if opt == 1:
+        m = sm.model_for(1, clip.width, clip.height, bytes=clip.bytes, bits=clip.bits, planes=clip.planes, subw=clip.subw, subh=clip.subh, **kw)
+        return lambda planes, parity: m.get_frame(planes, parity=parity)
+    o = Oracle(cfg_of(clip, **kw))
+    return lambda planes, parity: o.process(planes, parity=parity)
 
 
 def same(a, b):
@@ -34,7 +46,7 @@ def main():
     t_end = time.time() + a.seconds
     n = bad = 0
     stats = {"fused": 0, "pool": 0, "ring": 0, "host": 0, "batch": 0, "frames": 0, "pixels": 0, "banded_frames": 0, "band_fallbacks": 0, "chained_frames": 0,
-             "uv_sweep_configs": 0, "chain_redone": 0}
+             "uv_sweep_configs": 0, "chain_redone": 0, "opt1": 0, "opt1_sweeps": 0}
     while time.time() < t_end:
         fmt = rng.choice(FORMATS)
         wide = rng.random() < 0.15
@@ -61,13 +73,17 @@ def main():
         ext = rng.choice(["none", "none", "isolated", "fresh"])
         way = rng.choice(["host", "ring", "batch"])  # batch: device-resident frames, one launch (history-carrying 8-bit clips: the chain)
         nframes = rng.randint(1, 4) if way != "batch" else rng.randint(2, 10)
-        pattern = rng.choice(["noise", "noise", "checker", "edges", "sine"])
+        opt = 1 if clip.bytes < 4 and rng.random() < 0.25 else 0
+        knob = rng.choice([0, 1]) if opt == 1 else 0  # sn_policy.sse2_sweeps: which kernels run in the SSE2 arithmetic
+        if opt == 1 and min(w >> (clip.subw if p else 0) for p in range(clip.planes)) < 32 // clip.bytes:
+            continue  # the SSE2 path is defined from two vectors per row on
+        pattern = rng.choice(["noise", "noise", "checker", "edges", "sine"] + (["noise01", "noise01", "checker2"] if opt == 1 else []))
         frames = [synth.frame(clip, pattern, seed=rng.randint(0, 1 << 20)) for _ in range(nframes)]
         parity = [rng.randint(0, 1) for _ in range(nframes)]
         # expected
         if ext == "none":
-            ora = Oracle(cfg_of(clip, **kw))
-            want = [ora.process(frames[f], parity=parity[f]) for f in range(nframes)]
+            ora = reference(clip, opt, **kw)
+            want = [ora(frames[f], parity[f]) for f in range(nframes)]
         else:
             per_plane = {}
             want = []
@@ -77,15 +93,15 @@ def main():
                     pl = frames[f][p]
                     yclip = ClipFormat(width=pl.shape[1], height=pl.shape[0], bytes=clip.bytes, bits=clip.bits)
                     enabled = kw["luma"] if p == 0 else kw["chroma"]
-                    mk = lambda: Oracle(cfg_of(yclip, order=kw["order"], aa=kw["aa"] if p == 0 else kw["aac"], dh=kw["dh"], luma=enabled))
+                    mk = lambda: reference(yclip, opt, order=kw["order"], aa=kw["aa"] if p == 0 else kw["aac"], dh=kw["dh"], luma=enabled)
                     o = mk() if ext == "fresh" else per_plane.setdefault(p, mk())
-                    outs.append(o.process([pl], parity=parity[f])[0])
+                    outs.append(o([pl], parity[f])[0])
                 want.append(outs)
         small = rng.choice([1, 0])  # SN_SMALL_SWEEP: the whole-plane sweeps, or auto mode's small-launch paths (bands, pool kernels)
         try:
             sweeps = rng.choice([0, 0, 0, 1])  # 8-bit 4:2:0: U and V as one sweep (default) or a sweep each
             flt = SangNom2(clip, host_depth=rng.choice([1, 2, 3, 4, 5, 8, 12]), max_batch=nframes, isolated_planes=ext == "isolated", fresh_pool=ext == "fresh", small_launches=small,
-                           chroma_sweeps=sweeps, **kw)
+                           chroma_sweeps=sweeps, opt=opt, sse2_sweeps=knob, **kw)
         except Exception as e:  # a geometry the library rejects must be one it documents
             if "exceeds the supported maximum" in str(e):
                 continue
@@ -128,6 +144,8 @@ def main():
             stats["chained_frames"] += info.chained_frames
             stats["uv_sweep_configs"] += info.uv_sweeps
             stats["chain_redone"] += info.chain_redone
+            stats["opt1"] += opt
+            stats["opt1_sweeps"] += knob
         stats["fused" if fused else "pool"] += 1
         for f in range(nframes):
             for p in range(clip.planes):
@@ -137,7 +155,7 @@ def main():
                     np.savez(f"gpurun_out/fuzz_mismatch_{n}.npz", **{f"src{q}": frames[f][q] for q in range(clip.planes)},
                              **{f"want{q}": want[f][q] for q in range(clip.planes)}, **{f"got{q}": got[f][q] for q in range(clip.planes)})
                     print(f"MISMATCH {fmt} {w}x{h} {kw} ext={ext} way={way} frame {f}/{nframes} plane {p} pattern={pattern} parity={parity} "
-                          f"small_launches={small} chroma_sweeps={sweeps} uv={info.uv_sweeps} bands={band_set} banded={info.banded_frames} fallbacks={info.band_fallbacks} "
+                          f"small_launches={small} chroma_sweeps={sweeps} opt={opt} sse2_sweeps={knob} uv={info.uv_sweeps} bands={band_set} banded={info.banded_frames} fallbacks={info.band_fallbacks} "
                           f"fused={info.fused_frames} n={len(d)} rows {d[:, 0].min()}..{d[:, 0].max()} cols {d[:, 1].min()}..{d[:, 1].max()}", flush=True)
         n += 1
         if n % 50 == 0:
