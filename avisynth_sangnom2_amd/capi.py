@@ -30,6 +30,7 @@ EXPORTS = (
     "sn_create_ex", "sn_aa_create_ex", "sn_get_arithmetic",
     "sn_aa_process_device_strided", "sn_aa_synchronize", "sn_aa_get_stream", "sn_aa_get_info",
     "sn_aa_host_slots", "sn_aa_submit_host", "sn_aa_collect_host",
+    "sn_get_parts_info", "sn_aa_get_parts_info", "sn_debug_set_column_parts",
 )
 
 # sn_options.arithmetic: which of the reference's two code paths a context reproduces (sangnom_hip.h)
@@ -56,11 +57,19 @@ class SnPolicy(ctypes.Structure):
 
 
 class SnOptions(ctypes.Structure):
-    _fields_ = [("struct_size", ctypes.c_int32), ("arithmetic", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6)]
+    _fields_ = [("struct_size", ctypes.c_int32), ("arithmetic", ctypes.c_int32), ("column_parts", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 5)]
 
 
-def options(arithmetic: int = SN_ARITH_CXX) -> "SnOptions":
-    return SnOptions(struct_size=ctypes.sizeof(SnOptions), arithmetic=int(arithmetic))
+class SnPartsInfo(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_int32), ("parts", ctypes.c_int32 * 3), ("ghost_columns", ctypes.c_int32),
+                ("part_frames", ctypes.c_int64), ("part_fallbacks", ctypes.c_int64)]
+
+
+def options(arithmetic: int = SN_ARITH_CXX, column_parts: int = 0) -> "SnOptions":
+    """sn_options: what is fixed at creation.  column_parts=1: 16-bit and float planes wider than one workgroup of the
+    sweeps holds (3840 columns) are swept in column parts (sangnom_hip.h)."""
+    return SnOptions(struct_size=ctypes.sizeof(SnOptions), arithmetic=int(arithmetic), column_parts=int(column_parts))
 
 
 def arithmetic_of_opt(opt: int) -> int:
@@ -173,5 +182,8 @@ def load():
     L.sn_aa_host_slots.argtypes = [vp]
     L.sn_aa_submit_host.argtypes = [vp, p3v, p3i, i32, ctypes.POINTER(i32)]
     L.sn_aa_collect_host.argtypes = [vp, i32, p3v, p3i]
+    L.sn_get_parts_info.argtypes = [vp, ctypes.POINTER(SnPartsInfo)]
+    L.sn_aa_get_parts_info.argtypes = [vp, i32, ctypes.POINTER(SnPartsInfo)]
+    L.sn_debug_set_column_parts.argtypes = [vp, i32, i32]
     _lib = L
     return L

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "sn_copier.h"
+#include "sn_fused_v3_common.h"
 #include "sn_internal.h"
 
 constexpr int kSyncChunks = 4;  // chunks of rows a pageable plane of the synchronous call is staged in
@@ -148,6 +149,22 @@ struct Context {
     // a failure the next launches go straight to the pool path, twice as many after every further one
     int64_t band_fallbacks_seen = 0;
     int band_pause = 0, band_pause_next = 0, band_good = 0;
+
+    // column parts (sn_options.column_parts; sn_fused_v3_common.h, kParts): per scratch slot the frame's seam record and its
+    // flag, the count of failed frames on the device and mirrored to host memory (the pause looks at the mirror)
+    bool parts_on = false;
+    bool plane_parts[3] = {false, false, false};  // the plane is too wide for one workgroup and is cut
+    bool parts_eligible = false;                  // ... and what sn_info.fused_eligible says of such a context
+    int parts_force = 0, parts_ghost_force = 0;   // sn_debug_set_column_parts
+    uint8_t* parts_rec = nullptr;
+    int64_t parts_frame_bytes = 0;
+    int parts_slots = 0;
+    int32_t* parts_flags = nullptr;
+    int64_t* parts_fallbacks = nullptr;
+    int64_t* parts_fallbacks_dev = nullptr;
+    int64_t part_frames = 0;
+    int64_t parts_fallbacks_seen = 0;
+    int parts_pause = 0, parts_pause_next = 0, parts_good = 0;
 
     int plane_w(int p) const { return p == 0 ? cfg.width : cfg.width >> cfg.sub_w; }
     int plane_h_in(int p) const { return p == 0 ? cfg.height : cfg.height >> cfg.sub_h; }
@@ -351,6 +368,10 @@ void sn_destroy(sn_context* h)
     if (c->band_flags) (void)hipFree(c->band_flags);
     if (c->band_fallbacks) (void)hipHostFree(c->band_fallbacks);
     if (c->band_fallbacks_dev) (void)hipFree(c->band_fallbacks_dev);
+    if (c->parts_rec) (void)hipFree(c->parts_rec);
+    if (c->parts_flags) (void)hipFree(c->parts_flags);
+    if (c->parts_fallbacks) (void)hipHostFree(c->parts_fallbacks);
+    if (c->parts_fallbacks_dev) (void)hipFree(c->parts_fallbacks_dev);
     delete c->copier;
     for (int p = 0; p < 3; ++p) {
         if (c->ring_pin_in[p]) (void)hipHostFree(c->ring_pin_in[p]);
@@ -424,6 +445,112 @@ static int ensure_fpool(Context* c, int i)
     return SN_OK;
 }
 
+// Column parts (sn_options.column_parts): a 16-bit or float plane on its own that is too wide for one workgroup is cut into
+// 2 .. kMaxParts windows of at most kPartsWindow columns -- four waves, so that two workgroups share a compute unit as the
+// sweeps of narrower planes do.  Seams lie on multiples of 32; a window reaches at least kPartsGhost columns (rounded up to
+// 32) beyond each of its seams; all windows of a plane are equally wide, so that one launch sweeps them all (the narrower
+// ones are widened, away from the image edge or to both sides).  DESIGN.md 4.6 has the numbers behind the ghosts.
+constexpr int kMaxParts = sn::kMaxColumnParts;
+constexpr int kPartsWindow = (sn::v3c::kFirst + 3 * sn::v3c::kInner) * sn::v3c::PXL;  // 1936
+constexpr int kPartsGhost16 = 64, kPartsGhost32 = 96;
+struct PartsPlan {
+    int n = 0;
+    int win_w = 0;
+    int win_x[kMaxParts];
+    int seam[kMaxParts + 1];  // seam[k], k = 1 .. n - 1: the first own column of part k
+};
+static int parts_ghost(const Context* c) { return c->cfg.bytes_per_sample == 2 ? kPartsGhost16 : kPartsGhost32; }
+
+static bool plan_parts(const Context* c, int p, PartsPlan& pl)
+{
+    pl.n = 0;
+    const int B = c->cfg.bytes_per_sample;
+    if (!c->parts_on || B < 2 || c->fresh || p >= c->nplanes()) return false;
+    if (!(c->cfg.dh || c->process[p])) return false;
+    if (c->isolated ? c->plane_padded[p] : sn::fused_needs_pools(c->cfg)) return false;  // planes on their own only
+    const int w = c->plane_w(p);
+    if (w % 32 != 0 || c->plane_h_out(p) / 2 - 1 < 1) return false;
+    const int G = (parts_ghost(c) + 31) & ~31;
+    int P = c->parts_force;
+    if (P == 0) {
+        if (!sn::fused_parts_plane_eligible(B, w)) return false;
+        for (P = 2; P <= kMaxParts; ++P)
+            if ((((w + P - 1) / P + 31) & ~31) + 2 * G <= kPartsWindow) break;
+    }
+    if (P < 2 || P > kMaxParts) return false;
+    pl.seam[0] = 0;
+    pl.seam[P] = w;
+    for (int k = 1; k < P; ++k) pl.seam[k] = (int)(((int64_t)k * w / P + 16) & ~31);
+    int lo[kMaxParts], ww = 0;
+    for (int k = 0; k < P; ++k) {
+        if (pl.seam[k + 1] - pl.seam[k] < 32) return false;  // not wide enough to hold that many parts
+        lo[k] = k == 0 ? 0 : pl.seam[k] - G;
+        const int hi = k == P - 1 ? w : pl.seam[k + 1] + G;
+        if (lo[k] < 0 || hi > w) return false;
+        ww = hi - lo[k] > ww ? hi - lo[k] : ww;
+    }
+    if (sn::v3c::strips_for(ww / sn::v3c::PXL) > 8) return false;
+    pl.win_w = ww;
+    for (int k = 0; k < P; ++k) {  // every window as wide as the widest
+        const int hi = k == P - 1 ? w : pl.seam[k + 1] + G;
+        int x = lo[k] - (((ww - (hi - lo[k])) / 2) & ~31);
+        x = x < 0 ? 0 : x > w - ww ? w - ww : x;
+        pl.win_x[k] = x;
+    }
+    if (c->parts_ghost_force > 0) {  // the test hook: every seam that far from the end of the window left of it
+        for (int k = 1; k < P; ++k) {
+            pl.seam[k] = pl.win_x[k - 1] + pl.win_w - c->parts_ghost_force;
+            if (pl.seam[k] < pl.win_x[k] + 8 || pl.seam[k] <= pl.seam[k - 1]) return false;
+        }
+    }
+    pl.n = P;
+    return true;
+}
+
+// Seam records and flags for `nseams` seams per frame: allocated when the context is created (and by the test hook), never
+// inside a launch; counted against the scratch budget.
+static int ensure_parts(Context* c, int nseams)
+{
+    int nr_max = 0;
+    for (int p = 0; p < c->nplanes(); ++p)
+        if (c->cfg.dh || c->process[p]) nr_max = c->plane_h_out(p) / 2 - 1 > nr_max ? c->plane_h_out(p) / 2 - 1 : nr_max;
+    const int64_t need = (int64_t)nseams * 2 * sn::parts_side_bytes(c->cfg.bytes_per_sample, nr_max);
+    if (need <= 0) return SN_OK;
+    const int64_t want = c->cfg.max_batch > c->host_depth ? c->cfg.max_batch : c->host_depth;
+    if (c->parts_rec && need <= c->parts_frame_bytes) return SN_OK;
+    SN_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->parts_rec) SN_HIP(c, hipFree(c->parts_rec));
+    c->parts_rec = nullptr;
+    int64_t fit = scratch_budget(c) / need;
+    fit = fit < 1 ? 1 : fit > want ? want : fit;
+    c->parts_frame_bytes = need;
+    c->parts_slots = (int)fit;
+    SN_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->parts_rec), (size_t)need * fit));
+    if (!c->parts_flags) {
+        SN_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->parts_flags), sizeof(int32_t) * want));
+        SN_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->parts_fallbacks_dev), sizeof(int64_t)));
+        SN_HIP(c, hipMemsetAsync(c->parts_fallbacks_dev, 0, sizeof(int64_t), c->stream));
+        SN_HIP(c, hipStreamSynchronize(c->stream));
+        SN_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->parts_fallbacks), sizeof(int64_t), hipHostMallocMapped));
+        *c->parts_fallbacks = 0;
+    }
+    return SN_OK;
+}
+
+// ... and the pool slots the redo of a failed frame runs on
+static int ensure_parts_scratch(Context* c)
+{
+    int nseams = 0;
+    for (int p = 0; p < c->nplanes(); ++p) {
+        PartsPlan pl;
+        if (!plan_parts(c, p, pl)) continue;
+        nseams = pl.n - 1 > nseams ? pl.n - 1 : nseams;
+        const int rc = ensure_pool(c, c->isolated ? p : 0);
+        if (rc != SN_OK) return rc;
+    }
+    return nseams > 0 ? ensure_parts(c, nseams) : SN_OK;
+}
+
 static int create_impl(const sn_config* cfg, Context* c)
 {
     c->cfg = *cfg;
@@ -471,10 +598,18 @@ static int create_impl(const sn_config* cfg, Context* c)
             if (!(cfg->dh || c->process[p])) continue;  // copied planes need nothing
             if (pool.stride_e != c->plane_w(p) && !c->fresh) c->history_free = false;
             c->plane_fused[p] = sn::fused_plane_eligible(cfg->bytes_per_sample, c->plane_w(p));
+            if (!c->plane_fused[p] && c->parts_on && !c->fresh && sn::fused_parts_plane_eligible(cfg->bytes_per_sample, c->plane_w(p)))
+                c->plane_fused[p] = c->plane_parts[p] = true;  // in column parts
             if (c->fresh && !c->plane_fused[p] && sn::fused_padded_plane_eligible(cfg->bytes_per_sample, c->plane_w(p)))
                 c->plane_fused[p] = c->plane_padded[p] = true;
             eligible = eligible && c->plane_fused[p];
         }
+    }
+    if (!c->isolated && !eligible && c->parts_on && !sn::fused_needs_pools(c->cfg) &&
+        sn::fused_parts_plane_eligible(cfg->bytes_per_sample, cfg->width)) {
+        // Y and 4:4:4 (and clips whose subsampled chroma is only copied): every processed plane is as wide as the pool
+        eligible = true;
+        for (int p = 0; p < c->nplanes(); ++p) c->plane_parts[p] = (cfg->dh || c->process[p]) && c->plane_w(p) == cfg->width;
     }
     if (c->arith == SN_ARITH_SSE2) {
         // The reference's SSE2 stage drivers read one vector to the left of the last full one, so its output is defined
@@ -496,7 +631,7 @@ static int create_impl(const sn_config* cfg, Context* c)
                                 "this clip (%s) runs on the pool path in that mode",
                                 cfg->bytes_per_sample == 2 ? "9..16-bit samples" : "subsampled chroma sharing the luma pool");
             eligible = false;
-            for (int p = 0; p < 3; ++p) c->plane_fused[p] = c->plane_padded[p] = false;
+            for (int p = 0; p < 3; ++p) c->plane_fused[p] = c->plane_padded[p] = c->plane_parts[p] = false;
         }
         c->pool.arith = SN_ARITH_SSE2;
         for (int p = 0; p < 3; ++p) c->plane_pool[p].arith = SN_ARITH_SSE2;
@@ -504,6 +639,7 @@ static int create_impl(const sn_config* cfg, Context* c)
     if (cfg->mode == SN_MODE_FUSED && !eligible)
         return sn::fail(c, SN_ERR_UNSUPPORTED, "SN_MODE_FUSED requested but this configuration is not eligible");
     c->use_fused = eligible && cfg->mode != SN_MODE_POOL;
+    c->parts_eligible = eligible;
 
     c->fused420 = c->use_fused && !c->isolated && sn::fused_needs_pools(c->cfg);
     if (c->isolated && cfg->mode == SN_MODE_POOL)
@@ -580,6 +716,14 @@ static int create_impl(const sn_config* cfg, Context* c)
             if (rc2 != SN_OK) return rc2;
         }
     }
+    if (c->plane_parts[0] || c->plane_parts[1] || c->plane_parts[2]) {
+        if (cfg->mode == SN_MODE_POOL) {
+            for (int p = 0; p < 3; ++p) c->plane_parts[p] = false;
+        } else {
+            rc = ensure_parts_scratch(c);
+            if (rc != SN_OK) return rc;
+        }
+    }
     SN_HIP(c, hipStreamSynchronize(c->stream));
     return SN_OK;
 }
@@ -607,6 +751,7 @@ static const char* options_text(const sn_options* o)
     if (!o) return nullptr;
     if (o->struct_size != (int32_t)sizeof(sn_options)) return "sn_options.struct_size mismatch";
     if (o->arithmetic != SN_ARITH_CXX && o->arithmetic != SN_ARITH_SSE2) return "sn_options.arithmetic must be SN_ARITH_CXX or SN_ARITH_SSE2";
+    if (o->column_parts != 0 && o->column_parts != 1) return "sn_options.column_parts must be 0 (off) or 1 (wide 16-bit and float planes in column parts)";
     for (int32_t r : o->reserved)
         if (r != 0) return "sn_options.reserved must be zero";
     return nullptr;
@@ -624,6 +769,7 @@ int sn_create_ex(const sn_config* cfg, const sn_policy* policy, const sn_options
     Context* c = new (std::nothrow) Context();
     if (!c) return sn::fail(nullptr, SN_ERR_INVALID_ARG, "out of host memory");
     if (options) c->arith = options->arithmetic;
+    if (options) c->parts_on = options->column_parts == 1;
     if (policy) c->policy = *policy;
     c->policy.struct_size = (int32_t)sizeof(sn_policy);
     rc = create_impl(cfg, c);
@@ -769,6 +915,7 @@ constexpr int kMaxBandSlots = 192;  // launches of more frames than that fill th
 // Rows of the shortest processed plane if this context can cut small launches into bands at all, else 0.
 static int band_rows_available(const Context* c)
 {
+    if (c->plane_parts[0] || c->plane_parts[1] || c->plane_parts[2] || c->parts_force > 0) return 0;  // never combined with column parts
     if (c->band_force < 0 || c->cfg.mode != SN_MODE_AUTO || !c->history_free) return 0;
     if (c->isolated) {  // every processed plane must have the sweep for planes on their own (not the padded one)
         for (int p = 0; p < c->nplanes(); ++p)
@@ -958,6 +1105,39 @@ static int run_group(Context* c, hipStream_t st, int slot0, int n, const void* c
     const int nbands = all_fused ? band_count(c, n, slot0) : 0;
     if (nbands == 0 && prefer_pool(c, n, slot0))
         for (int p = 0; p < 3; ++p) fused[p] = false;
+    // Column parts: which planes of this launch are cut.  Under SN_SMALL_AUTO a launch small enough for row bands goes
+    // where it went before the option existed, to the pool path; after a launch with a failed frame the parts pause, as
+    // the bands do (band_count).
+    PartsPlan plan[3];
+    bool any_parts = false;
+    for (int p = 0; p < c->nplanes(); ++p) any_parts = (fused[p] && plan_parts(c, p, plan[p])) || any_parts;
+    if (any_parts) {
+        bool to_pool = slot0 >= c->parts_slots || slot0 >= c->slots || !c->parts_rec;
+        if (c->cfg.mode == SN_MODE_AUTO && !sweeps_always(c) && 512 / n >= 3) to_pool = true;
+        if (!to_pool && c->parts_fallbacks) {
+            const int64_t seen = *c->parts_fallbacks;  // as of the last launch in parts that has finished
+            if (seen != c->parts_fallbacks_seen) {
+                c->parts_fallbacks_seen = seen;
+                c->parts_pause_next = c->parts_pause_next < 8 ? 8 : c->parts_pause_next < 1024 ? 2 * c->parts_pause_next : 1024;
+                c->parts_pause = c->parts_pause_next;
+                c->parts_good = 0;
+            } else if (c->parts_pause == 0 && ++c->parts_good >= 64) {
+                c->parts_pause_next = 0;
+            }
+            if (c->parts_pause > 0) {
+                --c->parts_pause;
+                to_pool = true;
+            }
+        }
+        if (to_pool) {
+            // the planes that only the parts can sweep go to the pool path; forced parts of a narrower plane to its whole-plane sweep
+            for (int p = 0; p < c->nplanes(); ++p) {
+                if (plan[p].n > 0 && c->plane_parts[p]) fused[p] = false;
+                plan[p].n = 0;
+            }
+            any_parts = false;
+        }
+    }
     // sn_process_host's plane pipeline: a plane's kernels wait for its copy and announce their end; the paths that are
     // not written plane by plane wait for everything first (the caller records what was not announced)
     auto plane_in = [&](int p) -> hipError_t {
@@ -996,6 +1176,56 @@ static int run_group(Context* c, hipStream_t st, int slot0, int n, const void* c
         if (c->cfg.bytes_per_sample == 4) return sn::launch_fused_f32_v3(st, a, c->threshold(p), m, nullptr);
         if (c->cfg.bytes_per_sample == 2) return sn::launch_fused_u16_v3(st, a, c->threshold(p), m, nullptr);
         return sn::launch_fused_u8_v3(st, a, c->threshold(p), m, nullptr);
+    };
+
+    // One plane in column parts: a sweep per window, the check of the seams, and the pool path for the frames that fail it
+    // (guarded launches, a chunk of pool slots at a time, that exit at once otherwise).  No k_assemble: kept lines are right
+    // either way.
+    auto parts_plane = [&](int p, const sn::PlaneArgs& a0, sn::PoolArgs pool) -> int {
+        const PartsPlan& pl = plan[p];
+        const int B = c->cfg.bytes_per_sample;
+        const int64_t side = sn::parts_side_bytes(B, a0.h_out / 2 - 1);
+        const int nseams = pl.n - 1;
+        if ((int64_t)nseams * 2 * side > c->parts_frame_bytes) return sn::fail(c, SN_ERR_UNSUPPORTED, "column parts: the seam record is too small for %d parts", pl.n);
+        const int cap = c->parts_slots - slot0, pcap = c->slots - slot0;
+        uint8_t* rec = c->parts_rec + (int64_t)slot0 * c->parts_frame_bytes;
+        int32_t* flags = c->parts_flags + slot0;
+        for (int i = 0; i < n; i += cap) {
+            const int m = n - i < cap ? n - i : cap;
+            const sn::PlaneArgs a = frames_from(a0, i);
+            SN_HIP(c, hipMemsetAsync(flags, 0, sizeof(int32_t) * m, st));
+            sn::FusedPool fp{};
+            fp.mode = 5;  // kParts: one launch, a workgroup per part and frame
+            fp.nparts = pl.n;
+            fp.win_w = pl.win_w;
+            for (int k = 0; k < pl.n; ++k) {
+                fp.win_x[k] = pl.win_x[k];
+                fp.store_lo[k] = pl.seam[k] - pl.win_x[k];
+                fp.store_hi[k] = pl.seam[k + 1] - pl.win_x[k];
+                fp.seam_x[k][0] = k > 0 ? pl.seam[k] - pl.win_x[k] : -1;
+                fp.seam_off[k][0] = k > 0 ? (int)((2 * (k - 1) + 1) * side) : 0;  // side 1 of the seam on its left
+                fp.seam_x[k][1] = k < pl.n - 1 ? pl.seam[k + 1] - pl.win_x[k] : -1;
+                fp.seam_off[k][1] = k < pl.n - 1 ? (int)(2 * k * side) : 0;      // side 0 of the seam on its right
+            }
+            fp.seam_rec = rec;
+            fp.seam_frame_stride = c->parts_frame_bytes;
+            fp.seam_bytes = (int)(nseams * 2 * side);
+            if (B == 4) SN_HIP(c, sn::launch_fused_f32_v3(st, a, c->threshold(p), m, &fp));
+            else SN_HIP(c, sn::launch_fused_u16_v3(st, a, c->threshold(p), m, &fp));
+            SN_HIP(c, sn::launch_parts_verify(st, rec, c->parts_frame_bytes, side, nseams, m, flags, c->parts_fallbacks_dev, c->parts_fallbacks));
+            for (int j = 0; j < m; j += pcap) {
+                sn::PlaneArgs g = frames_from(a, j);
+                g.guard = flags + j;
+                pool.guard = flags + j;
+                SN_HIP(c, sn::launch_pool_plane(st, g, pool, B, c->threshold(p), m - j < pcap ? m - j : pcap, slot0));
+            }
+        }
+        return SN_OK;
+    };
+    bool parts_counted = false;
+    auto count_parts = [&]() {
+        if (!parts_counted) c->part_frames += n;
+        parts_counted = true;
     };
 
     // The latency path of one plane: bands, their check, and the pool path for the frames that fail it (its launches
@@ -1056,6 +1286,10 @@ static int run_group(Context* c, hipStream_t st, int slot0, int n, const void* c
                     if (c->cfg.bytes_per_sample == 4) SN_HIP(c, sn::launch_fused_f32_v3(st, a, c->threshold(p), n, &fp));
                     else if (c->cfg.bytes_per_sample == 2) SN_HIP(c, sn::launch_fused_u16_v3(st, a, c->threshold(p), n, &fp));
                     else SN_HIP(c, sn::launch_fused_u8_v3(st, a, c->threshold(p), n, &fp));
+                } else if (plan[p].n > 0) {
+                    const int rc = parts_plane(p, a, c->plane_pool[p]);
+                    if (rc != SN_OK) return rc;
+                    count_parts();
                 } else {
                     SN_HIP(c, launch_plain_fused(a, p, n));
                 }
@@ -1234,7 +1468,15 @@ static int run_group(Context* c, hipStream_t st, int slot0, int n, const void* c
     for (int p = 0; p < c->nplanes(); ++p) {
         const sn::PlaneArgs& a = pa[p];
         if (fused[p] && !c->fused420) {
-            SN_HIP(c, launch_plain_fused(a, p, n));
+            if (plan[p].n > 0) {
+                sn::PoolArgs pool = c->pool;
+                pool.rows = stop[p];
+                const int rc = parts_plane(p, a, pool);
+                if (rc != SN_OK) return rc;
+                count_parts();
+            } else {
+                SN_HIP(c, launch_plain_fused(a, p, n));
+            }
             if (!counted) c->fused_frames += n;
             counted = true;
             continue;
@@ -1998,6 +2240,7 @@ int sn_get_info(sn_context* h, sn_info* info)
                 !(c->fresh && sn::fused_padded_plane_eligible(c->cfg.bytes_per_sample, c->plane_w(p))))
                 info->fused_eligible = 0;
     }
+    if (c->plane_parts[0] || c->plane_parts[1] || c->plane_parts[2]) info->fused_eligible = c->parts_eligible ? 1 : 0;
     info->history_free = c->history_free ? 1 : 0;
     info->frames = c->frames;
     info->fused_frames = c->fused_frames;
@@ -2013,6 +2256,44 @@ int sn_get_info(sn_context* h, sn_info* info)
     }
     for (int p = 0; p < 3; ++p) info->threshold[p] = p < c->nplanes() ? c->threshold(p) : 0.0;
     return SN_OK;
+}
+
+int sn_get_parts_info(sn_context* h, sn_parts_info* info)
+{
+    Context* c = reinterpret_cast<Context*>(h);
+    if (!c) return sn::fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    if (!info || info->struct_size != (int32_t)sizeof(sn_parts_info))
+        return sn::fail(c, SN_ERR_INVALID_ARG, "sn_parts_info.struct_size mismatch");
+    bool any = false;
+    for (int p = 0; p < 3; ++p) {
+        PartsPlan pl;
+        const bool cut = p < c->nplanes() && (c->isolated ? c->plane_fused[p] : c->use_fused) && plan_parts(c, p, pl);
+        info->parts[p] = cut ? pl.n : 0;
+        any = any || cut;
+    }
+    info->ghost_columns = any ? (c->parts_ghost_force > 0 ? c->parts_ghost_force : parts_ghost(c)) : 0;
+    info->part_frames = c->part_frames;
+    info->part_fallbacks = 0;
+    if (c->parts_fallbacks_dev) {  // the device's own count (the host mirror may lag behind a launch with several failing frames)
+        SN_HIP(c, hipSetDevice(c->device));
+        SN_HIP(c, hipStreamSynchronize(c->stream));
+        SN_HIP(c, hipMemcpy(&info->part_fallbacks, c->parts_fallbacks_dev, sizeof(int64_t), hipMemcpyDeviceToHost));
+    }
+    return SN_OK;
+}
+
+int sn_debug_set_column_parts(sn_context* h, int32_t parts, int32_t ghost_columns)
+{
+    Context* c = reinterpret_cast<Context*>(h);
+    if (!c) return sn::fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    if (!c->parts_on || c->cfg.bytes_per_sample < 2) return sn::fail(c, SN_ERR_UNSUPPORTED, "sn_debug_set_column_parts: the context was created without sn_options.column_parts, or for 8-bit samples");
+    if (parts < 0 || parts == 1 || parts > kMaxParts) return sn::fail(c, SN_ERR_INVALID_ARG, "sn_debug_set_column_parts: parts must be 0 or 2..%d", kMaxParts);
+    if (ghost_columns < 0 || ghost_columns % 8 != 0) return sn::fail(c, SN_ERR_INVALID_ARG, "sn_debug_set_column_parts: ghost_columns must be 0 or a multiple of 8");
+    SN_HIP(c, hipSetDevice(c->device));
+    c->parts_force = parts;
+    c->parts_ghost_force = ghost_columns;
+    c->parts_pause = c->parts_pause_next = c->parts_good = 0;
+    return ensure_parts_scratch(c);  // (allocates here, outside any launch)
 }
 
 int sn_debug_read_pool(sn_context* h, int32_t slot, void* host_dst, size_t bytes)
@@ -2399,6 +2680,15 @@ int sn_aa_get_info(sn_aa_context* a, int32_t pass, sn_info* info)
     if (pass != 0 && pass != 1) return aa_fail(a, SN_ERR_INVALID_ARG, "pass must be 0 (the turned clip) or 1 (the clip)");
     sn_context* c = pass ? a->second : a->first;
     SN_AA_SN(c, sn_get_info(c, info));
+    return SN_OK;
+}
+
+int sn_aa_get_parts_info(sn_aa_context* a, int32_t pass, sn_parts_info* info)
+{
+    if (!a) return aa_fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    if (pass != 0 && pass != 1) return aa_fail(a, SN_ERR_INVALID_ARG, "pass must be 0 (the turned clip) or 1 (the clip)");
+    sn_context* c = pass ? a->second : a->first;
+    SN_AA_SN(c, sn_get_parts_info(c, info));
     return SN_OK;
 }
 

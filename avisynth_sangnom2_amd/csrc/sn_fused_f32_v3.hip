@@ -42,8 +42,8 @@ __device__ unsigned long long sn_wave_ticks[5][8][2];
 #define SN_WT_FLUSH()                                                                                         \
     do {                                                                                                      \
         if (lane == 0) {                                                                                      \
-            atomicAdd(&sn_wave_ticks[MODE][wave][0], __builtin_amdgcn_s_memtime() - wt_start);                \
-            atomicAdd(&sn_wave_ticks[MODE][wave][1], wt_barrier);                                             \
+            atomicAdd(&sn_wave_ticks[MODE == kParts ? 0 : MODE][wave][0], __builtin_amdgcn_s_memtime() - wt_start);                \
+            atomicAdd(&sn_wave_ticks[MODE == kParts ? 0 : MODE][wave][1], wt_barrier);                                             \
         }                                                                                                     \
     } while (0)
 #else
@@ -289,6 +289,9 @@ __device__ __forceinline__ void buffer_step(float (&A)[PXL], float (&vmin)[PXL],
     }
     if constexpr (MODE == kLumaSpill) {
         if (rc.any_out) io.store(BUF, rc.r, rc.vout, O);  // packed only where a lane of the wave stores
+    } else if constexpr (MODE == kParts) {
+        // waves that hold a lane next to a seam (FETCH != kQuiet: they run loops of their own): the seam record, [row][buffer][16 samples]
+        if constexpr (FETCH != kQuiet) io.store(BUF, rc.r - 1, io.v_out, O);
     } else if constexpr (MODE == kChroma) {
         if constexpr (FETCH == kPacked) {
             // the few lanes that hand a value on leave it in LDS; the row's end stores all nine buffers' with one store (the
@@ -497,12 +500,16 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_f32_v3(Args
     role.last_mask = role.last ? 0xffffffffu : 0u;
     role.edge_wave = __builtin_amdgcn_readfirstlane(__any((int)(role.first || role.last || role.line_last)) ? 1 : 0) != 0;
 
+    // kParts: this workgroup's window of the plane (blockIdx.y = part); everything below works in window columns
+    const int part = MODE == kParts ? (int)blockIdx.y : 0;
+    const int skip = MODE == kParts ? a.part_x[part] * 4 : 0;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t*>(a.src + (int64_t)f * a.src_frame_stride), 0, a.src_bytes, 0x00020000);
+        const_cast<uint8_t*>(a.src + (int64_t)f * a.src_frame_stride + skip), 0, a.src_bytes - skip, 0x00020000);
     const __amdgpu_buffer_rsrc_t rd =
-        __builtin_amdgcn_make_buffer_rsrc(a.dst + (int64_t)f * a.dst_frame_stride, 0, a.dst_bytes, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(a.dst + (int64_t)f * a.dst_frame_stride + skip, 0, a.dst_bytes - skip, 0x00020000);
     const int vload = line_live ? (x0 > 0 ? 4 * (x0 - 4) : 0) : kOutOfRange;
-    const int vstore = line_real ? 4 * x0 : kOutOfRange;
+    // kParts: only the part's own columns of the window are stored (interpolated lines, kept lines, the copied border line)
+    const int vstore = line_real && (MODE != kParts || (x0 >= a.part_store_lo[part] && x0 < a.part_store_hi[part])) ? 4 * x0 : kOutOfRange;
     const int src_step = (a.dh ? 1 : 2) * a.src_pitch;
     const int src_line = (a.dh ? 0 : a.offset) * a.src_pitch;
     const int dst_step = 2 * a.dst_pitch;
@@ -541,6 +548,19 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_f32_v3(Args
         if (lane >= 64 - GH && wave < NW - 1) ta = (wave + 1) * 64 + GH + (lane - (64 - GH));
         io.v_a = ta * 32;
         io.v_out = real ? (linear ? x0 * 4 : tid * 32) : kOutOfRange;
+    }
+    bool any_seam = false;  // kParts, wave-uniform: this wave holds one of the two lanes next to a seam of the cut
+    if constexpr (MODE == kParts) {
+        io.buf_stride = 16 * 4;  // 16 samples per buffer and row
+        io.row_stride = kBuffers * io.buf_stride;
+        io.rout = __builtin_amdgcn_make_buffer_rsrc(a.seam_rec + (int64_t)f * a.seam_frame_stride, 0, a.seam_bytes, 0x00020000);
+        io.v_out = kOutOfRange;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int sx = a.part_seam_x[part][k];
+            if (real && sx >= PXL && (x0 == sx - PXL || x0 == sx)) io.v_out = a.part_seam_off[part][k] + (x0 == sx ? PXL * 4 : 0);
+        }
+        any_seam = __builtin_amdgcn_readfirstlane(__any(io.v_out != kOutOfRange) ? 1 : 0) != 0;
     }
     // Does this lane's slot of pool row q matter (Args::cone_*)?  Its first column is 8 * lane + 480 * wave.
     auto in_cone_at = [&](int q, int extra, int xa) -> bool {
@@ -738,7 +758,8 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_f32_v3(Args
         rc.packed_lds = packed_lds;
         rc.packed_half = NT;
         rc.packed_out = packed_out;
-        constexpr int kKind = chroma_mode(MODE) ? decltype(fetch_tag)::value : (int)kQuiet;
+        // (kParts: the tag says whether this wave's rows leave the seam record)
+        constexpr int kKind = chroma_mode(MODE) || MODE == kParts ? decltype(fetch_tag)::value : (int)kQuiet;
         if constexpr (chroma_mode(MODE) && kKind == kPacked) rc.vin_next = (r + 2 <= a.rows_in && in_cone_at(r + 2, a.cone_in, packed_x)) ? packed_va : kOutOfRange;
         else if constexpr (chroma_mode(MODE)) rc.vin_next = (r + 2 <= a.rows_in && in_cone(r + 2, a.cone_in)) ? io.v_a : kOutOfRange;
         if constexpr (chroma_mode(MODE)) rc.vin = (r + 1 <= a.rows_in && in_cone(r + 1, a.cone_in)) ? io.v_a : kOutOfRange;
@@ -859,11 +880,29 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_f32_v3(Args
             // the first buffer of the first row that fetches buffer by buffer
             stale_next = io.issue(visit(0), from + 1, (from + 1 <= a.rows_in && in_cone(from + 1, a.cone_in)) ? io.v_a : kOutOfRange);
         }
+        if constexpr (MODE == kParts) {
+            // a wave next to a seam runs every row with the record's stores, the others none (two loops, one of them empty)
+            const int seam_end = any_seam ? nr : 1;
+            for (int r = 1; r < seam_end; ++r) {
+                step(r, L1, L0, T{}, T{}, std::integral_constant<int, kFetch>{});
+                L1 = L0;
+            }
+            from = seam_end > 1 ? seam_end : 1;
+            for (int r = from; r < nr; ++r) {
+                step(r, L1, L0, T{}, T{}, Quiet{});
+                L1 = L0;
+            }
+            if (nr >= 1) {
+                if (any_seam) step(nr, L1, L0, F{}, T{}, std::integral_constant<int, kFetch>{});
+                else step(nr, L1, L0, F{}, T{}, Quiet{});
+            }
+        } else {
         for (int r = from; r < nr; ++r) {
             step(r, L1, L0, T{}, T{}, T{});
             L1 = L0;
         }
         if (nr >= 1) step(nr, L1, L0, F{}, T{}, T{});
+        }
         if constexpr (chroma_mode(MODE)) {
             for (int r = nr + 1; r <= sweep; ++r) step(r, L1, L0, F{}, F{}, T{});
         }
@@ -905,7 +944,7 @@ static hipError_t launch_mode(hipStream_t st, const Args& a, float aaf, int nfra
         if (lds > 64 * 1024)                                                                                       \
             e = hipFuncSetAttribute((const void*)k_fused_f32_v3<NW, MODE, BAND>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
         if (e == hipSuccess)                                                                                       \
-            hipLaunchKernelGGL((k_fused_f32_v3<NW, MODE, BAND>), dim3((nframes + g - 1) / g, BAND ? a.nbands : 1), dim3(NW * g * 64), lds, st, a, aaf); \
+            hipLaunchKernelGGL((k_fused_f32_v3<NW, MODE, BAND>), dim3((nframes + g - 1) / g, BAND ? a.nbands : MODE == v3c::kParts ? a.nparts : 1), dim3(NW * g * 64), lds, st, a, aaf); \
         break;
     switch (a.nw) {
         SN_LAUNCH(1) SN_LAUNCH(2) SN_LAUNCH(3) SN_LAUNCH(4) SN_LAUNCH(5) SN_LAUNCH(6) SN_LAUNCH(7) SN_LAUNCH(8)
@@ -967,6 +1006,36 @@ hipError_t launch_fused_f32_v3(hipStream_t st, const PlaneArgs& p, double thresh
     a.dst_bytes = (int)((int64_t)p.dst_pitch * p.h_out);
     const float aaf = (float)threshold;
     if (!pool) return f32::launch_mode<v3c::kPlain>(st, a, aaf, nframes);
+    if (pool->mode == v3c::kParts) {  // a plane in column parts, all windows in one grid; never in row bands
+        if (pool->nbands > 1 || pool->nparts < 2 || pool->nparts > kMaxColumnParts || pool->win_w % 32 != 0 || !pool->seam_rec) return hipErrorInvalidValue;
+        a.w = a.region_w = pool->win_w;
+        a.nl = a.w / v3c::PXL;
+        a.nvw = a.nw = v3c::strips_for(a.nl);
+        if (a.nw > f32::kMaxWaves) return hipErrorInvalidValue;
+        a.turn_shift = v3c::turn_shift_for(a.nk, a.nw * v3c::group_of(a.nw), 4);
+        a.nparts = pool->nparts;
+        for (int k = 0; k < pool->nparts; ++k) {
+            // the window lies inside the plane, its own columns inside the window
+            if (pool->win_x[k] % v3c::PXL != 0 || pool->win_x[k] < 0 || pool->win_x[k] + pool->win_w > p.w || pool->store_lo[k] % v3c::PXL != 0 ||
+                pool->store_hi[k] % v3c::PXL != 0 || pool->store_lo[k] < 0 || pool->store_hi[k] > pool->win_w)
+                return hipErrorInvalidValue;
+            a.part_x[k] = pool->win_x[k];
+            a.part_store_lo[k] = pool->store_lo[k];
+            a.part_store_hi[k] = pool->store_hi[k];
+            for (int e = 0; e < 2; ++e) {
+                a.part_seam_x[k][e] = pool->seam_x[k][e];
+                a.part_seam_off[k][e] = pool->seam_off[k][e];
+                // both lanes next to a seam lie inside the window, and their rows inside the frame's record
+                if (a.part_seam_x[k][e] >= 0 && (a.part_seam_x[k][e] % v3c::PXL != 0 || a.part_seam_x[k][e] < v3c::PXL || a.part_seam_x[k][e] + v3c::PXL > a.w ||
+                                                 a.part_seam_off[k][e] < 0 || a.part_seam_off[k][e] + parts_side_bytes(4, a.nk - 1) > pool->seam_bytes))
+                    return hipErrorInvalidValue;
+            }
+        }
+        a.seam_rec = pool->seam_rec;
+        a.seam_frame_stride = pool->seam_frame_stride;
+        a.seam_bytes = pool->seam_bytes;
+        return f32::launch_mode<v3c::kParts>(st, a, aaf, nframes);
+    }
     if (pool->nbands > 1) {
         a.band_rows = pool->band_rows;
         a.band_warm = pool->band_warm;

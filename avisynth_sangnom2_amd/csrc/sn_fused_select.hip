@@ -32,6 +32,13 @@ bool fused_padded_plane_eligible(int bytes_per_sample, int w)
     return fused_plane_eligible(bytes_per_sample, (w + 31) & ~31);
 }
 
+bool fused_parts_plane_eligible(int bytes_per_sample, int w)
+{
+    if (bytes_per_sample != 2 && bytes_per_sample != 4) return false;
+    if (w % 32 != 0 || w > 8192) return false;
+    return !fused_plane_eligible(bytes_per_sample, w);
+}
+
 bool fused_eligible(const sn_config& c)
 {
     if (!fused_plane_eligible(c.bytes_per_sample, c.width)) return false;

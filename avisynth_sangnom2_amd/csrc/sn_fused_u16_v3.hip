@@ -34,8 +34,8 @@ __device__ unsigned long long sn_wave_ticks[5][8][2];
 #define SN_WT_FLUSH()                                                                                         \
     do {                                                                                                      \
         if (lane == 0) {                                                                                      \
-            atomicAdd(&sn_wave_ticks[MODE][wave][0], __builtin_amdgcn_s_memtime() - wt_start);                \
-            atomicAdd(&sn_wave_ticks[MODE][wave][1], wt_barrier);                                             \
+            atomicAdd(&sn_wave_ticks[MODE == kParts ? 0 : MODE][wave][0], __builtin_amdgcn_s_memtime() - wt_start);                \
+            atomicAdd(&sn_wave_ticks[MODE == kParts ? 0 : MODE][wave][1], wt_barrier);                                             \
         }                                                                                                     \
     } while (0)
 #else
@@ -339,10 +339,10 @@ __device__ __forceinline__ void buffer_step(unsigned (&A)[PXL], unsigned (&kmin)
                                             const LaneRole& role, const PoolIO& io, const RowCtx& rc, const u32x4& stale)
 {
     unsigned D[PXL], S[PXL], Bx[PXL], O[PXL];
-    if constexpr (MODE == kPlain || MODE == kLumaSpill) {
+    if constexpr (plain_mode(MODE) || MODE == kLumaSpill) {
 #pragma unroll
         for (int j = 0; j < PXL; ++j) S[j] = S1 ? cost_acc<BUF>(n, nn, j, A[j]) : A[j];
-        if constexpr (MODE == kPlain) {
+        if constexpr (plain_mode(MODE)) {
             if (role.edge_wave) box7_plain<true>(S, Bx, role);
             else box7_plain<false>(S, Bx, role);
         } else {
@@ -357,6 +357,8 @@ __device__ __forceinline__ void buffer_step(unsigned (&A)[PXL], unsigned (&kmin)
             kmin[j] = umin(kmin[j], key);
         }
         if constexpr (has_pools(MODE) && STORE) io.store(BUF, rc.r, rc.vout, O);  // lanes that keep nothing: out-of-range voffset
+        // kParts, waves that hold a lane next to a seam (they run loops of their own): the seam record, [row][buffer][16 samples]
+        if constexpr (MODE == kParts && STORE) io.store(BUF, rc.r - 1, io.v_out, O);
         return;
     }
     if constexpr (chroma_mode(MODE) && !FETCH) {
@@ -646,12 +648,16 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u16_v3(Args
 
     // buffer descriptors: row in the scalar offset, column in a constant per-lane voffset; dead lanes carry
     // an out-of-range voffset (loads return zero, stores are dropped)
+    // kParts: this workgroup's window of the plane (blockIdx.y = part); everything below works in window columns
+    const int part = MODE == kParts ? (int)blockIdx.y : 0;
+    const int skip = MODE == kParts ? a.part_x[part] * 2 : 0;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t*>(a.src + (int64_t)f * a.src_frame_stride), 0, a.src_bytes, 0x00020000);
+        const_cast<uint8_t*>(a.src + (int64_t)f * a.src_frame_stride + skip), 0, a.src_bytes - skip, 0x00020000);
     const __amdgpu_buffer_rsrc_t rd =
-        __builtin_amdgcn_make_buffer_rsrc(a.dst + (int64_t)f * a.dst_frame_stride, 0, a.dst_bytes, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(a.dst + (int64_t)f * a.dst_frame_stride + skip, 0, a.dst_bytes - skip, 0x00020000);
     const int vload = line_live ? (x0 > 0 ? 2 * (x0 - 4) : 0) : kOutOfRange;
-    const int vstore = line_real ? 2 * x0 : kOutOfRange;
+    // kParts: only the part's own columns of the window are stored (interpolated lines, kept lines, the copied border line)
+    const int vstore = line_real && (MODE != kParts || (x0 >= a.part_store_lo[part] && x0 < a.part_store_hi[part])) ? 2 * x0 : kOutOfRange;
     const int src_step = (a.dh ? 1 : 2) * a.src_pitch;
     const int src_line = (a.dh ? 0 : a.offset) * a.src_pitch;
     const int dst_step = 2 * a.dst_pitch;
@@ -687,6 +693,20 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u16_v3(Args
         if (lane >= 64 - GH && wave < NW - 1) ta = (wave + 1) * 64 + GH + (lane - (64 - GH));
         io.v_a = ta * 16;
         io.v_out = real ? (linear ? x0 * 2 : tid * 16) : kOutOfRange;
+    }
+
+    bool any_seam = false;  // kParts, wave-uniform: this wave holds one of the two lanes next to a seam of the cut
+    if constexpr (MODE == kParts) {
+        io.buf_stride = 16 * 2;  // 16 samples per buffer and row
+        io.row_stride = kBuffers * io.buf_stride;
+        io.rout = __builtin_amdgcn_make_buffer_rsrc(a.seam_rec + (int64_t)f * a.seam_frame_stride, 0, a.seam_bytes, 0x00020000);
+        io.v_out = kOutOfRange;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int sx = a.part_seam_x[part][k];
+            if (real && sx >= PXL && (x0 == sx - PXL || x0 == sx)) io.v_out = a.part_seam_off[part][k] + (x0 == sx ? PXL * 2 : 0);
+        }
+        any_seam = __builtin_amdgcn_readfirstlane(__any(io.v_out != kOutOfRange) ? 1 : 0) != 0;
     }
 
     // seam exchange: lanes 60, 61 feed the next wave's left ghosts, lanes 2, 3 the previous wave's right ghosts
@@ -1006,7 +1026,12 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u16_v3(Args
                 if (!__builtin_amdgcn_readfirstlane(__any(beyond) ? 1 : 0)) quiet = nr < a.cone_nr ? nr : a.cone_nr;
                 if (quiet < 1) quiet = 1;
             }
-            rows(1, quiet, F{}, F{});
+            if constexpr (MODE == kParts) {  // a wave next to a seam runs every row with the record's stores, the others none
+                quiet = any_seam ? (nr > 1 ? nr : 1) : 1;
+                rows(1, quiet, T{}, F{});
+            } else {
+                rows(1, quiet, F{}, F{});
+            }
             if constexpr (chroma_mode(MODE)) {  // the ring's first fill: the first buffers of the first row that fetches
                 const int v = (quiet + 1 <= a.rows_in && in_cone(quiet + 1, a.cone_in)) ? io.v_a : kOutOfRange;
 #pragma unroll
@@ -1014,7 +1039,12 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u16_v3(Args
             }
             rows(quiet, nr, F{}, T{});
             if (nr >= 1) {
-                step(nr, L1, L0, F{}, T{}, F{}, T{});
+                if constexpr (MODE == kParts) {
+                    if (any_seam) step(nr, L1, L0, F{}, T{}, T{}, T{});
+                    else step(nr, L1, L0, F{}, T{}, F{}, T{});
+                } else {
+                    step(nr, L1, L0, F{}, T{}, F{}, T{});
+                }
                 put(out_row, pending);
             }
             if constexpr (chroma_mode(MODE)) {
@@ -1059,7 +1089,7 @@ static hipError_t launch_mode(hipStream_t st, const Args& a, int nframes)
         if (lds > 64 * 1024)                                                                                       \
             e = hipFuncSetAttribute((const void*)k_fused_u16_v3<NW, MODE, BAND, ARITH>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
         if (e == hipSuccess)                                                                                       \
-            hipLaunchKernelGGL((k_fused_u16_v3<NW, MODE, BAND, ARITH>), dim3((nframes + g - 1) / g, BAND ? a.nbands : 1), dim3(NW * g * 64), lds, st, a); \
+            hipLaunchKernelGGL((k_fused_u16_v3<NW, MODE, BAND, ARITH>), dim3((nframes + g - 1) / g, BAND ? a.nbands : MODE == v3c::kParts ? a.nparts : 1), dim3(NW * g * 64), lds, st, a); \
         break;
     switch (a.nw) {
         SN_LAUNCH(1) SN_LAUNCH(2) SN_LAUNCH(3) SN_LAUNCH(4) SN_LAUNCH(5) SN_LAUNCH(6) SN_LAUNCH(7) SN_LAUNCH(8)
@@ -1135,6 +1165,36 @@ template <int ARITH>
 static hipError_t launch_arith(hipStream_t st, v3c::Args& a, const PlaneArgs& p, int nframes, const FusedPool* pool)
 {
     if (!pool) return w16::launch_mode<v3c::kPlain, false, ARITH>(st, a, nframes);
+    if (pool->mode == v3c::kParts) {  // a plane in column parts, all windows in one grid; never in row bands
+        if (pool->nbands > 1 || pool->nparts < 2 || pool->nparts > kMaxColumnParts || pool->win_w % 32 != 0 || !pool->seam_rec) return hipErrorInvalidValue;
+        a.w = pool->win_w;
+        a.nl = a.w / v3c::PXL;
+        a.nvw = a.nw = v3c::strips_for(a.nl);
+        if (a.nw > w16::kMaxWaves) return hipErrorInvalidValue;
+        a.turn_shift = v3c::turn_shift_for(a.nk, a.nw * v3c::group_of(a.nw), 2);
+        a.nparts = pool->nparts;
+        for (int k = 0; k < pool->nparts; ++k) {
+            // the window lies inside the plane, its own columns inside the window
+            if (pool->win_x[k] % v3c::PXL != 0 || pool->win_x[k] < 0 || pool->win_x[k] + pool->win_w > p.w || pool->store_lo[k] % v3c::PXL != 0 ||
+                pool->store_hi[k] % v3c::PXL != 0 || pool->store_lo[k] < 0 || pool->store_hi[k] > pool->win_w)
+                return hipErrorInvalidValue;
+            a.part_x[k] = pool->win_x[k];
+            a.part_store_lo[k] = pool->store_lo[k];
+            a.part_store_hi[k] = pool->store_hi[k];
+            for (int e = 0; e < 2; ++e) {
+                a.part_seam_x[k][e] = pool->seam_x[k][e];
+                a.part_seam_off[k][e] = pool->seam_off[k][e];
+                // both lanes next to a seam lie inside the window, and their rows inside the frame's record
+                if (a.part_seam_x[k][e] >= 0 && (a.part_seam_x[k][e] % v3c::PXL != 0 || a.part_seam_x[k][e] < v3c::PXL || a.part_seam_x[k][e] + v3c::PXL > a.w ||
+                                                 a.part_seam_off[k][e] < 0 || a.part_seam_off[k][e] + parts_side_bytes(2, a.nk - 1) > pool->seam_bytes))
+                    return hipErrorInvalidValue;
+            }
+        }
+        a.seam_rec = pool->seam_rec;
+        a.seam_frame_stride = pool->seam_frame_stride;
+        a.seam_bytes = pool->seam_bytes;
+        return w16::launch_mode<v3c::kParts, false, ARITH>(st, a, nframes);
+    }
     if (pool->nbands > 1) {
         a.band_rows = pool->band_rows;
         a.band_warm = pool->band_warm;

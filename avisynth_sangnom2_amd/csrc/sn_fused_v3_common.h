@@ -21,6 +21,8 @@ constexpr int kOutOfRange = 0x7fffffff;  // voffset that the buffer range check 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
+constexpr int kMaxColumnParts = sn::kMaxColumnParts;
+
 struct Args {
     const uint8_t* src;
     uint8_t* dst;
@@ -66,6 +68,16 @@ struct Args {
     int32_t* band_flags;      // [frame]: set by the verification that follows (sn_band.hip)
     int32_t band_reset;       // this sweep clears band_flags first (the first plane of a frame)
     int32_t arith;            // SN_ARITH_*: which instances the launcher picks (every integer sweep has both)
+    // column parts (mode kParts): blockIdx.y = part; every part sweeps a window of the same width w that starts at column
+    // part_x of the plane (the kernel advances src / dst and shortens src_bytes / dst_bytes by that much)
+    int32_t nparts;
+    int32_t part_x[kMaxColumnParts];
+    int32_t part_store_lo[kMaxColumnParts], part_store_hi[kMaxColumnParts];  // window columns [lo, hi) are the part's own: only those are stored to dst
+    int32_t part_seam_x[kMaxColumnParts][2];    // window column of the seam on the left / right inner side (multiple of 8), < 0: an image edge
+    int32_t part_seam_off[kMaxColumnParts][2];  // byte offset of this window's side of that seam's record in the frame's record
+    uint8_t* seam_rec;           // [frame][seam][side][row 1 .. nr][kBuffers][16 samples]: smoothed values of columns seam - 8 .. seam + 7
+    int64_t seam_frame_stride;
+    int32_t seam_bytes;          // bytes of one frame's record
 };
 
 // The reference's nine buffers are sized for the luma plane and shared by all planes, so a
@@ -91,6 +103,13 @@ struct Args {
 // sn_band.hip compares each band's end with the next band's start -- equal everywhere means, by induction from band 0,
 // that every band computed what the top-to-bottom sweep computes -- and a frame that fails is redone by the pool path
 // (guarded launches that otherwise exit at once). 
+// Column parts (kParts; 16-bit and float sweeps): the same trust-nothing pattern turned by ninety degrees, for planes wider
+// than one workgroup holds.  The plane is cut into windows that overlap by a ghost margin on each inner side; a window is
+// swept by a workgroup of its own (all parts of all frames in one grid) like a plane of its own (kPlain on advanced pointers: it clamps at the window's edges, which is wrong at an inner
+// edge, but the error dies out within the margin on ordinary content) and stores only its own columns.  For every smoothed
+// row both windows around a seam leave their values of the 16 columns around it; sn_band.hip compares them bit for bit.
+// Equal means exact: by induction over the rows, a window's own columns of row y depend on row y - 1 only up to three
+// columns beyond the seam, where agreement says the window holds what the other one -- exact there -- holds.
 // Planes on their own are cut (kPlain), and the luma sweep that leaves its rows in a pool of the POOL PATH
 // (kLumaSpill with pool_row_bytes): a single 4:2:0 frame takes its luma plane through the bands and its chroma planes
 // through the pool kernels, which find in the pool what the reference's luma pass would have left there.  The pool-coupled sweeps were tried and work mechanically -- a band
@@ -98,7 +117,9 @@ struct Args {
 // the check: outside the chroma region it re-smooths what two passes have smoothed already, data so even that the
 // rounding difference between the run-up and the true history does not die out (256 x 400 noise needs a run-up of 128
 // rows, 3840 x 2160 is still wrong after 128), so every such frame would be done twice.
-enum Mode { kPlain = 0, kLumaSpill = 1, kChroma = 2, kPadded = 3, kChromaLast = 4 };
+enum Mode { kPlain = 0, kLumaSpill = 1, kChroma = 2, kPadded = 3, kChromaLast = 4, kParts = 5 };
+constexpr int kModes = 6;
+__host__ __device__ constexpr bool plain_mode(int mode) { return mode == kPlain || mode == kParts; }  // a plane (or window) on its own
 __host__ __device__ constexpr bool chroma_mode(int mode) { return mode == kChroma || mode == kChromaLast; }
 __host__ __device__ constexpr bool has_region(int mode) { return chroma_mode(mode) || mode == kPadded; }  // lines narrower than the sweep
 __host__ __device__ constexpr bool has_pools(int mode) { return mode == kLumaSpill || chroma_mode(mode); }

@@ -10,6 +10,7 @@
 namespace sn {
 
 constexpr int kBuffers = 9;  // TOTAL_BUFFERS, /root/reference/src/SangNom2.h:22
+constexpr int kMaxColumnParts = 8;  // column parts of one plane (sn_options.column_parts)
 
 // One plane of one launch (all frames of a batch share it; frame f adds f * *_frame_stride).
 struct PlaneArgs {
@@ -90,13 +91,16 @@ bool fused_eligible(const sn_config& c);
 bool fused_plane_eligible(int bytes_per_sample, int w);
 // ... swept over its pool stride roundup(w, 32) with zero costs in the padding (fresh_pool)
 bool fused_padded_plane_eligible(int bytes_per_sample, int w);
+// ... too wide for one workgroup but served in column parts (sn_options.column_parts): 16-bit / float, w % 32 == 0, w <= 8192
+bool fused_parts_plane_eligible(int bytes_per_sample, int w);
 bool fused_needs_pools(const sn_config& c);  // subsampled chroma: luma / chroma sweeps coupled through scratch pools
 bool fused_layout_ok(const PlaneArgs& p);
 // sn_fused_u8_v3.hip: the 8-bit sweep, two virtual wavefronts packed into every register.
 bool fused_v3_plane_ok(int w);
 // Scratch-pool coupling between the luma sweep and the subsampled-chroma sweeps (sn_fused_u8_v3.hip, Mode).
 struct FusedPool {
-    int mode;                // 0 = plane on its own, 1 = luma sweep that leaves its smoothed rows, 2 = chroma sweep, 3 = padded plane (no pools)
+    int mode;                // 0 = plane on its own, 1 = luma sweep that leaves its smoothed rows, 2 = chroma sweep, 3 = padded plane (no pools),
+                             // 5 = one column part of a plane (the win_* / store_* / seam_* fields below)
     int sweep_w;             // luma width (the pool's width)
     const uint8_t* pool_in;  // chroma: what the previous pass left
     uint8_t* pool_out;       // luma / first chroma pass: where this pass leaves its rows (may be null)
@@ -111,7 +115,22 @@ struct FusedPool {
     int band_rows, band_warm, nbands, band_reset;
     uint32_t* band_state;    // nframes * band_state_words(threads, nbands) words
     int32_t* band_flags;     // one per frame
+    // mode 5 (column parts, sn_fused_v3_common.h): nparts windows [win_x[k], win_x[k] + win_w) of the plane, each swept as a
+    // plane of its own by one launch; columns [store_lo[k], store_hi[k]) of the WINDOW are stored; seam_x[k][side] (window
+    // columns, < 0: none) are the seams next to the window's inner edges and seam_off[k][side] where its half of each seam's
+    // record starts in the frame's record
+    int nparts, win_w;
+    int win_x[kMaxColumnParts], store_lo[kMaxColumnParts], store_hi[kMaxColumnParts];
+    int seam_x[kMaxColumnParts][2], seam_off[kMaxColumnParts][2];
+    uint8_t* seam_rec;
+    int64_t seam_frame_stride;
+    int seam_bytes;
 };
+// sn_band.hip: the check of a launch in column parts.  A frame's record is [seam][side][rows][kBuffers][16] samples; side 0
+// (the window left of the seam) must equal side 1 bit for bit, else flags[f] is raised and the frame counted, as above.
+inline int64_t parts_side_bytes(int bytes, int rows) { return (int64_t)rows * kBuffers * 16 * bytes; }
+hipError_t launch_parts_verify(hipStream_t s, const uint8_t* rec, int64_t frame_stride, int64_t side_bytes, int nseams, int nframes,
+                               int32_t* flags, int64_t* fallbacks, int64_t* host_mirror);
 // sn_band.hip: words of band state per frame for a sweep of `threads` threads; the check of a band launch -- flags[f] != 0
 // afterwards means frame f has to be redone by the pool path (its guarded launches look at the same flags);
 // *fallbacks (device memory, may be null) counts such frames, *host_mirror (host memory the device can write, may be

@@ -67,7 +67,8 @@ class SangNom2:
                  device: int = 0, max_batch: int = 1, mode: str = "auto", stream: int | None = None,
                  host_depth: int = 0, isolated_planes: bool = False, fresh_pool: bool = False,
                  small_launches: int | None = None, chain: int | None = None, copy_threads: int | None = None,
-                 scratch_budget_mb: int | None = None, chroma_sweeps: int | None = None, sse2_sweeps: int | None = None):
+                 scratch_budget_mb: int | None = None, chroma_sweeps: int | None = None, sse2_sweeps: int | None = None,
+                 column_parts: int = 0):
         # `threads` is a dummy in the reference (README.md:40-41); `opt` picks its CPU code path, and with it the
         # arithmetic: opt=1 reproduces its SSE2 path (SN_ARITH_SSE2), opt=0 and opt=-1 its C++ path.
         if opt < -1 or opt > 1:
@@ -90,7 +91,8 @@ class SangNom2:
         pol = capi.policy(small_launches=small_launches, chain=chain, copy_threads=copy_threads, scratch_budget_mb=scratch_budget_mb,
                           chroma_sweeps=chroma_sweeps, sse2_sweeps=sse2_sweeps)
         self.arithmetic = capi.arithmetic_of_opt(opt)
-        opts = capi.options(self.arithmetic)
+        # column_parts=1 (sn_options, fixed at creation): 16-bit and float planes wider than 3840 in column parts
+        opts = capi.options(self.arithmetic, column_parts=column_parts)
         rc = self._lib.sn_create_ex(ctypes.byref(cfg), ctypes.byref(pol), ctypes.byref(opts), ctypes.byref(self._h))
         if rc != capi.SN_OK:
             self._h = None
@@ -168,6 +170,16 @@ class SangNom2:
     def set_bands(self, bands: int = 0, warm_rows: int = 0) -> None:
         """Test hook: row bands of the small-launch path (sn_debug_set_bands)."""
         self._check(self._lib.sn_debug_set_bands(self._h, bands, warm_rows))
+
+    def parts_info(self) -> capi.SnPartsInfo:
+        """The column parts of this context (sn_get_parts_info); synchronises the stream."""
+        i = capi.SnPartsInfo(struct_size=ctypes.sizeof(capi.SnPartsInfo))
+        self._check(self._lib.sn_get_parts_info(self._h, ctypes.byref(i)))
+        return i
+
+    def debug_set_column_parts(self, parts: int = 0, ghost_columns: int = 0) -> None:
+        """Test hook: force the number of column parts / the seams' distance from a window's end (sn_debug_set_column_parts)."""
+        self._check(self._lib.sn_debug_set_column_parts(self._h, int(parts), int(ghost_columns)))
 
     def read_coupled_rows(self, which: int) -> np.ndarray:
         """Rows the fused 4:2:0 sweep of plane `which` left for the next plane: [9, rows, width]."""
@@ -307,7 +319,7 @@ class _AAContext:
 
     def __init__(self, clip: ClipFormat, order: int = 1, aa: int = 48, aac: int = 0, luma: bool = True, chroma: bool = True,
                  device: int = 0, isolated_planes: bool = False, fresh_pool: bool = False, opt: int = -1, max_batch: int = 1,
-                 host_depth: int = 0, stream: int | None = None, dh: bool = False, **policy_kw):
+                 host_depth: int = 0, stream: int | None = None, dh: bool = False, column_parts: int = 0, **policy_kw):
         if opt < -1 or opt > 1:
             raise SangNomError(capi.SN_ERR_CONFIG, "SangNom2: opt must be between -1..2.")  # sic, SangNom2.cpp:420
         self.clip = clip
@@ -321,7 +333,7 @@ class _AAContext:
             isolated_planes=int(isolated_planes), fresh_pool=int(fresh_pool), stream=stream)
         self._h = ctypes.c_void_p()
         pol = capi.policy(**{k: policy_kw.get(k) for k in ("small_launches", "chain", "copy_threads", "scratch_budget_mb", "chroma_sweeps", "sse2_sweeps")})
-        opts = capi.options(capi.arithmetic_of_opt(opt))
+        opts = capi.options(capi.arithmetic_of_opt(opt), column_parts=column_parts)
         rc = self._lib.sn_aa_create_ex(ctypes.byref(cfg), ctypes.byref(pol), ctypes.byref(opts), ctypes.byref(self._h))
         if rc != capi.SN_OK:
             self._h = None
@@ -369,6 +381,12 @@ class _AAContext:
         """sn_get_info of one of the two filter instances: 0 the turned clip's, 1 the clip's."""
         i = capi.SnInfo(struct_size=ctypes.sizeof(capi.SnInfo))
         self._check(self._lib.sn_aa_get_info(self._h, int(pass_), ctypes.byref(i)))
+        return i
+
+    def parts_info(self, pass_: int) -> capi.SnPartsInfo:
+        """sn_get_parts_info of one of the two filter instances (the second pass of dh=True is twice the clip's width)."""
+        i = capi.SnPartsInfo(struct_size=ctypes.sizeof(capi.SnPartsInfo))
+        self._check(self._lib.sn_aa_get_parts_info(self._h, int(pass_), ctypes.byref(i)))
         return i
 
 

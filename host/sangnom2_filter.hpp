@@ -38,8 +38,17 @@ struct Args {  // SangNom2(clip, order, aa, aac, threads, dh, luma, chroma, opt)
     int lookahead = -1;  // frames in flight behind GetFrame; -1: $SANGNOM_LOOKAHEAD or 1 (synchronous)
     bool isolated = false;  // extension: every plane filtered as a Y clip of its own (sn_config.isolated_planes)
     bool fresh = false;     // extension: ... and every frame by a new instance (sn_config.fresh_pool)
+    int column_parts = -1;  // sn_options.column_parts (16-bit / float planes wider than 3840 in column parts); -1: $SANGNOM_COLUMN_PARTS or 0
     sn_policy policy{};     // scheduling only (sangnom_hip.h); zeros = the defaults
 };
+
+// Args::column_parts, or the environment's word for it (read here, by the host adapter: the library reads no environment)
+inline int column_parts_of(const Args& a)
+{
+    if (a.column_parts >= 0) return a.column_parts;
+    const char* e = std::getenv("SANGNOM_COLUMN_PARTS");
+    return e ? std::atoi(e) : 0;
+}
 
 template <class Host>
 class Filter {
@@ -94,6 +103,7 @@ public:
         sn_options opts{};
         opts.struct_size = (int32_t)sizeof opts;
         opts.arithmetic = a.opt == 1 ? SN_ARITH_SSE2 : SN_ARITH_CXX;
+        opts.column_parts = column_parts_of(a);
         const int rc = sn_create_ex(&c, &pol, &opts, &ctx_);
         if (rc != SN_OK) env->ThrowError("%s: %s", name, sn_last_error(nullptr));
         if (a.dh) Host::SetHeight(vi_, Host::Height(vi_) * 2);  // src/SangNom2.cpp:284-285
@@ -278,6 +288,7 @@ public:
         sn_options opts{};
         opts.struct_size = (int32_t)sizeof opts;
         opts.arithmetic = a.opt == 1 ? SN_ARITH_SSE2 : SN_ARITH_CXX;
+        opts.column_parts = column_parts_of(a);
         if (sn_aa_create_ex(&c, &pol, &opts, &ctx_) != SN_OK) env->ThrowError("%s: %s", name, sn_aa_last_error(nullptr));
         if (a.dh) {  // each pass doubles the height of what it is given: the clip comes out twice as wide and twice as high
             Host::SetWidth(vi_, Host::Width(vi_) * 2);

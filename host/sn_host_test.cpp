@@ -2,7 +2,8 @@
 // engine drives the reference plugin: build a source clip, construct SangNom2(clip, ...), request
 // frames with GetFrame(n).  tests/test_host_adapter.py feeds it frames and compares the output with
 // the oracle.
-//   sn_host_test <in.bin> <out.bin> [lookahead | aa | aa:<lookahead> [first-frame-order...]]
+//   sn_host_test <in.bin> <out.bin> [parts] [lookahead | aa | aa:<lookahead> [first-frame-order...]]
+// "parts" (before the other arguments) sets Args::column_parts = 1;
 // lookahead > 1 runs GetFrame over the host ring; "aa" constructs SangNomAA (sangnom::AAFilter) instead of SangNom2,
 // "aa:<N>" with look-ahead N; the header's dh word reaches either filter (SangNomAA with dh: frames twice as wide and
 // twice as high);
@@ -46,6 +47,11 @@ public:
 int main(int argc, char** argv)
 {
     if (argc < 3) return 2;
+    const bool parts = argc > 3 && strcmp(argv[3], "parts") == 0;
+    if (parts) {  // taken out of the list: the other arguments keep their places
+        for (int i = 3; i + 1 < argc; ++i) argv[i] = argv[i + 1];
+        --argc;
+    }
     FILE* in = fopen(argv[1], "rb");
     if (!in) return 2;
     int32_t h[14];
@@ -66,6 +72,7 @@ int main(int argc, char** argv)
     a.luma = h[11] != 0;
     a.chroma = h[12] != 0;
     const int nframes = h[13];
+    if (parts) a.column_parts = 1;
     clip->vi.num_frames = nframes;
     // the test clips are small: SN_HOST_TEST_SWEEPS=1 (read by this TEST program, the library reads no environment) asks
     // for the whole-plane sweeps instead of the small-launch paths

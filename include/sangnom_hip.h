@@ -145,11 +145,31 @@ enum {
     SN_ARITH_CXX = 0,   /* the reference's opt=0                                              */
     SN_ARITH_SSE2 = 1   /* the reference's opt=1 (its default on x86-64)                      */
 };
+/* sn_options: what is fixed when the context is created (sn_policy holds what may change between launches, and has no
+ * free word left).
+ * column_parts = 1: 9..16-bit and float planes too wide for one workgroup of the fused sweeps (more than 3840 columns;
+ * width a multiple of 32, at most 8192) are swept in 2..N column parts, one workgroup each, over windows that overlap
+ * by a ghost margin; no workgroup waits for another.  Each frame is checked -- both windows around a seam must agree bit
+ * for bit on the smoothed values of the 16 columns around it, which proves the parts exact -- and a frame that fails is
+ * redone by the pool path, so the output is the same either way (sn_get_parts_info counts such frames).  It applies to
+ * planes on their own (Y, 4:4:4, isolated_planes); then sn_info.fused_eligible is 1 and SN_MODE_FUSED is accepted.  A wide
+ * 4:2:0 / 4:2:2 clip whose chroma shares the luma pool stays on the pool path.  8-bit contexts accept the option; it has
+ * no effect there.  0, the default, changes nothing. */
 typedef struct sn_options {
     int32_t struct_size;   /* = sizeof(sn_options)                                           */
     int32_t arithmetic;    /* SN_ARITH_*                                                     */
-    int32_t reserved[6];   /* zero                                                           */
+    int32_t column_parts;  /* 0 (default) or 1; took the place of reserved[0]                */
+    int32_t reserved[5];   /* zero                                                           */
 } sn_options;
+
+/* The column parts of a live context (all zero without sn_options.column_parts). */
+typedef struct sn_parts_info {
+    int32_t struct_size;
+    int32_t parts[3];        /* per plane; 0 = not in parts                                  */
+    int32_t ghost_columns;   /* least overlap of a window beyond a seam, per side            */
+    int64_t part_frames;     /* frames swept in parts                                        */
+    int64_t part_fallbacks;  /* ... of which the check sent to the pool path                 */
+} sn_parts_info;
 
 /* Geometry and counters of a live context. */
 typedef struct sn_info {
@@ -328,6 +348,7 @@ int sn_aa_synchronize(sn_aa_context* ctx);
 void* sn_aa_get_stream(sn_aa_context* ctx);
 /* sn_get_info of one of the two filter instances: pass 0 is the turned clip's, pass 1 the clip's. */
 int sn_aa_get_info(sn_aa_context* ctx, int32_t pass, sn_info* info);
+int sn_aa_get_parts_info(sn_aa_context* ctx, int32_t pass, sn_parts_info* info);
 /* The host ring of the anti-aliasing call, with the contract of sn_host_slots / sn_submit_host / sn_collect_host: slots
  * are taken round-robin, SN_ERR_BUSY when the next slot has not been collected, and collecting in submission order never
  * waits for a later frame.  Upload, device work and download of different frames overlap; the device work runs in
@@ -340,6 +361,7 @@ int sn_aa_collect_host(sn_aa_context* ctx, int32_t slot, void* const dst[3], con
 int sn_synchronize(sn_context* ctx);
 void* sn_get_stream(sn_context* ctx); /* the hipStream_t the context launches on */
 int sn_get_info(sn_context* ctx, sn_info* info);
+int sn_get_parts_info(sn_context* ctx, sn_parts_info* info); /* synchronises the stream */
 
 /* Test hook: copy the device scratch pool of batch slot `slot` to host memory
  * (9 x pool_rows x pool_stride elements).  Synchronises the stream. */
@@ -356,6 +378,13 @@ int sn_debug_read_coupled_rows(sn_context* ctx, int32_t which, void* host_dst, s
  * redone by the pool path): bands > 0 forces that many bands per frame, 0 restores the automatic choice, < 0
  * turns the bands off; warm_rows = 0 restores the default run-up.  A run-up of 1 makes nearly every frame fail. */
 int sn_debug_set_bands(sn_context* ctx, int32_t bands, int32_t warm_rows);
+
+/* Test hook for the column parts (sn_options.column_parts = 1; tests and the bench tool only): parts > 0 forces that
+ * many parts for every 16-bit or float plane on its own that is wide enough to hold them, planes that fit one workgroup
+ * included; 0 restores the automatic choice.  ghost_columns > 0 (a multiple of 8) moves every seam to that distance from
+ * the end of the window left of it (windows keep their widths): 8 makes nearly every frame fail the check; 0 restores the
+ * default.  SN_ERR_UNSUPPORTED without the option. */
+int sn_debug_set_column_parts(sn_context* ctx, int32_t parts, int32_t ghost_columns);
 
 /* Test hook for the chains over several workgroups per cost buffer (sn_policy.chain): the NEXT such launch starts with
  * its fault word up, as if a workgroup had given up waiting at once -- its waves then take rows before they are written,

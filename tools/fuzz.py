@@ -2,6 +2,7 @@
 """Randomised parity run on the GPU: random formats, sizes, arguments, extension flags and frame sequences through
 the C ABI (host frames, device batches and the host ring) against oracle instances.  A quarter of the integer
 configurations run with opt=1 (the SSE2 arithmetic, against tests/sse2_model.py), and those draw sn_policy.sse2_sweeps too.
+Wide 16-bit and float configurations (3872 .. 8192 columns) draw sn_options.column_parts.
 usage: python tools/fuzz.py [--seconds 120] [--seed 1]"""
 import argparse
 import os
@@ -46,7 +47,7 @@ def main():
     t_end = time.time() + a.seconds
     n = bad = 0
     stats = {"fused": 0, "pool": 0, "ring": 0, "host": 0, "batch": 0, "frames": 0, "pixels": 0, "banded_frames": 0, "band_fallbacks": 0, "chained_frames": 0,
-             "uv_sweep_configs": 0, "chain_redone": 0, "opt1": 0, "opt1_sweeps": 0}
+             "uv_sweep_configs": 0, "chain_redone": 0, "opt1": 0, "opt1_sweeps": 0, "part_frames": 0, "part_fallbacks": 0}
     while time.time() < t_end:
         fmt = rng.choice(FORMATS)
         wide = rng.random() < 0.15
@@ -67,6 +68,11 @@ def main():
                 w += 2
         if probe.bytes > 1 and w > 3840 and rng.random() < 0.7:
             w = 3840
+        # 16-bit and float planes wider than one workgroup of the sweeps: now and then in column parts (sn_options.column_parts)
+        column_parts = 0
+        if probe.bytes > 1 and wide and rng.random() < 0.5:
+            w = rng.choice([3872, 4096, 5120, 6144, 7680, 8192])
+            column_parts = 1
         clip = clip_format(fmt, w, h)
         kw = dict(order=rng.randint(0, 2), aa=rng.choice([0, 1, 20, 48, 100, 128]), aac=rng.choice([0, 48, 128]),
                   dh=rng.random() < 0.2, luma=rng.random() < 0.85, chroma=rng.random() < 0.8)
@@ -101,7 +107,7 @@ def main():
         try:
             sweeps = rng.choice([0, 0, 0, 1])  # 8-bit 4:2:0: U and V as one sweep (default) or a sweep each
             flt = SangNom2(clip, host_depth=rng.choice([1, 2, 3, 4, 5, 8, 12]), max_batch=nframes, isolated_planes=ext == "isolated", fresh_pool=ext == "fresh", small_launches=small,
-                           chroma_sweeps=sweeps, opt=opt, sse2_sweeps=knob, **kw)
+                           chroma_sweeps=sweeps, opt=opt, sse2_sweeps=knob, column_parts=column_parts, **kw)
         except Exception as e:  # a geometry the library rejects must be one it documents
             if "exceeds the supported maximum" in str(e):
                 continue
@@ -146,6 +152,9 @@ def main():
             stats["chain_redone"] += info.chain_redone
             stats["opt1"] += opt
             stats["opt1_sweeps"] += knob
+            pinfo = flt.parts_info()
+            stats["part_frames"] += pinfo.part_frames
+            stats["part_fallbacks"] += pinfo.part_fallbacks
         stats["fused" if fused else "pool"] += 1
         for f in range(nframes):
             for p in range(clip.planes):
@@ -155,7 +164,7 @@ def main():
                     np.savez(f"gpurun_out/fuzz_mismatch_{n}.npz", **{f"src{q}": frames[f][q] for q in range(clip.planes)},
                              **{f"want{q}": want[f][q] for q in range(clip.planes)}, **{f"got{q}": got[f][q] for q in range(clip.planes)})
                     print(f"MISMATCH {fmt} {w}x{h} {kw} ext={ext} way={way} frame {f}/{nframes} plane {p} pattern={pattern} parity={parity} "
-                          f"small_launches={small} chroma_sweeps={sweeps} opt={opt} sse2_sweeps={knob} uv={info.uv_sweeps} bands={band_set} banded={info.banded_frames} fallbacks={info.band_fallbacks} "
+                          f"small_launches={small} chroma_sweeps={sweeps} opt={opt} sse2_sweeps={knob} column_parts={column_parts} part_frames={pinfo.part_frames} part_fallbacks={pinfo.part_fallbacks} uv={info.uv_sweeps} bands={band_set} banded={info.banded_frames} fallbacks={info.band_fallbacks} "
                           f"fused={info.fused_frames} n={len(d)} rows {d[:, 0].min()}..{d[:, 0].max()} cols {d[:, 1].min()}..{d[:, 1].max()}", flush=True)
         n += 1
         if n % 50 == 0:
