@@ -49,12 +49,17 @@ bool fused_eligible(const sn_config& c)
     return true;
 }
 
-// Pointer / pitch alignment the 8-byte vector accesses need.
+// Pointer / pitch alignment the 8-byte vector accesses need, and the size the sweeps' addressing holds: they reach a plane
+// through a buffer descriptor of pitch * rows bytes and form row offsets as 32-bit integers (a few rows past the last one
+// included, which the descriptor's range check drops), so pitch * (rows + kFusedRowSlack) has to fit in 31 bits on both
+// sides.  A larger plane -- a column window of a very wide surface -- is served by the pool path, whose kernels address
+// rows with 64-bit pointers.
 bool fused_layout_ok(const PlaneArgs& p)
 {
     auto a8 = [](uintptr_t v) { return (v & 7) == 0; };
+    auto fits = [](int32_t pitch, int32_t rows) { return (int64_t)pitch * ((int64_t)rows + kFusedRowSlack) <= (int64_t)INT32_MAX; };
     return a8((uintptr_t)p.src) && a8((uintptr_t)p.dst) && a8((uintptr_t)p.src_pitch) && a8((uintptr_t)p.dst_pitch) &&
-           a8((uintptr_t)p.src_frame_stride) && a8((uintptr_t)p.dst_frame_stride);
+           a8((uintptr_t)p.src_frame_stride) && a8((uintptr_t)p.dst_frame_stride) && fits(p.src_pitch, p.h_in) && fits(p.dst_pitch, p.h_out);
 }
 
 }  // namespace sn

@@ -94,6 +94,8 @@ bool fused_padded_plane_eligible(int bytes_per_sample, int w);
 // ... too wide for one workgroup but served in column parts (sn_options.column_parts): 16-bit / float, w % 32 == 0, w <= 8192
 bool fused_parts_plane_eligible(int bytes_per_sample, int w);
 bool fused_needs_pools(const sn_config& c);  // subsampled chroma: luma / chroma sweeps coupled through scratch pools
+// 8-byte alignment of bases, pitches and frame strides, and pitch * (rows + kFusedRowSlack) <= INT32_MAX on both sides
+constexpr int kFusedRowSlack = 16;
 bool fused_layout_ok(const PlaneArgs& p);
 // sn_fused_u8_v3.hip: the 8-bit sweep, two virtual wavefronts packed into every register.
 bool fused_v3_plane_ok(int w);
