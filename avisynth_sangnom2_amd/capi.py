@@ -31,7 +31,11 @@ EXPORTS = (
     "sn_aa_process_device_strided", "sn_aa_synchronize", "sn_aa_get_stream", "sn_aa_get_info",
     "sn_aa_host_slots", "sn_aa_submit_host", "sn_aa_collect_host",
     "sn_get_parts_info", "sn_aa_get_parts_info", "sn_debug_set_column_parts",
+    "sn_process_device_surfaces", "sn_aa_process_device_surfaces", "sn_get_surface_info", "sn_aa_get_surface_info",
 )
+
+# sn_surfaces.layout: planar Y, U, V or Y plus one plane of U,V pairs (NV12, P010 / P016, NV16, NV24)
+SN_LAYOUT_PLANAR, SN_LAYOUT_SEMIPLANAR = 0, 1
 
 # sn_options.arithmetic: which of the reference's two code paths a context reproduces (sangnom_hip.h)
 SN_ARITH_CXX, SN_ARITH_SSE2 = 0, 1
@@ -64,6 +68,24 @@ class SnOptions(ctypes.Structure):
 class SnPartsInfo(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_int32), ("parts", ctypes.c_int32 * 3), ("ghost_columns", ctypes.c_int32),
                 ("part_frames", ctypes.c_int64), ("part_fallbacks", ctypes.c_int64)]
+
+
+class SnSurfaces(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_int32), ("layout", ctypes.c_int32), ("plane", ctypes.c_void_p * 3), ("pitch", ctypes.c_int32 * 3),
+                ("reserved", ctypes.c_int32), ("frame_stride", ctypes.c_int64 * 3)]
+
+
+class SnSurfaceInfo(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_int32), ("reserved", ctypes.c_int32), ("scratch_bytes", ctypes.c_int64),
+                ("split_frames", ctypes.c_int64), ("merged_frames", ctypes.c_int64), ("copied_frames", ctypes.c_int64)]
+
+
+def surfaces(layout: int, planes, pitches, frame_strides) -> "SnSurfaces":
+    """sn_surfaces from device pointers, pitches and frame strides in bytes (two entries for SN_LAYOUT_SEMIPLANAR: Y, UV)."""
+    s = SnSurfaces(struct_size=ctypes.sizeof(SnSurfaces), layout=int(layout))
+    for p, (ptr, pitch, fs) in enumerate(zip(planes, pitches, frame_strides)):
+        s.plane[p], s.pitch[p], s.frame_stride[p] = ptr, int(pitch), int(fs)
+    return s
 
 
 def options(arithmetic: int = SN_ARITH_CXX, column_parts: int = 0) -> "SnOptions":
@@ -185,5 +207,9 @@ def load():
     L.sn_get_parts_info.argtypes = [vp, ctypes.POINTER(SnPartsInfo)]
     L.sn_aa_get_parts_info.argtypes = [vp, i32, ctypes.POINTER(SnPartsInfo)]
     L.sn_debug_set_column_parts.argtypes = [vp, i32, i32]
+    L.sn_process_device_surfaces.argtypes = [vp, i32, ctypes.POINTER(SnSurfaces), ctypes.POINTER(SnSurfaces), p3i]
+    L.sn_aa_process_device_surfaces.argtypes = [vp, i32, ctypes.POINTER(SnSurfaces), ctypes.POINTER(SnSurfaces), p3i]
+    L.sn_get_surface_info.argtypes = [vp, ctypes.POINTER(SnSurfaceInfo)]
+    L.sn_aa_get_surface_info.argtypes = [vp, ctypes.POINTER(SnSurfaceInfo)]
     _lib = L
     return L

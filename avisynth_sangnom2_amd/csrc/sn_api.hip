@@ -22,7 +22,17 @@ constexpr int kSyncChunks = 4;  // chunks of rows a pageable plane of the synchr
 
 namespace sn {
 
-
+// Planar chroma scratch of the surface calls (sn_process_device_surfaces, sn_aa_process_device_surfaces): U and V of `cap`
+// frames in the source's chroma geometry (a semi-planar source is split into it) and in the destination's (merged from it).
+struct UvScratch {
+    uint8_t* in[2] = {nullptr, nullptr};   // full height; a split writes the lines the pass keeps, the rest stays 0xA5
+    uint8_t* out[2] = {nullptr, nullptr};  // full height, every line written by the pass
+    int cap = 0;                           // frames (0: not allocated yet)
+    int pitch_in = 0, pitch_out = 0;
+    int64_t in_bytes = 0, out_bytes = 0;   // one frame of one plane
+    int64_t bytes = 0;                     // all of it
+    int64_t split_frames = 0, merged_frames = 0, copied_frames = 0;  // sn_surface_info
+};
 
 struct Context {
     sn_config cfg{};
@@ -41,6 +51,7 @@ struct Context {
     bool process[3] = {true, true, true};
     bool history_free = false;
     bool copies_elsewhere = false;  // a pass of sn_aa_*: planes that are not processed are copied by that call, once
+    bool chroma_elsewhere = false;  // during a surface call: chroma that is not processed has gone from src to dst already
     bool use_fused = false;
     int arith = SN_ARITH_CXX;  // sn_options.arithmetic, fixed for the context's life
     // SN_ARITH_SSE2 on integer samples: the saturating instances of the pool kernels (float has one arithmetic)
@@ -125,6 +136,7 @@ struct Context {
 
     int64_t frames = 0, fused_frames = 0;
     std::string err;
+    UvScratch uv;  // sn_process_device_surfaces
 
     // row-band sweeps of small launches (sn_fused_v3_common.h): per scratch slot the bands' state
     // snapshots and the frame's flag; the verification counts failed frames in band_fallbacks_dev and mirrors the count
@@ -356,6 +368,8 @@ void sn_destroy(sn_context* h)
         if (c->plane_pool[p].base) (void)hipFree(c->plane_pool[p].base);
     for (int i = 0; i < 2; ++i)
         if (c->fpool[i]) (void)hipFree(c->fpool[i]);
+    for (uint8_t* q : {c->uv.in[0], c->uv.in[1], c->uv.out[0], c->uv.out[1]})
+        if (q) (void)hipFree(q);
     if (c->gate.in) (void)hipStreamSynchronize(c->gate.in);
     if (c->gate.out) (void)hipStreamSynchronize(c->gate.out);
     for (int p = 0; p < 3; ++p) {
@@ -1096,7 +1110,7 @@ static int run_group(Context* c, hipStream_t st, int slot0, int n, const void* c
         a.offset = offset;
         a.dh = c->cfg.dh;
         a.enabled = (c->cfg.dh || c->process[p]) ? 1 : 0;
-        a.copied_elsewhere = c->copies_elsewhere ? 1 : 0;
+        a.copied_elsewhere = (c->copies_elsewhere || (p > 0 && c->chroma_elsewhere)) ? 1 : 0;
         a.arith = c->saturating() ? SN_ARITH_SSE2 : SN_ARITH_CXX;
         fused[p] = a.enabled && (c->isolated ? c->plane_fused[p] : c->use_fused) && sn::fused_layout_ok(a);
     }
@@ -1627,7 +1641,7 @@ static int run_chain(Context* c, hipStream_t st, int n, const void* const src[3]
         a.offset = offset;
         a.dh = c->cfg.dh;
         a.enabled = (c->cfg.dh || c->process[p]) ? 1 : 0;
-        a.copied_elsewhere = c->copies_elsewhere ? 1 : 0;
+        a.copied_elsewhere = (c->copies_elsewhere || (p > 0 && c->chroma_elsewhere)) ? 1 : 0;
         SN_HIP(c, sn::launch_assemble(st, a, B, n));
     }
     sn::PoolArgs ring = c->pool;
@@ -1756,6 +1770,241 @@ int sn_process_device(sn_context* h, const void* const src[3], const int32_t sp[
     if (!c) return sn::fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
     const int64_t zero[3] = {0, 0, 0};
     return sn_process_device_strided(h, 1, src, zero, sp, dst, zero, dp, &parity);
+}
+
+// -- decoder and encoder surfaces (sn_surfaces) -------------------------------------------------------------------------
+// What both surface calls share: the checks of a surface description, the chroma scratch, and the walk over a batch in chunks
+// of what the scratch holds -- split, the call's passes on planar chroma, merge.
+
+struct SurfaceGeometry {  // of the call that walks: the batch call's clip, or the anti-aliasing call's (dh: output twice as wide and high)
+    int B = 1, planes = 1, max_batch = 1;
+    int w_in[3] = {0, 0, 0}, h_in[3] = {0, 0, 0}, w_out[3] = {0, 0, 0}, h_out[3] = {0, 0, 0};
+    bool chroma_processed = true;
+    bool all_lines = true;  // the passes read every line of the source's chroma (dh; the anti-aliasing call's turns)
+};
+
+struct SurfaceSide {  // a checked sn_surfaces
+    bool semi = false;
+    uint8_t* p[3] = {nullptr, nullptr, nullptr};
+    int32_t pitch[3] = {0, 0, 0};
+    int64_t fs[3] = {0, 0, 0};
+};
+
+// the description on its own: SN_OK, or the code and the text that names the field
+static int surface_header(const char* name, const sn_surfaces* s, std::string& msg)
+{
+    if (!s) return msg = std::string(name) + " is NULL", SN_ERR_INVALID_ARG;
+    if (s->struct_size != (int32_t)sizeof(sn_surfaces)) return msg = std::string(name) + ": sn_surfaces.struct_size mismatch", SN_ERR_INVALID_ARG;
+    if (s->layout != SN_LAYOUT_PLANAR && s->layout != SN_LAYOUT_SEMIPLANAR)
+        return msg = std::string(name) + ": sn_surfaces.layout must be SN_LAYOUT_PLANAR or SN_LAYOUT_SEMIPLANAR", SN_ERR_INVALID_ARG;
+    if (s->reserved != 0) return msg = std::string(name) + ": sn_surfaces.reserved must be zero", SN_ERR_INVALID_ARG;
+    return SN_OK;
+}
+
+// ... against the planes it has to hold: w[p] samples per row of plane p (the UV plane: 2 w[1])
+static int surface_side(const char* name, const sn_surfaces* s, const int w[3], int planes, int B, SurfaceSide& out, std::string& msg)
+{
+    const std::string n(name);
+    out.semi = s->layout == SN_LAYOUT_SEMIPLANAR;
+    if (out.semi && planes < 3) return msg = n + ": SN_LAYOUT_SEMIPLANAR needs a context with num_planes == 3", SN_ERR_UNSUPPORTED;
+    if (out.semi && B == 4) return msg = n + ": SN_LAYOUT_SEMIPLANAR with bytes_per_sample == 4: no such surface exists", SN_ERR_UNSUPPORTED;
+    if (out.semi && s->plane[2]) return msg = n + ": sn_surfaces.plane[2] must be NULL with SN_LAYOUT_SEMIPLANAR (plane[1] is the UV plane)", SN_ERR_INVALID_ARG;
+    const int np = out.semi ? 2 : planes;
+    for (int p = 0; p < np; ++p) {
+        const int64_t row = (int64_t)(out.semi && p == 1 ? 2 : 1) * w[p] * B;
+        const std::string ps = std::to_string(p);
+        if (!s->plane[p]) return msg = n + ": sn_surfaces.plane[" + ps + "] is NULL", SN_ERR_INVALID_ARG;
+        if (s->pitch[p] < row)
+            return msg = n + ": sn_surfaces.pitch[" + ps + "] " + std::to_string(s->pitch[p]) + " smaller than the row size " + std::to_string(row), SN_ERR_INVALID_ARG;
+        if (s->pitch[p] % B || s->frame_stride[p] % B || (uintptr_t)s->plane[p] % B)
+            return msg = n + ": sn_surfaces plane[" + ps + "] / pitch / frame_stride not aligned to the sample size", SN_ERR_INVALID_ARG;
+        out.p[p] = static_cast<uint8_t*>(s->plane[p]);
+        out.pitch[p] = s->pitch[p];
+        out.fs[p] = s->frame_stride[p];
+    }
+    return SN_OK;
+}
+
+// The scratch, once: for min(max_batch, what a sixteenth of the budget holds, at least 1) frames (sangnom_hip.h).
+// Allocated before anything of the call is queued; the stream is drained so that whichever stream comes first finds it filled.
+static hipError_t surface_scratch(sn::UvScratch& S, hipStream_t st, const SurfaceGeometry& g, int64_t budget)
+{
+    if (S.cap > 0) return hipSuccess;
+    S.pitch_in = (g.w_in[1] * g.B + 255) & ~255;
+    S.pitch_out = (g.w_out[1] * g.B + 255) & ~255;
+    S.in_bytes = (int64_t)S.pitch_in * g.h_in[1];
+    S.out_bytes = (int64_t)S.pitch_out * g.h_out[1];
+    const int64_t per_frame = 2 * (S.in_bytes + S.out_bytes);
+    const int64_t fit = budget / 16 / per_frame;
+    const int cap = (int)(fit < 1 ? 1 : fit < g.max_batch ? fit : g.max_batch);
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+        e = hipMalloc(reinterpret_cast<void**>(&S.in[k]), (size_t)S.in_bytes * cap);
+        // a split writes only the lines its pass keeps: a pass that read another line would read this pattern
+        if (e == hipSuccess) e = hipMemsetAsync(S.in[k], 0xA5, (size_t)S.in_bytes * cap, st);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&S.out[k]), (size_t)S.out_bytes * cap);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(st);
+        for (uint8_t** q : {&S.in[0], &S.in[1], &S.out[0], &S.out[1]}) {
+            if (*q) (void)hipFree(*q);
+            *q = nullptr;
+        }
+        return e;
+    }
+    S.cap = cap;
+    S.bytes = per_frame * cap;
+    return hipSuccess;
+}
+
+struct SurfacePasses {  // the call's passes on planar planes: `m` frames, pointers at the first of them
+    void* self;
+    int (*run)(void* self, int m, const void* const s[3], const int64_t sfs[3], const int32_t sp[3], void* const d[3], const int64_t dfs[3],
+               const int32_t dp[3], const int32_t* parity);
+    int (*offset)(void* self, int parity);  // the field offset of a frame (unless all_lines)
+};
+
+// A HIP error of the walk itself comes back as SN_ERR_HIP with its text in msg; an error of the passes leaves msg empty (the
+// context holds the text).
+static int surface_walk(sn::UvScratch& S, hipStream_t st, const SurfaceGeometry& g, int n, const SurfaceSide& src, const SurfaceSide& dst,
+                        const int32_t* parity, const SurfacePasses& passes, std::string& msg)
+{
+#define SN_UV_HIP(call)                                                      \
+    do {                                                                     \
+        hipError_t e_ = (call);                                              \
+        if (e_ != hipSuccess) {                                              \
+            msg = std::string(#call " failed: ") + hipGetErrorString(e_);    \
+            return SN_ERR_HIP;                                               \
+        }                                                                    \
+    } while (0)
+    const int B = g.B;
+    const void* s[3];
+    void* d[3];
+    int64_t sfs[3], dfs[3];
+    int32_t sp[3], dp[3];
+    if (!g.chroma_processed) {
+        // never through a pass and never through scratch: one copy of the UV plane, or one conversion from src to dst
+        const int cw = g.w_in[1], h = g.h_in[1];
+        if (src.semi && dst.semi) {
+            for (int f = 0; f < n; ++f)
+                SN_UV_HIP(hipMemcpy2DAsync(dst.p[1] + f * dst.fs[1], (size_t)dst.pitch[1], src.p[1] + f * src.fs[1], (size_t)src.pitch[1],
+                                           (size_t)2 * cw * B, (size_t)h, hipMemcpyDeviceToDevice, st));
+        } else if (src.semi) {
+            SN_UV_HIP(sn::launch_uv_split(st, B, n, src.p[1], src.fs[1], src.pitch[1], cw, h, dst.p[1], dst.fs[1], dst.pitch[1], dst.p[2], dst.fs[2],
+                                          dst.pitch[2], -1));
+        } else {
+            SN_UV_HIP(sn::launch_uv_merge(st, B, n, src.p[1], src.fs[1], src.pitch[1], src.p[2], src.fs[2], src.pitch[2], cw, h, dst.p[1], dst.fs[1],
+                                          dst.pitch[1]));
+        }
+        S.copied_frames += n;
+        for (int p = 0; p < 3; ++p) {  // the passes leave planes 1 and 2 alone: their pointers only have to be there
+            s[p] = src.p[0], sfs[p] = src.fs[0], sp[p] = src.pitch[0];
+            d[p] = dst.p[0], dfs[p] = dst.fs[0], dp[p] = dst.pitch[0];
+        }
+        return passes.run(passes.self, n, s, sfs, sp, d, dfs, dp, parity);
+    }
+    for (int f0 = 0; f0 < n; f0 += S.cap) {
+        const int m = n - f0 < S.cap ? n - f0 : S.cap;
+        const int32_t* par = parity ? parity + f0 : nullptr;
+        for (int p = 0; p < 3; ++p) {
+            const int q = src.semi && p == 2 ? 1 : p, r = dst.semi && p == 2 ? 1 : p;  // (placeholders, replaced below)
+            s[p] = src.p[q] + (int64_t)f0 * src.fs[q], sfs[p] = src.fs[q], sp[p] = src.pitch[q];
+            d[p] = dst.p[r] + (int64_t)f0 * dst.fs[r], dfs[p] = dst.fs[r], dp[p] = dst.pitch[r];
+        }
+        if (src.semi) {
+            const uint8_t* uv = src.p[1] + (int64_t)f0 * src.fs[1];
+            // the lines the pass keeps: one launch per run of frames with the same field offset, as run_batch cuts them
+            for (int g0 = 0; g0 < m;) {
+                int g1 = m, lines = -1;
+                if (!g.all_lines) {
+                    lines = passes.offset(passes.self, par ? par[g0] : 1);
+                    for (g1 = g0 + 1; g1 < m && passes.offset(passes.self, par ? par[g1] : 1) == lines;) ++g1;
+                }
+                SN_UV_HIP(sn::launch_uv_split(st, B, g1 - g0, uv + g0 * src.fs[1], src.fs[1], src.pitch[1], g.w_in[1], g.h_in[1], S.in[0] + g0 * S.in_bytes,
+                                              S.in_bytes, S.pitch_in, S.in[1] + g0 * S.in_bytes, S.in_bytes, S.pitch_in, lines));
+                g0 = g1;
+            }
+            for (int k = 0; k < 2; ++k) s[1 + k] = S.in[k], sfs[1 + k] = S.in_bytes, sp[1 + k] = S.pitch_in;
+            S.split_frames += m;
+        }
+        if (dst.semi)
+            for (int k = 0; k < 2; ++k) d[1 + k] = S.out[k], dfs[1 + k] = S.out_bytes, dp[1 + k] = S.pitch_out;
+        const int rc = passes.run(passes.self, m, s, sfs, sp, d, dfs, dp, par);
+        if (rc != SN_OK) return rc;
+        if (dst.semi) {
+            SN_UV_HIP(sn::launch_uv_merge(st, B, m, S.out[0], S.out_bytes, S.pitch_out, S.out[1], S.out_bytes, S.pitch_out, g.w_out[1], g.h_out[1],
+                                          dst.p[1] + (int64_t)f0 * dst.fs[1], dst.fs[1], dst.pitch[1]));
+            S.merged_frames += m;
+        }
+    }
+    return SN_OK;
+#undef SN_UV_HIP
+}
+
+static int surface_info(const sn::UvScratch& S, sn_surface_info* info)
+{
+    if (!info || info->struct_size != (int32_t)sizeof(sn_surface_info)) return SN_ERR_INVALID_ARG;
+    info->reserved = 0;
+    info->scratch_bytes = S.bytes;
+    info->split_frames = S.split_frames;
+    info->merged_frames = S.merged_frames;
+    info->copied_frames = S.copied_frames;
+    return SN_OK;
+}
+
+static int sn_surface_offset(void* self, int parity) { return field_offset(static_cast<Context*>(self), parity); }
+
+static int sn_surface_run(void* self, int m, const void* const s[3], const int64_t sfs[3], const int32_t sp[3], void* const d[3], const int64_t dfs[3],
+                          const int32_t dp[3], const int32_t* parity)
+{
+    Context* c = static_cast<Context*>(self);
+    // chroma that is not processed has gone from src to dst already: launch_assemble leaves those planes alone
+    // (PlaneArgs::copied_elsewhere) and copies a luma plane that is not processed either, as in the planar call
+    c->chroma_elsewhere = !(c->cfg.dh || c->process[1]);
+    const int rc = run_batch(c, c->stream, 0, m, s, sfs, sp, d, dfs, dp, parity);
+    c->chroma_elsewhere = false;
+    return rc;
+}
+
+int sn_process_device_surfaces(sn_context* h, int32_t nframes, const sn_surfaces* src, const sn_surfaces* dst, const int32_t* parity)
+{
+    Context* c = reinterpret_cast<Context*>(h);
+    if (!c) return sn::fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    std::string msg;
+    int rc = surface_header("src", src, msg);
+    if (rc == SN_OK) rc = surface_header("dst", dst, msg);
+    if (rc != SN_OK) return sn::fail(c, rc, "%s", msg.c_str());
+    if (src->layout == SN_LAYOUT_PLANAR && dst->layout == SN_LAYOUT_PLANAR)  // the planar call itself
+        return sn_process_device_strided(h, nframes, src->plane, src->frame_stride, src->pitch, dst->plane, dst->frame_stride, dst->pitch, parity);
+    if (nframes < 0 || nframes > c->cfg.max_batch)
+        return sn::fail(c, SN_ERR_INVALID_ARG, "nframes %d outside 0..max_batch (%d)", nframes, c->cfg.max_batch);
+    SurfaceGeometry g;
+    g.B = c->cfg.bytes_per_sample;
+    g.planes = c->nplanes();
+    g.max_batch = c->cfg.max_batch;
+    for (int p = 0; p < g.planes; ++p) g.w_in[p] = g.w_out[p] = c->plane_w(p), g.h_in[p] = c->plane_h_in(p), g.h_out[p] = c->plane_h_out(p);
+    g.chroma_processed = c->cfg.dh || c->process[1];
+    g.all_lines = c->cfg.dh != 0;
+    SurfaceSide ss, ds;
+    rc = surface_side("src", src, g.w_in, g.planes, g.B, ss, msg);
+    if (rc == SN_OK) rc = surface_side("dst", dst, g.w_out, g.planes, g.B, ds, msg);
+    if (rc != SN_OK) return sn::fail(c, rc, "%s", msg.c_str());
+    if (nframes == 0) return SN_OK;
+    SN_HIP(c, hipSetDevice(c->device));
+    if (g.chroma_processed) SN_HIP(c, surface_scratch(c->uv, c->stream, g, scratch_budget(c)));
+    const SurfacePasses passes{c, sn_surface_run, sn_surface_offset};
+    rc = surface_walk(c->uv, c->stream, g, nframes, ss, ds, parity, passes, msg);
+    if (rc != SN_OK && !msg.empty()) return sn::fail(c, rc, "%s", msg.c_str());
+    return rc;
+}
+
+int sn_get_surface_info(sn_context* h, sn_surface_info* info)
+{
+    Context* c = reinterpret_cast<Context*>(h);
+    if (!c) return sn::fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    if (surface_info(c->uv, info) != SN_OK) return sn::fail(c, SN_ERR_INVALID_ARG, "info is NULL or sn_surface_info.struct_size mismatch");
+    return SN_OK;
 }
 
 int sn_process_host(sn_context* h, const void* const src[3], const int32_t sp[3], void* const dst[3],
@@ -2420,6 +2669,7 @@ struct sn_aa_context {
         std::vector<Slot> slot;
     };
     std::vector<Group> groups;  // [0, ring_groups): the ring; [ring_groups]: the synchronous call's
+    sn::UvScratch uv;           // sn_aa_process_device_surfaces
     int depth = 0, per_group = 1, ring_groups = 0, ring_next = 0;
     bool ring_ready = false;
     Copier* copier = nullptr;  // the first context's
@@ -2500,6 +2750,8 @@ void sn_aa_destroy(sn_aa_context* a)
     for (int p = 0; p < 3; ++p)
         for (uint8_t* q : {a->d_t1[p], a->d_u1[p], a->d_t2[p]})
             if (q) (void)hipFree(q);
+    for (uint8_t* q : {a->uv.in[0], a->uv.in[1], a->uv.out[0], a->uv.out[1]})
+        if (q) (void)hipFree(q);
     for (auto& g : a->groups) aa_free_group(g);
     for (hipStream_t st : {a->up, a->down})
         if (st) (void)hipStreamDestroy(st);
@@ -2660,6 +2912,55 @@ int sn_aa_process_device_strided(sn_aa_context* a, int32_t nframes, const void* 
                                        (size_t)sp[p], (size_t)a->w[p] * B, a->h[p], hipMemcpyDeviceToDevice, a->stream));
     }
     return aa_run(a, nframes, src, sfs, sp, dst, dfs, dp, parity);
+}
+
+static int aa_surface_run(void* self, int m, const void* const s[3], const int64_t sfs[3], const int32_t sp[3], void* const d[3], const int64_t dfs[3],
+                          const int32_t dp[3], const int32_t* parity)
+{
+    sn_aa_context* a = static_cast<sn_aa_context*>(self);
+    if (!a->process[0])  // luma that is not processed: source to destination, once (chroma: surface_walk)
+        for (int f = 0; f < m; ++f)
+            SN_AA_HIP(hipMemcpy2DAsync(static_cast<uint8_t*>(d[0]) + f * dfs[0], (size_t)dp[0], static_cast<const uint8_t*>(s[0]) + f * sfs[0],
+                                       (size_t)sp[0], (size_t)a->w[0] * a->cfg.bytes_per_sample, a->h[0], hipMemcpyDeviceToDevice, a->stream));
+    return aa_run(a, m, s, sfs, sp, d, dfs, dp, parity);
+}
+
+int sn_aa_process_device_surfaces(sn_aa_context* a, int32_t nframes, const sn_surfaces* src, const sn_surfaces* dst, const int32_t* parity)
+{
+    if (!a) return aa_fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    std::string msg;
+    int rc = surface_header("src", src, msg);
+    if (rc == SN_OK) rc = surface_header("dst", dst, msg);
+    if (rc != SN_OK) return aa_fail(a, rc, msg);
+    if (src->layout == SN_LAYOUT_PLANAR && dst->layout == SN_LAYOUT_PLANAR)  // the planar call itself
+        return sn_aa_process_device_strided(a, nframes, src->plane, src->frame_stride, src->pitch, dst->plane, dst->frame_stride, dst->pitch, parity);
+    if (nframes < 0 || nframes > a->max_batch)
+        return aa_fail(a, SN_ERR_INVALID_ARG, "nframes " + std::to_string(nframes) + " outside 0..max_batch (" + std::to_string(a->max_batch) + ")");
+    SurfaceGeometry g;
+    g.B = a->cfg.bytes_per_sample;
+    g.planes = a->planes;
+    g.max_batch = a->max_batch;
+    for (int p = 0; p < g.planes; ++p) g.w_in[p] = a->w[p], g.h_in[p] = a->h[p], g.w_out[p] = a->ow[p], g.h_out[p] = a->oh[p];
+    g.chroma_processed = g.planes < 3 || a->process[1];
+    g.all_lines = true;  // a turn reads whole source rows, whichever destination lines it writes
+    SurfaceSide ss, ds;
+    rc = surface_side("src", src, g.w_in, g.planes, g.B, ss, msg);
+    if (rc == SN_OK) rc = surface_side("dst", dst, g.w_out, g.planes, g.B, ds, msg);
+    if (rc != SN_OK) return aa_fail(a, rc, msg);
+    if (nframes == 0) return SN_OK;
+    SN_AA_HIP(hipSetDevice(a->cfg.device));
+    if (g.chroma_processed) SN_AA_HIP(surface_scratch(a->uv, a->stream, g, scratch_budget(reinterpret_cast<Context*>(a->first))));
+    const SurfacePasses passes{a, aa_surface_run, nullptr};
+    rc = surface_walk(a->uv, a->stream, g, nframes, ss, ds, parity, passes, msg);
+    if (rc != SN_OK && !msg.empty()) return aa_fail(a, rc, msg);
+    return rc;
+}
+
+int sn_aa_get_surface_info(sn_aa_context* a, sn_surface_info* info)
+{
+    if (!a) return aa_fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    if (surface_info(a->uv, info) != SN_OK) return aa_fail(a, SN_ERR_INVALID_ARG, "info is NULL or sn_surface_info.struct_size mismatch");
+    return SN_OK;
 }
 
 int sn_aa_synchronize(sn_aa_context* a)

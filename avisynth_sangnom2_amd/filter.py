@@ -59,6 +59,27 @@ def clip_format(name: str, width: int, height: int) -> ClipFormat:
     return ClipFormat(width=width, height=height, **_FORMATS[name])
 
 
+def _surfaces_of(planes, shape_of, nplanes, B, what):
+    """sn_surfaces of device tensors: the planar tensors process_batch takes ([N, H_p, W_p] each), or two tensors
+    [Y [N, H, W], UV [N, Hc, Wc, 2]] for a semi-planar surface (NV12, P010 / P016, NV16, NV24; UV[..., 0] is U)."""
+    planes = list(planes)
+    semi = len(planes) == 2 and planes[1].dim() == 4
+    if not semi and len(planes) < nplanes:
+        raise ValueError(f"{what}: {nplanes} planar tensors or [Y, UV] expected")
+    N = planes[0].shape[0]
+    ptr, pitch, fs = [], [], []
+    for p, t in enumerate(planes[:2 if semi else nplanes]):
+        want = (N,) + tuple(shape_of(1 if p else 0)) + ((2,) if semi and p else ())
+        if tuple(t.shape) != want:
+            raise ValueError(f"{what} plane {p}: shape {tuple(t.shape)}, expected {want}")
+        if t.element_size() != B or not t.is_cuda:
+            raise ValueError(f"{what}: device-resident tensors of the clip's sample type expected")
+        if t.stride(-1) != 1 or (semi and p and t.stride(2) != 2):
+            raise ValueError(f"{what} plane {p}: rows must be contiguous (a UV tensor: stride(2) == 2, last stride 1)")
+        ptr.append(t.data_ptr()), pitch.append(t.stride(1) * B), fs.append(t.stride(0) * B)
+    return capi.surfaces(capi.SN_LAYOUT_SEMIPLANAR if semi else capi.SN_LAYOUT_PLANAR, ptr, pitch, fs), N
+
+
 class SangNom2:
     """One filter instance == one sn_context (its own stream and device pool)."""
 
@@ -287,6 +308,24 @@ class SangNom2:
         self._check(self._lib.sn_process_device_strided(self._h, N, sp, sfs, spi, dp, dfs, dpi, par))
         return dst
 
+    def process_surfaces(self, src, dst, parity=None):
+        """process_batch for decoder and encoder surfaces (sn_process_device_surfaces): each of src and dst is either the
+        planar tensors process_batch takes or [Y [N, H, W], UV [N, Hc, Wc, 2]], independently.  Asynchronous on the
+        context's stream (the first semi-planar call allocates the chroma scratch)."""
+        s, N = _surfaces_of(src, self.plane_shape_in, self.nplanes, self.clip.bytes, "src")
+        d, Nd = _surfaces_of(dst, self.plane_shape_out, self.nplanes, self.clip.bytes, "dst")
+        if N != Nd:
+            raise ValueError("src and dst must carry the same number of frames")
+        par = None if parity is None else (ctypes.c_int32 * N)(*[int(x) for x in parity])
+        self._check(self._lib.sn_process_device_surfaces(self._h, N, ctypes.byref(s), ctypes.byref(d), par))
+        return dst
+
+    def surface_info(self) -> capi.SnSurfaceInfo:
+        """What the surface calls of this context have done (sn_get_surface_info)."""
+        i = capi.SnSurfaceInfo(struct_size=ctypes.sizeof(capi.SnSurfaceInfo))
+        self._check(self._lib.sn_get_surface_info(self._h, ctypes.byref(i)))
+        return i
+
 
 def pin_host_array(a: np.ndarray) -> None:
     """sn_pin_host_buffer on a numpy array's memory: frames inside it then move over PCIe without staging copies.
@@ -419,6 +458,23 @@ class SangNomAA(_AAContext):
         par = None if parity is None else (ctypes.c_int32 * N)(*[int(x) for x in parity])
         self._check(self._lib.sn_aa_process_device_strided(self._h, N, sp, sfs, spi, dp, dfs, dpi, par))
         return dst
+
+    def process_surfaces(self, src, dst, parity=None):
+        """process_batch for decoder and encoder surfaces (sn_aa_process_device_surfaces): each of src and dst is either
+        the planar tensors or [Y [N, H, W], UV [N, Hc, Wc, 2]] (dh: dst is [Y [N, 2 H, 2 W], UV [N, 2 Hc, 2 Wc, 2]])."""
+        s, N = _surfaces_of(src, self.plane_shape, self.nplanes, self.clip.bytes, "src")
+        d, Nd = _surfaces_of(dst, self.plane_shape_out, self.nplanes, self.clip.bytes, "dst")
+        if N != Nd:
+            raise ValueError("src and dst must carry the same number of frames")
+        par = None if parity is None else (ctypes.c_int32 * N)(*[int(x) for x in parity])
+        self._check(self._lib.sn_aa_process_device_surfaces(self._h, N, ctypes.byref(s), ctypes.byref(d), par))
+        return dst
+
+    def surface_info(self) -> capi.SnSurfaceInfo:
+        """What the surface calls of this context have done (sn_aa_get_surface_info)."""
+        i = capi.SnSurfaceInfo(struct_size=ctypes.sizeof(capi.SnSurfaceInfo))
+        self._check(self._lib.sn_aa_get_surface_info(self._h, ctypes.byref(i)))
+        return i
 
 
 class SangNomAAHost(_AAContext):

@@ -358,6 +358,63 @@ int sn_aa_host_slots(sn_aa_context* ctx);
 int sn_aa_submit_host(sn_aa_context* ctx, const void* const src[3], const int32_t src_pitch[3], int32_t parity, int32_t* slot);
 int sn_aa_collect_host(sn_aa_context* ctx, int32_t slot, void* const dst[3], const int32_t dst_pitch[3]);
 
+/* Decoder and encoder surfaces: device-resident frames whose chroma is ONE plane of U,V pairs (semi-planar) -- NV12
+ * (8-bit 4:2:0), P010 / P016 (the same with 16-bit words), NV16 (4:2:2), NV24 (4:4:4) -- in and out of the two batch
+ * calls, without the caller converting anything.  A surface description names its layout; source and destination are
+ * independent (NV12 in and planar out, or the reverse, are fine).
+ *   SN_LAYOUT_PLANAR      plane[0..2] = Y, U, V, as for sn_process_device_strided (a Y clip: plane[0] only)
+ *   SN_LAYOUT_SEMIPLANAR  plane[0] = Y, plane[1] = the UV plane: row y of frame f is U0 V0 U1 V1 ... at plane[1] +
+ *                         f * frame_stride[1] + y * pitch[1], 2 * chroma width samples long; plane[2] must be NULL and
+ *                         pitch[2] / frame_stride[2] are ignored
+ * Pointers, pitches and frame strides need the alignment of the sample size only (a UV plane may start at an odd byte);
+ * surfaces whose bases, pitches and frame strides are multiples of 16 bytes -- every decoder's -- move 16 bytes per
+ * lane and access.  With both sides SN_LAYOUT_PLANAR the call IS sn_process_device_strided / sn_aa_process_device_strided
+ * (same checks, same result, no scratch).  Otherwise the result for a semi-planar surface is, bit for bit, what the planar
+ * call gives on the de-interleaved planes, re-interleaved, in every configuration the context accepts: the library splits
+ * the lines the filter keeps of a semi-planar source into planar chroma scratch of its own (every line with dh and in the
+ * anti-aliasing call), runs its passes there, and merges their output into the destination's UV plane; luma never goes
+ * through scratch.  Chroma that is not processed (chroma = 0 without dh) never reaches a pass: with the same layout on both
+ * sides the UV plane is copied once, with different layouts it is converted straight from src to dst.
+ * Scratch: two planes of the source's and two of the destination's chroma geometry per frame, pitches rounded up to 256
+ * bytes, for min(max_batch, what fits) frames, where a SIXTEENTH of sn_policy.scratch_budget_mb is what may be taken
+ * (1.5 GiB by default: 180 frames of 8-bit 2160p 4:2:0, 90 of 16-bit) and one frame is always held; a batch beyond that
+ * is walked in chunks, in order, so history-carrying clips stay exact.  It is allocated by the first call that has a
+ * semi-planar side with processed chroma, before anything of that call is queued, and freed with the context.
+ * Both calls are asynchronous on the context's stream, like the planar calls; that first call allocates and may
+ * synchronise the stream.
+ * P010 is a 16-bit clip whose values sit in the high bits of the word: create the context with bits_per_sample = 16
+ * and the result is what the reference gives on that 16-bit clip.  That is NOT the 10-bit result shifted left by six: the
+ * floor of stage 2 (sum / 16) does not commute with the shift, so low bits differ.  A caller who wants the reference's 10-bit
+ * result shifts the samples down first and creates a 10-bit context.
+ * SN_ERR_INVALID_ARG names the field: struct_size, layout, reserved, plane[2] set with SN_LAYOUT_SEMIPLANAR, a NULL
+ * plane, a pitch below the row (the UV plane's row is 2 * chroma width * bytes_per_sample; the anti-aliasing call with dh
+ * writes planes twice as wide and twice as high: 2 * (2 * chroma width) * bytes_per_sample).  SN_ERR_UNSUPPORTED:
+ * SN_LAYOUT_SEMIPLANAR on a context with num_planes == 1 or bytes_per_sample == 4 (no such surface exists).  A refused
+ * call queues nothing and leaves the context usable. */
+enum { SN_LAYOUT_PLANAR = 0, SN_LAYOUT_SEMIPLANAR = 1 };
+typedef struct sn_surfaces {
+    int32_t struct_size;      /* = sizeof(sn_surfaces)                                        */
+    int32_t layout;           /* SN_LAYOUT_*                                                 */
+    void*   plane[3];         /* SEMIPLANAR: plane[1] = the UV plane, plane[2] = NULL         */
+    int32_t pitch[3];         /* bytes; SEMIPLANAR: pitch[1] >= 2 * chroma width * bytes_per_sample */
+    int32_t reserved;         /* zero                                                        */
+    int64_t frame_stride[3];  /* bytes, as for sn_process_device_strided                     */
+} sn_surfaces;
+int sn_process_device_surfaces(sn_context* ctx, int32_t nframes, const sn_surfaces* src, const sn_surfaces* dst,
+                               const int32_t* parity /* NULL = all 1 */);
+int sn_aa_process_device_surfaces(sn_aa_context* ctx, int32_t nframes, const sn_surfaces* src, const sn_surfaces* dst,
+                                  const int32_t* parity /* NULL = all 1 */);
+/* What the surface calls of a context have done so far (all zero while every call had planar surfaces on both sides). */
+typedef struct sn_surface_info {
+    int32_t struct_size, reserved;
+    int64_t scratch_bytes;     /* planar chroma scratch this context holds for the call (0 until first needed) */
+    int64_t split_frames;      /* frames whose UV plane was split into U and V for the passes                  */
+    int64_t merged_frames;     /* frames whose U and V were merged into a UV plane                             */
+    int64_t copied_frames;     /* frames whose unprocessed chroma went from src to dst without a pass (copied or converted) */
+} sn_surface_info;
+int sn_get_surface_info(sn_context* ctx, sn_surface_info* info);
+int sn_aa_get_surface_info(sn_aa_context* ctx, sn_surface_info* info);
+
 int sn_synchronize(sn_context* ctx);
 void* sn_get_stream(sn_context* ctx); /* the hipStream_t the context launches on */
 int sn_get_info(sn_context* ctx, sn_info* info);

@@ -3,6 +3,7 @@
 the C ABI (host frames, device batches and the host ring) against oracle instances.  A quarter of the integer
 configurations run with opt=1 (the SSE2 arithmetic, against tests/sse2_model.py), and those draw sn_policy.sse2_sweeps too.
 Wide 16-bit and float configurations (3872 .. 8192 columns) draw sn_options.column_parts.
+Device batches of three-plane 8 / 16-bit clips draw the layout of each side: planar, or semi-planar (a UV plane; sn_process_device_surfaces).
 usage: python tools/fuzz.py [--seconds 120] [--seed 1]"""
 import argparse
 import os
@@ -47,7 +48,7 @@ def main():
     t_end = time.time() + a.seconds
     n = bad = 0
     stats = {"fused": 0, "pool": 0, "ring": 0, "host": 0, "batch": 0, "frames": 0, "pixels": 0, "banded_frames": 0, "band_fallbacks": 0, "chained_frames": 0,
-             "uv_sweep_configs": 0, "chain_redone": 0, "opt1": 0, "opt1_sweeps": 0, "part_frames": 0, "part_fallbacks": 0}
+             "uv_sweep_configs": 0, "chain_redone": 0, "opt1": 0, "opt1_sweeps": 0, "part_frames": 0, "part_fallbacks": 0, "semi_sides": 0}
     while time.time() < t_end:
         fmt = rng.choice(FORMATS)
         wide = rng.random() < 0.15
@@ -130,9 +131,21 @@ def main():
                 view = {1: np.uint8, 2: np.int16, 4: np.float32}[clip.bytes]
                 src = [torch.from_numpy(np.stack([fr[p] for fr in frames]).view(view)).to(dev) for p in range(clip.planes)]
                 dst = [torch.zeros((nframes,) + flt.plane_shape_out(p), dtype=src[p].dtype, device=dev) for p in range(clip.planes)]
+                # three-plane 8 / 16-bit clips: each side planar or semi-planar (NV12 / P016 / NV16 / NV24), independently
+                semi_in, semi_out = (rng.random() < 0.5, rng.random() < 0.5) if clip.planes == 3 and clip.bytes < 4 else (False, False)
+                if semi_in:
+                    src = [src[0], torch.stack([src[1], src[2]], dim=-1).contiguous()]
+                if semi_out:
+                    dst = [dst[0], torch.zeros(tuple(dst[1].shape) + (2,), dtype=dst[1].dtype, device=dev)]
+                stats["semi_sides"] += int(semi_in) + int(semi_out)
                 torch.cuda.synchronize()
-                flt.process_batch(src, dst, parity=parity)
+                if semi_in or semi_out or rng.random() < 0.25:
+                    flt.process_surfaces(src, dst, parity=parity)
+                else:
+                    flt.process_batch(src, dst, parity=parity)
                 flt.synchronize()
+                if semi_out:
+                    dst = [dst[0], dst[1][..., 0], dst[1][..., 1]]
                 got = [[to_host(dst[p][f]).view(clip.dtype) for p in range(clip.planes)] for f in range(nframes)]
             else:
                 slots = flt.host_slots()
