@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "sn_copier.h"
-#include "sn_fused_v3_common.h"
+#include "sn_sweep_args.h"
 #include "sn_internal.h"
 
 constexpr int kSyncChunks = 4;  // chunks of rows a pageable plane of the synchronous call is staged in
@@ -138,7 +138,7 @@ struct Context {
     std::string err;
     UvScratch uv;  // sn_process_device_surfaces
 
-    // row-band sweeps of small launches (sn_fused_v3_common.h): per scratch slot the bands' state
+    // row-band sweeps of small launches (sn_sweep_args.h): per scratch slot the bands' state
     // snapshots and the frame's flag; the verification counts failed frames in band_fallbacks_dev and mirrors the count
     // into band_fallbacks, host memory the device can write (what the pause heuristic of band_count looks at)
     // the chain of a history-carrying stream (run_chain): a ring of pool slots, one per pass in flight
@@ -162,7 +162,7 @@ struct Context {
     int64_t band_fallbacks_seen = 0;
     int band_pause = 0, band_pause_next = 0, band_good = 0;
 
-    // column parts (sn_options.column_parts; sn_fused_v3_common.h, kParts): per scratch slot the frame's seam record and its
+    // column parts (sn_options.column_parts; sn_sweep_args.h, kParts): per scratch slot the frame's seam record and its
     // flag, the count of failed frames on the device and mirrored to host memory (the pause looks at the mirror)
     bool parts_on = false;
     bool plane_parts[3] = {false, false, false};  // the plane is too wide for one workgroup and is cut
@@ -697,14 +697,10 @@ static int create_impl(const sn_config* cfg, Context* c)
         const int nr_c = c->plane_h_out(1) / 2 - 1;
         const int reach = nr_c + 2 < c->bh - 1 ? nr_c + 2 : c->bh - 1;
         c->fpool_rows = reach + 1;
-        c->fpool_frame_bytes = cfg->bytes_per_sample == 4   ? sn::fused_f32_pool_bytes(cfg->width, c->fpool_rows)
-                               : cfg->bytes_per_sample == 2 ? sn::fused_u16_pool_bytes(cfg->width, c->fpool_rows)
-                                                            : sn::fused_v3_pool_bytes(cfg->width, c->fpool_rows);
+        c->fpool_frame_bytes = sn::sweep_pool_bytes(cfg->bytes_per_sample, cfg->width, c->fpool_rows);
         // a chunk is three launches of one workgroup per frame: whole rounds of resident workgroups
         // (two waves per SIMD, 256 CUs) leave no partly filled round at the end of each launch
-        const int nw = cfg->bytes_per_sample == 4   ? sn::fused_f32_waves(cfg->width)
-                       : cfg->bytes_per_sample == 2 ? sn::fused_u16_waves(cfg->width)
-                                                    : sn::fused_v3_waves(cfg->width);
+        const int nw = sn::sweep_waves(cfg->bytes_per_sample, cfg->width);
         const int round = 256 * (8 / nw);
         // 8-bit clips whose U and V passes run as one sweep (sn_fused_u8_uv.hip) need the luma -> U pool only; the U -> V pool of
         // the two-sweep form is allocated when that form first runs (sn_policy.chroma_sweeps = 1, or a launch of planes the one
@@ -913,7 +909,7 @@ static bool prefer_pool(const Context* c, int n, int slot0)
 
 // Row bands: a launch of a few frames -- a synchronous GetFrame, a short look-ahead -- cannot fill the
 // device with one workgroup per frame, so each frame is cut into bands of rows that start from a guessed state and are
-// verified afterwards (sn_fused_v3_common.h, sn_band.hip).  The run-up is what the guess needs to be forgotten on
+// verified afterwards (sn_sweep_args.h, sn_band.hip).  The run-up is what the guess needs to be forgotten on
 // ordinary content: 8-bit sums settle within 17-23 rows of noise, 16-bit within 30, float within 37.
 constexpr int kMaxBands = 128;
 constexpr int kMinBandRows = 8;
@@ -1027,8 +1023,7 @@ static void set_bands(const Context* c, sn::FusedPool& fp, int want, int last, i
 
 static int band_threads(const Context* c)
 {
-    const int B = c->cfg.bytes_per_sample;
-    return 64 * (B == 4 ? sn::fused_f32_waves(c->cfg.width) : B == 2 ? sn::fused_u16_waves(c->cfg.width) : sn::fused_v3_waves(c->cfg.width));
+    return 64 * sn::sweep_waves(c->cfg.bytes_per_sample, c->cfg.width);
 }
 
 static int ensure_bands(Context* c)
@@ -1087,433 +1082,434 @@ static int prepare_small_launch_scratch(Context* c)
     return rc;
 }
 
-// Runs frames [f0, f0 + n) of a strided batch with one common field offset.
-// `st` is the stream to launch on and `slot0` the first scratch slot the frames may use (the batch entry points
-// pass the context's stream and slot 0, the host ring one frame on its slot's stream and scratch).
-static int run_group(Context* c, hipStream_t st, int slot0, int n, const void* const src[3], const int64_t sfs[3],
-                     const int32_t sp[3], void* const dst[3], const int64_t dfs[3], const int32_t dp[3], int f0, int offset)
+// One plane of frames [f0, ...) of a strided batch, as the launchers take it.
+static sn::PlaneArgs plane_args(const Context* c, int p, const void* const src[3], const int64_t sfs[3], const int32_t sp[3], void* const dst[3],
+                                const int64_t dfs[3], const int32_t dp[3], int f0, int offset)
 {
+    sn::PlaneArgs a{};
+    a.src = static_cast<const uint8_t*>(src[p]) + (int64_t)f0 * sfs[p];
+    a.dst = static_cast<uint8_t*>(dst[p]) + (int64_t)f0 * dfs[p];
+    a.src_frame_stride = sfs[p];
+    a.dst_frame_stride = dfs[p];
+    a.src_pitch = sp[p];
+    a.dst_pitch = dp[p];
+    a.w = c->plane_w(p);
+    a.h_in = c->plane_h_in(p);
+    a.h_out = c->plane_h_out(p);
+    a.offset = offset;
+    a.dh = c->cfg.dh;
+    a.enabled = (c->cfg.dh || c->process[p]) ? 1 : 0;
+    a.copied_elsewhere = (c->copies_elsewhere || (p > 0 && c->chroma_elsewhere)) ? 1 : 0;
+    a.arith = c->saturating() ? SN_ARITH_SSE2 : SN_ARITH_CXX;  // (the sweeps; the pool kernels take PoolArgs::arith)
+    return a;
+}
+
+static sn::PlaneArgs frames_from(sn::PlaneArgs a, int i)
+{
+    a.src += (int64_t)i * a.src_frame_stride;
+    a.dst += (int64_t)i * a.dst_frame_stride;
+    return a;
+}
+
+// What run_group has decided about one launch, for the route that carries it out.
+struct GroupLaunch {
+    Context* c;
+    hipStream_t st;
+    int slot0, n;
     sn::PlaneArgs pa[3];
-    bool fused[3] = {false, false, false};
-    for (int p = 0; p < c->nplanes(); ++p) {
-        sn::PlaneArgs& a = pa[p];
-        a = sn::PlaneArgs{};
-        a.src = static_cast<const uint8_t*>(src[p]) + (int64_t)f0 * sfs[p];
-        a.dst = static_cast<uint8_t*>(dst[p]) + (int64_t)f0 * dfs[p];
-        a.src_frame_stride = sfs[p];
-        a.dst_frame_stride = dfs[p];
-        a.src_pitch = sp[p];
-        a.dst_pitch = dp[p];
-        a.w = c->plane_w(p);
-        a.h_in = c->plane_h_in(p);
-        a.h_out = c->plane_h_out(p);
-        a.offset = offset;
-        a.dh = c->cfg.dh;
-        a.enabled = (c->cfg.dh || c->process[p]) ? 1 : 0;
-        a.copied_elsewhere = (c->copies_elsewhere || (p > 0 && c->chroma_elsewhere)) ? 1 : 0;
-        a.arith = c->saturating() ? SN_ARITH_SSE2 : SN_ARITH_CXX;
-        fused[p] = a.enabled && (c->isolated ? c->plane_fused[p] : c->use_fused) && sn::fused_layout_ok(a);
-    }
-    bool all_fused = true;
-    for (int p = 0; p < c->nplanes(); ++p) all_fused = all_fused && (fused[p] || !pa[p].enabled);
-    const int nbands = all_fused ? band_count(c, n, slot0) : 0;
-    if (nbands == 0 && prefer_pool(c, n, slot0))
-        for (int p = 0; p < 3; ++p) fused[p] = false;
-    // Column parts: which planes of this launch are cut.  Under SN_SMALL_AUTO a launch small enough for row bands goes
-    // where it went before the option existed, to the pool path; after a launch with a failed frame the parts pause, as
-    // the bands do (band_count).
-    PartsPlan plan[3];
-    bool any_parts = false;
-    for (int p = 0; p < c->nplanes(); ++p) any_parts = (fused[p] && plan_parts(c, p, plan[p])) || any_parts;
-    if (any_parts) {
-        bool to_pool = slot0 >= c->parts_slots || slot0 >= c->slots || !c->parts_rec;
-        if (c->cfg.mode == SN_MODE_AUTO && !sweeps_always(c) && 512 / n >= 3) to_pool = true;
-        if (!to_pool && c->parts_fallbacks) {
-            const int64_t seen = *c->parts_fallbacks;  // as of the last launch in parts that has finished
-            if (seen != c->parts_fallbacks_seen) {
-                c->parts_fallbacks_seen = seen;
-                c->parts_pause_next = c->parts_pause_next < 8 ? 8 : c->parts_pause_next < 1024 ? 2 * c->parts_pause_next : 1024;
-                c->parts_pause = c->parts_pause_next;
-                c->parts_good = 0;
-            } else if (c->parts_pause == 0 && ++c->parts_good >= 64) {
-                c->parts_pause_next = 0;
-            }
-            if (c->parts_pause > 0) {
-                --c->parts_pause;
-                to_pool = true;
-            }
-        }
-        if (to_pool) {
-            // the planes that only the parts can sweep go to the pool path; forced parts of a narrower plane to its whole-plane sweep
-            for (int p = 0; p < c->nplanes(); ++p) {
-                if (plan[p].n > 0 && c->plane_parts[p]) fused[p] = false;
-                plan[p].n = 0;
-            }
-            any_parts = false;
-        }
-    }
+    bool fused[3] = {false, false, false};  // the plane goes through the sweeps
+    PartsPlan plan[3];                       // ... in column parts where plan[p].n > 0
+    int stop[3] = {0, 0, 0};                 // where stage 2 of the pool path may stop (PoolArgs::rows)
+    int nbands = 0;                          // > 0: the launch is small enough for row bands
+    bool parts_counted = false;
+
     // sn_process_host's plane pipeline: a plane's kernels wait for its copy and announce their end; the paths that are
     // not written plane by plane wait for everything first (the caller records what was not announced)
-    auto plane_in = [&](int p) -> hipError_t {
+    hipError_t plane_in(int p) const
+    {
         if (!c->gate.on || c->gate.waited[p]) return hipSuccess;
         c->gate.waited[p] = true;
         return hipStreamWaitEvent(st, c->gate.arrived[p], 0);
-    };
-    auto plane_out = [&](int p) -> hipError_t {
+    }
+    hipError_t plane_out(int p) const
+    {
         if (!c->gate.on) return hipSuccess;
         c->gate.recorded[p] = true;
         return hipEventRecord(c->gate.done[p], st);
+    }
+    void count_parts()
+    {
+        if (!parts_counted) c->part_frames += n;
+        parts_counted = true;
+    }
+};
+
+// Column parts pause after a launch with a failed frame, as the bands do (band_count); under SN_SMALL_AUTO a launch small
+// enough for row bands goes where it went before the option existed.  True: this launch's cut planes go to the pool path.
+static bool parts_to_pool(Context* c, int slot0, int n)
+{
+    bool to_pool = slot0 >= c->parts_slots || slot0 >= c->slots || !c->parts_rec;
+    if (c->cfg.mode == SN_MODE_AUTO && !sweeps_always(c) && 512 / n >= 3) to_pool = true;
+    if (!to_pool && c->parts_fallbacks) {
+        const int64_t seen = *c->parts_fallbacks;  // as of the last launch in parts that has finished
+        if (seen != c->parts_fallbacks_seen) {
+            c->parts_fallbacks_seen = seen;
+            c->parts_pause_next = c->parts_pause_next < 8 ? 8 : c->parts_pause_next < 1024 ? 2 * c->parts_pause_next : 1024;
+            c->parts_pause = c->parts_pause_next;
+            c->parts_good = 0;
+        } else if (c->parts_pause == 0 && ++c->parts_good >= 64) {
+            c->parts_pause_next = 0;
+        }
+        if (c->parts_pause > 0) {
+            --c->parts_pause;
+            to_pool = true;
+        }
+    }
+    return to_pool;
+}
+
+// One plane in column parts: a sweep per window, the check of the seams, and the pool path for the frames that fail it
+// (guarded launches, a chunk of pool slots at a time, that exit at once otherwise).  No k_assemble: kept lines are right
+// either way.
+static int parts_plane(const GroupLaunch& g, int p, const sn::PlaneArgs& a0, sn::PoolArgs pool)
+{
+    Context* c = g.c;
+    const PartsPlan& pl = g.plan[p];
+    const int B = c->cfg.bytes_per_sample;
+    const int64_t side = sn::parts_side_bytes(B, a0.h_out / 2 - 1);
+    const int nseams = pl.n - 1;
+    if ((int64_t)nseams * 2 * side > c->parts_frame_bytes) return sn::fail(c, SN_ERR_UNSUPPORTED, "column parts: the seam record is too small for %d parts", pl.n);
+    const int cap = c->parts_slots - g.slot0, pcap = c->slots - g.slot0;
+    uint8_t* rec = c->parts_rec + (int64_t)g.slot0 * c->parts_frame_bytes;
+    int32_t* flags = c->parts_flags + g.slot0;
+    for (int i = 0; i < g.n; i += cap) {
+        const int m = g.n - i < cap ? g.n - i : cap;
+        const sn::PlaneArgs a = frames_from(a0, i);
+        SN_HIP(c, hipMemsetAsync(flags, 0, sizeof(int32_t) * m, g.st));
+        sn::FusedPool fp{};
+        fp.mode = sn::v3c::kParts;  // one launch, a workgroup per part and frame
+        fp.nparts = pl.n;
+        fp.win_w = pl.win_w;
+        for (int k = 0; k < pl.n; ++k) {
+            fp.win_x[k] = pl.win_x[k];
+            fp.store_lo[k] = pl.seam[k] - pl.win_x[k];
+            fp.store_hi[k] = pl.seam[k + 1] - pl.win_x[k];
+            fp.seam_x[k][0] = k > 0 ? pl.seam[k] - pl.win_x[k] : -1;
+            fp.seam_off[k][0] = k > 0 ? (int)((2 * (k - 1) + 1) * side) : 0;  // side 1 of the seam on its left
+            fp.seam_x[k][1] = k < pl.n - 1 ? pl.seam[k + 1] - pl.win_x[k] : -1;
+            fp.seam_off[k][1] = k < pl.n - 1 ? (int)(2 * k * side) : 0;      // side 0 of the seam on its right
+        }
+        fp.seam_rec = rec;
+        fp.seam_frame_stride = c->parts_frame_bytes;
+        fp.seam_bytes = (int)(nseams * 2 * side);
+        SN_HIP(c, sn::launch_sweep(g.st, B, a, c->threshold(p), m, &fp));
+        SN_HIP(c, sn::launch_parts_verify(g.st, rec, c->parts_frame_bytes, side, nseams, m, flags, c->parts_fallbacks_dev, c->parts_fallbacks));
+        for (int j = 0; j < m; j += pcap) {
+            sn::PlaneArgs r = frames_from(a, j);
+            r.guard = flags + j;
+            pool.guard = flags + j;
+            SN_HIP(c, sn::launch_pool_plane(g.st, r, pool, B, c->threshold(p), m - j < pcap ? m - j : pcap, g.slot0));
+        }
+    }
+    return SN_OK;
+}
+
+// The latency path of one plane: bands, their check, and the pool path for the frames that fail it (its launches
+// exit at once otherwise).
+static int banded_plane(const GroupLaunch& g, int p, sn::PlaneArgs a, sn::PoolArgs pool)
+{
+    Context* c = g.c;
+    const int B = c->cfg.bytes_per_sample;
+    sn::FusedPool fp{};
+    fp.mode = sn::v3c::kPlain;  // in bands
+    set_bands(c, fp, g.nbands, a.h_out / 2 - 1, g.slot0, true);
+    SN_HIP(c, sn::launch_sweep(g.st, B, a, c->threshold(p), g.n, &fp));
+    SN_HIP(c, sn::launch_band_verify(g.st, fp.band_state, 64 * sn::sweep_waves(B, a.w), fp.nbands, g.n, fp.band_flags, c->band_fallbacks_dev, c->band_fallbacks));
+    a.guard = fp.band_flags;
+    pool.guard = fp.band_flags;
+    // (no k_assemble: the kept lines the bands have copied are right whatever the check says)
+    SN_HIP(c, sn::launch_pool_plane(g.st, a, pool, B, c->threshold(p), g.n, g.slot0));
+    return SN_OK;
+}
+
+// Route: every plane in bands (the latency path) -- planes with pools of their own (isolated) or the shared pool.
+static int run_banded_planes(GroupLaunch& g)
+{
+    Context* c = g.c;
+    int rc = ensure_bands(c);
+    if (rc == SN_OK && !c->isolated) rc = ensure_pool(c);
+    if (rc != SN_OK) return rc;
+    for (int p = 0; p < c->nplanes(); ++p) {
+        SN_HIP(c, g.plane_in(p));
+        if (!g.pa[p].enabled) {
+            SN_HIP(c, sn::launch_assemble(g.st, g.pa[p], c->cfg.bytes_per_sample, g.n));
+            SN_HIP(c, g.plane_out(p));
+            continue;
+        }
+        if (c->isolated) {
+            rc = ensure_pool(c, p);
+            if (rc != SN_OK) return rc;
+            const sn::PoolArgs& pool = c->plane_pool[p];
+            if (c->fresh) SN_HIP(c, hipMemsetAsync(pool.base + (int64_t)g.slot0 * pool.slot_bytes, 0, (size_t)pool.slot_bytes * g.n, g.st));
+        }
+        rc = banded_plane(g, p, g.pa[p], c->isolated ? c->plane_pool[p] : c->pool);
+        if (rc != SN_OK) return rc;
+        SN_HIP(c, g.plane_out(p));
+    }
+    c->fused_frames += g.n;
+    c->banded_frames += g.n;
+    return SN_OK;
+}
+
+// Route: every plane on its own -- a whole-plane sweep (plain, padded or in column parts) or the pool path, over the
+// plane's own pool (isolated) or the shared one.
+static int run_planes(GroupLaunch& g)
+{
+    Context* c = g.c;
+    const int B = c->cfg.bytes_per_sample;
+    auto swept = [&](int p) { return g.fused[p] && (c->isolated ? c->plane_fused[p] : !c->fused420); };
+    auto pool_of = [&](int p) {
+        sn::PoolArgs pool = c->isolated ? c->plane_pool[p] : c->pool;
+        if (!c->isolated) pool.rows = g.stop[p];
+        return pool;
     };
-    if (nbands == 0)
-        for (int p = 0; p < c->nplanes(); ++p) SN_HIP(c, plane_in(p));
+    bool counted = false, shared_pool_path = false;
+    for (int p = 0; p < c->nplanes(); ++p) {
+        const sn::PlaneArgs& a = g.pa[p];
+        if (swept(p)) {
+            if (c->isolated && c->plane_padded[p]) {
+                // the sweep covers the whole pool stride: costs are zero outside the plane, the box filter clamps
+                // at the end of the stride (SangNom2.cpp:144-150)
+                sn::FusedPool fp{};
+                fp.mode = sn::v3c::kPadded;
+                fp.sweep_w = c->plane_pool[p].stride_e;
+                SN_HIP(c, sn::launch_sweep(g.st, B, a, c->threshold(p), g.n, &fp));
+            } else if (g.plan[p].n > 0) {
+                const int rc = parts_plane(g, p, a, pool_of(p));
+                if (rc != SN_OK) return rc;
+                g.count_parts();
+            } else {
+                SN_HIP(c, sn::launch_sweep(g.st, B, a, c->threshold(p), g.n, nullptr));
+            }
+            if (!counted) c->fused_frames += g.n;
+            counted = true;
+            continue;
+        }
+        SN_HIP(c, sn::launch_assemble(g.st, a, B, g.n));
+        if (!a.enabled) continue;
+        if (!c->isolated) {  // after the loop, chunk by chunk
+            shared_pool_path = true;
+            continue;
+        }
+        const int rc = ensure_pool(c, p);
+        if (rc != SN_OK) return rc;
+        const sn::PoolArgs pool = pool_of(p);
+        for (int i = 0; i < g.n; i += c->slots) {
+            const int m = g.n - i < c->slots ? g.n - i : c->slots;
+            if (c->fresh) SN_HIP(c, hipMemsetAsync(pool.base + (int64_t)g.slot0 * pool.slot_bytes, 0, (size_t)pool.slot_bytes * m, g.st));
+            SN_HIP(c, sn::launch_pool_plane(g.st, frames_from(a, i), pool, B, c->threshold(p), m, g.slot0));
+        }
+    }
+    if (!shared_pool_path) return SN_OK;
+    // Pool path, a chunk of frames at a time on the chunk's slots; within a chunk the planes run in the
+    // reference's order, because with subsampled chroma a frame's chroma result depends on what its own luma
+    // pass left in the slot (SangNom2.cpp:322-329).
+    const int rc = ensure_pool(c);
+    if (rc != SN_OK) return rc;
+    for (int i = 0; i < g.n; i += c->slots) {
+        const int m = g.n - i < c->slots ? g.n - i : c->slots;
+        for (int p = 0; p < c->nplanes(); ++p) {
+            if (!g.pa[p].enabled || swept(p)) continue;
+            SN_HIP(c, sn::launch_pool_plane(g.st, frames_from(g.pa[p], i), pool_of(p), B, c->threshold(p), m, g.slot0));
+        }
+    }
+    return SN_OK;
+}
+
+// Route: a small launch of a 4:2:0 clip.  The luma plane in bands, leaving its smoothed rows where the pool path's luma
+// pass would (the chroma sweeps of the coupling cannot be cut: sn_sweep_args.h); the luma plane of a frame that
+// fails the check is redone by the pool kernels; then the chroma planes by the pool kernels.
+static int run_coupled_banded(GroupLaunch& g)
+{
+    Context* c = g.c;
+    hipStream_t st = g.st;
+    const int n = g.n, slot0 = g.slot0;
+    const sn::PlaneArgs* pa = g.pa;
+    int rc = ensure_bands(c);
+    if (rc == SN_OK) rc = ensure_pool(c);
+    if (rc != SN_OK) return rc;
+    const int B = c->cfg.bytes_per_sample;
+    // Round 3: U and V as ONE chain of two passes per frame (k_smooth_*_chain; 8-bit: both in the same waves, V fifteen rows
+    // behind U) on ring slots 3 f (luma's smoothed rows), 3 f + 1 (U), 3 f + 2 (V), instead of two stage-2 launches one after
+    // the other: a 2160p YUV420P8 frame 0.617 -> 0.486 ms on the device, YUV420P16 0.73 -> 0.65.  Not for float samples: two
+    // float passes on one CU take longer than one after the other (0.94 -> 1.11 ms).
+    const bool chroma_chain = B != 4 && pa[1].enabled && pa[2].enabled && pa[1].w == pa[2].w && pa[1].h_out == pa[2].h_out && pa[1].w % 8 == 0 &&
+                              ensure_chroma_chains(c, slot0, n, st);
+    sn::PoolArgs ring = c->pool;
+    if (chroma_chain) {
+        ring.base = c->chain_base;
+        ring.guard = nullptr;
+        ring.rows = 0;
+        ring.slot_step = 3;
+        ring.slot_mod = c->chain_slots;
+    }
+    sn::FusedPool fp{};
+    fp.mode = sn::v3c::kLumaSpill;
+    fp.sweep_w = c->cfg.width;
+    fp.pool_out = chroma_chain ? c->chain_base + (int64_t)3 * slot0 * c->pool.slot_bytes : c->pool.base + (int64_t)slot0 * c->pool.slot_bytes;
+    fp.frame_stride = chroma_chain ? 3 * c->pool.slot_bytes : c->pool.slot_bytes;
+    fp.pool_rows = c->bh + 1;
+    fp.pool_row_bytes = c->stride_e * B;
+    fp.rows_out = g.stop[1] < c->bh - 1 ? g.stop[1] : c->bh - 1;  // what U's stage 2 reads: rows up to the one it stops at
+    fp.cone_nr = 1 << 20;  // every column is kept
+    set_bands(c, fp, g.nbands, pa[0].h_out / 2 - 1, slot0, true);
+    SN_HIP(c, g.plane_in(0));
+    SN_HIP(c, sn::launch_sweep(st, B, pa[0], c->threshold(0), n, &fp));
+    SN_HIP(c, sn::launch_band_verify(st, fp.band_state, band_threads(c), fp.nbands, n, fp.band_flags, c->band_fallbacks_dev, c->band_fallbacks));
+    sn::PlaneArgs a = pa[0];
+    a.guard = fp.band_flags;
+    sn::PoolArgs pool = chroma_chain ? ring : c->pool;
+    pool.guard = fp.band_flags;
+    pool.rows = g.stop[0];
+    SN_HIP(c, sn::launch_pool_plane(st, a, pool, B, c->threshold(0), n, chroma_chain ? 3 * slot0 : slot0));  // (kept lines: already copied by the bands)
+    SN_HIP(c, g.plane_out(0));
+    if (chroma_chain) {
+        sn::ChainArgs ch{};
+        ch.npass = 2;
+        ch.pn = 2;
+        ch.origin = 3 * slot0;
+        ch.rows = g.stop[1] > g.stop[2] ? g.stop[1] : g.stop[2];
+        ch.nchains = n;
+        ch.chain_step = 3;
+        for (int p = 1; p < 3; ++p) {
+            ch.w[p - 1] = pa[p].w;
+            ch.nr[p - 1] = pa[p].h_out / 2 - 1;
+            SN_HIP(c, g.plane_in(p));
+            SN_HIP(c, sn::launch_assemble(st, pa[p], B, n));
+            SN_HIP(c, sn::launch_pool_prepare(st, pa[p], ring, B, n, 3 * slot0 + p));
+        }
+        SN_HIP(c, sn::launch_pool_chain(st, ring, ch, B));
+        for (int p = 1; p < 3; ++p) {
+            SN_HIP(c, sn::launch_pool_finalize(st, pa[p], ring, B, c->threshold(p), n, 3 * slot0 + p));
+            SN_HIP(c, g.plane_out(p));
+        }
+    } else {
+        for (int p = 1; p < 3; ++p) {
+            pool = c->pool;
+            pool.rows = g.stop[p];
+            SN_HIP(c, g.plane_in(p));
+            SN_HIP(c, sn::launch_assemble(st, pa[p], B, n));
+            SN_HIP(c, sn::launch_pool_plane(st, pa[p], pool, B, c->threshold(p), n, slot0));
+            SN_HIP(c, g.plane_out(p));
+        }
+    }
+    c->fused_frames += n;  // (luma through the sweeps; banded_frames counts a subset of fused_frames, sangnom_hip.h)
+    c->banded_frames += n;
+    return SN_OK;
+}
+
+// Route: fused 4:2:0.  The luma sweep leaves its smoothed rows in hand-off pool 0, U reads pool 0 and leaves pool 1,
+// V reads pool 1 -- so the three sweeps of a chunk of frames run back to back on that chunk's pools.
+static int run_coupled(GroupLaunch& g)
+{
+    Context* c = g.c;
+    const int n = g.n, slot0 = g.slot0;
+    const sn::PlaneArgs* pa = g.pa;
+    const int nr_c = c->plane_h_out(1) / 2 - 1;
+    const int reach = c->fpool_rows - 1;
+    const int sweep_u = nr_c + 1 < c->bh - 1 ? nr_c + 1 : c->bh - 1;
+    // 8-bit: U and V as ONE sweep (sn_fused_u8_uv.hip) -- only the luma -> U hand-off goes through a pool
+    const bool one_chroma_sweep = c->uv_geometry && c->policy.chroma_sweeps == 0 && pa[1].enabled && pa[2].enabled && pa[1].h_in == pa[2].h_in;
+    if (!one_chroma_sweep) {
+        const int rc2 = ensure_fpool(c, 1);
+        if (rc2 != SN_OK) return rc2;
+    }
+    for (int i = 0; i < n; i += c->fslots) {
+        const int m = n - i < c->fslots ? n - i : c->fslots;
+        for (int p = 0; p < 3; ++p) {
+            sn::FusedPool fp{};
+            fp.sweep_w = c->cfg.width;
+            fp.frame_stride = c->fpool_frame_bytes;
+            fp.pool_rows = c->fpool_rows;
+            fp.cone_w = c->plane_w(1);  // the hand-off's dependency cone (sn_sweep_args.h, Args)
+            fp.cone_nr = nr_c;
+            fp.cone_in = p == 1 ? 6 : 0;
+            fp.cone_out = p == 0 ? 6 : 0;
+            if (p == 0) {
+                fp.mode = sn::v3c::kLumaSpill;
+                fp.pool_out = c->fpool[0] + (int64_t)slot0 * c->fpool_frame_bytes;
+                fp.rows_out = reach;
+            } else {
+                fp.mode = sn::v3c::kChroma;
+                fp.pool_in = c->fpool[p - 1] + (int64_t)slot0 * c->fpool_frame_bytes;
+                fp.pool_out = p == 1 ? c->fpool[1] + (int64_t)slot0 * c->fpool_frame_bytes : nullptr;
+                fp.rows_in = p == 1 ? reach : sweep_u;
+                fp.sweep_rows = p == 1 ? sweep_u : nr_c;
+                fp.rows_out = p == 1 ? sweep_u : 0;
+            }
+            const sn::PlaneArgs a = frames_from(pa[p], i);
+            if (p == 1 && one_chroma_sweep) {
+                SN_HIP(c, sn::launch_fused_u8_uv(g.st, a, frames_from(pa[2], i), c->threshold(1), c->threshold(2), m, fp));
+                break;
+            }
+            SN_HIP(c, sn::launch_sweep(g.st, c->cfg.bytes_per_sample, a, c->threshold(p), m, &fp));
+        }
+    }
+    if (one_chroma_sweep) c->uv_frames += n;
+    c->fused_frames += n;
+    return SN_OK;
+}
+
+// Runs frames [f0, f0 + n) of a strided batch with one common field offset.
+// `st` is the stream to launch on and `slot0` the first scratch slot the frames may use (the batch entry points
+// pass the context's stream and slot 0, the host ring one frame on its slot's stream and scratch).
+// Builds the planes' arguments, decides what each plane goes through, and hands the launch to ONE route (run_* above).
+static int run_group(Context* c, hipStream_t st, int slot0, int n, const void* const src[3], const int64_t sfs[3],
+                     const int32_t sp[3], void* const dst[3], const int64_t dfs[3], const int32_t dp[3], int f0, int offset)
+{
+    GroupLaunch g;
+    g.c = c;
+    g.st = st;
+    g.slot0 = slot0;
+    g.n = n;
+    for (int p = 0; p < c->nplanes(); ++p) {
+        g.pa[p] = plane_args(c, p, src, sfs, sp, dst, dfs, dp, f0, offset);
+        g.fused[p] = g.pa[p].enabled && (c->isolated ? c->plane_fused[p] : c->use_fused) && sn::fused_layout_ok(g.pa[p]);
+    }
+    bool all_fused = true;
+    for (int p = 0; p < c->nplanes(); ++p) all_fused = all_fused && (g.fused[p] || !g.pa[p].enabled);
+    g.nbands = all_fused ? band_count(c, n, slot0) : 0;
+    if (g.nbands == 0 && prefer_pool(c, n, slot0))
+        for (int p = 0; p < 3; ++p) g.fused[p] = false;
+    // Column parts: which planes of this launch are cut
+    bool any_parts = false;
+    for (int p = 0; p < c->nplanes(); ++p) any_parts = (g.fused[p] && plan_parts(c, p, g.plan[p])) || any_parts;
+    if (any_parts && parts_to_pool(c, slot0, n)) {
+        // the planes that only the parts can sweep go to the pool path; forced parts of a narrower plane to its whole-plane sweep
+        for (int p = 0; p < c->nplanes(); ++p) {
+            if (g.plan[p].n > 0 && c->plane_parts[p]) g.fused[p] = false;
+            g.plan[p].n = 0;
+        }
+    }
+    if (g.nbands == 0)
+        for (int p = 0; p < c->nplanes(); ++p) SN_HIP(c, g.plane_in(p));
     // The reference smooths the whole luma-sized pool in every pass (SangNom2.cpp:126-159).  A plane of fewer lines reads
     // back only rows 1 .. nr of it, and a later pass of this frame reads one row further than it smooths -- when nothing
     // is carried into the next frame, rows beyond that are never looked at again and stage 2 of the pool path stops
     // there (4:2:0: the two chroma passes take half the time).  SN_MODE_POOL keeps the full emulation, pool contents included.
-    int stop[3] = {0, 0, 0};
     if (c->history_free && c->cfg.mode != SN_MODE_POOL) {
         int later = 0;
         for (int p = c->nplanes() - 1; p >= 0; --p) {
-            if (!pa[p].enabled) continue;
-            const int own = pa[p].h_out / 2;  // rows 1 .. nr = own - 1
-            stop[p] = own > later + 1 ? own : later + 1;
-            later = stop[p];
+            if (!g.pa[p].enabled) continue;
+            const int own = g.pa[p].h_out / 2;  // rows 1 .. nr = own - 1
+            g.stop[p] = own > later + 1 ? own : later + 1;
+            later = g.stop[p];
         }
     }
-    auto frames_from = [](sn::PlaneArgs a, int i) {
-        a.src += (int64_t)i * a.src_frame_stride;
-        a.dst += (int64_t)i * a.dst_frame_stride;
-        return a;
-    };
-
-    auto launch_plain_fused = [&](const sn::PlaneArgs& a, int p, int m) -> hipError_t {
-        if (c->cfg.bytes_per_sample == 4) return sn::launch_fused_f32_v3(st, a, c->threshold(p), m, nullptr);
-        if (c->cfg.bytes_per_sample == 2) return sn::launch_fused_u16_v3(st, a, c->threshold(p), m, nullptr);
-        return sn::launch_fused_u8_v3(st, a, c->threshold(p), m, nullptr);
-    };
-
-    // One plane in column parts: a sweep per window, the check of the seams, and the pool path for the frames that fail it
-    // (guarded launches, a chunk of pool slots at a time, that exit at once otherwise).  No k_assemble: kept lines are right
-    // either way.
-    auto parts_plane = [&](int p, const sn::PlaneArgs& a0, sn::PoolArgs pool) -> int {
-        const PartsPlan& pl = plan[p];
-        const int B = c->cfg.bytes_per_sample;
-        const int64_t side = sn::parts_side_bytes(B, a0.h_out / 2 - 1);
-        const int nseams = pl.n - 1;
-        if ((int64_t)nseams * 2 * side > c->parts_frame_bytes) return sn::fail(c, SN_ERR_UNSUPPORTED, "column parts: the seam record is too small for %d parts", pl.n);
-        const int cap = c->parts_slots - slot0, pcap = c->slots - slot0;
-        uint8_t* rec = c->parts_rec + (int64_t)slot0 * c->parts_frame_bytes;
-        int32_t* flags = c->parts_flags + slot0;
-        for (int i = 0; i < n; i += cap) {
-            const int m = n - i < cap ? n - i : cap;
-            const sn::PlaneArgs a = frames_from(a0, i);
-            SN_HIP(c, hipMemsetAsync(flags, 0, sizeof(int32_t) * m, st));
-            sn::FusedPool fp{};
-            fp.mode = 5;  // kParts: one launch, a workgroup per part and frame
-            fp.nparts = pl.n;
-            fp.win_w = pl.win_w;
-            for (int k = 0; k < pl.n; ++k) {
-                fp.win_x[k] = pl.win_x[k];
-                fp.store_lo[k] = pl.seam[k] - pl.win_x[k];
-                fp.store_hi[k] = pl.seam[k + 1] - pl.win_x[k];
-                fp.seam_x[k][0] = k > 0 ? pl.seam[k] - pl.win_x[k] : -1;
-                fp.seam_off[k][0] = k > 0 ? (int)((2 * (k - 1) + 1) * side) : 0;  // side 1 of the seam on its left
-                fp.seam_x[k][1] = k < pl.n - 1 ? pl.seam[k + 1] - pl.win_x[k] : -1;
-                fp.seam_off[k][1] = k < pl.n - 1 ? (int)(2 * k * side) : 0;      // side 0 of the seam on its right
-            }
-            fp.seam_rec = rec;
-            fp.seam_frame_stride = c->parts_frame_bytes;
-            fp.seam_bytes = (int)(nseams * 2 * side);
-            if (B == 4) SN_HIP(c, sn::launch_fused_f32_v3(st, a, c->threshold(p), m, &fp));
-            else SN_HIP(c, sn::launch_fused_u16_v3(st, a, c->threshold(p), m, &fp));
-            SN_HIP(c, sn::launch_parts_verify(st, rec, c->parts_frame_bytes, side, nseams, m, flags, c->parts_fallbacks_dev, c->parts_fallbacks));
-            for (int j = 0; j < m; j += pcap) {
-                sn::PlaneArgs g = frames_from(a, j);
-                g.guard = flags + j;
-                pool.guard = flags + j;
-                SN_HIP(c, sn::launch_pool_plane(st, g, pool, B, c->threshold(p), m - j < pcap ? m - j : pcap, slot0));
-            }
-        }
-        return SN_OK;
-    };
-    bool parts_counted = false;
-    auto count_parts = [&]() {
-        if (!parts_counted) c->part_frames += n;
-        parts_counted = true;
-    };
-
-    // The latency path of one plane: bands, their check, and the pool path for the frames that fail it (its launches
-    // exit at once otherwise).
-    auto banded_plane = [&](int p, sn::PlaneArgs a, sn::PoolArgs pool) -> int {
-        sn::FusedPool fp{};
-        fp.mode = 0;  // kPlain, in bands
-        set_bands(c, fp, nbands, a.h_out / 2 - 1, slot0, true);
-        const int B = c->cfg.bytes_per_sample;
-        if (B == 4) SN_HIP(c, sn::launch_fused_f32_v3(st, a, c->threshold(p), n, &fp));
-        else if (B == 2) SN_HIP(c, sn::launch_fused_u16_v3(st, a, c->threshold(p), n, &fp));
-        else SN_HIP(c, sn::launch_fused_u8_v3(st, a, c->threshold(p), n, &fp));
-        const int threads = 64 * (B == 4 ? sn::fused_f32_waves(a.w) : B == 2 ? sn::fused_u16_waves(a.w) : sn::fused_v3_waves(a.w));
-        SN_HIP(c, sn::launch_band_verify(st, fp.band_state, threads, fp.nbands, n, fp.band_flags, c->band_fallbacks_dev, c->band_fallbacks));
-        a.guard = fp.band_flags;
-        pool.guard = fp.band_flags;
-        // (no k_assemble: the kept lines the bands have copied are right whatever the check says)
-        SN_HIP(c, sn::launch_pool_plane(st, a, pool, B, c->threshold(p), n, slot0));
-        return SN_OK;
-    };
-
-    if (c->isolated && nbands) {
-        int rc = ensure_bands(c);
-        if (rc != SN_OK) return rc;
-        for (int p = 0; p < c->nplanes(); ++p) {
-            SN_HIP(c, plane_in(p));
-            if (!pa[p].enabled) {
-                SN_HIP(c, sn::launch_assemble(st, pa[p], c->cfg.bytes_per_sample, n));
-                SN_HIP(c, plane_out(p));
-                continue;
-            }
-            rc = ensure_pool(c, p);
-            if (rc != SN_OK) return rc;
-            const sn::PoolArgs& pool = c->plane_pool[p];
-            if (c->fresh) SN_HIP(c, hipMemsetAsync(pool.base + (int64_t)slot0 * pool.slot_bytes, 0, (size_t)pool.slot_bytes * n, st));
-            rc = banded_plane(p, pa[p], pool);
-            if (rc != SN_OK) return rc;
-            SN_HIP(c, plane_out(p));
-        }
-        c->fused_frames += n;
-        c->banded_frames += n;
-        return SN_OK;
-    }
-
-    if (c->isolated) {  // every plane on its own: plain fused sweep or the pool path over the plane's own pool
-        bool counted = false;
-        for (int p = 0; p < c->nplanes(); ++p) {
-            const sn::PlaneArgs& a = pa[p];
-            if (fused[p] && c->plane_fused[p]) {
-                if (c->plane_padded[p]) {
-                    // the sweep covers the whole pool stride: costs are zero outside the plane, the box filter clamps
-                    // at the end of the stride (SangNom2.cpp:144-150)
-                    sn::FusedPool fp{};
-                    fp.mode = 3;  // kPadded
-                    fp.sweep_w = c->plane_pool[p].stride_e;
-                    fp.pool_rows = 1;
-                    fp.sweep_rows = a.h_out / 2 - 1;
-                    if (c->cfg.bytes_per_sample == 4) SN_HIP(c, sn::launch_fused_f32_v3(st, a, c->threshold(p), n, &fp));
-                    else if (c->cfg.bytes_per_sample == 2) SN_HIP(c, sn::launch_fused_u16_v3(st, a, c->threshold(p), n, &fp));
-                    else SN_HIP(c, sn::launch_fused_u8_v3(st, a, c->threshold(p), n, &fp));
-                } else if (plan[p].n > 0) {
-                    const int rc = parts_plane(p, a, c->plane_pool[p]);
-                    if (rc != SN_OK) return rc;
-                    count_parts();
-                } else {
-                    SN_HIP(c, launch_plain_fused(a, p, n));
-                }
-                if (!counted) c->fused_frames += n;
-                counted = true;
-                continue;
-            }
-            SN_HIP(c, sn::launch_assemble(st, a, c->cfg.bytes_per_sample, n));
-            if (!a.enabled) continue;
-            const int rc = ensure_pool(c, p);
-            if (rc != SN_OK) return rc;
-            const sn::PoolArgs& pool = c->plane_pool[p];
-            for (int i = 0; i < n; i += c->slots) {
-                const int m = n - i < c->slots ? n - i : c->slots;
-                if (c->fresh) SN_HIP(c, hipMemsetAsync(pool.base + (int64_t)slot0 * pool.slot_bytes, 0, (size_t)pool.slot_bytes * m, st));
-                SN_HIP(c, sn::launch_pool_plane(st, frames_from(a, i), pool, c->cfg.bytes_per_sample, c->threshold(p), m, slot0));
-            }
-        }
-        return SN_OK;
-    }
-
-    // Fused 4:2:0: the luma sweep leaves its smoothed rows in hand-off pool 0, U reads pool 0 and leaves pool 1,
-    // V reads pool 1 -- so the three sweeps of a chunk of frames run back to back on that chunk's pools.
-    const bool coupled = c->fused420 && fused[0] && fused[1] && fused[2];
-    if (coupled && nbands) {
-        // A small launch of a 4:2:0 clip: the luma plane in bands, leaving its smoothed rows where the pool path's luma
-        // pass would (the chroma sweeps of the coupling cannot be cut: sn_fused_v3_common.h); the luma plane of a
-        // frame that fails the check is redone by the pool kernels; then the chroma planes by the pool kernels.
-        int rc = ensure_bands(c);
-        if (rc == SN_OK) rc = ensure_pool(c);
-        if (rc != SN_OK) return rc;
-        const int B = c->cfg.bytes_per_sample;
-        // Round 3: U and V as ONE chain of two passes per frame (k_smooth_*_chain; 8-bit: both in the same waves, V fifteen rows
-        // behind U) on ring slots 3 f (luma's smoothed rows), 3 f + 1 (U), 3 f + 2 (V), instead of two stage-2 launches one after
-        // the other: a 2160p YUV420P8 frame 0.617 -> 0.486 ms on the device, YUV420P16 0.73 -> 0.65.  Not for float samples: two
-        // float passes on one CU take longer than one after the other (0.94 -> 1.11 ms).
-        const bool chroma_chain = c->cfg.bytes_per_sample != 4 && pa[1].enabled && pa[2].enabled && pa[1].w == pa[2].w && pa[1].h_out == pa[2].h_out && pa[1].w % 8 == 0 &&
-                                  ensure_chroma_chains(c, slot0, n, st);
-        sn::PoolArgs ring = c->pool;
-        if (chroma_chain) {
-            ring.base = c->chain_base;
-            ring.guard = nullptr;
-            ring.rows = 0;
-            ring.slot_step = 3;
-            ring.slot_mod = c->chain_slots;
-        }
-        sn::FusedPool fp{};
-        fp.mode = 1;  // kLumaSpill
-        fp.sweep_w = c->cfg.width;
-        fp.pool_out = chroma_chain ? c->chain_base + (int64_t)3 * slot0 * c->pool.slot_bytes : c->pool.base + (int64_t)slot0 * c->pool.slot_bytes;
-        fp.frame_stride = chroma_chain ? 3 * c->pool.slot_bytes : c->pool.slot_bytes;
-        fp.pool_rows = c->bh + 1;
-        fp.pool_row_bytes = c->stride_e * B;
-        fp.rows_out = stop[1] < c->bh - 1 ? stop[1] : c->bh - 1;  // what U's stage 2 reads: rows up to the one it stops at
-        fp.cone_nr = 1 << 20;  // every column is kept
-        set_bands(c, fp, nbands, pa[0].h_out / 2 - 1, slot0, true);
-        SN_HIP(c, plane_in(0));
-        if (B == 4) SN_HIP(c, sn::launch_fused_f32_v3(st, pa[0], c->threshold(0), n, &fp));
-        else if (B == 2) SN_HIP(c, sn::launch_fused_u16_v3(st, pa[0], c->threshold(0), n, &fp));
-        else SN_HIP(c, sn::launch_fused_u8_v3(st, pa[0], c->threshold(0), n, &fp));
-        SN_HIP(c, sn::launch_band_verify(st, fp.band_state, band_threads(c), fp.nbands, n, fp.band_flags, c->band_fallbacks_dev, c->band_fallbacks));
-        sn::PlaneArgs a = pa[0];
-        a.guard = fp.band_flags;
-        sn::PoolArgs pool = chroma_chain ? ring : c->pool;
-        pool.guard = fp.band_flags;
-        pool.rows = stop[0];
-        SN_HIP(c, sn::launch_pool_plane(st, a, pool, B, c->threshold(0), n, chroma_chain ? 3 * slot0 : slot0));  // (kept lines: already copied by the bands)
-        SN_HIP(c, plane_out(0));
-        if (chroma_chain) {
-            sn::ChainArgs ch{};
-            ch.npass = 2;
-            ch.pn = 2;
-            ch.origin = 3 * slot0;
-            ch.rows = stop[1] > stop[2] ? stop[1] : stop[2];
-            ch.nchains = n;
-            ch.chain_step = 3;
-            for (int p = 1; p < 3; ++p) {
-                ch.w[p - 1] = pa[p].w;
-                ch.nr[p - 1] = pa[p].h_out / 2 - 1;
-                SN_HIP(c, plane_in(p));
-                SN_HIP(c, sn::launch_assemble(st, pa[p], B, n));
-                SN_HIP(c, sn::launch_pool_prepare(st, pa[p], ring, B, n, 3 * slot0 + p));
-            }
-            SN_HIP(c, sn::launch_pool_chain(st, ring, ch, B));
-            for (int p = 1; p < 3; ++p) {
-                SN_HIP(c, sn::launch_pool_finalize(st, pa[p], ring, B, c->threshold(p), n, 3 * slot0 + p));
-                SN_HIP(c, plane_out(p));
-            }
-            c->fused_frames += n;
-            c->banded_frames += n;
-            return SN_OK;
-        }
-        for (int p = 1; p < 3; ++p) {
-            pool = c->pool;
-            pool.rows = stop[p];
-            SN_HIP(c, plane_in(p));
-            SN_HIP(c, sn::launch_assemble(st, pa[p], B, n));
-            SN_HIP(c, sn::launch_pool_plane(st, pa[p], pool, B, c->threshold(p), n, slot0));
-            SN_HIP(c, plane_out(p));
-        }
-        c->fused_frames += n;  // (luma through the sweeps; banded_frames counts a subset of fused_frames, sangnom_hip.h)
-        c->banded_frames += n;
-        return SN_OK;
-    }
-    if (coupled) {
-        const int nr_c = c->plane_h_out(1) / 2 - 1;
-        const int reach = c->fpool_rows - 1;
-        const int sweep_u = nr_c + 1 < c->bh - 1 ? nr_c + 1 : c->bh - 1;
-        // 8-bit: U and V as ONE sweep (sn_fused_u8_uv.hip) -- only the luma -> U hand-off goes through a pool
-        const bool one_chroma_sweep = c->uv_geometry && c->policy.chroma_sweeps == 0 && pa[1].enabled && pa[2].enabled && pa[1].h_in == pa[2].h_in;
-        if (!one_chroma_sweep) {
-            const int rc2 = ensure_fpool(c, 1);
-            if (rc2 != SN_OK) return rc2;
-        }
-        for (int i = 0; i < n; i += c->fslots) {
-            const int m = n - i < c->fslots ? n - i : c->fslots;
-            for (int p = 0; p < 3; ++p) {
-                sn::FusedPool fp{};
-                fp.sweep_w = c->cfg.width;
-                fp.frame_stride = c->fpool_frame_bytes;
-                fp.pool_rows = c->fpool_rows;
-                fp.cone_w = c->plane_w(1);  // the hand-off's dependency cone (sn_fused_v3_common.h, Args)
-                fp.cone_nr = nr_c;
-                fp.cone_in = p == 1 ? 6 : 0;
-                fp.cone_out = p == 0 ? 6 : 0;
-                if (p == 0) {
-                    fp.mode = 1;
-                    fp.pool_out = c->fpool[0] + (int64_t)slot0 * c->fpool_frame_bytes;
-                    fp.rows_out = reach;
-                } else {
-                    fp.mode = 2;
-                    fp.pool_in = c->fpool[p - 1] + (int64_t)slot0 * c->fpool_frame_bytes;
-                    fp.pool_out = p == 1 ? c->fpool[1] + (int64_t)slot0 * c->fpool_frame_bytes : nullptr;
-                    fp.rows_in = p == 1 ? reach : sweep_u;
-                    fp.sweep_rows = p == 1 ? sweep_u : nr_c;
-                    fp.rows_out = p == 1 ? sweep_u : 0;
-                }
-                const sn::PlaneArgs a = frames_from(pa[p], i);
-                if (p == 1 && one_chroma_sweep) {
-                    SN_HIP(c, sn::launch_fused_u8_uv(st, a, frames_from(pa[2], i), c->threshold(1), c->threshold(2), m, fp));
-                    break;
-                }
-                if (c->cfg.bytes_per_sample == 4) SN_HIP(c, sn::launch_fused_f32_v3(st, a, c->threshold(p), m, &fp));
-                else if (c->cfg.bytes_per_sample == 2) SN_HIP(c, sn::launch_fused_u16_v3(st, a, c->threshold(p), m, &fp));
-                else SN_HIP(c, sn::launch_fused_u8_v3(st, a, c->threshold(p), m, &fp));
-            }
-        }
-        if (one_chroma_sweep) c->uv_frames += n;
-        c->fused_frames += n;
-        return SN_OK;
-    }
-
-    if (nbands && !c->fused420) {
-        // the latency path: bands, their check, and the pool path for the frames that fail it (it exits at once otherwise)
-        int rc = ensure_bands(c);
-        if (rc == SN_OK) rc = ensure_pool(c);
-        if (rc != SN_OK) return rc;
-        for (int p = 0; p < c->nplanes(); ++p) {
-            sn::PlaneArgs a = pa[p];
-            SN_HIP(c, plane_in(p));
-            if (!a.enabled) {
-                SN_HIP(c, sn::launch_assemble(st, a, c->cfg.bytes_per_sample, n));
-                SN_HIP(c, plane_out(p));
-                continue;
-            }
-            rc = banded_plane(p, a, c->pool);
-            if (rc != SN_OK) return rc;
-            SN_HIP(c, plane_out(p));
-        }
-        c->fused_frames += n;
-        c->banded_frames += n;
-        return SN_OK;
-    }
-
-    bool counted = false, pool_path = false;
-    for (int p = 0; p < c->nplanes(); ++p) {
-        const sn::PlaneArgs& a = pa[p];
-        if (fused[p] && !c->fused420) {
-            if (plan[p].n > 0) {
-                sn::PoolArgs pool = c->pool;
-                pool.rows = stop[p];
-                const int rc = parts_plane(p, a, pool);
-                if (rc != SN_OK) return rc;
-                count_parts();
-            } else {
-                SN_HIP(c, launch_plain_fused(a, p, n));
-            }
-            if (!counted) c->fused_frames += n;
-            counted = true;
-            continue;
-        }
-        SN_HIP(c, sn::launch_assemble(st, a, c->cfg.bytes_per_sample, n));
-        pool_path = pool_path || a.enabled;
-    }
-    if (!pool_path) return SN_OK;
-    // Pool path, a chunk of frames at a time on the chunk's slots; within a chunk the planes run in the
-    // reference's order, because with subsampled chroma a frame's chroma result depends on what its own luma
-    // pass left in the slot (SangNom2.cpp:322-329).
-    int rc = ensure_pool(c);
-    if (rc != SN_OK) return rc;
-    for (int i = 0; i < n; i += c->slots) {
-        const int m = n - i < c->slots ? n - i : c->slots;
-        for (int p = 0; p < c->nplanes(); ++p) {
-            if (!pa[p].enabled || (fused[p] && !c->fused420)) continue;
-            sn::PoolArgs pool = c->pool;
-            pool.rows = stop[p];
-            SN_HIP(c, sn::launch_pool_plane(st, frames_from(pa[p], i), pool, c->cfg.bytes_per_sample, c->threshold(p), m, slot0));
-        }
-    }
-    return SN_OK;
+    if (c->isolated) return g.nbands ? run_banded_planes(g) : run_planes(g);
+    if (c->fused420 && g.fused[0] && g.fused[1] && g.fused[2]) return g.nbands ? run_coupled_banded(g) : run_coupled(g);
+    if (g.nbands && !c->fused420) return run_banded_planes(g);
+    return run_planes(g);
 }
 
 // History-carrying clips, two passes or more of one field offset (several frames, or one frame with two or three processed
@@ -1598,7 +1594,6 @@ static int ensure_chain(Context* c, int pn, hipStream_t st)
 // after wrong frames had been delivered.  Now every such launch is followed by its own guarded redo (run_chain): stage 1 of
 // all passes again and the chain on ONE workgroup per buffer, which waits for nobody; they exit at once unless the word is
 // up.  The count of redone launches travels to sn_info.chain_redone.
-static int chain_fault(Context*) { return SN_OK; }
 
 // Workgroups per buffer for a chain of npass passes.  A short chain -- a single frame's two or three passes, two frames --
 // stays on one workgroup, where a pass follows its predecessor without a trip through memory: 720x480 YUV420P8, one frame
@@ -1627,22 +1622,8 @@ static int run_chain(Context* c, hipStream_t st, int n, const void* const src[3]
             c->gate.waited[p] = true;
             SN_HIP(c, hipStreamWaitEvent(st, c->gate.arrived[p], 0));
         }
-        sn::PlaneArgs& a = pa[p];
-        a = sn::PlaneArgs{};
-        a.src = static_cast<const uint8_t*>(src[p]) + (int64_t)f0 * sfs[p];
-        a.dst = static_cast<uint8_t*>(dst[p]) + (int64_t)f0 * dfs[p];
-        a.src_frame_stride = sfs[p];
-        a.dst_frame_stride = dfs[p];
-        a.src_pitch = sp[p];
-        a.dst_pitch = dp[p];
-        a.w = c->plane_w(p);
-        a.h_in = c->plane_h_in(p);
-        a.h_out = c->plane_h_out(p);
-        a.offset = offset;
-        a.dh = c->cfg.dh;
-        a.enabled = (c->cfg.dh || c->process[p]) ? 1 : 0;
-        a.copied_elsewhere = (c->copies_elsewhere || (p > 0 && c->chroma_elsewhere)) ? 1 : 0;
-        SN_HIP(c, sn::launch_assemble(st, a, B, n));
+        pa[p] = plane_args(c, p, src, sfs, sp, dst, dfs, dp, f0, offset);
+        SN_HIP(c, sn::launch_assemble(st, pa[p], B, n));
     }
     sn::PoolArgs ring = c->pool;
     ring.base = c->chain_base;
@@ -1672,25 +1653,21 @@ static int run_chain(Context* c, hipStream_t st, int n, const void* const src[3]
             }
         }
         for (int k = 0; k < pn; ++k) {
-            sn::PlaneArgs a = pa[planes[k]];
-            a.src += (int64_t)i * a.src_frame_stride;
-            a.dst += (int64_t)i * a.dst_frame_stride;
+            sn::PlaneArgs a = frames_from(pa[planes[k]], i);
             ch.w[k] = a.w;
             ch.nr[k] = a.h_out / 2 - 1;
             SN_HIP(c, sn::launch_pool_prepare(st, a, ring, B, m, (c->chain_origin + 1 + k) % c->chain_slots));
         }
         SN_HIP(c, sn::launch_pool_chain(st, ring, ch, B));
         if (ch.groups > 1) {
-            // the guarded redo (see chain_fault): the costs again -- stage 2 has smoothed them in place -- and the chain on one
+            // the guarded redo (see the comment above chain_groups): the costs again -- stage 2 has smoothed them in place -- and the chain on one
             // workgroup per buffer; every cell a pass's slot holds is rewritten by one of the two, the slot the chain starts
             // from (the copy of the pool before this launch) is only ever read
             sn::PoolArgs guarded = ring;
             guarded.guard = reinterpret_cast<const int32_t*>(fault);
             guarded.guard_single = 1;
             for (int k = 0; k < pn; ++k) {
-                sn::PlaneArgs a = pa[planes[k]];
-                a.src += (int64_t)i * a.src_frame_stride;
-                a.dst += (int64_t)i * a.dst_frame_stride;
+                sn::PlaneArgs a = frames_from(pa[planes[k]], i);
                 a.guard = reinterpret_cast<const int32_t*>(fault);
                 a.guard_single = 1;
                 SN_HIP(c, sn::launch_pool_prepare(st, a, guarded, B, m, (c->chain_origin + 1 + k) % c->chain_slots));
@@ -1705,9 +1682,7 @@ static int run_chain(Context* c, hipStream_t st, int n, const void* const src[3]
             SN_HIP(c, sn::launch_chain_redo_count(st, fault, c->chain_flags + kChainRedoneWord, c->chain_status));
         }
         for (int k = 0; k < pn; ++k) {
-            sn::PlaneArgs a = pa[planes[k]];
-            a.src += (int64_t)i * a.src_frame_stride;
-            a.dst += (int64_t)i * a.dst_frame_stride;
+            sn::PlaneArgs a = frames_from(pa[planes[k]], i);
             SN_HIP(c, sn::launch_pool_finalize(st, a, ring, B, c->threshold(planes[k]), m, (c->chain_origin + 1 + k) % c->chain_slots));
         }
         c->chain_origin = (c->chain_origin + ch.npass) % c->chain_slots;
@@ -1725,7 +1700,6 @@ static int run_batch(Context* c, hipStream_t st, int slot0, int nframes, const v
 {
     int f = 0;
     int planes[3] = {0, 0, 0};
-    if (int rc = chain_fault(c)) return rc;
     const int pn = slot0 == 0 ? chain_planes(c, planes) : 0;
     while (f < nframes) {
         const int off = field_offset(c, parity ? parity[f] : 1);
@@ -2143,7 +2117,7 @@ int sn_process_host(sn_context* h, const void* const src[3], const int32_t sp[3]
     // stream that is never synchronised keeps its commands -- and with them the runtime's transient registration of the
     // caller's pageable planes -- alive after the call has returned and the caller has freed or recycled that memory.
     if (piped) SN_HIP(c, hipStreamSynchronize(g.in));
-    return chain_fault(c);
+    return SN_OK;
 }
 
 // ---- the host ring: SURVEY 8(f)-1, pipelining behind GetFrame --------------------------------------------
@@ -2364,7 +2338,6 @@ int sn_collect_host(sn_context* h, int32_t slot, void* const dst_arg[3], const i
         if (rc != SN_OK) return rc;
     }
     SN_HIP(c, hipEventSynchronize(c->ring[gi].done));
-    if (int rc = chain_fault(c)) return rc;
     Copier::Job jobs[3];
     int njobs = 0;
     for (int p = 0; p < c->nplanes(); ++p) {
@@ -2455,7 +2428,7 @@ int sn_synchronize(sn_context* h)
     SN_HIP(c, hipStreamSynchronize(c->stream));
     for (auto& g : c->ring)
         if (g.stream) SN_HIP(c, hipStreamSynchronize(g.stream));
-    return chain_fault(c);
+    return SN_OK;
 }
 
 void* sn_get_stream(sn_context* h)
@@ -2612,9 +2585,7 @@ int sn_debug_read_coupled_rows(sn_context* h, int32_t which, void* host_dst, siz
     SN_HIP(c, hipStreamSynchronize(c->stream));
     std::vector<uint32_t> raw((size_t)c->fpool_frame_bytes / 4);
     SN_HIP(c, hipMemcpy(raw.data(), c->fpool[which], (size_t)c->fpool_frame_bytes, hipMemcpyDeviceToHost));
-    if (c->cfg.bytes_per_sample == 4) sn::fused_f32_pool_unpack(raw.data(), c->cfg.width, c->fpool_rows, static_cast<float*>(host_dst));
-    else if (c->cfg.bytes_per_sample == 2) sn::fused_u16_pool_unpack(raw.data(), c->cfg.width, c->fpool_rows, static_cast<uint16_t*>(host_dst));
-    else sn::fused_v3_pool_unpack(raw.data(), c->cfg.width, c->fpool_rows, static_cast<uint8_t*>(host_dst));
+    sn::sweep_pool_unpack(c->cfg.bytes_per_sample, raw.data(), c->cfg.width, c->fpool_rows, host_dst);
     return SN_OK;
 }
 
@@ -3144,8 +3115,6 @@ static int aa_finish(sn_aa_context* a, sn_aa_context::Group& g, int k, void* con
     if (sl.state == Context::kStaged)  // its group is not full yet: run what is staged
         if (int rc = aa_launch(a, g)) return rc;
     SN_AA_HIP(hipEventSynchronize(g.done));
-    SN_AA_SN(a->first, chain_fault(reinterpret_cast<Context*>(a->first)));
-    SN_AA_SN(a->second, chain_fault(reinterpret_cast<Context*>(a->second)));
     Copier::Job jobs[3];
     int nj = 0;
     for (int p = 0; p < a->planes; ++p) {

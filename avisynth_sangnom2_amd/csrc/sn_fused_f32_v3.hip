@@ -26,8 +26,6 @@
 
 #include "sn_fused_v3_common.h"
 
-#include <cstring>
-
 namespace sn {
 namespace f32 {
 
@@ -957,113 +955,25 @@ static hipError_t launch_mode(hipStream_t st, const Args& a, float aaf, int nfra
 
 }  // namespace f32
 
-bool fused_f32_plane_ok(int w)
+static_assert(f32::kMaxWaves == v3c::kSweepF32.max_waves, "sn_sweep_args.h refuses what launch_mode has no case for");
+
+// (The kernels stand in the code object in the order of their first use here, and a kernel's speed has depended on where it
+// stands: csrc/Makefile on -falign-loops.  Hence plain sweeps first.)
+hipError_t launch_sweep_f32(hipStream_t st, const v3c::Sweep& s, float aaf)
 {
-    if (w % 32 != 0) return false;
-    return v3c::strips_for(w / v3c::PXL) <= f32::kMaxWaves;
-}
-
-int fused_f32_waves(int sweep_w) { return v3c::strips_for(sweep_w / v3c::PXL); }
-
-int64_t fused_f32_pool_bytes(int sweep_w, int rows) { return (int64_t)kBuffers * rows * fused_f32_waves(sweep_w) * 64 * 32; }
-
-// Slot of thread t = the O values of the 8 columns the lane owns (PoolIO::store); ghost lanes and lanes past the
-// sweep width own nothing.
-void fused_f32_pool_unpack(const uint32_t* raw, int sweep_w, int rows, float* out)
-{
-    using namespace v3c;
-    const int nl = sweep_w / PXL, nw = strips_for(nl), nt = nw * 64;
-    for (int64_t br = 0; br < (int64_t)kBuffers * rows; ++br)
-        for (int t = 0; t < nt; ++t) {
-            const int wave = t / 64, lane = t % 64;
-            const int gl = wave == 0 ? lane : kFirst + kInner * (wave - 1) + (lane - GH);
-            const bool ghost = wave == 0 ? (nw > 1 && lane >= 64 - GH) : (lane < GH || (lane >= 64 - GH && wave < nw - 1));
-            if (ghost || gl >= nl) continue;
-            std::memcpy(out + br * sweep_w + gl * PXL, raw + (br * nt + t) * 8, 8 * sizeof(float));
-        }
-}
-
-hipError_t launch_fused_f32_v3(hipStream_t st, const PlaneArgs& p, double threshold, int nframes, const FusedPool* pool)
-{
-    v3c::Args a{};
-    a.src = p.src;
-    a.dst = p.dst;
-    a.src_frame_stride = p.src_frame_stride;
-    a.dst_frame_stride = p.dst_frame_stride;
-    a.src_pitch = p.src_pitch;
-    a.dst_pitch = p.dst_pitch;
-    a.w = pool && pool->mode != v3c::kPlain ? pool->sweep_w : p.w;  // sweep_w: the pool stride a narrower plane is swept over
-    a.region_w = p.w;
-    a.nk = p.h_out / 2;
-    a.offset = p.offset;
-    a.dh = p.dh;
-    a.nl = a.w / v3c::PXL;
-    a.nvw = v3c::strips_for(a.nl);
-    a.nw = a.nvw;
-    a.turn_shift = v3c::turn_shift_for(a.nk, a.nw * v3c::group_of(a.nw), 4);
-    a.nframes = nframes;
-    a.src_bytes = (int)((int64_t)p.src_pitch * p.h_in);
-    a.dst_bytes = (int)((int64_t)p.dst_pitch * p.h_out);
-    const float aaf = (float)threshold;
-    if (!pool) return f32::launch_mode<v3c::kPlain>(st, a, aaf, nframes);
-    if (pool->mode == v3c::kParts) {  // a plane in column parts, all windows in one grid; never in row bands
-        if (pool->nbands > 1 || pool->nparts < 2 || pool->nparts > kMaxColumnParts || pool->win_w % 32 != 0 || !pool->seam_rec) return hipErrorInvalidValue;
-        a.w = a.region_w = pool->win_w;
-        a.nl = a.w / v3c::PXL;
-        a.nvw = a.nw = v3c::strips_for(a.nl);
-        if (a.nw > f32::kMaxWaves) return hipErrorInvalidValue;
-        a.turn_shift = v3c::turn_shift_for(a.nk, a.nw * v3c::group_of(a.nw), 4);
-        a.nparts = pool->nparts;
-        for (int k = 0; k < pool->nparts; ++k) {
-            // the window lies inside the plane, its own columns inside the window
-            if (pool->win_x[k] % v3c::PXL != 0 || pool->win_x[k] < 0 || pool->win_x[k] + pool->win_w > p.w || pool->store_lo[k] % v3c::PXL != 0 ||
-                pool->store_hi[k] % v3c::PXL != 0 || pool->store_lo[k] < 0 || pool->store_hi[k] > pool->win_w)
-                return hipErrorInvalidValue;
-            a.part_x[k] = pool->win_x[k];
-            a.part_store_lo[k] = pool->store_lo[k];
-            a.part_store_hi[k] = pool->store_hi[k];
-            for (int e = 0; e < 2; ++e) {
-                a.part_seam_x[k][e] = pool->seam_x[k][e];
-                a.part_seam_off[k][e] = pool->seam_off[k][e];
-                // both lanes next to a seam lie inside the window, and their rows inside the frame's record
-                if (a.part_seam_x[k][e] >= 0 && (a.part_seam_x[k][e] % v3c::PXL != 0 || a.part_seam_x[k][e] < v3c::PXL || a.part_seam_x[k][e] + v3c::PXL > a.w ||
-                                                 a.part_seam_off[k][e] < 0 || a.part_seam_off[k][e] + parts_side_bytes(4, a.nk - 1) > pool->seam_bytes))
-                    return hipErrorInvalidValue;
-            }
-        }
-        a.seam_rec = pool->seam_rec;
-        a.seam_frame_stride = pool->seam_frame_stride;
-        a.seam_bytes = pool->seam_bytes;
-        return f32::launch_mode<v3c::kParts>(st, a, aaf, nframes);
+    const v3c::Args& a = s.args;
+    if (s.mode == v3c::kPlain && !s.band) return f32::launch_mode<v3c::kPlain>(st, a, aaf, a.nframes);
+    switch (s.mode) {
+    case v3c::kParts: return f32::launch_mode<v3c::kParts>(st, a, aaf, a.nframes);
+    case v3c::kPlain: return f32::launch_mode<v3c::kPlain, true>(st, a, aaf, a.nframes);
+    case v3c::kPadded: return f32::launch_mode<v3c::kPadded>(st, a, aaf, a.nframes);
+    case v3c::kLumaSpill:
+        if (s.band) return f32::launch_mode<v3c::kLumaSpill, true>(st, a, aaf, a.nframes);
+        return f32::launch_mode<v3c::kLumaSpill>(st, a, aaf, a.nframes);
+    case v3c::kChromaLast: return f32::launch_mode<v3c::kChromaLast>(st, a, aaf, a.nframes);
+    case v3c::kChroma: return f32::launch_mode<v3c::kChroma>(st, a, aaf, a.nframes);
     }
-    if (pool->nbands > 1) {
-        a.band_rows = pool->band_rows;
-        a.band_warm = pool->band_warm;
-        a.nbands = pool->nbands;
-        a.band_state = pool->band_state;
-        a.band_flags = pool->band_flags;
-        a.band_reset = pool->band_reset;
-        if (pool->mode == v3c::kPlain) return f32::launch_mode<v3c::kPlain, true>(st, a, aaf, nframes);
-        if (pool->mode != v3c::kLumaSpill) return hipErrorInvalidValue;  // of the pool-coupled sweeps only the luma one is cut
-    }
-    if (pool->mode == v3c::kPlain) return f32::launch_mode<v3c::kPlain>(st, a, aaf, nframes);
-    if (pool->mode == v3c::kPadded) return f32::launch_mode<v3c::kPadded>(st, a, aaf, nframes);
-    a.pool_in = pool->pool_in;
-    a.pool_out = pool->pool_out;
-    a.pool_frame_stride = pool->frame_stride;
-    a.pool_rows = pool->pool_rows;
-    a.rows_in = pool->rows_in;
-    a.rows_out = pool->pool_out ? pool->rows_out : 0;
-    a.sweep_rows = pool->sweep_rows;
-    a.cone_w = pool->cone_w;
-    a.cone_nr = pool->cone_nr;
-    a.cone_in = pool->cone_in;
-    a.cone_out = pool->cone_out;
-    a.pool_row_bytes = pool->mode == v3c::kLumaSpill ? pool->pool_row_bytes : 0;
-    if (pool->mode == v3c::kLumaSpill && a.nbands > 1) return f32::launch_mode<v3c::kLumaSpill, true>(st, a, aaf, nframes);
-    if (pool->mode == v3c::kLumaSpill) return f32::launch_mode<v3c::kLumaSpill>(st, a, aaf, nframes);
-    if (!pool->pool_out) return f32::launch_mode<v3c::kChromaLast>(st, a, aaf, nframes);
-    return f32::launch_mode<v3c::kChroma>(st, a, aaf, nframes);
+    return hipErrorInvalidValue;
 }
 
 }  // namespace sn

@@ -1,4 +1,4 @@
-// sn_fused_select.hip -- which configurations the fused sweeps serve (host code only).
+// sn_fused_select.hip -- which configurations the fused sweeps serve, and the sweeps' one entry point (host code only).
 //
 // A configuration is eligible when every plane fits one workgroup (width a multiple of 32; up to 7680 columns for
 // 8-bit, 3840 for 16-bit and float samples) and either every processed plane is as large as the pool (no pass can
@@ -6,8 +6,9 @@
 // then the sweeps couple the passes through hand-off pools; without a luma pass the chroma passes
 // would see the previous FRAME's leftovers, which only the pool path reproduces.
 #include <stdint.h>
+#include <string.h>
 
-#include "sn_internal.h"
+#include "sn_sweep_args.h"
 
 namespace sn {
 
@@ -19,12 +20,57 @@ static bool chroma_subsampled_and_processed(const sn_config& c)
 
 bool fused_needs_pools(const sn_config& c) { return chroma_subsampled_and_processed(c); }
 
-bool fused_plane_eligible(int bytes_per_sample, int w)
+bool sweep_plane_ok(int bytes_per_sample, int w) { return w % 32 == 0 && sweep_waves(bytes_per_sample, w) <= v3c::sweep_traits(bytes_per_sample).max_waves; }
+
+int sweep_waves(int bytes_per_sample, int sweep_w)
 {
-    if (bytes_per_sample == 1) return fused_v3_plane_ok(w);
-    if (bytes_per_sample == 2) return fused_u16_plane_ok(w);
-    return fused_f32_plane_ok(w);
+    const int nvw = v3c::strips_for(sweep_w / v3c::PXL);
+    return v3c::sweep_traits(bytes_per_sample).packed ? (nvw + 1) / 2 : nvw;
 }
+
+// a slot per thread and pool row: the eight columns of each strip the thread holds (two for 8-bit samples)
+static int slot_bytes(const v3c::SweepTraits& t) { return (t.packed ? 2 : 1) * v3c::PXL * t.bytes; }
+
+int64_t sweep_pool_bytes(int bytes_per_sample, int sweep_w, int rows)
+{
+    return (int64_t)kBuffers * rows * sweep_waves(bytes_per_sample, sweep_w) * 64 * slot_bytes(v3c::sweep_traits(bytes_per_sample));
+}
+
+// A pool row is [strip kinds][threads][8 samples]: the eight columns the lane owns in its strip `wave` and, 8-bit only (kind 1,
+// the high halves of the registers), in its strip `wave + nw`, as the kernels' PoolIO::store leaves them.  Ghost lanes and lanes
+// past the sweep width own nothing; cells outside the dependency cone are never written: `out` keeps what the caller put there.
+void sweep_pool_unpack(int bytes_per_sample, const uint32_t* raw, int sweep_w, int rows, void* out)
+{
+    using namespace v3c;
+    const SweepTraits& t = sweep_traits(bytes_per_sample);
+    const int nl = sweep_w / PXL, nvw = strips_for(nl), nw = sweep_waves(bytes_per_sample, sweep_w), nt = nw * 64, cell = PXL * t.bytes;
+    const uint8_t* from = reinterpret_cast<const uint8_t*>(raw);
+    uint8_t* to = static_cast<uint8_t*>(out);
+    for (int64_t br = 0; br < (int64_t)kBuffers * rows; ++br)
+        for (int tid = 0; tid < nt; ++tid)
+            for (int h = 0; h < (t.packed ? 2 : 1); ++h) {
+                const int wave = tid / 64, lane = tid % 64, vw = wave + h * nw;
+                const int gl = vw == 0 ? lane : kFirst + kInner * (vw - 1) + (lane - GH);
+                const bool ghost = vw == 0 ? (nvw > 1 && lane >= 64 - GH) : (lane < GH || (lane >= 64 - GH && vw < nvw - 1));
+                if (vw >= nvw || ghost || gl >= nl) continue;
+                memcpy(to + (br * sweep_w + gl * PXL) * t.bytes, from + (br * nt * slot_bytes(t) + ((int64_t)h * nt + tid) * cell), cell);
+            }
+}
+
+hipError_t launch_sweep(hipStream_t st, int bytes_per_sample, const PlaneArgs& p, double threshold, int nframes, const FusedPool* pool)
+{
+#ifdef SN_EXPERIMENT_V4  // A/B builds of tools/experiments only
+    if (bytes_per_sample == 1 && !pool && fused_v4_plane_ok(p.w)) return launch_fused_u8_v4(st, p, threshold, nframes);
+#endif
+    v3c::Sweep s;
+    const hipError_t e = v3c::build_sweep(v3c::sweep_traits(bytes_per_sample), p, threshold, nframes, pool, s);
+    if (e != hipSuccess) return e;
+    if (bytes_per_sample == 4) return launch_sweep_f32(st, s, (float)threshold);
+    if (bytes_per_sample == 2) return launch_sweep_u16(st, s);
+    return launch_sweep_u8(st, s);
+}
+
+bool fused_plane_eligible(int bytes_per_sample, int w) { return sweep_plane_ok(bytes_per_sample, w); }
 
 bool fused_padded_plane_eligible(int bytes_per_sample, int w)
 {

@@ -719,7 +719,7 @@ hipError_t launch_fused_u8_uv(hipStream_t st, const PlaneArgs& pu, const PlaneAr
     a.pool_frame_stride = pool.frame_stride;
     a.pool_rows = pool.pool_rows;
     a.rows_in = pool.rows_in;
-    a.pool_threads = fused_v3_waves(pool.sweep_w) * 64;
+    a.pool_threads = sweep_waves(1, pool.sweep_w) * 64;
     a.sweep_u = pool.sweep_rows;
     a.nframes = nframes;
     if (a.sweep_u != a.nk && a.sweep_u != a.nk - 1) return hipErrorInvalidValue;  // nr_c + 1, or nr_c where the pool has no row below (4:2:2)

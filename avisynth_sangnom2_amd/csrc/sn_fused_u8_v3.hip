@@ -879,8 +879,6 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args 
     }
 }
 
-static int virtual_waves_for(int nl) { return strips_for(nl); }
-
 }  // namespace v3
 
 // This file is compiled twice (csrc/Makefile).  The sweeps of planes on their own (kPlain, kPadded) go into an object
@@ -920,118 +918,36 @@ extern "C" __attribute__((visibility("default"))) int sn_debug_row_cycles(unsign
     return 0;
 }
 #endif
+static_assert(v3::kMaxWaves == v3c::kSweepU8.max_waves, "sn_sweep_args.h refuses what launch_mode has no case for");
 #ifdef SN_TU_PLAIN
-hipError_t launch_fused_u8_v3_plain(hipStream_t st, const v3c::Args& a, int nframes, int mode)
+hipError_t launch_fused_u8_v3_plain(hipStream_t st, const v3c::Sweep& s)
 {
-    if (a.arith == SN_ARITH_SSE2) {  // the saturating instances (planes on their own are the sweeps that have them)
-        if (a.nbands > 1) return mode == v3::kPlain ? launch_mode<v3::kPlain, true, 1>(st, a, nframes) : hipErrorInvalidValue;
-        return mode == v3::kPadded ? launch_mode<v3::kPadded, false, 1>(st, a, nframes) : launch_mode<v3::kPlain, false, 1>(st, a, nframes);
+    const v3c::Args& a = s.args;
+    if (a.arith == SN_ARITH_SSE2) {  // the saturating instances
+        if (s.band) return launch_mode<v3::kPlain, true, 1>(st, a, a.nframes);
+        return s.mode == v3::kPadded ? launch_mode<v3::kPadded, false, 1>(st, a, a.nframes) : launch_mode<v3::kPlain, false, 1>(st, a, a.nframes);
     }
-    if (a.nbands > 1) return mode == v3::kPlain ? launch_mode<v3::kPlain, true>(st, a, nframes) : hipErrorInvalidValue;  // only planes on their own are cut
-    return mode == v3::kPadded ? launch_mode<v3::kPadded>(st, a, nframes) : launch_mode<v3::kPlain>(st, a, nframes);
+    if (s.band) return launch_mode<v3::kPlain, true>(st, a, a.nframes);
+    return s.mode == v3::kPadded ? launch_mode<v3::kPadded>(st, a, a.nframes) : launch_mode<v3::kPlain>(st, a, a.nframes);
 }
 #else
-
-bool fused_v3_plane_ok(int w)
-{
-    if (w % 32 != 0) return false;
-    return v3::virtual_waves_for(w / v3::PXL) <= 2 * v3::kMaxWaves;
-}
-
-int fused_v3_waves(int sweep_w) { return (v3::virtual_waves_for(sweep_w / v3::PXL) + 1) / 2; }
-
-// bytes of one scratch pool of one frame: [9][rows][threads][16]
-int64_t fused_v3_pool_bytes(int sweep_w, int rows) { return (int64_t)kBuffers * rows * fused_v3_waves(sweep_w) * 64 * 16; }
-
-// A pool row is [2 chunk kinds][threads][8 bytes]: kind 0 = the eight columns of the thread's strip in the low halves (strip
-// `wave`), kind 1 = those of its strip in the high halves (strip `wave + nw`), as PoolIO::store packs them.  Cells outside the dependency cone are
-// never written; `out` keeps what the caller put there.
-void fused_v3_pool_unpack(const uint32_t* raw, int sweep_w, int rows, uint8_t* out)
-{
-    using namespace v3c;
-    const int nl = sweep_w / PXL, nvw = v3::virtual_waves_for(nl), nw = (nvw + 1) / 2, nt = nw * 64;
-    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(raw);
-    for (int64_t br = 0; br < (int64_t)kBuffers * rows; ++br)
-        for (int t = 0; t < nt; ++t)
-            for (int h = 0; h < 2; ++h) {
-                const int wave = t / 64, lane = t % 64, vw = wave + h * nw;
-                const int gl = vw == 0 ? lane : kFirst + kInner * (vw - 1) + (lane - GH);
-                const bool ghost = vw == 0 ? (nvw > 1 && lane >= 64 - GH) : (lane < GH || (lane >= 64 - GH && vw < nvw - 1));
-                if (vw >= nvw || ghost || gl >= nl) continue;
-                const uint8_t* d = bytes + br * nt * 16 + (int64_t)h * nt * 8 + t * 8;
-                uint8_t* o = out + br * sweep_w + gl * PXL;
-                for (int k = 0; k < PXL; ++k) o[k] = d[k];
-            }
-}
 
 // The pool-coupled sweeps in the arithmetic ARITH (SN_ARITH_*).  What they take from a pool is a saturated O of the
 // previous pass (at most 255, like a cost), so the bounds next to box7 and box_sat hold with stale values in the sum.
 template <int ARITH>
-static hipError_t launch_coupled(hipStream_t st, const v3::Args& a, int nframes, const FusedPool& pool)
+static hipError_t launch_coupled(hipStream_t st, const v3c::Sweep& s)
 {
-    if (a.nbands > 1) {  // of the pool-coupled sweeps only the luma one is cut (sn_fused_v3_common.h)
-        if (pool.mode != v3::kLumaSpill) return hipErrorInvalidValue;
-        return launch_mode<v3::kLumaSpill, true, ARITH>(st, a, nframes);
-    }
-    if (pool.mode == v3::kLumaSpill) return launch_mode<v3::kLumaSpill, false, ARITH>(st, a, nframes);
-    if (!pool.pool_out) return launch_mode<v3::kChromaLast, false, ARITH>(st, a, nframes);
-    return launch_mode<v3::kChroma, false, ARITH>(st, a, nframes);
+    const v3c::Args& a = s.args;
+    if (s.band) return launch_mode<v3::kLumaSpill, true, ARITH>(st, a, a.nframes);
+    if (s.mode == v3::kLumaSpill) return launch_mode<v3::kLumaSpill, false, ARITH>(st, a, a.nframes);
+    if (s.mode == v3::kChromaLast) return launch_mode<v3::kChromaLast, false, ARITH>(st, a, a.nframes);
+    return launch_mode<v3::kChroma, false, ARITH>(st, a, a.nframes);
 }
 
-// pool == nullptr: a plane on its own (kPlain).  Otherwise pool->mode selects kLumaSpill / kChroma and
-// pool->sweep_w is the luma width the sweep covers (p describes the plane being interpolated).
-hipError_t launch_fused_u8_v3(hipStream_t st, const PlaneArgs& p, double threshold, int nframes, const FusedPool* pool)
+hipError_t launch_sweep_u8(hipStream_t st, const v3c::Sweep& s)
 {
-#ifdef SN_EXPERIMENT_V4  // A/B builds of tools/experiments only
-    if (!pool && fused_v4_plane_ok(p.w)) return launch_fused_u8_v4(st, p, threshold, nframes);
-#endif
-    v3::Args a{};
-    a.src = p.src;
-    a.dst = p.dst;
-    a.src_frame_stride = p.src_frame_stride;
-    a.dst_frame_stride = p.dst_frame_stride;
-    a.src_pitch = p.src_pitch;
-    a.dst_pitch = p.dst_pitch;
-    a.w = pool && pool->mode != v3::kPlain ? pool->sweep_w : p.w;
-    a.nk = p.h_out / 2;
-    a.offset = p.offset;
-    a.dh = p.dh;
-    a.thr = (int)threshold;
-    a.nl = a.w / v3::PXL;
-    a.nvw = v3::virtual_waves_for(a.nl);
-    a.nw = (a.nvw + 1) / 2;
-    a.src_bytes = (int)((int64_t)p.src_pitch * p.h_in);
-    a.dst_bytes = (int)((int64_t)p.dst_pitch * p.h_out);
-
-    a.turn_shift = v3c::turn_shift_for(a.nk, a.nw * v3c::group_of(a.nw), 1);
-    a.nframes = nframes;
-    a.arith = p.arith;
-    if (!pool) return launch_fused_u8_v3_plain(st, a, nframes, v3::kPlain);
-    if (pool->nbands > 1) {
-        a.band_rows = pool->band_rows;
-        a.band_warm = pool->band_warm;
-        a.nbands = pool->nbands;
-        a.band_state = pool->band_state;
-        a.band_flags = pool->band_flags;
-        a.band_reset = pool->band_reset;
-    }
-    if (pool->mode == v3::kPlain) return launch_fused_u8_v3_plain(st, a, nframes, v3::kPlain);
-    if (a.arith != SN_ARITH_CXX && a.arith != SN_ARITH_SSE2) return hipErrorInvalidValue;  // no instance: an error, never wrapping pixels
-    a.pool_in = pool->pool_in;
-    a.pool_out = pool->pool_out;
-    a.pool_frame_stride = pool->frame_stride;
-    a.pool_rows = pool->pool_rows;
-    a.rows_in = pool->rows_in;
-    a.rows_out = pool->pool_out ? pool->rows_out : 0;
-    a.region_w = p.w;
-    a.sweep_rows = pool->sweep_rows;
-    a.cone_w = pool->cone_w;
-    a.cone_nr = pool->cone_nr;
-    a.cone_in = pool->cone_in;
-    a.cone_out = pool->cone_out;
-    if (pool->mode == v3::kPadded) return launch_fused_u8_v3_plain(st, a, nframes, v3::kPadded);
-    a.pool_row_bytes = pool->mode == v3::kLumaSpill ? pool->pool_row_bytes : 0;
-    return a.arith == SN_ARITH_CXX ? launch_coupled<0>(st, a, nframes, *pool) : launch_coupled<1>(st, a, nframes, *pool);
+    if (!v3c::has_pools(s.mode)) return launch_fused_u8_v3_plain(st, s);  // kPlain, kPadded: the other object of this file
+    return s.args.arith == SN_ARITH_CXX ? launch_coupled<0>(st, s) : launch_coupled<1>(st, s);
 }
 
 #endif  // SN_TU_PLAIN

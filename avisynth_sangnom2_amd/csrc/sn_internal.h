@@ -105,27 +105,29 @@ bool fused_needs_pools(const sn_config& c);  // subsampled chroma: luma / chroma
 // 8-byte alignment of bases, pitches and frame strides, and pitch * (rows + kFusedRowSlack) <= INT32_MAX on both sides
 constexpr int kFusedRowSlack = 16;
 bool fused_layout_ok(const PlaneArgs& p);
-// sn_fused_u8_v3.hip: the 8-bit sweep, two virtual wavefronts packed into every register.
-bool fused_v3_plane_ok(int w);
-// Scratch-pool coupling between the luma sweep and the subsampled-chroma sweeps (sn_fused_u8_v3.hip, Mode).
+// The fused sweeps (sn_fused_u8_v3.hip: 8-bit, two virtual wavefronts packed into every register, up to 7680 wide;
+// sn_fused_u16_v3.hip: 9..16-bit and sn_fused_f32_v3.hip: float, one pixel per register, up to 3840 wide) behind one entry,
+// launch_sweep below.  FusedPool says which sweep a launch is (`mode`: a v3c::Mode of sn_sweep_args.h, which also holds
+// the one function that turns a PlaneArgs and a FusedPool into the kernels' arguments) and carries what that mode needs:
+// the scratch-pool coupling between the luma sweep and the subsampled-chroma sweeps, the row bands, the column parts.
 struct FusedPool {
-    int mode;                // 0 = plane on its own, 1 = luma sweep that leaves its smoothed rows, 2 = chroma sweep, 3 = padded plane (no pools),
-                             // 5 = one column part of a plane (the win_* / store_* / seam_* fields below)
+    int mode;                // v3c::kPlain = plane on its own, kLumaSpill = luma sweep that leaves its smoothed rows, kChroma = chroma sweep,
+                             // kPadded = padded plane (no pools), kParts = a plane in column parts (the win_* / store_* / seam_* fields below)
     int sweep_w;             // luma width (the pool's width)
     const uint8_t* pool_in;  // chroma: what the previous pass left
     uint8_t* pool_out;       // luma / first chroma pass: where this pass leaves its rows (may be null)
     int64_t frame_stride;    // bytes between the pools of consecutive frames
     int pool_rows;           // rows per pool buffer
-    int pool_row_bytes;      // > 0 (mode 1): pool_out is a pool of the pool path with this row pitch (Args::pool_row_bytes)
+    int pool_row_bytes;      // > 0 (kLumaSpill): pool_out is a pool of the pool path with this row pitch (Args::pool_row_bytes)
     int rows_in, rows_out;   // valid rows in pool_in / rows to write to pool_out
     int sweep_rows;          // chroma: pool rows to sweep
     int cone_w, cone_nr;     // the chroma plane's width and interpolated lines (dependency cone of the hand-off, Args)
     int cone_in, cone_out;   // extra columns: what this pass loads / stores beyond the final pass's cone
-    // nbands > 1: the sweep is cut into bands of rows (sn_fused_v3_common.h); to be verified by launch_band_verify
+    // nbands > 1: the sweep is cut into bands of rows (sn_sweep_args.h); to be verified by launch_band_verify
     int band_rows, band_warm, nbands, band_reset;
     uint32_t* band_state;    // nframes * band_state_words(threads, nbands) words
     int32_t* band_flags;     // one per frame
-    // mode 5 (column parts, sn_fused_v3_common.h): nparts windows [win_x[k], win_x[k] + win_w) of the plane, each swept as a
+    // kParts (column parts, sn_sweep_args.h): nparts windows [win_x[k], win_x[k] + win_w) of the plane, each swept as a
     // plane of its own by one launch; columns [store_lo[k], store_hi[k]) of the WINDOW are stored; seam_x[k][side] (window
     // columns, < 0: none) are the seams next to the window's inner edges and seam_off[k][side] where its half of each seam's
     // record starts in the frame's record
@@ -148,11 +150,14 @@ hipError_t launch_parts_verify(hipStream_t s, const uint8_t* rec, int64_t frame_
 inline int64_t band_state_words(int threads, int nbands) { return (int64_t)nbands * 2 * kBuffers * 8 * threads; }
 hipError_t launch_band_verify(hipStream_t s, const uint32_t* state, int threads, int nbands, int nframes, int32_t* flags, int64_t* fallbacks,
                               int64_t* host_mirror);
-int fused_v3_waves(int sweep_w);
-int64_t fused_v3_pool_bytes(int sweep_w, int rows);
-// host: scatter one scratch pool (thread-slot layout) into [9][rows][sweep_w] samples (test hook)
-void fused_v3_pool_unpack(const uint32_t* raw, int sweep_w, int rows, uint8_t* out);
-hipError_t launch_fused_u8_v3(hipStream_t s, const PlaneArgs& p, double threshold, int nframes, const FusedPool* pool);
+// sn_fused_select.hip: one sweep of `nframes` frames of plane p.  pool == nullptr: a plane on its own (kPlain); a launch the
+// kernels have no instance for is hipErrorInvalidValue (v3c::build_sweep)
+hipError_t launch_sweep(hipStream_t s, int bytes_per_sample, const PlaneArgs& p, double threshold, int nframes, const FusedPool* pool);
+bool sweep_plane_ok(int bytes_per_sample, int w);     // w within what one workgroup of the type's sweep takes (a multiple of 32)
+int sweep_waves(int bytes_per_sample, int sweep_w);   // waves of a workgroup that sweeps sweep_w columns
+int64_t sweep_pool_bytes(int bytes_per_sample, int sweep_w, int rows);  // one hand-off pool of one frame: [9][rows][threads] slots
+// host: scatter one hand-off pool (thread-slot layout) into [9][rows][sweep_w] samples (test hook)
+void sweep_pool_unpack(int bytes_per_sample, const uint32_t* raw, int sweep_w, int rows, void* out);
 // sn_fused_u8_uv.hip: the U and V passes of an 8-bit 4:2:0 frame as one sweep (U in the low halves of the registers, V in the
 // high halves two rows behind); `pool`: sweep_w, pool_in / frame_stride / pool_rows / rows_in = the luma sweep's hand-off
 // pool, sweep_rows = the U pass's last row.
@@ -163,17 +168,5 @@ bool fused_v4_plane_ok(int w);
 int fused_v4_waves(int w);
 hipError_t launch_fused_u8_v4(hipStream_t s, const PlaneArgs& p, double threshold, int nframes);
 #endif
-// sn_fused_u16_v3.hip: the same sweep for 9..16-bit samples (one pixel per register, up to 3840 wide).
-bool fused_u16_plane_ok(int w);
-// sn_fused_f32_v3.hip: the sweep for float samples.
-bool fused_f32_plane_ok(int w);
-int fused_f32_waves(int sweep_w);
-int64_t fused_f32_pool_bytes(int sweep_w, int rows);
-void fused_f32_pool_unpack(const uint32_t* raw, int sweep_w, int rows, float* out);
-hipError_t launch_fused_f32_v3(hipStream_t s, const PlaneArgs& p, double threshold, int nframes, const FusedPool* pool);
-int fused_u16_waves(int sweep_w);
-int64_t fused_u16_pool_bytes(int sweep_w, int rows);
-void fused_u16_pool_unpack(const uint32_t* raw, int sweep_w, int rows, uint16_t* out);
-hipError_t launch_fused_u16_v3(hipStream_t s, const PlaneArgs& p, double threshold, int nframes, const FusedPool* pool);
 
 }  // namespace sn

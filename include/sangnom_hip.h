@@ -282,7 +282,7 @@ int sn_collect_host(sn_context* ctx, int32_t slot, void* const dst[3], const int
  * EXPERIMENTAL on ROCm 7.2 / gfx950: a process that has registered and later UNREGISTERED host memory was seen to abort,
  * about once in twenty young processes, inside a LATER asynchronous copy from or to PAGEABLE memory -- the runtime's
  * own pin-on-the-fly path, torch's transfers included; never inside this library, which stages every pageable plane
- * through its own pinned buffers (profiles/r3_page_fault.md, tools/repro_pageable_after_unpin.py).  A host that uses
+ * through its own pinned buffers (profiles/r3_page_fault.md, tools/repro_pageable_after_unpin.sh).  A host that uses
  * these two entry points should (a) pin its frame arenas once and unpin them only at shutdown, and (b) keep its other
  * device transfers on pinned memory as well.  Without them nothing is registered and the hazard does not arise. */
 int sn_pin_host_buffer(void* ptr, size_t bytes);

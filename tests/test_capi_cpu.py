@@ -133,6 +133,21 @@ def test_header_is_plain_c_and_every_entry_point_links(tmp_path):
     assert r.returncode == 0 and "ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
 
 
+def test_sweep_arguments_are_built_once_for_every_sample_type(tmp_path):
+    """v3c::build_sweep (csrc/sn_sweep_args.h), the one place where a plane and its pool coupling become a sweep's kernel
+    arguments: tests/c/sweep_args_check.cpp checks the geometry, the fields every mode's kernel reads and every refusal
+    against values written out by hand.  A host compiler takes the header as it is -- no device code, no GPU."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    exe = str(tmp_path / "sweep_args_check")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(rocm, "include"),
+                           "-I", os.path.join(root, "include"), "-I", os.path.join(root, "avisynth_sangnom2_amd", "csrc"),
+                           os.path.join(root, "tests", "c", "sweep_args_check.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", (r.returncode, r.stdout[-3000:], r.stderr[-2000:])
+
+
 def test_chain_hand_off_between_workgroups_drains_its_stores_before_the_barrier():
     """Release side of the chains over several workgroups per buffer (sn_pool_kernels.hip, chain_release_barrier): in
     the gfx950 ISA of every k_smooth_*_chain<true> kernel an `s_waitcnt vmcnt(0)` stands in front of the round loop's

@@ -33,7 +33,7 @@ def to_host(t) -> np.ndarray:
     sn_pin_host_buffer / sn_unpin_host_buffer = hipHostRegister / hipHostUnregister) aborts now and then inside a LATER
     pageable copy of the HIP runtime, torch's included (about one fresh suite run in twenty; 0 in 44 with pinned
     transfers: profiles/r3_page_fault.md 6.).  The hazard stays visible outside the suite:
-    tools/repro_pageable_after_unpin.py runs exactly that sequence in young child processes, and
+    tools/repro_pageable_after_unpin.sh runs exactly that sequence in young child processes, and
     include/sangnom_hip.h marks the pin entry points accordingly."""
     import torch
     if not t.is_cuda:
