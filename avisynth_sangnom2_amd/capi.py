@@ -34,8 +34,9 @@ EXPORTS = (
     "sn_process_device_surfaces", "sn_aa_process_device_surfaces", "sn_get_surface_info", "sn_aa_get_surface_info",
 )
 
-# sn_surfaces.layout: planar Y, U, V or Y plus one plane of U,V pairs (NV12, P010 / P016, NV16, NV24)
-SN_LAYOUT_PLANAR, SN_LAYOUT_SEMIPLANAR = 0, 1
+# sn_surfaces.layout: planar Y, U, V or Y plus one plane of U,V pairs (NV12, P010 / P016, NV16, NV24); _MSB: 16-bit words
+# with the sample in the high bits (P010 on a 10-bit context, P012 on a 12-bit one)
+SN_LAYOUT_PLANAR, SN_LAYOUT_SEMIPLANAR, SN_LAYOUT_PLANAR_MSB, SN_LAYOUT_SEMIPLANAR_MSB = 0, 1, 2, 3
 
 # sn_options.arithmetic: which of the reference's two code paths a context reproduces (sangnom_hip.h)
 SN_ARITH_CXX, SN_ARITH_SSE2 = 0, 1
@@ -81,7 +82,8 @@ class SnSurfaceInfo(ctypes.Structure):
 
 
 def surfaces(layout: int, planes, pitches, frame_strides) -> "SnSurfaces":
-    """sn_surfaces from device pointers, pitches and frame strides in bytes (two entries for SN_LAYOUT_SEMIPLANAR: Y, UV)."""
+    """sn_surfaces from device pointers, pitches and frame strides in bytes (two entries for SN_LAYOUT_SEMIPLANAR and
+    SN_LAYOUT_SEMIPLANAR_MSB: Y, UV)."""
     s = SnSurfaces(struct_size=ctypes.sizeof(SnSurfaces), layout=int(layout))
     for p, (ptr, pitch, fs) in enumerate(zip(planes, pitches, frame_strides)):
         s.plane[p], s.pitch[p], s.frame_stride[p] = ptr, int(pitch), int(fs)

@@ -23,13 +23,15 @@ constexpr int kSyncChunks = 4;  // chunks of rows a pageable plane of the synchr
 namespace sn {
 
 // Planar chroma scratch of the surface calls (sn_process_device_surfaces, sn_aa_process_device_surfaces): U and V of `cap`
-// frames in the source's chroma geometry (a semi-planar source is split into it) and in the destination's (merged from it).
+// frames in the source's chroma geometry (a semi-planar source is split into it, the planes of an MSB-aligned one are shifted
+// into it) and in the destination's (merged from it); and, for an MSB-aligned source only, its luma shifted down.
 struct UvScratch {
     uint8_t* in[2] = {nullptr, nullptr};   // full height; a split writes the lines the pass keeps, the rest stays 0xA5
     uint8_t* out[2] = {nullptr, nullptr};  // full height, every line written by the pass
+    uint8_t* y = nullptr;                  // luma of an MSB-aligned source, LSB-aligned: as `in`
     int cap = 0;                           // frames (0: not allocated yet)
-    int pitch_in = 0, pitch_out = 0;
-    int64_t in_bytes = 0, out_bytes = 0;   // one frame of one plane
+    int pitch_in = 0, pitch_out = 0, pitch_y = 0;
+    int64_t in_bytes = 0, out_bytes = 0, y_bytes = 0;  // one frame of one plane
     int64_t bytes = 0;                     // all of it
     int64_t split_frames = 0, merged_frames = 0, copied_frames = 0;  // sn_surface_info
 };
@@ -52,6 +54,7 @@ struct Context {
     bool history_free = false;
     bool copies_elsewhere = false;  // a pass of sn_aa_*: planes that are not processed are copied by that call, once
     bool chroma_elsewhere = false;  // during a surface call: chroma that is not processed has gone from src to dst already
+    bool luma_elsewhere = false;    // ... with an MSB-aligned side: so has luma that is not processed
     bool use_fused = false;
     int arith = SN_ARITH_CXX;  // sn_options.arithmetic, fixed for the context's life
     // SN_ARITH_SSE2 on integer samples: the saturating instances of the pool kernels (float has one arithmetic)
@@ -368,7 +371,7 @@ void sn_destroy(sn_context* h)
         if (c->plane_pool[p].base) (void)hipFree(c->plane_pool[p].base);
     for (int i = 0; i < 2; ++i)
         if (c->fpool[i]) (void)hipFree(c->fpool[i]);
-    for (uint8_t* q : {c->uv.in[0], c->uv.in[1], c->uv.out[0], c->uv.out[1]})
+    for (uint8_t* q : {c->uv.in[0], c->uv.in[1], c->uv.out[0], c->uv.out[1], c->uv.y})
         if (q) (void)hipFree(q);
     if (c->gate.in) (void)hipStreamSynchronize(c->gate.in);
     if (c->gate.out) (void)hipStreamSynchronize(c->gate.out);
@@ -1099,7 +1102,7 @@ static sn::PlaneArgs plane_args(const Context* c, int p, const void* const src[3
     a.offset = offset;
     a.dh = c->cfg.dh;
     a.enabled = (c->cfg.dh || c->process[p]) ? 1 : 0;
-    a.copied_elsewhere = (c->copies_elsewhere || (p > 0 && c->chroma_elsewhere)) ? 1 : 0;
+    a.copied_elsewhere = (c->copies_elsewhere || (p > 0 ? c->chroma_elsewhere : c->luma_elsewhere)) ? 1 : 0;
     a.arith = c->saturating() ? SN_ARITH_SSE2 : SN_ARITH_CXX;  // (the sweeps; the pool kernels take PoolArgs::arith)
     return a;
 }
@@ -1747,18 +1750,19 @@ int sn_process_device(sn_context* h, const void* const src[3], const int32_t sp[
 }
 
 // -- decoder and encoder surfaces (sn_surfaces) -------------------------------------------------------------------------
-// What both surface calls share: the checks of a surface description, the chroma scratch, and the walk over a batch in chunks
-// of what the scratch holds -- split, the call's passes on planar chroma, merge.
+// What both surface calls share: the checks of a surface description, the scratch, and the walk over a batch in chunks of what
+// the scratch holds -- split (and shift down), the call's passes on planar LSB-aligned planes, merge (and shift up).
 
 struct SurfaceGeometry {  // of the call that walks: the batch call's clip, or the anti-aliasing call's (dh: output twice as wide and high)
-    int B = 1, planes = 1, max_batch = 1;
+    int B = 1, bits = 8, planes = 1, max_batch = 1;
     int w_in[3] = {0, 0, 0}, h_in[3] = {0, 0, 0}, w_out[3] = {0, 0, 0}, h_out[3] = {0, 0, 0};
-    bool chroma_processed = true;
-    bool all_lines = true;  // the passes read every line of the source's chroma (dh; the anti-aliasing call's turns)
+    bool luma_processed = true, chroma_processed = true;
+    bool all_lines = true;  // the passes read every line of the source's planes (dh; the anti-aliasing call's turns)
 };
 
 struct SurfaceSide {  // a checked sn_surfaces
     bool semi = false;
+    int shift = 0;  // SN_LAYOUT_*_MSB: 16 - bits_per_sample, the zero bits below every sample (0: the layout without _MSB)
     uint8_t* p[3] = {nullptr, nullptr, nullptr};
     int32_t pitch[3] = {0, 0, 0};
     int64_t fs[3] = {0, 0, 0};
@@ -1769,17 +1773,23 @@ static int surface_header(const char* name, const sn_surfaces* s, std::string& m
 {
     if (!s) return msg = std::string(name) + " is NULL", SN_ERR_INVALID_ARG;
     if (s->struct_size != (int32_t)sizeof(sn_surfaces)) return msg = std::string(name) + ": sn_surfaces.struct_size mismatch", SN_ERR_INVALID_ARG;
-    if (s->layout != SN_LAYOUT_PLANAR && s->layout != SN_LAYOUT_SEMIPLANAR)
-        return msg = std::string(name) + ": sn_surfaces.layout must be SN_LAYOUT_PLANAR or SN_LAYOUT_SEMIPLANAR", SN_ERR_INVALID_ARG;
+    if (s->layout < SN_LAYOUT_PLANAR || s->layout > SN_LAYOUT_SEMIPLANAR_MSB)
+        return msg = std::string(name) + ": sn_surfaces.layout must be SN_LAYOUT_PLANAR, SN_LAYOUT_SEMIPLANAR or one of their _MSB forms", SN_ERR_INVALID_ARG;
     if (s->reserved != 0) return msg = std::string(name) + ": sn_surfaces.reserved must be zero", SN_ERR_INVALID_ARG;
     return SN_OK;
 }
 
+static bool surface_plain(const sn_surfaces* s) { return s->layout == SN_LAYOUT_PLANAR; }
+
 // ... against the planes it has to hold: w[p] samples per row of plane p (the UV plane: 2 w[1])
-static int surface_side(const char* name, const sn_surfaces* s, const int w[3], int planes, int B, SurfaceSide& out, std::string& msg)
+static int surface_side(const char* name, const sn_surfaces* s, const int w[3], int planes, int B, int bits, SurfaceSide& out, std::string& msg)
 {
     const std::string n(name);
-    out.semi = s->layout == SN_LAYOUT_SEMIPLANAR;
+    const bool msb = s->layout == SN_LAYOUT_PLANAR_MSB || s->layout == SN_LAYOUT_SEMIPLANAR_MSB;
+    out.semi = s->layout == SN_LAYOUT_SEMIPLANAR || s->layout == SN_LAYOUT_SEMIPLANAR_MSB;
+    if (msb && B != 2)
+        return msg = n + ": sn_surfaces.layout SN_LAYOUT_*_MSB needs bytes_per_sample == 2 (the sample in the high bits of a 16-bit word)", SN_ERR_UNSUPPORTED;
+    out.shift = msb ? 16 - bits : 0;
     if (out.semi && planes < 3) return msg = n + ": SN_LAYOUT_SEMIPLANAR needs a context with num_planes == 3", SN_ERR_UNSUPPORTED;
     if (out.semi && B == 4) return msg = n + ": SN_LAYOUT_SEMIPLANAR with bytes_per_sample == 4: no such surface exists", SN_ERR_UNSUPPORTED;
     if (out.semi && s->plane[2]) return msg = n + ": sn_surfaces.plane[2] must be NULL with SN_LAYOUT_SEMIPLANAR (plane[1] is the UV plane)", SN_ERR_INVALID_ARG;
@@ -1799,32 +1809,65 @@ static int surface_side(const char* name, const sn_surfaces* s, const int w[3], 
     return SN_OK;
 }
 
-// The scratch, once: for min(max_batch, what a sixteenth of the budget holds, at least 1) frames (sangnom_hip.h).
-// Allocated before anything of the call is queued; the stream is drained so that whichever stream comes first finds it filled.
-static hipError_t surface_scratch(sn::UvScratch& S, hipStream_t st, const SurfaceGeometry& g, int64_t budget)
+// What a call needs of the scratch: the chroma planes (both geometries, as ever) when processed chroma passes through a
+// semi-planar side or comes from an MSB-aligned source; the luma plane when processed luma comes from an MSB-aligned source.
+struct SurfaceNeeds {
+    bool chroma = false, luma = false;
+};
+
+static SurfaceNeeds surface_needs(const SurfaceGeometry& g, const SurfaceSide& src, const SurfaceSide& dst)
 {
-    if (S.cap > 0) return hipSuccess;
+    SurfaceNeeds n;
+    n.chroma = g.planes >= 3 && g.chroma_processed && (src.semi || dst.semi || src.shift != 0);
+    n.luma = g.luma_processed && src.shift != 0;
+    return n;
+}
+
+static void surface_scratch_free(sn::UvScratch& S)
+{
+    for (uint8_t** q : {&S.in[0], &S.in[1], &S.out[0], &S.out[1], &S.y}) {
+        if (*q) (void)hipFree(*q);
+        *q = nullptr;
+    }
+    S.cap = 0;
+    S.bytes = 0;
+}
+
+// The scratch, once per part: for min(max_batch, what a sixteenth of the budget holds, at least 1) frames (sangnom_hip.h).
+// Allocated before anything of the call is queued; the stream is drained so that whichever stream comes first finds it filled.
+// A context that held one part and now needs the other as well gives the first back and takes both, so that the sum obeys
+// the rule; calls without an MSB-aligned source never ask for luma and allocate what they always did.
+static hipError_t surface_scratch(sn::UvScratch& S, hipStream_t st, const SurfaceGeometry& g, int64_t budget, SurfaceNeeds need)
+{
+    if ((!need.chroma || S.in[0]) && (!need.luma || S.y)) return hipSuccess;
+    need.chroma = need.chroma || S.in[0];
+    need.luma = need.luma || S.y;
+    hipError_t e = hipStreamSynchronize(st);  // (what an earlier call queued may still read the part that goes)
+    if (e != hipSuccess) return e;
+    surface_scratch_free(S);
     S.pitch_in = (g.w_in[1] * g.B + 255) & ~255;
     S.pitch_out = (g.w_out[1] * g.B + 255) & ~255;
+    S.pitch_y = (g.w_in[0] * g.B + 255) & ~255;
     S.in_bytes = (int64_t)S.pitch_in * g.h_in[1];
     S.out_bytes = (int64_t)S.pitch_out * g.h_out[1];
-    const int64_t per_frame = 2 * (S.in_bytes + S.out_bytes);
+    S.y_bytes = (int64_t)S.pitch_y * g.h_in[0];
+    const int64_t per_frame = (need.chroma ? 2 * (S.in_bytes + S.out_bytes) : 0) + (need.luma ? S.y_bytes : 0);
     const int64_t fit = budget / 16 / per_frame;
     const int cap = (int)(fit < 1 ? 1 : fit < g.max_batch ? fit : g.max_batch);
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+    for (int k = 0; k < 2 && need.chroma && e == hipSuccess; ++k) {
         e = hipMalloc(reinterpret_cast<void**>(&S.in[k]), (size_t)S.in_bytes * cap);
         // a split writes only the lines its pass keeps: a pass that read another line would read this pattern
         if (e == hipSuccess) e = hipMemsetAsync(S.in[k], 0xA5, (size_t)S.in_bytes * cap, st);
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&S.out[k]), (size_t)S.out_bytes * cap);
     }
+    if (need.luma && e == hipSuccess) {
+        e = hipMalloc(reinterpret_cast<void**>(&S.y), (size_t)S.y_bytes * cap);
+        if (e == hipSuccess) e = hipMemsetAsync(S.y, 0xA5, (size_t)S.y_bytes * cap, st);
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(st);
-        for (uint8_t** q : {&S.in[0], &S.in[1], &S.out[0], &S.out[1]}) {
-            if (*q) (void)hipFree(*q);
-            *q = nullptr;
-        }
+        surface_scratch_free(S);
         return e;
     }
     S.cap = cap;
@@ -1841,6 +1884,10 @@ struct SurfacePasses {  // the call's passes on planar planes: `m` frames, point
 
 // A HIP error of the walk itself comes back as SN_ERR_HIP with its text in msg; an error of the passes leaves msg empty (the
 // context holds the text).
+// MSB-aligned sides (shift ss of the source, ds of the destination): the passes see LSB-aligned planes.  The source's planes
+// go through scratch, shifted down on the way (chroma inside the split when it is semi-planar); the passes write LSB-aligned
+// samples into the destination's planes (or the chroma scratch a merge reads), which are then shifted up where they lie (inside
+// the merge for a UV plane).  A plane that is not processed goes from src to dst as (x >> ss) << ds, once, before the chunks.
 static int surface_walk(sn::UvScratch& S, hipStream_t st, const SurfaceGeometry& g, int n, const SurfaceSide& src, const SurfaceSide& dst,
                         const int32_t* parity, const SurfacePasses& passes, std::string& msg)
 {
@@ -1852,64 +1899,87 @@ static int surface_walk(sn::UvScratch& S, hipStream_t st, const SurfaceGeometry&
             return SN_ERR_HIP;                                               \
         }                                                                    \
     } while (0)
-    const int B = g.B;
+    const int B = g.B, ss = src.shift, ds = dst.shift;
+    const bool msb = ss != 0 || ds != 0, chroma = g.planes >= 3;
+    const SurfaceNeeds need = surface_needs(g, src, dst);
     const void* s[3];
     void* d[3];
     int64_t sfs[3], dfs[3];
     int32_t sp[3], dp[3];
-    if (!g.chroma_processed) {
+    if (chroma && !g.chroma_processed) {
         // never through a pass and never through scratch: one copy of the UV plane, or one conversion from src to dst
         const int cw = g.w_in[1], h = g.h_in[1];
-        if (src.semi && dst.semi) {
+        if (src.semi && dst.semi && !msb) {
             for (int f = 0; f < n; ++f)
                 SN_UV_HIP(hipMemcpy2DAsync(dst.p[1] + f * dst.fs[1], (size_t)dst.pitch[1], src.p[1] + f * src.fs[1], (size_t)src.pitch[1],
                                            (size_t)2 * cw * B, (size_t)h, hipMemcpyDeviceToDevice, st));
+        } else if (src.semi && dst.semi) {  // the UV plane as a plane of 2 cw samples (ss == ds: only the low bits go)
+            SN_UV_HIP(sn::launch_shift16(st, n, src.p[1], src.fs[1], src.pitch[1], 2 * cw, h, dst.p[1], dst.fs[1], dst.pitch[1], -1, ss, ds));
         } else if (src.semi) {
             SN_UV_HIP(sn::launch_uv_split(st, B, n, src.p[1], src.fs[1], src.pitch[1], cw, h, dst.p[1], dst.fs[1], dst.pitch[1], dst.p[2], dst.fs[2],
-                                          dst.pitch[2], -1));
-        } else {
+                                          dst.pitch[2], -1, ss, ds));
+        } else if (dst.semi) {
             SN_UV_HIP(sn::launch_uv_merge(st, B, n, src.p[1], src.fs[1], src.pitch[1], src.p[2], src.fs[2], src.pitch[2], cw, h, dst.p[1], dst.fs[1],
-                                          dst.pitch[1]));
+                                          dst.pitch[1], ss, ds));
+        } else {  // planar on both sides, one of them MSB-aligned
+            for (int p = 1; p < 3; ++p)
+                SN_UV_HIP(sn::launch_shift16(st, n, src.p[p], src.fs[p], src.pitch[p], cw, h, dst.p[p], dst.fs[p], dst.pitch[p], -1, ss, ds));
         }
         S.copied_frames += n;
-        for (int p = 0; p < 3; ++p) {  // the passes leave planes 1 and 2 alone: their pointers only have to be there
-            s[p] = src.p[0], sfs[p] = src.fs[0], sp[p] = src.pitch[0];
-            d[p] = dst.p[0], dfs[p] = dst.fs[0], dp[p] = dst.pitch[0];
-        }
-        return passes.run(passes.self, n, s, sfs, sp, d, dfs, dp, parity);
     }
-    for (int f0 = 0; f0 < n; f0 += S.cap) {
-        const int m = n - f0 < S.cap ? n - f0 : S.cap;
+    if (msb && !g.luma_processed)  // (the caller has told its passes: luma_elsewhere)
+        SN_UV_HIP(sn::launch_shift16(st, n, src.p[0], src.fs[0], src.pitch[0], g.w_in[0], g.h_in[0], dst.p[0], dst.fs[0], dst.pitch[0], -1, ss, ds));
+    const int cap = need.chroma || need.luma ? S.cap : n;
+    for (int f0 = 0; f0 < n; f0 += cap) {
+        const int m = n - f0 < cap ? n - f0 : cap;
         const int32_t* par = parity ? parity + f0 : nullptr;
         for (int p = 0; p < 3; ++p) {
-            const int q = src.semi && p == 2 ? 1 : p, r = dst.semi && p == 2 ? 1 : p;  // (placeholders, replaced below)
+            // planes the passes leave alone (a Y clip's chroma, chroma that is not processed), and the third of a semi-planar
+            // side until its scratch replaces it below: their pointers only have to be there
+            const bool real = p < g.planes && (p == 0 || g.chroma_processed);
+            const int q = !real ? 0 : src.semi && p == 2 ? 1 : p, r = !real ? 0 : dst.semi && p == 2 ? 1 : p;
             s[p] = src.p[q] + (int64_t)f0 * src.fs[q], sfs[p] = src.fs[q], sp[p] = src.pitch[q];
             d[p] = dst.p[r] + (int64_t)f0 * dst.fs[r], dfs[p] = dst.fs[r], dp[p] = dst.pitch[r];
         }
-        if (src.semi) {
-            const uint8_t* uv = src.p[1] + (int64_t)f0 * src.fs[1];
-            // the lines the pass keeps: one launch per run of frames with the same field offset, as run_batch cuts them
-            for (int g0 = 0; g0 < m;) {
-                int g1 = m, lines = -1;
-                if (!g.all_lines) {
-                    lines = passes.offset(passes.self, par ? par[g0] : 1);
-                    for (g1 = g0 + 1; g1 < m && passes.offset(passes.self, par ? par[g1] : 1) == lines;) ++g1;
-                }
-                SN_UV_HIP(sn::launch_uv_split(st, B, g1 - g0, uv + g0 * src.fs[1], src.fs[1], src.pitch[1], g.w_in[1], g.h_in[1], S.in[0] + g0 * S.in_bytes,
-                                              S.in_bytes, S.pitch_in, S.in[1] + g0 * S.in_bytes, S.in_bytes, S.pitch_in, lines));
-                g0 = g1;
+        // the lines the pass keeps: one launch per run of frames with the same field offset, as run_batch cuts them
+        for (int g0 = 0; g0 < m && (need.luma || (need.chroma && (src.semi || ss != 0)));) {
+            int g1 = m, lines = -1;
+            if (!g.all_lines) {
+                lines = passes.offset(passes.self, par ? par[g0] : 1);
+                for (g1 = g0 + 1; g1 < m && passes.offset(passes.self, par ? par[g1] : 1) == lines;) ++g1;
             }
-            for (int k = 0; k < 2; ++k) s[1 + k] = S.in[k], sfs[1 + k] = S.in_bytes, sp[1 + k] = S.pitch_in;
-            S.split_frames += m;
+            if (need.luma)
+                SN_UV_HIP(sn::launch_shift16(st, g1 - g0, src.p[0] + (f0 + g0) * src.fs[0], src.fs[0], src.pitch[0], g.w_in[0], g.h_in[0],
+                                             S.y + g0 * S.y_bytes, S.y_bytes, S.pitch_y, lines, ss, 0));
+            if (need.chroma && src.semi) {
+                SN_UV_HIP(sn::launch_uv_split(st, B, g1 - g0, src.p[1] + (f0 + g0) * src.fs[1], src.fs[1], src.pitch[1], g.w_in[1], g.h_in[1],
+                                              S.in[0] + g0 * S.in_bytes, S.in_bytes, S.pitch_in, S.in[1] + g0 * S.in_bytes, S.in_bytes, S.pitch_in, lines, ss, 0));
+            } else if (need.chroma && ss != 0) {
+                for (int k = 0; k < 2; ++k)
+                    SN_UV_HIP(sn::launch_shift16(st, g1 - g0, src.p[1 + k] + (f0 + g0) * src.fs[1 + k], src.fs[1 + k], src.pitch[1 + k], g.w_in[1], g.h_in[1],
+                                                 S.in[k] + g0 * S.in_bytes, S.in_bytes, S.pitch_in, lines, ss, 0));
+            }
+            g0 = g1;
         }
-        if (dst.semi)
+        if (need.luma) s[0] = S.y, sfs[0] = S.y_bytes, sp[0] = S.pitch_y;
+        if (need.chroma && (src.semi || ss != 0)) {
+            for (int k = 0; k < 2; ++k) s[1 + k] = S.in[k], sfs[1 + k] = S.in_bytes, sp[1 + k] = S.pitch_in;
+            if (src.semi) S.split_frames += m;
+        }
+        if (need.chroma && dst.semi)
             for (int k = 0; k < 2; ++k) d[1 + k] = S.out[k], dfs[1 + k] = S.out_bytes, dp[1 + k] = S.pitch_out;
         const int rc = passes.run(passes.self, m, s, sfs, sp, d, dfs, dp, par);
         if (rc != SN_OK) return rc;
-        if (dst.semi) {
+        if (need.chroma && dst.semi) {
             SN_UV_HIP(sn::launch_uv_merge(st, B, m, S.out[0], S.out_bytes, S.pitch_out, S.out[1], S.out_bytes, S.pitch_out, g.w_out[1], g.h_out[1],
-                                          dst.p[1] + (int64_t)f0 * dst.fs[1], dst.fs[1], dst.pitch[1]));
+                                          dst.p[1] + (int64_t)f0 * dst.fs[1], dst.fs[1], dst.pitch[1], 0, ds));
             S.merged_frames += m;
+        }
+        // the planes the passes wrote straight into an MSB-aligned destination: shifted up where they lie
+        for (int p = 0; p < g.planes && p < 3 && ds != 0; ++p) {
+            if (p == 0 ? !g.luma_processed : (!g.chroma_processed || dst.semi)) continue;
+            uint8_t* const q = dst.p[p] + (int64_t)f0 * dst.fs[p];
+            SN_UV_HIP(sn::launch_shift16(st, m, q, dst.fs[p], dst.pitch[p], g.w_out[p], g.h_out[p], q, dst.fs[p], dst.pitch[p], -1, 0, ds));
         }
     }
     return SN_OK;
@@ -1949,26 +2019,30 @@ int sn_process_device_surfaces(sn_context* h, int32_t nframes, const sn_surfaces
     int rc = surface_header("src", src, msg);
     if (rc == SN_OK) rc = surface_header("dst", dst, msg);
     if (rc != SN_OK) return sn::fail(c, rc, "%s", msg.c_str());
-    if (src->layout == SN_LAYOUT_PLANAR && dst->layout == SN_LAYOUT_PLANAR)  // the planar call itself
+    if (surface_plain(src) && surface_plain(dst))  // the planar call itself
         return sn_process_device_strided(h, nframes, src->plane, src->frame_stride, src->pitch, dst->plane, dst->frame_stride, dst->pitch, parity);
     if (nframes < 0 || nframes > c->cfg.max_batch)
         return sn::fail(c, SN_ERR_INVALID_ARG, "nframes %d outside 0..max_batch (%d)", nframes, c->cfg.max_batch);
     SurfaceGeometry g;
     g.B = c->cfg.bytes_per_sample;
+    g.bits = c->cfg.bits_per_sample;
     g.planes = c->nplanes();
     g.max_batch = c->cfg.max_batch;
     for (int p = 0; p < g.planes; ++p) g.w_in[p] = g.w_out[p] = c->plane_w(p), g.h_in[p] = c->plane_h_in(p), g.h_out[p] = c->plane_h_out(p);
+    g.luma_processed = c->cfg.dh || c->process[0];
     g.chroma_processed = c->cfg.dh || c->process[1];
     g.all_lines = c->cfg.dh != 0;
     SurfaceSide ss, ds;
-    rc = surface_side("src", src, g.w_in, g.planes, g.B, ss, msg);
-    if (rc == SN_OK) rc = surface_side("dst", dst, g.w_out, g.planes, g.B, ds, msg);
+    rc = surface_side("src", src, g.w_in, g.planes, g.B, g.bits, ss, msg);
+    if (rc == SN_OK) rc = surface_side("dst", dst, g.w_out, g.planes, g.B, g.bits, ds, msg);
     if (rc != SN_OK) return sn::fail(c, rc, "%s", msg.c_str());
     if (nframes == 0) return SN_OK;
     SN_HIP(c, hipSetDevice(c->device));
-    if (g.chroma_processed) SN_HIP(c, surface_scratch(c->uv, c->stream, g, scratch_budget(c)));
+    SN_HIP(c, surface_scratch(c->uv, c->stream, g, scratch_budget(c), surface_needs(g, ss, ds)));
     const SurfacePasses passes{c, sn_surface_run, sn_surface_offset};
+    c->luma_elsewhere = (ss.shift != 0 || ds.shift != 0) && !g.luma_processed;
     rc = surface_walk(c->uv, c->stream, g, nframes, ss, ds, parity, passes, msg);
+    c->luma_elsewhere = false;
     if (rc != SN_OK && !msg.empty()) return sn::fail(c, rc, "%s", msg.c_str());
     return rc;
 }
@@ -2641,6 +2715,7 @@ struct sn_aa_context {
     };
     std::vector<Group> groups;  // [0, ring_groups): the ring; [ring_groups]: the synchronous call's
     sn::UvScratch uv;           // sn_aa_process_device_surfaces
+    bool luma_elsewhere = false;  // ... with an MSB-aligned side: luma that is not processed has gone from src to dst already
     int depth = 0, per_group = 1, ring_groups = 0, ring_next = 0;
     bool ring_ready = false;
     Copier* copier = nullptr;  // the first context's
@@ -2721,7 +2796,7 @@ void sn_aa_destroy(sn_aa_context* a)
     for (int p = 0; p < 3; ++p)
         for (uint8_t* q : {a->d_t1[p], a->d_u1[p], a->d_t2[p]})
             if (q) (void)hipFree(q);
-    for (uint8_t* q : {a->uv.in[0], a->uv.in[1], a->uv.out[0], a->uv.out[1]})
+    for (uint8_t* q : {a->uv.in[0], a->uv.in[1], a->uv.out[0], a->uv.out[1], a->uv.y})
         if (q) (void)hipFree(q);
     for (auto& g : a->groups) aa_free_group(g);
     for (hipStream_t st : {a->up, a->down})
@@ -2889,7 +2964,7 @@ static int aa_surface_run(void* self, int m, const void* const s[3], const int64
                           const int32_t dp[3], const int32_t* parity)
 {
     sn_aa_context* a = static_cast<sn_aa_context*>(self);
-    if (!a->process[0])  // luma that is not processed: source to destination, once (chroma: surface_walk)
+    if (!a->process[0] && !a->luma_elsewhere)  // luma that is not processed: source to destination, once (chroma: surface_walk)
         for (int f = 0; f < m; ++f)
             SN_AA_HIP(hipMemcpy2DAsync(static_cast<uint8_t*>(d[0]) + f * dfs[0], (size_t)dp[0], static_cast<const uint8_t*>(s[0]) + f * sfs[0],
                                        (size_t)sp[0], (size_t)a->w[0] * a->cfg.bytes_per_sample, a->h[0], hipMemcpyDeviceToDevice, a->stream));
@@ -2903,26 +2978,30 @@ int sn_aa_process_device_surfaces(sn_aa_context* a, int32_t nframes, const sn_su
     int rc = surface_header("src", src, msg);
     if (rc == SN_OK) rc = surface_header("dst", dst, msg);
     if (rc != SN_OK) return aa_fail(a, rc, msg);
-    if (src->layout == SN_LAYOUT_PLANAR && dst->layout == SN_LAYOUT_PLANAR)  // the planar call itself
+    if (surface_plain(src) && surface_plain(dst))  // the planar call itself
         return sn_aa_process_device_strided(a, nframes, src->plane, src->frame_stride, src->pitch, dst->plane, dst->frame_stride, dst->pitch, parity);
     if (nframes < 0 || nframes > a->max_batch)
         return aa_fail(a, SN_ERR_INVALID_ARG, "nframes " + std::to_string(nframes) + " outside 0..max_batch (" + std::to_string(a->max_batch) + ")");
     SurfaceGeometry g;
     g.B = a->cfg.bytes_per_sample;
+    g.bits = a->cfg.bits_per_sample;
     g.planes = a->planes;
     g.max_batch = a->max_batch;
     for (int p = 0; p < g.planes; ++p) g.w_in[p] = a->w[p], g.h_in[p] = a->h[p], g.w_out[p] = a->ow[p], g.h_out[p] = a->oh[p];
+    g.luma_processed = a->process[0];
     g.chroma_processed = g.planes < 3 || a->process[1];
     g.all_lines = true;  // a turn reads whole source rows, whichever destination lines it writes
     SurfaceSide ss, ds;
-    rc = surface_side("src", src, g.w_in, g.planes, g.B, ss, msg);
-    if (rc == SN_OK) rc = surface_side("dst", dst, g.w_out, g.planes, g.B, ds, msg);
+    rc = surface_side("src", src, g.w_in, g.planes, g.B, g.bits, ss, msg);
+    if (rc == SN_OK) rc = surface_side("dst", dst, g.w_out, g.planes, g.B, g.bits, ds, msg);
     if (rc != SN_OK) return aa_fail(a, rc, msg);
     if (nframes == 0) return SN_OK;
     SN_AA_HIP(hipSetDevice(a->cfg.device));
-    if (g.chroma_processed) SN_AA_HIP(surface_scratch(a->uv, a->stream, g, scratch_budget(reinterpret_cast<Context*>(a->first))));
+    SN_AA_HIP(surface_scratch(a->uv, a->stream, g, scratch_budget(reinterpret_cast<Context*>(a->first)), surface_needs(g, ss, ds)));
     const SurfacePasses passes{a, aa_surface_run, nullptr};
+    a->luma_elsewhere = (ss.shift != 0 || ds.shift != 0) && !g.luma_processed;
     rc = surface_walk(a->uv, a->stream, g, nframes, ss, ds, parity, passes, msg);
+    a->luma_elsewhere = false;
     if (rc != SN_OK && !msg.empty()) return aa_fail(a, rc, msg);
     return rc;
 }

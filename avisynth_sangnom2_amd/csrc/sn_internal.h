@@ -74,10 +74,15 @@ hipError_t launch_turn(hipStream_t s, int bytes, int right, int nframes, const u
 // sn_uv.hip: semi-planar chroma (a UV plane of U,V sample pairs: NV12 / P016 / NV16 / NV24) <-> a U and a V plane of cw x h
 // samples each.  line_parity 0 / 1: only the lines of that parity are read and written (the lines the pass that follows
 // keeps), < 0: all of them.  One side is never written: split reads uv, merge reads u and v.
+// ss / ds (16-bit samples only): every sample goes through (x >> ss) << ds on its way (MSB-aligned sides: P010 / P012).
 hipError_t launch_uv_split(hipStream_t s, int bytes, int nframes, const uint8_t* uv, int64_t uv_frame_stride, int uv_pitch, int cw, int h,
-                           uint8_t* u, int64_t u_frame_stride, int u_pitch, uint8_t* v, int64_t v_frame_stride, int v_pitch, int line_parity = -1);
+                           uint8_t* u, int64_t u_frame_stride, int u_pitch, uint8_t* v, int64_t v_frame_stride, int v_pitch, int line_parity = -1,
+                           int ss = 0, int ds = 0);
 hipError_t launch_uv_merge(hipStream_t s, int bytes, int nframes, const uint8_t* u, int64_t u_frame_stride, int u_pitch, const uint8_t* v,
-                           int64_t v_frame_stride, int v_pitch, int cw, int h, uint8_t* uv, int64_t uv_frame_stride, int uv_pitch);
+                           int64_t v_frame_stride, int v_pitch, int cw, int h, uint8_t* uv, int64_t uv_frame_stride, int uv_pitch, int ss = 0, int ds = 0);
+// ... and one plane of w x h 16-bit words on its own: dst = (src >> ss) << ds, the same line_parity; src == dst is allowed
+hipError_t launch_shift16(hipStream_t s, int nframes, const uint8_t* src, int64_t src_frame_stride, int src_pitch, int w, int h, uint8_t* dst,
+                          int64_t dst_frame_stride, int dst_pitch, int line_parity, int ss, int ds);
 
 // sn_pool_kernels.hip: the three-kernel path over the HBM-resident pool (every format).
 hipError_t launch_assemble(hipStream_t s, const PlaneArgs& p, int bytes, int nframes);

@@ -11,6 +11,13 @@
 // Field form (line_parity 0 / 1): only the lines of that parity are read and written, the lines the SangNom2 pass that
 // follows keeps and the only ones it reads; the other lines of the destination are left as they were.
 // Rows are addressed with 64-bit offsets; a store never reaches beyond cw x B bytes of a U or V row, 2 x cw x B of a UV row.
+// MSB-aligned surfaces (SN_LAYOUT_*_MSB: P010 / P012, the sample in the HIGH bits of its 16-bit word): the passes see
+// LSB-aligned planes, so a side with shift s = 16 - bits_per_sample is converted where its samples move anyway --
+//   (x >> ss) << ds   with ss the source's shift and ds the destination's (0 for an LSB side), wave-uniform arguments.
+// The MSB instances of k_uv do it inside the split (ss, 0), the merge (0, ds) or a straight conversion (ss, ds), on each
+// dword as two packed 16-bit shifts (v_pk_lshrrev_b16 / v_pk_lshlrev_b16); k_shift16 is the same for ONE plane -- luma, the
+// planar chroma of a PLANAR_MSB side, a copied plane (ss == ds != 0: the mask) --, shaped as k_uv is, and safe in place
+// (src == dst): a lane reads its 16 bytes, or its sample, before it writes them, and no two lanes share a byte.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -28,6 +35,21 @@ struct UvPlane {
     int32_t pitch;
 };
 
+typedef uint16_t U16x2 __attribute__((ext_vector_type(2)));
+
+// (x >> ss) << ds on both 16-bit halves of a dword
+__device__ __forceinline__ uint32_t shift_pk(uint32_t x, int ss, int ds)
+{
+    U16x2 v = __builtin_bit_cast(U16x2, x);
+    v = (v >> (uint16_t)ss) << (uint16_t)ds;
+    return __builtin_bit_cast(uint32_t, v);
+}
+__device__ __forceinline__ uint4 shift_pk(uint4 a, int ss, int ds)
+{
+    return make_uint4(shift_pk(a.x, ss, ds), shift_pk(a.y, ss, ds), shift_pk(a.z, ss, ds), shift_pk(a.w, ss, ds));
+}
+__device__ __forceinline__ uint16_t shift_one(uint16_t x, int ss, int ds) { return (uint16_t)(((uint32_t)x >> ss) << ds); }
+
 // v_perm_b32 takes bytes 0..3 from its second operand and 4..7 from its first
 template <int B>
 struct UvSel;
@@ -44,10 +66,14 @@ struct UvSel<2> {  // d0 = U0 V0, d1 = U1 V1
 
 // vec_ok: vectors i < nvec of a row are 16 bytes of U and of V (32 of UV); the lanes behind them take the row's remaining
 // samples.  Otherwise every lane walks samples.  Rows and frames beyond what the grid holds are looped over.
-template <class T, bool kMerge>
+// kMsb (uint16_t only): every sample read goes through (x >> ss) << ds; the other instances ignore ss and ds.
+template <class T, bool kMerge, bool kMsb = false>
 __global__ void __launch_bounds__(kUvLanes* kUvRows) k_uv(UvPlane uv, UvPlane pu, UvPlane pv, int cw, int row0, int rstep, int nrows, int nframes,
-                                                          int vec_ok)
+                                                          int vec_ok, int ss, int ds)
 {
+    static_assert(!kMsb || sizeof(T) == 2, "MSB-aligned samples are 16-bit words");
+    [[maybe_unused]] auto conv4 = [=](uint4 a) { if constexpr (kMsb) return shift_pk(a, ss, ds); else return a; };
+    [[maybe_unused]] auto conv1 = [=](T x) { if constexpr (kMsb) return (T)shift_one(x, ss, ds); else return x; };
     constexpr int B = (int)sizeof(T);
     constexpr int per = 16 / B;  // samples per 16 bytes
     const int nvec = vec_ok ? cw / per : 0;
@@ -61,7 +87,7 @@ __global__ void __launch_bounds__(kUvLanes* kUvRows) k_uv(UvPlane uv, UvPlane pu
             uint8_t* const pvb = pv.base + (int64_t)f * pv.fs + y * pv.pitch;
             if (i < nvec) {
                 if constexpr (!kMerge) {
-                    const uint4 a = reinterpret_cast<const uint4*>(puv)[2 * i], b = reinterpret_cast<const uint4*>(puv)[2 * i + 1];
+                    const uint4 a = conv4(reinterpret_cast<const uint4*>(puv)[2 * i]), b = conv4(reinterpret_cast<const uint4*>(puv)[2 * i + 1]);
                     uint4 u, v;
                     u.x = __builtin_amdgcn_perm(a.y, a.x, UvSel<B>::even), v.x = __builtin_amdgcn_perm(a.y, a.x, UvSel<B>::odd);
                     u.y = __builtin_amdgcn_perm(a.w, a.z, UvSel<B>::even), v.y = __builtin_amdgcn_perm(a.w, a.z, UvSel<B>::odd);
@@ -70,7 +96,7 @@ __global__ void __launch_bounds__(kUvLanes* kUvRows) k_uv(UvPlane uv, UvPlane pu
                     reinterpret_cast<uint4*>(pub)[i] = u;
                     reinterpret_cast<uint4*>(pvb)[i] = v;
                 } else {
-                    const uint4 u = reinterpret_cast<const uint4*>(pub)[i], v = reinterpret_cast<const uint4*>(pvb)[i];
+                    const uint4 u = conv4(reinterpret_cast<const uint4*>(pub)[i]), v = conv4(reinterpret_cast<const uint4*>(pvb)[i]);
                     uint4 a, b;
                     a.x = __builtin_amdgcn_perm(v.x, u.x, UvSel<B>::lo), a.y = __builtin_amdgcn_perm(v.x, u.x, UvSel<B>::hi);
                     a.z = __builtin_amdgcn_perm(v.y, u.y, UvSel<B>::lo), a.w = __builtin_amdgcn_perm(v.y, u.y, UvSel<B>::hi);
@@ -83,11 +109,11 @@ __global__ void __launch_bounds__(kUvLanes* kUvRows) k_uv(UvPlane uv, UvPlane pu
                 // the ragged tail of an aligned row, or the whole row of a launch that is not: one sample per access
                 for (int x = nvec * per + (i - nvec); x < cw; x += lanes - nvec) {
                     if constexpr (!kMerge) {
-                        reinterpret_cast<T*>(pub)[x] = reinterpret_cast<const T*>(puv)[2 * x];
-                        reinterpret_cast<T*>(pvb)[x] = reinterpret_cast<const T*>(puv)[2 * x + 1];
+                        reinterpret_cast<T*>(pub)[x] = conv1(reinterpret_cast<const T*>(puv)[2 * x]);
+                        reinterpret_cast<T*>(pvb)[x] = conv1(reinterpret_cast<const T*>(puv)[2 * x + 1]);
                     } else {
-                        reinterpret_cast<T*>(puv)[2 * x] = reinterpret_cast<const T*>(pub)[x];
-                        reinterpret_cast<T*>(puv)[2 * x + 1] = reinterpret_cast<const T*>(pvb)[x];
+                        reinterpret_cast<T*>(puv)[2 * x] = conv1(reinterpret_cast<const T*>(pub)[x]);
+                        reinterpret_cast<T*>(puv)[2 * x + 1] = conv1(reinterpret_cast<const T*>(pvb)[x]);
                     }
                 }
             }
@@ -95,44 +121,95 @@ __global__ void __launch_bounds__(kUvLanes* kUvRows) k_uv(UvPlane uv, UvPlane pu
     }
 }
 
+// One plane of 16-bit words: dst[y][x] = (src[y][x] >> ss) << ds for x < w, the rows row0 + rstep r.  The shape of k_uv: vectors
+// i < nvec of a row are 16 bytes (vec_ok), the lanes behind them take the row's remaining samples; never a byte beyond 2 w.
+__global__ void __launch_bounds__(kUvLanes* kUvRows) k_shift16(UvPlane src, UvPlane dst, int w, int row0, int rstep, int nrows, int nframes, int vec_ok,
+                                                               int ss, int ds)
+{
+    constexpr int per = 8;
+    const int nvec = vec_ok ? w / per : 0;
+    const int i = blockIdx.x * kUvLanes + threadIdx.x;
+    const int lanes = gridDim.x * kUvLanes;
+    for (int f = blockIdx.z; f < nframes; f += gridDim.z) {
+        for (int r = blockIdx.y * kUvRows + threadIdx.y; r < nrows; r += gridDim.y * kUvRows) {
+            const int64_t y = row0 + (int64_t)rstep * r;
+            const uint8_t* const ps = src.base + (int64_t)f * src.fs + y * src.pitch;
+            uint8_t* const pd = dst.base + (int64_t)f * dst.fs + y * dst.pitch;
+            if (i < nvec) {
+                const uint4 a = reinterpret_cast<const uint4*>(ps)[i];
+                reinterpret_cast<uint4*>(pd)[i] = shift_pk(a, ss, ds);
+            } else {
+                for (int x = nvec * per + (i - nvec); x < w; x += lanes - nvec) {
+                    const uint16_t a = reinterpret_cast<const uint16_t*>(ps)[x];
+                    reinterpret_cast<uint16_t*>(pd)[x] = shift_one(a, ss, ds);
+                }
+            }
+        }
+    }
+}
+
+static bool uv_aligned(const UvPlane& p) { return (uintptr_t)p.base % 16 == 0 && p.pitch % 16 == 0 && p.fs % 16 == 0; }
+
+// aligned: a lane per vector and one per sample of the tail (fewer than `per`); otherwise up to 16 waves walk a row's samples
+static dim3 uv_grid(int vec_ok, int w, int per, int nrows, int nframes)
+{
+    const int64_t want = vec_ok ? w / per + w % per : (w < 16 * kUvLanes ? w : 16 * kUvLanes);
+    const unsigned gx = (unsigned)((want + kUvLanes - 1) / kUvLanes);
+    const int gy = (nrows + kUvRows - 1) / kUvRows;
+    return dim3(gx < 1 ? 1 : gx, gy > 65535 ? 65535 : gy, nframes > 65535 ? 65535 : nframes);
+}
+
 static hipError_t launch_uv(hipStream_t st, bool merge, int bytes, int nframes, const UvPlane& uv, const UvPlane& pu, const UvPlane& pv, int cw, int h,
-                            int line_parity)
+                            int line_parity, int ss, int ds)
 {
     if (nframes <= 0 || cw <= 0 || h <= 0) return hipSuccess;
     if (bytes != 1 && bytes != 2) return hipErrorInvalidValue;
+    const bool msb = ss != 0 || ds != 0;
+    if (msb && (bytes != 2 || ss < 0 || ss > 15 || ds < 0 || ds > 15)) return hipErrorInvalidValue;
     const int row0 = line_parity < 0 ? 0 : line_parity & 1, rstep = line_parity < 0 ? 1 : 2;
     const int nrows = (h - row0 + rstep - 1) / rstep;
     if (nrows <= 0) return hipSuccess;
-    auto aligned = [](const UvPlane& p) { return (uintptr_t)p.base % 16 == 0 && p.pitch % 16 == 0 && p.fs % 16 == 0; };
-    const int vec_ok = aligned(uv) && aligned(pu) && aligned(pv) ? 1 : 0;
-    const int per = 16 / bytes;
-    // aligned: a lane per vector and one per sample of the tail (fewer than `per`); otherwise up to 16 waves walk a row's samples
-    int64_t want = vec_ok ? cw / per + cw % per : (cw < 16 * kUvLanes ? cw : 16 * kUvLanes);
-    const unsigned gx = (unsigned)((want + kUvLanes - 1) / kUvLanes);
-    const int gy = (nrows + kUvRows - 1) / kUvRows;
-    dim3 grid(gx < 1 ? 1 : gx, gy > 65535 ? 65535 : gy, nframes > 65535 ? 65535 : nframes), block(kUvLanes, kUvRows);
+    const int vec_ok = uv_aligned(uv) && uv_aligned(pu) && uv_aligned(pv) ? 1 : 0;
+    const dim3 grid = uv_grid(vec_ok, cw, 16 / bytes, nrows, nframes), block(kUvLanes, kUvRows);
     if (bytes == 1) {
-        if (merge) hipLaunchKernelGGL((k_uv<uint8_t, true>), grid, block, 0, st, uv, pu, pv, cw, row0, rstep, nrows, nframes, vec_ok);
-        else hipLaunchKernelGGL((k_uv<uint8_t, false>), grid, block, 0, st, uv, pu, pv, cw, row0, rstep, nrows, nframes, vec_ok);
+        if (merge) hipLaunchKernelGGL((k_uv<uint8_t, true>), grid, block, 0, st, uv, pu, pv, cw, row0, rstep, nrows, nframes, vec_ok, 0, 0);
+        else hipLaunchKernelGGL((k_uv<uint8_t, false>), grid, block, 0, st, uv, pu, pv, cw, row0, rstep, nrows, nframes, vec_ok, 0, 0);
+    } else if (!msb) {
+        if (merge) hipLaunchKernelGGL((k_uv<uint16_t, true>), grid, block, 0, st, uv, pu, pv, cw, row0, rstep, nrows, nframes, vec_ok, 0, 0);
+        else hipLaunchKernelGGL((k_uv<uint16_t, false>), grid, block, 0, st, uv, pu, pv, cw, row0, rstep, nrows, nframes, vec_ok, 0, 0);
     } else {
-        if (merge) hipLaunchKernelGGL((k_uv<uint16_t, true>), grid, block, 0, st, uv, pu, pv, cw, row0, rstep, nrows, nframes, vec_ok);
-        else hipLaunchKernelGGL((k_uv<uint16_t, false>), grid, block, 0, st, uv, pu, pv, cw, row0, rstep, nrows, nframes, vec_ok);
+        if (merge) hipLaunchKernelGGL((k_uv<uint16_t, true, true>), grid, block, 0, st, uv, pu, pv, cw, row0, rstep, nrows, nframes, vec_ok, ss, ds);
+        else hipLaunchKernelGGL((k_uv<uint16_t, false, true>), grid, block, 0, st, uv, pu, pv, cw, row0, rstep, nrows, nframes, vec_ok, ss, ds);
     }
     return hipGetLastError();
 }
 
 hipError_t launch_uv_split(hipStream_t st, int bytes, int nframes, const uint8_t* uv, int64_t uv_fs, int uv_pitch, int cw, int h, uint8_t* u,
-                           int64_t u_fs, int u_pitch, uint8_t* v, int64_t v_fs, int v_pitch, int line_parity)
+                           int64_t u_fs, int u_pitch, uint8_t* v, int64_t v_fs, int v_pitch, int line_parity, int ss, int ds)
 {
     return launch_uv(st, false, bytes, nframes, UvPlane{const_cast<uint8_t*>(uv), uv_fs, uv_pitch}, UvPlane{u, u_fs, u_pitch}, UvPlane{v, v_fs, v_pitch}, cw,
-                     h, line_parity);
+                     h, line_parity, ss, ds);
 }
 
 hipError_t launch_uv_merge(hipStream_t st, int bytes, int nframes, const uint8_t* u, int64_t u_fs, int u_pitch, const uint8_t* v, int64_t v_fs,
-                           int v_pitch, int cw, int h, uint8_t* uv, int64_t uv_fs, int uv_pitch)
+                           int v_pitch, int cw, int h, uint8_t* uv, int64_t uv_fs, int uv_pitch, int ss, int ds)
 {
     return launch_uv(st, true, bytes, nframes, UvPlane{uv, uv_fs, uv_pitch}, UvPlane{const_cast<uint8_t*>(u), u_fs, u_pitch},
-                     UvPlane{const_cast<uint8_t*>(v), v_fs, v_pitch}, cw, h, -1);
+                     UvPlane{const_cast<uint8_t*>(v), v_fs, v_pitch}, cw, h, -1, ss, ds);
+}
+
+hipError_t launch_shift16(hipStream_t st, int nframes, const uint8_t* src, int64_t src_fs, int src_pitch, int w, int h, uint8_t* dst, int64_t dst_fs,
+                          int dst_pitch, int line_parity, int ss, int ds)
+{
+    if (nframes <= 0 || w <= 0 || h <= 0) return hipSuccess;
+    if (ss < 0 || ss > 15 || ds < 0 || ds > 15) return hipErrorInvalidValue;
+    const int row0 = line_parity < 0 ? 0 : line_parity & 1, rstep = line_parity < 0 ? 1 : 2;
+    const int nrows = (h - row0 + rstep - 1) / rstep;
+    if (nrows <= 0) return hipSuccess;
+    const UvPlane s{const_cast<uint8_t*>(src), src_fs, src_pitch}, d{dst, dst_fs, dst_pitch};
+    const int vec_ok = uv_aligned(s) && uv_aligned(d) ? 1 : 0;
+    hipLaunchKernelGGL(k_shift16, uv_grid(vec_ok, w, 8, nrows, nframes), dim3(kUvLanes, kUvRows), 0, st, s, d, w, row0, rstep, nrows, nframes, vec_ok, ss, ds);
+    return hipGetLastError();
 }
 
 }  // namespace sn

@@ -46,6 +46,7 @@ _FORMATS = {
     "YUV422P16": dict(bytes=2, bits=16, planes=3, subw=1, subh=0),
     "YUV420P8": dict(bytes=1, bits=8, planes=3, subw=1, subh=1),
     "YUV420P10": dict(bytes=2, bits=10, planes=3, subw=1, subh=1),
+    "YUV420P12": dict(bytes=2, bits=12, planes=3, subw=1, subh=1),
     "YUV420P16": dict(bytes=2, bits=16, planes=3, subw=1, subh=1),
     "YUV422P8": dict(bytes=1, bits=8, planes=3, subw=1, subh=0),
     "YUV444P8": dict(bytes=1, bits=8, planes=3), "YUV444P16": dict(bytes=2, bits=16, planes=3),
@@ -59,9 +60,10 @@ def clip_format(name: str, width: int, height: int) -> ClipFormat:
     return ClipFormat(width=width, height=height, **_FORMATS[name])
 
 
-def _surfaces_of(planes, shape_of, nplanes, B, what):
+def _surfaces_of(planes, shape_of, nplanes, B, what, msb=False):
     """sn_surfaces of device tensors: the planar tensors process_batch takes ([N, H_p, W_p] each), or two tensors
-    [Y [N, H, W], UV [N, Hc, Wc, 2]] for a semi-planar surface (NV12, P010 / P016, NV16, NV24; UV[..., 0] is U)."""
+    [Y [N, H, W], UV [N, Hc, Wc, 2]] for a semi-planar surface (NV12, P010 / P016, NV16, NV24; UV[..., 0] is U).
+    msb: 16-bit words with the sample in the high bits (SN_LAYOUT_*_MSB)."""
     planes = list(planes)
     semi = len(planes) == 2 and planes[1].dim() == 4
     if not semi and len(planes) < nplanes:
@@ -77,7 +79,9 @@ def _surfaces_of(planes, shape_of, nplanes, B, what):
         if t.stride(-1) != 1 or (semi and p and t.stride(2) != 2):
             raise ValueError(f"{what} plane {p}: rows must be contiguous (a UV tensor: stride(2) == 2, last stride 1)")
         ptr.append(t.data_ptr()), pitch.append(t.stride(1) * B), fs.append(t.stride(0) * B)
-    return capi.surfaces(capi.SN_LAYOUT_SEMIPLANAR if semi else capi.SN_LAYOUT_PLANAR, ptr, pitch, fs), N
+    layout = (capi.SN_LAYOUT_SEMIPLANAR_MSB if semi else capi.SN_LAYOUT_PLANAR_MSB) if msb else \
+        (capi.SN_LAYOUT_SEMIPLANAR if semi else capi.SN_LAYOUT_PLANAR)
+    return capi.surfaces(layout, ptr, pitch, fs), N
 
 
 class SangNom2:
@@ -308,12 +312,14 @@ class SangNom2:
         self._check(self._lib.sn_process_device_strided(self._h, N, sp, sfs, spi, dp, dfs, dpi, par))
         return dst
 
-    def process_surfaces(self, src, dst, parity=None):
+    def process_surfaces(self, src, dst, parity=None, src_msb=False, dst_msb=False):
         """process_batch for decoder and encoder surfaces (sn_process_device_surfaces): each of src and dst is either the
-        planar tensors process_batch takes or [Y [N, H, W], UV [N, Hc, Wc, 2]], independently.  Asynchronous on the
-        context's stream (the first semi-planar call allocates the chroma scratch)."""
-        s, N = _surfaces_of(src, self.plane_shape_in, self.nplanes, self.clip.bytes, "src")
-        d, Nd = _surfaces_of(dst, self.plane_shape_out, self.nplanes, self.clip.bytes, "dst")
+        planar tensors process_batch takes or [Y [N, H, W], UV [N, Hc, Wc, 2]], independently.  src_msb / dst_msb: that
+        side's 16-bit words hold the sample in their high bits (P010 on a 10-bit clip, P012 on a 12-bit one); the result is
+        the clip's own, aligned as dst_msb says.  Asynchronous on the context's stream (the first call that needs scratch
+        allocates it)."""
+        s, N = _surfaces_of(src, self.plane_shape_in, self.nplanes, self.clip.bytes, "src", src_msb)
+        d, Nd = _surfaces_of(dst, self.plane_shape_out, self.nplanes, self.clip.bytes, "dst", dst_msb)
         if N != Nd:
             raise ValueError("src and dst must carry the same number of frames")
         par = None if parity is None else (ctypes.c_int32 * N)(*[int(x) for x in parity])
@@ -459,11 +465,12 @@ class SangNomAA(_AAContext):
         self._check(self._lib.sn_aa_process_device_strided(self._h, N, sp, sfs, spi, dp, dfs, dpi, par))
         return dst
 
-    def process_surfaces(self, src, dst, parity=None):
+    def process_surfaces(self, src, dst, parity=None, src_msb=False, dst_msb=False):
         """process_batch for decoder and encoder surfaces (sn_aa_process_device_surfaces): each of src and dst is either
-        the planar tensors or [Y [N, H, W], UV [N, Hc, Wc, 2]] (dh: dst is [Y [N, 2 H, 2 W], UV [N, 2 Hc, 2 Wc, 2]])."""
-        s, N = _surfaces_of(src, self.plane_shape, self.nplanes, self.clip.bytes, "src")
-        d, Nd = _surfaces_of(dst, self.plane_shape_out, self.nplanes, self.clip.bytes, "dst")
+        the planar tensors or [Y [N, H, W], UV [N, Hc, Wc, 2]] (dh: dst is [Y [N, 2 H, 2 W], UV [N, 2 Hc, 2 Wc, 2]]).
+        src_msb / dst_msb: as for SangNom2.process_surfaces."""
+        s, N = _surfaces_of(src, self.plane_shape, self.nplanes, self.clip.bytes, "src", src_msb)
+        d, Nd = _surfaces_of(dst, self.plane_shape_out, self.nplanes, self.clip.bytes, "dst", dst_msb)
         if N != Nd:
             raise ValueError("src and dst must carry the same number of frames")
         par = None if parity is None else (ctypes.c_int32 * N)(*[int(x) for x in parity])

@@ -366,6 +366,9 @@ int sn_aa_collect_host(sn_aa_context* ctx, int32_t slot, void* const dst[3], con
  *   SN_LAYOUT_SEMIPLANAR  plane[0] = Y, plane[1] = the UV plane: row y of frame f is U0 V0 U1 V1 ... at plane[1] +
  *                         f * frame_stride[1] + y * pitch[1], 2 * chroma width samples long; plane[2] must be NULL and
  *                         pitch[2] / frame_stride[2] are ignored
+ *   SN_LAYOUT_PLANAR_MSB, SN_LAYOUT_SEMIPLANAR_MSB
+ *                         the same two, except that every sample is a 16-bit word whose bits_per_sample significant bits
+ *                         are the HIGH bits (P010 on a 10-bit context, P012 on a 12-bit one; see below)
  * Pointers, pitches and frame strides need the alignment of the sample size only (a UV plane may start at an odd byte);
  * surfaces whose bases, pitches and frame strides are multiples of 16 bytes -- every decoder's -- move 16 bytes per
  * lane and access.  With both sides SN_LAYOUT_PLANAR the call IS sn_process_device_strided / sn_aa_process_device_strided
@@ -373,8 +376,9 @@ int sn_aa_collect_host(sn_aa_context* ctx, int32_t slot, void* const dst[3], con
  * call gives on the de-interleaved planes, re-interleaved, in every configuration the context accepts: the library splits
  * the lines the filter keeps of a semi-planar source into planar chroma scratch of its own (every line with dh and in the
  * anti-aliasing call), runs its passes there, and merges their output into the destination's UV plane; luma never goes
- * through scratch.  Chroma that is not processed (chroma = 0 without dh) never reaches a pass: with the same layout on both
- * sides the UV plane is copied once, with different layouts it is converted straight from src to dst.
+ * through scratch (but for an MSB-aligned source, below).  Chroma that is not processed (chroma = 0 without dh) never
+ * reaches a pass: with the same layout on both sides the UV plane is copied once, with different layouts it is converted
+ * straight from src to dst.
  * Scratch: two planes of the source's and two of the destination's chroma geometry per frame, pitches rounded up to 256
  * bytes, for min(max_batch, what fits) frames, where a SIXTEENTH of sn_policy.scratch_budget_mb is what may be taken
  * (1.5 GiB by default: 180 frames of 8-bit 2160p 4:2:0, 90 of 16-bit) and one frame is always held; a batch beyond that
@@ -382,16 +386,31 @@ int sn_aa_collect_host(sn_aa_context* ctx, int32_t slot, void* const dst[3], con
  * semi-planar side with processed chroma, before anything of that call is queued, and freed with the context.
  * Both calls are asynchronous on the context's stream, like the planar calls; that first call allocates and may
  * synchronise the stream.
- * P010 is a 16-bit clip whose values sit in the high bits of the word: create the context with bits_per_sample = 16
- * and the result is what the reference gives on that 16-bit clip.  That is NOT the 10-bit result shifted left by six: the
- * floor of stage 2 (sum / 16) does not commute with the shift, so low bits differ.  A caller who wants the reference's 10-bit
- * result shifts the samples down first and creates a 10-bit context.
+ * P010 / P012 keep the sample in the high bits of a 16-bit word.  There are two ways to take them, and they give different
+ * pixels: the floor of stage 2 (sum / 16) does not commute with the shift, so low bits differ.
+ *   - As a 16-bit clip: a context with bits_per_sample = 16 and SN_LAYOUT_SEMIPLANAR.  The result is what the reference
+ *     gives on that 16-bit clip, low bits of the words included.
+ *   - As the 10- / 12-bit clip it is: a context with bits_per_sample = 10 (12) and SN_LAYOUT_SEMIPLANAR_MSB.  The result is
+ *     the reference's on the YUV420P10 (P12) clip, MSB-aligned again.
+ * The _MSB layouts: the shift s = 16 - bits_per_sample is implied (6 for P010, 4 for P012, 0 on a 16-bit context, where the
+ * _MSB layouts are the plain ones).  With ss and ds the shifts of the two sides (0 for a layout without _MSB) the destination
+ * holds, bit for bit, what the call gives on src >> ss (logical, every plane and line), every sample shifted left by ds:
+ * interpolated lines, kept lines, planes that are only copied and the copied border line alike.  Low bits of an MSB source
+ * never reach the output (a plane copied between two MSB sides is masked), and the input is always in range for the context.
+ * (The output need not be: like the reference the filter does not clamp to the clip's range, and an interpolated sample above
+ * 2^bits - 1 loses its high bits when it is shifted up inside its 16-bit word.)
+ * The two sides are independent: P010 in and planar YUV420P10 out is fine, as is every other pairing.  The passes see
+ * LSB-aligned planes: the planes of an MSB source are shifted down into scratch (its UV plane inside the split; luma into a
+ * luma plane of scratch, pitch rounded up to 256 bytes, which an MSB source with processed luma adds to the sum below), those
+ * of an MSB destination are shifted up where the passes wrote them (its UV plane inside the merge).  A context that first
+ * needs the luma scratch after the chroma scratch (or the reverse) gives back what it held and takes both under the same rule.
  * SN_ERR_INVALID_ARG names the field: struct_size, layout, reserved, plane[2] set with SN_LAYOUT_SEMIPLANAR, a NULL
  * plane, a pitch below the row (the UV plane's row is 2 * chroma width * bytes_per_sample; the anti-aliasing call with dh
  * writes planes twice as wide and twice as high: 2 * (2 * chroma width) * bytes_per_sample).  SN_ERR_UNSUPPORTED:
- * SN_LAYOUT_SEMIPLANAR on a context with num_planes == 1 or bytes_per_sample == 4 (no such surface exists).  A refused
- * call queues nothing and leaves the context usable. */
-enum { SN_LAYOUT_PLANAR = 0, SN_LAYOUT_SEMIPLANAR = 1 };
+ * SN_LAYOUT_SEMIPLANAR on a context with num_planes == 1 or bytes_per_sample == 4 (no such surface exists); an _MSB
+ * layout on a context with bytes_per_sample != 2 (the text names layout).  A refused call queues nothing and leaves the
+ * context usable. */
+enum { SN_LAYOUT_PLANAR = 0, SN_LAYOUT_SEMIPLANAR = 1, SN_LAYOUT_PLANAR_MSB = 2, SN_LAYOUT_SEMIPLANAR_MSB = 3 };
 typedef struct sn_surfaces {
     int32_t struct_size;      /* = sizeof(sn_surfaces)                                        */
     int32_t layout;           /* SN_LAYOUT_*                                                 */
@@ -407,7 +426,7 @@ int sn_aa_process_device_surfaces(sn_aa_context* ctx, int32_t nframes, const sn_
 /* What the surface calls of a context have done so far (all zero while every call had planar surfaces on both sides). */
 typedef struct sn_surface_info {
     int32_t struct_size, reserved;
-    int64_t scratch_bytes;     /* planar chroma scratch this context holds for the call (0 until first needed) */
+    int64_t scratch_bytes;     /* planar scratch this context holds for the call: chroma plus luma (0 until first needed) */
     int64_t split_frames;      /* frames whose UV plane was split into U and V for the passes                  */
     int64_t merged_frames;     /* frames whose U and V were merged into a UV plane                             */
     int64_t copied_frames;     /* frames whose unprocessed chroma went from src to dst without a pass (copied or converted) */

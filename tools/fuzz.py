@@ -4,6 +4,7 @@ the C ABI (host frames, device batches and the host ring) against oracle instanc
 configurations run with opt=1 (the SSE2 arithmetic, against tests/sse2_model.py), and those draw sn_policy.sse2_sweeps too.
 Wide 16-bit and float configurations (3872 .. 8192 columns) draw sn_options.column_parts.
 Device batches of three-plane 8 / 16-bit clips draw the layout of each side: planar, or semi-planar (a UV plane; sn_process_device_surfaces).
+Device batches of 9..15-bit clips also draw each side's alignment: LSB, or MSB (P010 / P012: the sample in the high bits, random low bits below it).
 usage: python tools/fuzz.py [--seconds 120] [--seed 1]"""
 import argparse
 import os
@@ -19,7 +20,8 @@ from oracle.oracle import Config, Oracle  # noqa: E402
 from tests import sse2_model as sm  # noqa: E402
 from tests.util import to_host  # noqa: E402
 
-FORMATS = ["Y8", "Y8", "Y8", "Y10", "Y16", "Y32", "YUV420P8", "YUV420P8", "YUV420P16", "YUV422P8", "YUV444P8", "YUV444PS", "YUV420PS"]
+FORMATS = ["Y8", "Y8", "Y8", "Y10", "Y16", "Y32", "YUV420P8", "YUV420P8", "YUV420P16", "YUV422P8", "YUV444P8", "YUV444PS", "YUV420PS", "YUV420P10",
+           "YUV420P12"]
 
 
 def cfg_of(clip, **kw):
@@ -48,7 +50,7 @@ def main():
     t_end = time.time() + a.seconds
     n = bad = 0
     stats = {"fused": 0, "pool": 0, "ring": 0, "host": 0, "batch": 0, "frames": 0, "pixels": 0, "banded_frames": 0, "band_fallbacks": 0, "chained_frames": 0,
-             "uv_sweep_configs": 0, "chain_redone": 0, "opt1": 0, "opt1_sweeps": 0, "part_frames": 0, "part_fallbacks": 0, "semi_sides": 0}
+             "uv_sweep_configs": 0, "chain_redone": 0, "opt1": 0, "opt1_sweeps": 0, "part_frames": 0, "part_fallbacks": 0, "semi_sides": 0, "msb_sides": 0}
     while time.time() < t_end:
         fmt = rng.choice(FORMATS)
         wide = rng.random() < 0.15
@@ -129,7 +131,14 @@ def main():
                 import torch
                 dev = torch.device("cuda:0")
                 view = {1: np.uint8, 2: np.int16, 4: np.float32}[clip.bytes]
-                src = [torch.from_numpy(np.stack([fr[p] for fr in frames]).view(view)).to(dev) for p in range(clip.planes)]
+                # 9..15-bit clips: each side LSB- or MSB-aligned, independently; an MSB source has random low bits, which must not matter
+                shift = 16 - clip.bits if clip.bytes == 2 else 0
+                msb_in, msb_out = (rng.random() < 0.5, rng.random() < 0.5) if shift else (False, False)
+                words = frames
+                if msb_in:
+                    low = np.random.default_rng(rng.randint(0, 1 << 30))
+                    words = [[(pl << np.uint16(shift)) | low.integers(0, 1 << shift, pl.shape, dtype=np.uint16) for pl in fr] for fr in frames]
+                src = [torch.from_numpy(np.stack([fr[p] for fr in words]).view(view)).to(dev) for p in range(clip.planes)]
                 dst = [torch.zeros((nframes,) + flt.plane_shape_out(p), dtype=src[p].dtype, device=dev) for p in range(clip.planes)]
                 # three-plane 8 / 16-bit clips: each side planar or semi-planar (NV12 / P016 / NV16 / NV24), independently
                 semi_in, semi_out = (rng.random() < 0.5, rng.random() < 0.5) if clip.planes == 3 and clip.bytes < 4 else (False, False)
@@ -138,15 +147,18 @@ def main():
                 if semi_out:
                     dst = [dst[0], torch.zeros(tuple(dst[1].shape) + (2,), dtype=dst[1].dtype, device=dev)]
                 stats["semi_sides"] += int(semi_in) + int(semi_out)
+                stats["msb_sides"] += int(msb_in) + int(msb_out)
                 torch.cuda.synchronize()
-                if semi_in or semi_out or rng.random() < 0.25:
-                    flt.process_surfaces(src, dst, parity=parity)
+                if semi_in or semi_out or msb_in or msb_out or rng.random() < 0.25:
+                    flt.process_surfaces(src, dst, parity=parity, src_msb=msb_in, dst_msb=msb_out)
                 else:
                     flt.process_batch(src, dst, parity=parity)
                 flt.synchronize()
                 if semi_out:
                     dst = [dst[0], dst[1][..., 0], dst[1][..., 1]]
                 got = [[to_host(dst[p][f]).view(clip.dtype) for p in range(clip.planes)] for f in range(nframes)]
+                if msb_out:  # the rule: the LSB result shifted left inside its 16-bit word
+                    want = [[(pl << np.uint16(shift)).astype(np.uint16) for pl in fr] for fr in want]
             else:
                 slots = flt.host_slots()
                 inflight = []
