@@ -2,6 +2,7 @@
 // fields each mode's kernel reads, and every refusal.  Every expected value below is written out by hand from the definitions
 // (8 pixels per lane; strip 0 holds 62 real lanes of 64, later strips 60; a plane of at most 64 lanes is one strip).
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "sn_sweep_args.h"
@@ -335,8 +336,30 @@ static void parts_refusals()
     CHECK(s.args.nparts == 8 && s.args.part_x[7] == 3360 && s.args.part_seam_off[7][0] == 13 * 8640 && s.args.nw == 1);
 }
 
-int main()
+// `sweep_args_check bytes width[:sweep_w] ...`: one line "nvw nw" per plane, from build_sweep -- a plane on its own, or
+// (width:sweep_w) the padded sweep of a plane over its pool stride; "refused" where build_sweep has no instance.
+// tests/test_sweep_geometry_cpu.py holds the table of tests/sweep_geometry_cases.py against it.
+static int query(int argc, char** argv)
 {
+    const int bytes = atoi(argv[1]);
+    if (bytes != 1 && bytes != 2 && bytes != 4) return 2;
+    for (int i = 2; i < argc; ++i) {
+        int w = 0, sweep_w = 0;
+        const int n = sscanf(argv[i], "%d:%d", &w, &sweep_w);
+        if (n < 1 || w <= 0) return 2;
+        FusedPool fp{};
+        fp.mode = kPadded;
+        fp.sweep_w = sweep_w;
+        Sweep s;
+        if (build_sweep(sweep_traits(bytes), plane(bytes, w, 16), 0.0, 1, n == 2 ? &fp : nullptr, s) != hipSuccess) printf("refused\n");
+        else printf("%d %d\n", s.args.nvw, s.args.nw);
+    }
+    return 0;
+}
+
+int main(int argc, char** argv)
+{
+    if (argc > 2) return query(argc, argv);
     geometry();
     modes();
     parts_refusals();
