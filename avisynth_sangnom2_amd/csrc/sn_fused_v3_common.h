@@ -128,6 +128,49 @@ __device__ __forceinline__ unsigned pk_absdiff(unsigned a, unsigned b) { return 
 // (m & x) | (~m & y): v_bfi_b32
 __device__ __forceinline__ unsigned bfi(unsigned m, unsigned x, unsigned y) { return (m & x) | (~m & y); }
 
+// A lane's place in a row cut into strips (sn_sweep_args.h: GH, kFirst, kInner, K): strip `wave` of `nw`, `nl` lanes of
+// PXL columns in the row.  Strip 0 starts at the image edge; every inner side of a strip has GH ghost lanes that repeat
+// the neighbouring strip's seam columns and, every K rows, take the seam lanes' state from a mailbox in LDS laid out
+// [copy][strip][side][slot] (records of whatever a lane hands over: the index counts records).
+struct StripLane {
+    int wave, lane, nw;
+    int gl;      // the lane among all of the row's
+    bool ghost;  // repeats columns another strip owns
+    bool live;   // has columns at all: dead lanes shadow column 0 and store nothing
+    bool real;   // stores its columns
+    int x0;      // its first column
+    unsigned first_mask, last_mask;  // all ones in the lane that holds the row's first / last columns
+    bool pub_right;  // feeds the next strip's left ghosts
+    bool pub_left;   // ... the previous strip's right ghosts
+    bool recv;       // a ghost that takes a record in
+    int slot;        // which of the GH records of its side
+    __device__ __forceinline__ StripLane(int wave_, int lane_, int nw_, int nl) : wave(wave_), lane(lane_), nw(nw_)
+    {
+        if (wave == 0) {
+            gl = lane;
+            ghost = nw > 1 && lane >= 64 - GH;
+        } else {
+            gl = kFirst + kInner * (wave - 1) + (lane - GH);
+            ghost = lane < GH || (lane >= 64 - GH && wave < nw - 1);
+        }
+        live = gl < nl;
+        real = live && !ghost;
+        x0 = live ? gl * PXL : 0;
+        first_mask = live && gl == 0 ? 0xffffffffu : 0u;
+        last_mask = live && gl == nl - 1 ? 0xffffffffu : 0u;
+        pub_right = lane >= 64 - 2 * GH && lane < 64 - GH && wave < nw - 1;
+        pub_left = lane >= GH && lane < 2 * GH && wave > 0;
+        recv = ghost && live;
+        slot = lane < GH ? lane : lane >= 64 - GH ? lane - (64 - GH) : pub_right ? lane - (64 - 2 * GH) : lane - GH;
+    }
+    __device__ __forceinline__ int mailbox(int copy, int w, int side, int s) const { return ((copy * nw + w) * 2 + side) * GH + s; }
+    __device__ __forceinline__ int recv_from(int copy) const { return mailbox(copy, wave, lane < GH ? 0 : 1, slot); }  // recv lanes
+    __device__ __forceinline__ int publish_to(int copy) const  // pub_right / pub_left lanes
+    {
+        return pub_right ? mailbox(copy, wave + 1, 0, slot) : mailbox(copy, wave - 1, 1, slot);
+    }
+};
+
 // Two workgroups share every SIMD (one wave each), and the issue arbiter serves equal priorities oldest first:
 // left alone, the wave dispatched first runs at nearly its solo speed and the other one on the leftovers, so the
 // first finishes a 2160p sweep after 3.6 ms and the second only after 5.7 ms -- the last 2.1 ms with one wave per

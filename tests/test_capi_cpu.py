@@ -148,6 +148,22 @@ def test_sweep_arguments_are_built_once_for_every_sample_type(tmp_path):
     assert r.returncode == 0 and r.stdout.strip() == "ok", (r.returncode, r.stdout[-3000:], r.stderr[-2000:])
 
 
+def test_pool_stage2_dispatch_rule_matches_the_boundaries_written_out_by_hand(tmp_path):
+    """sn::pool_stage2_for (csrc/sn_pool_dispatch.h), the rule that gives a pool of the pool path its stage-2 kernel:
+    tests/c/pool_dispatch_check.cpp walks it for 1, 2 and 4 bytes per sample, every pool stride from 32 to 8192, 1, 2 and 16
+    pool rows and launches of 1, 8 and 9 frames against the boundaries, the workgroup sizes and the LDS figures written out
+    by hand.  A host compiler takes the header as it is -- no device code, no GPU."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    exe = str(tmp_path / "pool_dispatch_check")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(rocm, "include"),
+                           "-I", os.path.join(root, "include"), "-I", os.path.join(root, "avisynth_sangnom2_amd", "csrc"),
+                           os.path.join(root, "tests", "c", "pool_dispatch_check.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", (r.returncode, r.stdout[-3000:], r.stderr[-2000:])
+
+
 def test_chain_hand_off_between_workgroups_drains_its_stores_before_the_barrier():
     """Release side of the chains over several workgroups per buffer (sn_pool_kernels.hip, chain_release_barrier): in
     the gfx950 ISA of every k_smooth_*_chain<true> kernel an `s_waitcnt vmcnt(0)` stands in front of the round loop's

@@ -74,20 +74,34 @@ def test_host_frames_match_oracle(hip_lib, fmt, w, h, kw, pattern):
     _run_case(fmt, w, h, kw, pattern)
 
 
-@pytest.mark.parametrize("fmt,w,h,kw", CASES[:4] + CASES[10:13], ids=lambda v: str(v) if not isinstance(v, dict) else "kw")
+# The smallest pools at which the stage-2 kernels of the pool path can still go wrong, by the dispatch rule
+# (sn_pool_dispatch.h), in each sample size: 256 and 480 columns (eight columns per thread, a barrier per row), 512 (strips:
+# one wave, no mailbox), 544 (two waves; fifteen smoothed rows, so the ghost lanes are refreshed twice), 7680 (sixteen waves,
+# 1 024 threads), 7712 and 8192 (eight columns per thread again, above the strips; at 8192 the 16-bit and float LDS lines
+# take 64 KiB, which a kernel has to ask for).
+POOL_STAGE2_CASES = [(fmt, w, h, {}) for fmt in ("Y8", "Y16", "Y32")
+                     for w, h in ((256, 32), (480, 32), (512, 32), (544, 32), (7680, 24), (7712, 24), (8192, 24))]
+
+
+@pytest.mark.parametrize("fmt,w,h,kw", CASES[:4] + CASES[10:13] + POOL_STAGE2_CASES, ids=lambda v: str(v) if not isinstance(v, dict) else "kw")
 def test_pool_mode_matches_oracle(hip_lib, fmt, w, h, kw):
     _run_case(fmt, w, h, kw, "noise", mode="pool")
 
 
 def test_pool_contents_match_oracle(hip_lib):
-    """The smoothed pool itself (stage 1 + 2) is bit-identical, including rows 0 / bh and stale cells."""
-    clip = clip_format("YUV420P8", 96, 32)
-    ora = Oracle(oracle_cfg(clip, aac=48))
-    with SangNom2(clip, aac=48, mode="pool") as flt:
-        for f, src in enumerate(make_frames(clip, "noise", 2)):
-            ora.process(src)
-            flt.get_frame(src)
-            assert np.array_equal(ora.pool(), flt.read_pool(0)), f"pool differs after frame {f}"
+    """The smoothed pool itself (stage 1 + 2) is bit-identical, including rows 0 / bh and stale cells: a 4:2:0 clip, and
+    520-wide clips of each sample size frame by frame (pool stride 544; columns 520 .. 543 are never written by stage 1 and
+    are smoothed again with every frame)."""
+    for fmt, w, h, kw, n in (("YUV420P8", 96, 32, dict(aac=48), 2), ("Y8", 520, 24, {}, 3), ("Y16", 520, 24, {}, 3), ("Y32", 520, 24, {}, 3)):
+        clip = clip_format(fmt, w, h)
+        ora = Oracle(oracle_cfg(clip, **kw))
+        with SangNom2(clip, mode="pool", **kw) as flt:
+            for f, src in enumerate(make_frames(clip, "noise", n)):
+                want = ora.process(src)
+                got = flt.get_frame(src)
+                assert np.array_equal(ora.pool(), flt.read_pool(0)), f"{fmt} {w}x{h}: pool differs after frame {f}"
+                for p in range(len(want)):
+                    assert same(want[p], got[p]), f"{fmt} {w}x{h} frame {f} plane {p}: " + describe_diff(want[p], got[p])
 
 
 def test_pitched_host_planes(hip_lib):
@@ -420,8 +434,10 @@ def test_fused_420_hand_off_rows_match_the_shared_pool(hip_lib, fmt, w, h):
 # Stage 2 of the pool path picks its kernel by sample type, pool stride and frames per launch (sn_pool_kernels.hip):
 # strips of 60 lanes x 8 columns from 512 columns on (float: launches of up to eight frames), eight columns per thread
 # below / otherwise.  Widths: 512 (two lanes in the second strip), 736 (a 720-wide clip's stride is the same: second
-# strip partly idle), 1000 (stride 1024: three strips), 1504 (four strips), 480 (below the strips).
-STAGE2_WIDTHS = (480, 512, 736, 1000, 1504)
+# strip partly idle), 1000 (stride 1024: three strips), 1504 (four strips), 480 (below the strips), 544 (the narrowest
+# pool of two strips: a float launch of ten frames takes it through the kernel with eight columns per thread, one of three
+# through the strips).
+STAGE2_WIDTHS = (480, 512, 544, 736, 1000, 1504)
 
 
 @pytest.mark.parametrize("w", STAGE2_WIDTHS)

@@ -153,6 +153,11 @@ WIDE = [
     ("YUV420P8", 128, 32, dict(aac=48), dict(fresh_pool=True), 2, "noise01"),
     ("YUV444P8", 64, 16, dict(aac=48, dh=True), {}, 1, "noise01"),
 ]
+# the pools at which the pool path's stage 2 changes its kernel (csrc/sn_pool_dispatch.h; tests/test_gpu_parity.py,
+# POOL_STAGE2_CASES, has the same shapes in the default arithmetic), and a 520-wide clip whose pool (stride 544) carries
+# its stale columns from frame to frame
+WIDE += [(fmt, w, h, {}, {}, 3, "noise") for fmt in ("Y8", "Y16")
+         for w, h in ((256, 32), (480, 32), (512, 32), (544, 32), (7680, 24), (7712, 24), (8192, 24), (520, 24))]
 
 
 # how a context is asked to run: whole-plane sweeps wherever the configuration has them (8-bit planes on their own, in this
