@@ -37,6 +37,10 @@ EXPORTS = (
 # sn_surfaces.layout: planar Y, U, V or Y plus one plane of U,V pairs (NV12, P010 / P016, NV16, NV24); _MSB: 16-bit words
 # with the sample in the high bits (P010 on a 10-bit context, P012 on a 12-bit one)
 SN_LAYOUT_PLANAR, SN_LAYOUT_SEMIPLANAR, SN_LAYOUT_PLANAR_MSB, SN_LAYOUT_SEMIPLANAR_MSB = 0, 1, 2, 3
+# packed 4:2:2, one plane: YUY2 / Y216, UYVY / v216, their MSB-aligned forms (Y210 on a 10-bit context, Y212 on a 12-bit one), v210
+SN_LAYOUT_PACKED_YUYV, SN_LAYOUT_PACKED_UYVY, SN_LAYOUT_PACKED_YUYV_MSB, SN_LAYOUT_PACKED_UYVY_MSB, SN_LAYOUT_PACKED_V210 = 8, 9, 10, 11, 12
+PACKED_LAYOUTS = {("yuyv", False): SN_LAYOUT_PACKED_YUYV, ("uyvy", False): SN_LAYOUT_PACKED_UYVY, ("yuyv", True): SN_LAYOUT_PACKED_YUYV_MSB,
+                  ("uyvy", True): SN_LAYOUT_PACKED_UYVY_MSB, ("v210", False): SN_LAYOUT_PACKED_V210}
 
 # sn_options.arithmetic: which of the reference's two code paths a context reproduces (sangnom_hip.h)
 SN_ARITH_CXX, SN_ARITH_SSE2 = 0, 1
@@ -83,7 +87,7 @@ class SnSurfaceInfo(ctypes.Structure):
 
 def surfaces(layout: int, planes, pitches, frame_strides) -> "SnSurfaces":
     """sn_surfaces from device pointers, pitches and frame strides in bytes (two entries for SN_LAYOUT_SEMIPLANAR and
-    SN_LAYOUT_SEMIPLANAR_MSB: Y, UV)."""
+    SN_LAYOUT_SEMIPLANAR_MSB: Y, UV; one for SN_LAYOUT_PACKED_*).  The planes that are not given stay NULL."""
     s = SnSurfaces(struct_size=ctypes.sizeof(SnSurfaces), layout=int(layout))
     for p, (ptr, pitch, fs) in enumerate(zip(planes, pitches, frame_strides)):
         s.plane[p], s.pitch[p], s.frame_stride[p] = ptr, int(pitch), int(fs)

@@ -16,6 +16,7 @@
 
 #include "sn_copier.h"
 #include "sn_sweep_args.h"
+#include "sn_surface_layout.h"
 #include "sn_internal.h"
 
 constexpr int kSyncChunks = 4;  // chunks of rows a pageable plane of the synchronous call is staged in
@@ -28,10 +29,11 @@ namespace sn {
 struct UvScratch {
     uint8_t* in[2] = {nullptr, nullptr};   // full height; a split writes the lines the pass keeps, the rest stays 0xA5
     uint8_t* out[2] = {nullptr, nullptr};  // full height, every line written by the pass
-    uint8_t* y = nullptr;                  // luma of an MSB-aligned source, LSB-aligned: as `in`
+    uint8_t* y = nullptr;                  // luma of an MSB-aligned or packed source, LSB-aligned: as `in`
+    uint8_t* yo = nullptr;                 // luma a packed destination is packed from: as `out`
     int cap = 0;                           // frames (0: not allocated yet)
-    int pitch_in = 0, pitch_out = 0, pitch_y = 0;
-    int64_t in_bytes = 0, out_bytes = 0, y_bytes = 0;  // one frame of one plane
+    int pitch_in = 0, pitch_out = 0, pitch_y = 0, pitch_yo = 0;
+    int64_t in_bytes = 0, out_bytes = 0, y_bytes = 0, yo_bytes = 0;  // one frame of one plane
     int64_t bytes = 0;                     // all of it
     int64_t split_frames = 0, merged_frames = 0, copied_frames = 0;  // sn_surface_info
 };
@@ -371,7 +373,7 @@ void sn_destroy(sn_context* h)
         if (c->plane_pool[p].base) (void)hipFree(c->plane_pool[p].base);
     for (int i = 0; i < 2; ++i)
         if (c->fpool[i]) (void)hipFree(c->fpool[i]);
-    for (uint8_t* q : {c->uv.in[0], c->uv.in[1], c->uv.out[0], c->uv.out[1], c->uv.y})
+    for (uint8_t* q : {c->uv.in[0], c->uv.in[1], c->uv.out[0], c->uv.out[1], c->uv.y, c->uv.yo})
         if (q) (void)hipFree(q);
     if (c->gate.in) (void)hipStreamSynchronize(c->gate.in);
     if (c->gate.out) (void)hipStreamSynchronize(c->gate.out);
@@ -1754,7 +1756,7 @@ int sn_process_device(sn_context* h, const void* const src[3], const int32_t sp[
 // the scratch holds -- split (and shift down), the call's passes on planar LSB-aligned planes, merge (and shift up).
 
 struct SurfaceGeometry {  // of the call that walks: the batch call's clip, or the anti-aliasing call's (dh: output twice as wide and high)
-    int B = 1, bits = 8, planes = 1, max_batch = 1;
+    int B = 1, bits = 8, planes = 1, max_batch = 1, sub_w = 0, sub_h = 0;
     int w_in[3] = {0, 0, 0}, h_in[3] = {0, 0, 0}, w_out[3] = {0, 0, 0}, h_out[3] = {0, 0, 0};
     bool luma_processed = true, chroma_processed = true;
     bool all_lines = true;  // the passes read every line of the source's planes (dh; the anti-aliasing call's turns)
@@ -1762,6 +1764,7 @@ struct SurfaceGeometry {  // of the call that walks: the batch call's clip, or t
 
 struct SurfaceSide {  // a checked sn_surfaces
     bool semi = false;
+    int packing = 0;  // sn::Packing: plane[0] holds Y, U and V (SN_LAYOUT_PACKED_*)
     int shift = 0;  // SN_LAYOUT_*_MSB: 16 - bits_per_sample, the zero bits below every sample (0: the layout without _MSB)
     uint8_t* p[3] = {nullptr, nullptr, nullptr};
     int32_t pitch[3] = {0, 0, 0};
@@ -1773,35 +1776,41 @@ static int surface_header(const char* name, const sn_surfaces* s, std::string& m
 {
     if (!s) return msg = std::string(name) + " is NULL", SN_ERR_INVALID_ARG;
     if (s->struct_size != (int32_t)sizeof(sn_surfaces)) return msg = std::string(name) + ": sn_surfaces.struct_size mismatch", SN_ERR_INVALID_ARG;
-    if (s->layout < SN_LAYOUT_PLANAR || s->layout > SN_LAYOUT_SEMIPLANAR_MSB)
-        return msg = std::string(name) + ": sn_surfaces.layout must be SN_LAYOUT_PLANAR, SN_LAYOUT_SEMIPLANAR or one of their _MSB forms", SN_ERR_INVALID_ARG;
+    if (!sn::surface_layout(s->layout).valid)
+        return msg = std::string(name) + ": sn_surfaces.layout must be SN_LAYOUT_PLANAR, SN_LAYOUT_SEMIPLANAR, one of their _MSB forms or SN_LAYOUT_PACKED_*",
+               SN_ERR_INVALID_ARG;
     if (s->reserved != 0) return msg = std::string(name) + ": sn_surfaces.reserved must be zero", SN_ERR_INVALID_ARG;
     return SN_OK;
 }
 
 static bool surface_plain(const sn_surfaces* s) { return s->layout == SN_LAYOUT_PLANAR; }
 
-// ... against the planes it has to hold: w[p] samples per row of plane p (the UV plane: 2 w[1])
-static int surface_side(const char* name, const sn_surfaces* s, const int w[3], int planes, int B, int bits, SurfaceSide& out, std::string& msg)
+// ... against the planes it has to hold: w[p] samples per row of plane p (the UV plane: 2 w[1]; a packed plane: sn_surface_layout.h)
+static int surface_side(const char* name, const sn_surfaces* s, const int w[3], const SurfaceGeometry& g, SurfaceSide& out, std::string& msg)
 {
     const std::string n(name);
-    const bool msb = s->layout == SN_LAYOUT_PLANAR_MSB || s->layout == SN_LAYOUT_SEMIPLANAR_MSB;
-    out.semi = s->layout == SN_LAYOUT_SEMIPLANAR || s->layout == SN_LAYOUT_SEMIPLANAR_MSB;
-    if (msb && B != 2)
-        return msg = n + ": sn_surfaces.layout SN_LAYOUT_*_MSB needs bytes_per_sample == 2 (the sample in the high bits of a 16-bit word)", SN_ERR_UNSUPPORTED;
-    out.shift = msb ? 16 - bits : 0;
-    if (out.semi && planes < 3) return msg = n + ": SN_LAYOUT_SEMIPLANAR needs a context with num_planes == 3", SN_ERR_UNSUPPORTED;
-    if (out.semi && B == 4) return msg = n + ": SN_LAYOUT_SEMIPLANAR with bytes_per_sample == 4: no such surface exists", SN_ERR_UNSUPPORTED;
-    if (out.semi && s->plane[2]) return msg = n + ": sn_surfaces.plane[2] must be NULL with SN_LAYOUT_SEMIPLANAR (plane[1] is the UV plane)", SN_ERR_INVALID_ARG;
-    const int np = out.semi ? 2 : planes;
+    const sn::SurfaceLayout L = sn::surface_layout(s->layout);
+    const int B = g.B;
+    if (const char* why = sn::surface_refusal(L, g.planes, g.sub_w, g.sub_h, B, g.bits)) return msg = n + ": " + why, SN_ERR_UNSUPPORTED;
+    out.semi = L.semi;
+    out.packing = L.packing;
+    out.shift = sn::surface_shift(L, g.bits);
+    for (int p = sn::surface_null_from(L); p < 3; ++p)
+        if (s->plane[p])
+            return msg = n + ": sn_surfaces.plane[" + std::to_string(p) + "] must be NULL with " +
+                         (L.packing ? "SN_LAYOUT_PACKED_* (plane[0] is the whole surface)" : "SN_LAYOUT_SEMIPLANAR (plane[1] is the UV plane)"),
+                   SN_ERR_INVALID_ARG;
+    const int np = sn::surface_planes(L, g.planes), unit = sn::surface_align(L, B);
     for (int p = 0; p < np; ++p) {
-        const int64_t row = (int64_t)(out.semi && p == 1 ? 2 : 1) * w[p] * B;
+        const int64_t row = sn::surface_row_bytes(L, p, w[0], w[1], B);
         const std::string ps = std::to_string(p);
         if (!s->plane[p]) return msg = n + ": sn_surfaces.plane[" + ps + "] is NULL", SN_ERR_INVALID_ARG;
         if (s->pitch[p] < row)
             return msg = n + ": sn_surfaces.pitch[" + ps + "] " + std::to_string(s->pitch[p]) + " smaller than the row size " + std::to_string(row), SN_ERR_INVALID_ARG;
-        if (s->pitch[p] % B || s->frame_stride[p] % B || (uintptr_t)s->plane[p] % B)
-            return msg = n + ": sn_surfaces plane[" + ps + "] / pitch / frame_stride not aligned to the sample size", SN_ERR_INVALID_ARG;
+        if (s->pitch[p] % unit || s->frame_stride[p] % unit || (uintptr_t)s->plane[p] % unit)
+            return msg = n + ": sn_surfaces plane[" + ps + "] / pitch[" + ps + "] / frame_stride not aligned to " +
+                         (unit == B ? std::string("the sample size") : std::to_string(unit) + " bytes"),
+                   SN_ERR_INVALID_ARG;
         out.p[p] = static_cast<uint8_t*>(s->plane[p]);
         out.pitch[p] = s->pitch[p];
         out.fs[p] = s->frame_stride[p];
@@ -1809,23 +1818,33 @@ static int surface_side(const char* name, const sn_surfaces* s, const int w[3], 
     return SN_OK;
 }
 
-// What a call needs of the scratch: the chroma planes (both geometries, as ever) when processed chroma passes through a
-// semi-planar side or comes from an MSB-aligned source; the luma plane when processed luma comes from an MSB-aligned source.
+// What a call needs of the scratch.  Without a packed side: the chroma planes (both geometries, as ever) when processed chroma
+// passes through a semi-planar side or comes from an MSB-aligned source; the luma plane when processed luma comes from an
+// MSB-aligned source.  With a packed side (surface_walk_packed): the source's planes where they are not planar LSB-aligned
+// planes already, the destination's where the passes cannot write them in place (sangnom_hip.h has the table).
 struct SurfaceNeeds {
-    bool chroma = false, luma = false;
+    bool in = false, out = false;  // U and V in the source's / the destination's geometry
+    bool y = false, yo = false;    // luma likewise
 };
 
 static SurfaceNeeds surface_needs(const SurfaceGeometry& g, const SurfaceSide& src, const SurfaceSide& dst)
 {
     SurfaceNeeds n;
-    n.chroma = g.planes >= 3 && g.chroma_processed && (src.semi || dst.semi || src.shift != 0);
-    n.luma = g.luma_processed && src.shift != 0;
+    if (src.packing || dst.packing) {
+        n.in = src.packing || src.semi || src.shift != 0;
+        n.y = src.packing || src.shift != 0;
+        n.out = dst.packing || dst.semi;
+        n.yo = dst.packing != 0;
+        return n;
+    }
+    n.in = n.out = g.planes >= 3 && g.chroma_processed && (src.semi || dst.semi || src.shift != 0);
+    n.y = g.luma_processed && src.shift != 0;
     return n;
 }
 
 static void surface_scratch_free(sn::UvScratch& S)
 {
-    for (uint8_t** q : {&S.in[0], &S.in[1], &S.out[0], &S.out[1], &S.y}) {
+    for (uint8_t** q : {&S.in[0], &S.in[1], &S.out[0], &S.out[1], &S.y, &S.yo}) {
         if (*q) (void)hipFree(*q);
         *q = nullptr;
     }
@@ -1835,35 +1854,42 @@ static void surface_scratch_free(sn::UvScratch& S)
 
 // The scratch, once per part: for min(max_batch, what a sixteenth of the budget holds, at least 1) frames (sangnom_hip.h).
 // Allocated before anything of the call is queued; the stream is drained so that whichever stream comes first finds it filled.
-// A context that held one part and now needs the other as well gives the first back and takes both, so that the sum obeys
-// the rule; calls without an MSB-aligned source never ask for luma and allocate what they always did.
+// A context that holds some parts and now needs another gives back what it holds and takes the union, so that the sum obeys
+// the rule; calls without an MSB-aligned source or a packed side never ask for luma and allocate what they always did.
 static hipError_t surface_scratch(sn::UvScratch& S, hipStream_t st, const SurfaceGeometry& g, int64_t budget, SurfaceNeeds need)
 {
-    if ((!need.chroma || S.in[0]) && (!need.luma || S.y)) return hipSuccess;
-    need.chroma = need.chroma || S.in[0];
-    need.luma = need.luma || S.y;
+    if ((!need.in || S.in[0]) && (!need.out || S.out[0]) && (!need.y || S.y) && (!need.yo || S.yo)) return hipSuccess;
+    need.in = need.in || S.in[0];
+    need.out = need.out || S.out[0];
+    need.y = need.y || S.y;
+    need.yo = need.yo || S.yo;
     hipError_t e = hipStreamSynchronize(st);  // (what an earlier call queued may still read the part that goes)
     if (e != hipSuccess) return e;
     surface_scratch_free(S);
     S.pitch_in = (g.w_in[1] * g.B + 255) & ~255;
     S.pitch_out = (g.w_out[1] * g.B + 255) & ~255;
     S.pitch_y = (g.w_in[0] * g.B + 255) & ~255;
+    S.pitch_yo = (g.w_out[0] * g.B + 255) & ~255;
     S.in_bytes = (int64_t)S.pitch_in * g.h_in[1];
     S.out_bytes = (int64_t)S.pitch_out * g.h_out[1];
     S.y_bytes = (int64_t)S.pitch_y * g.h_in[0];
-    const int64_t per_frame = (need.chroma ? 2 * (S.in_bytes + S.out_bytes) : 0) + (need.luma ? S.y_bytes : 0);
+    S.yo_bytes = (int64_t)S.pitch_yo * g.h_out[0];
+    const int64_t per_frame = (need.in ? 2 * S.in_bytes : 0) + (need.out ? 2 * S.out_bytes : 0) + (need.y ? S.y_bytes : 0) + (need.yo ? S.yo_bytes : 0);
     const int64_t fit = budget / 16 / per_frame;
     const int cap = (int)(fit < 1 ? 1 : fit < g.max_batch ? fit : g.max_batch);
-    for (int k = 0; k < 2 && need.chroma && e == hipSuccess; ++k) {
-        e = hipMalloc(reinterpret_cast<void**>(&S.in[k]), (size_t)S.in_bytes * cap);
-        // a split writes only the lines its pass keeps: a pass that read another line would read this pattern
-        if (e == hipSuccess) e = hipMemsetAsync(S.in[k], 0xA5, (size_t)S.in_bytes * cap, st);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&S.out[k]), (size_t)S.out_bytes * cap);
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+        if (need.in) {
+            e = hipMalloc(reinterpret_cast<void**>(&S.in[k]), (size_t)S.in_bytes * cap);
+            // a split writes only the lines its pass keeps: a pass that read another line would read this pattern
+            if (e == hipSuccess) e = hipMemsetAsync(S.in[k], 0xA5, (size_t)S.in_bytes * cap, st);
+        }
+        if (need.out && e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&S.out[k]), (size_t)S.out_bytes * cap);
     }
-    if (need.luma && e == hipSuccess) {
+    if (need.y && e == hipSuccess) {
         e = hipMalloc(reinterpret_cast<void**>(&S.y), (size_t)S.y_bytes * cap);
         if (e == hipSuccess) e = hipMemsetAsync(S.y, 0xA5, (size_t)S.y_bytes * cap, st);
     }
+    if (need.yo && e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&S.yo), (size_t)S.yo_bytes * cap);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(st);
@@ -1882,8 +1908,11 @@ struct SurfacePasses {  // the call's passes on planar planes: `m` frames, point
     int (*offset)(void* self, int parity);  // the field offset of a frame (unless all_lines)
 };
 
+static int surface_walk_packed(sn::UvScratch& S, hipStream_t st, const SurfaceGeometry& g, int n, const SurfaceSide& src, const SurfaceSide& dst,
+                               const int32_t* parity, const SurfacePasses& passes, std::string& msg);
+
 // A HIP error of the walk itself comes back as SN_ERR_HIP with its text in msg; an error of the passes leaves msg empty (the
-// context holds the text).
+// context holds the text).  A call with a packed side is surface_walk_packed's.
 // MSB-aligned sides (shift ss of the source, ds of the destination): the passes see LSB-aligned planes.  The source's planes
 // go through scratch, shifted down on the way (chroma inside the split when it is semi-planar); the passes write LSB-aligned
 // samples into the destination's planes (or the chroma scratch a merge reads), which are then shifted up where they lie (inside
@@ -1899,6 +1928,7 @@ static int surface_walk(sn::UvScratch& S, hipStream_t st, const SurfaceGeometry&
             return SN_ERR_HIP;                                               \
         }                                                                    \
     } while (0)
+    if (src.packing || dst.packing) return surface_walk_packed(S, st, g, n, src, dst, parity, passes, msg);
     const int B = g.B, ss = src.shift, ds = dst.shift;
     const bool msb = ss != 0 || ds != 0, chroma = g.planes >= 3;
     const SurfaceNeeds need = surface_needs(g, src, dst);
@@ -1929,7 +1959,7 @@ static int surface_walk(sn::UvScratch& S, hipStream_t st, const SurfaceGeometry&
     }
     if (msb && !g.luma_processed)  // (the caller has told its passes: luma_elsewhere)
         SN_UV_HIP(sn::launch_shift16(st, n, src.p[0], src.fs[0], src.pitch[0], g.w_in[0], g.h_in[0], dst.p[0], dst.fs[0], dst.pitch[0], -1, ss, ds));
-    const int cap = need.chroma || need.luma ? S.cap : n;
+    const int cap = need.in || need.y ? S.cap : n;
     for (int f0 = 0; f0 < n; f0 += cap) {
         const int m = n - f0 < cap ? n - f0 : cap;
         const int32_t* par = parity ? parity + f0 : nullptr;
@@ -1942,35 +1972,35 @@ static int surface_walk(sn::UvScratch& S, hipStream_t st, const SurfaceGeometry&
             d[p] = dst.p[r] + (int64_t)f0 * dst.fs[r], dfs[p] = dst.fs[r], dp[p] = dst.pitch[r];
         }
         // the lines the pass keeps: one launch per run of frames with the same field offset, as run_batch cuts them
-        for (int g0 = 0; g0 < m && (need.luma || (need.chroma && (src.semi || ss != 0)));) {
+        for (int g0 = 0; g0 < m && (need.y || (need.in && (src.semi || ss != 0)));) {
             int g1 = m, lines = -1;
             if (!g.all_lines) {
                 lines = passes.offset(passes.self, par ? par[g0] : 1);
                 for (g1 = g0 + 1; g1 < m && passes.offset(passes.self, par ? par[g1] : 1) == lines;) ++g1;
             }
-            if (need.luma)
+            if (need.y)
                 SN_UV_HIP(sn::launch_shift16(st, g1 - g0, src.p[0] + (f0 + g0) * src.fs[0], src.fs[0], src.pitch[0], g.w_in[0], g.h_in[0],
                                              S.y + g0 * S.y_bytes, S.y_bytes, S.pitch_y, lines, ss, 0));
-            if (need.chroma && src.semi) {
+            if (need.in && src.semi) {
                 SN_UV_HIP(sn::launch_uv_split(st, B, g1 - g0, src.p[1] + (f0 + g0) * src.fs[1], src.fs[1], src.pitch[1], g.w_in[1], g.h_in[1],
                                               S.in[0] + g0 * S.in_bytes, S.in_bytes, S.pitch_in, S.in[1] + g0 * S.in_bytes, S.in_bytes, S.pitch_in, lines, ss, 0));
-            } else if (need.chroma && ss != 0) {
+            } else if (need.in && ss != 0) {
                 for (int k = 0; k < 2; ++k)
                     SN_UV_HIP(sn::launch_shift16(st, g1 - g0, src.p[1 + k] + (f0 + g0) * src.fs[1 + k], src.fs[1 + k], src.pitch[1 + k], g.w_in[1], g.h_in[1],
                                                  S.in[k] + g0 * S.in_bytes, S.in_bytes, S.pitch_in, lines, ss, 0));
             }
             g0 = g1;
         }
-        if (need.luma) s[0] = S.y, sfs[0] = S.y_bytes, sp[0] = S.pitch_y;
-        if (need.chroma && (src.semi || ss != 0)) {
+        if (need.y) s[0] = S.y, sfs[0] = S.y_bytes, sp[0] = S.pitch_y;
+        if (need.in && (src.semi || ss != 0)) {
             for (int k = 0; k < 2; ++k) s[1 + k] = S.in[k], sfs[1 + k] = S.in_bytes, sp[1 + k] = S.pitch_in;
             if (src.semi) S.split_frames += m;
         }
-        if (need.chroma && dst.semi)
+        if (need.in && dst.semi)
             for (int k = 0; k < 2; ++k) d[1 + k] = S.out[k], dfs[1 + k] = S.out_bytes, dp[1 + k] = S.pitch_out;
         const int rc = passes.run(passes.self, m, s, sfs, sp, d, dfs, dp, par);
         if (rc != SN_OK) return rc;
-        if (need.chroma && dst.semi) {
+        if (need.in && dst.semi) {
             SN_UV_HIP(sn::launch_uv_merge(st, B, m, S.out[0], S.out_bytes, S.pitch_out, S.out[1], S.out_bytes, S.pitch_out, g.w_out[1], g.h_out[1],
                                           dst.p[1] + (int64_t)f0 * dst.fs[1], dst.fs[1], dst.pitch[1], 0, ds));
             S.merged_frames += m;
@@ -1981,6 +2011,117 @@ static int surface_walk(sn::UvScratch& S, hipStream_t st, const SurfaceGeometry&
             uint8_t* const q = dst.p[p] + (int64_t)f0 * dst.fs[p];
             SN_UV_HIP(sn::launch_shift16(st, m, q, dst.fs[p], dst.pitch[p], g.w_out[p], g.h_out[p], q, dst.fs[p], dst.pitch[p], -1, 0, ds));
         }
+    }
+    return SN_OK;
+#undef SN_UV_HIP
+}
+
+// A call with a packed side (SN_LAYOUT_PACKED_*: one plane of Y, U and V).  Per chunk: the source becomes three planar LSB-aligned
+// planes -- a packed source unpacked into the scratch (MSB words shifted down inside the unpack), another one as surface_walk has
+// it --, the passes run on them into the destination's planes or, for a packed or semi-planar destination, into the output
+// scratch, and a packed destination is packed from there (MSB shift and v210 mask inside the pack), all lines.  A plane that is
+// not processed never reaches a pass (the caller has told its passes: luma_elsewhere; chroma_elsewhere): every line of the source
+// is made planar, and the plane goes from there to the destination -- read by the pack, or converted as in surface_walk.
+static int surface_walk_packed(sn::UvScratch& S, hipStream_t st, const SurfaceGeometry& g, int n, const SurfaceSide& src, const SurfaceSide& dst,
+                               const int32_t* parity, const SurfacePasses& passes, std::string& msg)
+{
+#define SN_UV_HIP(call)                                                      \
+    do {                                                                     \
+        hipError_t e_ = (call);                                              \
+        if (e_ != hipSuccess) {                                              \
+            msg = std::string(#call " failed: ") + hipGetErrorString(e_);    \
+            return SN_ERR_HIP;                                               \
+        }                                                                    \
+    } while (0)
+    const int B = g.B, ss = src.shift, ds = dst.shift;
+    const bool lp = g.luma_processed, cp = g.chroma_processed;
+    const bool every_line = g.all_lines || !lp || !cp;
+    const bool y_scratch = src.packing || ss != 0, c_scratch = src.packing || src.semi || ss != 0;
+    for (int f0 = 0; f0 < n; f0 += S.cap) {
+        const int m = n - f0 < S.cap ? n - f0 : S.cap;
+        const int32_t* par = parity ? parity + f0 : nullptr;
+        // ---- the source as planar LSB-aligned planes: one launch per run of frames with the same field offset
+        for (int g0 = 0; g0 < m && (y_scratch || c_scratch);) {
+            int g1 = m, lines = -1;
+            if (!every_line) {
+                lines = passes.offset(passes.self, par ? par[g0] : 1);
+                for (g1 = g0 + 1; g1 < m && passes.offset(passes.self, par ? par[g1] : 1) == lines;) ++g1;
+            }
+            const int k = g1 - g0;
+            const int64_t f = f0 + g0;
+            if (src.packing) {
+                SN_UV_HIP(sn::launch_unpack(st, src.packing, B, k, src.p[0] + f * src.fs[0], src.fs[0], src.pitch[0], g.w_in[0], g.h_in[0],
+                                            S.y + g0 * S.y_bytes, S.y_bytes, S.pitch_y, S.in[0] + g0 * S.in_bytes, S.in_bytes, S.pitch_in,
+                                            S.in[1] + g0 * S.in_bytes, S.in_bytes, S.pitch_in, lines, ss));
+            } else {
+                if (y_scratch)
+                    SN_UV_HIP(sn::launch_shift16(st, k, src.p[0] + f * src.fs[0], src.fs[0], src.pitch[0], g.w_in[0], g.h_in[0], S.y + g0 * S.y_bytes,
+                                                 S.y_bytes, S.pitch_y, lines, ss, 0));
+                if (src.semi) {
+                    SN_UV_HIP(sn::launch_uv_split(st, B, k, src.p[1] + f * src.fs[1], src.fs[1], src.pitch[1], g.w_in[1], g.h_in[1], S.in[0] + g0 * S.in_bytes,
+                                                  S.in_bytes, S.pitch_in, S.in[1] + g0 * S.in_bytes, S.in_bytes, S.pitch_in, lines, ss, 0));
+                } else if (c_scratch) {
+                    for (int c = 0; c < 2; ++c)
+                        SN_UV_HIP(sn::launch_shift16(st, k, src.p[1 + c] + f * src.fs[1 + c], src.fs[1 + c], src.pitch[1 + c], g.w_in[1], g.h_in[1],
+                                                     S.in[c] + g0 * S.in_bytes, S.in_bytes, S.pitch_in, lines, ss, 0));
+                }
+            }
+            g0 = g1;
+        }
+        if (src.packing || src.semi) S.split_frames += m;
+        const void* s[3];
+        void* d[3];
+        int64_t sfs[3], dfs[3];
+        int32_t sp[3], dp[3];
+        for (int p = 0; p < 3; ++p) {
+            if (p == 0 ? y_scratch : c_scratch) {
+                s[p] = p == 0 ? S.y : S.in[p - 1], sfs[p] = p == 0 ? S.y_bytes : S.in_bytes, sp[p] = p == 0 ? S.pitch_y : S.pitch_in;
+            } else {
+                s[p] = src.p[p] + (int64_t)f0 * src.fs[p], sfs[p] = src.fs[p], sp[p] = src.pitch[p];
+            }
+            if (dst.packing || (dst.semi && p > 0)) {
+                d[p] = p == 0 ? S.yo : S.out[p - 1], dfs[p] = p == 0 ? S.yo_bytes : S.out_bytes, dp[p] = p == 0 ? S.pitch_yo : S.pitch_out;
+            } else {
+                d[p] = dst.p[p] + (int64_t)f0 * dst.fs[p], dfs[p] = dst.fs[p], dp[p] = dst.pitch[p];
+            }
+        }
+        // ---- the passes
+        const int rc = passes.run(passes.self, m, s, sfs, sp, d, dfs, dp, par);
+        if (rc != SN_OK) return rc;
+        // ---- the destination.  A plane that is not processed has the source's geometry and is read where the source's lies.
+        const uint8_t* o[3];
+        int64_t ofs[3];
+        int32_t op[3];
+        for (int p = 0; p < 3; ++p) {
+            const bool processed = p == 0 ? lp : cp;
+            o[p] = static_cast<const uint8_t*>(processed ? d[p] : s[p]), ofs[p] = processed ? dfs[p] : sfs[p], op[p] = processed ? dp[p] : sp[p];
+        }
+        if (dst.packing) {
+            SN_UV_HIP(sn::launch_pack(st, dst.packing, B, m, o[0], ofs[0], op[0], o[1], ofs[1], op[1], o[2], ofs[2], op[2], g.w_out[0], g.h_out[0],
+                                      dst.p[0] + (int64_t)f0 * dst.fs[0], dst.fs[0], dst.pitch[0], ds));
+            S.merged_frames += m;
+        } else {
+            for (int p = 0; p < 3; ++p) {
+                if (dst.semi && p > 0) continue;
+                const bool processed = p == 0 ? lp : cp;
+                uint8_t* const q = dst.p[p] + (int64_t)f0 * dst.fs[p];
+                if (processed && ds != 0) {  // shifted up where the passes wrote it
+                    SN_UV_HIP(sn::launch_shift16(st, m, q, dst.fs[p], dst.pitch[p], g.w_out[p], g.h_out[p], q, dst.fs[p], dst.pitch[p], -1, 0, ds));
+                } else if (!processed && B == 2) {
+                    SN_UV_HIP(sn::launch_shift16(st, m, o[p], ofs[p], op[p], g.w_out[p], g.h_out[p], q, dst.fs[p], dst.pitch[p], -1, 0, ds));
+                } else if (!processed) {
+                    for (int f = 0; f < m; ++f)
+                        SN_UV_HIP(hipMemcpy2DAsync(q + f * dst.fs[p], (size_t)dst.pitch[p], o[p] + f * ofs[p], (size_t)op[p], (size_t)g.w_out[p] * B,
+                                                   (size_t)g.h_out[p], hipMemcpyDeviceToDevice, st));
+                }
+            }
+            if (dst.semi) {
+                SN_UV_HIP(sn::launch_uv_merge(st, B, m, o[1], ofs[1], op[1], o[2], ofs[2], op[2], g.w_out[1], g.h_out[1], dst.p[1] + (int64_t)f0 * dst.fs[1],
+                                              dst.fs[1], dst.pitch[1], 0, ds));
+                S.merged_frames += m;
+            }
+        }
+        if (!cp) S.copied_frames += m;
     }
     return SN_OK;
 #undef SN_UV_HIP
@@ -2027,20 +2168,21 @@ int sn_process_device_surfaces(sn_context* h, int32_t nframes, const sn_surfaces
     g.B = c->cfg.bytes_per_sample;
     g.bits = c->cfg.bits_per_sample;
     g.planes = c->nplanes();
+    g.sub_w = c->cfg.sub_w, g.sub_h = c->cfg.sub_h;
     g.max_batch = c->cfg.max_batch;
     for (int p = 0; p < g.planes; ++p) g.w_in[p] = g.w_out[p] = c->plane_w(p), g.h_in[p] = c->plane_h_in(p), g.h_out[p] = c->plane_h_out(p);
     g.luma_processed = c->cfg.dh || c->process[0];
     g.chroma_processed = c->cfg.dh || c->process[1];
     g.all_lines = c->cfg.dh != 0;
     SurfaceSide ss, ds;
-    rc = surface_side("src", src, g.w_in, g.planes, g.B, g.bits, ss, msg);
-    if (rc == SN_OK) rc = surface_side("dst", dst, g.w_out, g.planes, g.B, g.bits, ds, msg);
+    rc = surface_side("src", src, g.w_in, g, ss, msg);
+    if (rc == SN_OK) rc = surface_side("dst", dst, g.w_out, g, ds, msg);
     if (rc != SN_OK) return sn::fail(c, rc, "%s", msg.c_str());
     if (nframes == 0) return SN_OK;
     SN_HIP(c, hipSetDevice(c->device));
     SN_HIP(c, surface_scratch(c->uv, c->stream, g, scratch_budget(c), surface_needs(g, ss, ds)));
     const SurfacePasses passes{c, sn_surface_run, sn_surface_offset};
-    c->luma_elsewhere = (ss.shift != 0 || ds.shift != 0) && !g.luma_processed;
+    c->luma_elsewhere = (ss.shift != 0 || ds.shift != 0 || ss.packing || ds.packing) && !g.luma_processed;
     rc = surface_walk(c->uv, c->stream, g, nframes, ss, ds, parity, passes, msg);
     c->luma_elsewhere = false;
     if (rc != SN_OK && !msg.empty()) return sn::fail(c, rc, "%s", msg.c_str());
@@ -2796,7 +2938,7 @@ void sn_aa_destroy(sn_aa_context* a)
     for (int p = 0; p < 3; ++p)
         for (uint8_t* q : {a->d_t1[p], a->d_u1[p], a->d_t2[p]})
             if (q) (void)hipFree(q);
-    for (uint8_t* q : {a->uv.in[0], a->uv.in[1], a->uv.out[0], a->uv.out[1], a->uv.y})
+    for (uint8_t* q : {a->uv.in[0], a->uv.in[1], a->uv.out[0], a->uv.out[1], a->uv.y, a->uv.yo})
         if (q) (void)hipFree(q);
     for (auto& g : a->groups) aa_free_group(g);
     for (hipStream_t st : {a->up, a->down})
@@ -2986,20 +3128,21 @@ int sn_aa_process_device_surfaces(sn_aa_context* a, int32_t nframes, const sn_su
     g.B = a->cfg.bytes_per_sample;
     g.bits = a->cfg.bits_per_sample;
     g.planes = a->planes;
+    g.sub_w = a->cfg.sub_w, g.sub_h = a->cfg.sub_h;
     g.max_batch = a->max_batch;
     for (int p = 0; p < g.planes; ++p) g.w_in[p] = a->w[p], g.h_in[p] = a->h[p], g.w_out[p] = a->ow[p], g.h_out[p] = a->oh[p];
     g.luma_processed = a->process[0];
     g.chroma_processed = g.planes < 3 || a->process[1];
     g.all_lines = true;  // a turn reads whole source rows, whichever destination lines it writes
     SurfaceSide ss, ds;
-    rc = surface_side("src", src, g.w_in, g.planes, g.B, g.bits, ss, msg);
-    if (rc == SN_OK) rc = surface_side("dst", dst, g.w_out, g.planes, g.B, g.bits, ds, msg);
+    rc = surface_side("src", src, g.w_in, g, ss, msg);
+    if (rc == SN_OK) rc = surface_side("dst", dst, g.w_out, g, ds, msg);
     if (rc != SN_OK) return aa_fail(a, rc, msg);
     if (nframes == 0) return SN_OK;
     SN_AA_HIP(hipSetDevice(a->cfg.device));
     SN_AA_HIP(surface_scratch(a->uv, a->stream, g, scratch_budget(reinterpret_cast<Context*>(a->first)), surface_needs(g, ss, ds)));
     const SurfacePasses passes{a, aa_surface_run, nullptr};
-    a->luma_elsewhere = (ss.shift != 0 || ds.shift != 0) && !g.luma_processed;
+    a->luma_elsewhere = (ss.shift != 0 || ds.shift != 0 || ss.packing || ds.packing) && !g.luma_processed;
     rc = surface_walk(a->uv, a->stream, g, nframes, ss, ds, parity, passes, msg);
     a->luma_elsewhere = false;
     if (rc != SN_OK && !msg.empty()) return aa_fail(a, rc, msg);

@@ -84,6 +84,17 @@ hipError_t launch_uv_merge(hipStream_t s, int bytes, int nframes, const uint8_t*
 hipError_t launch_shift16(hipStream_t s, int nframes, const uint8_t* src, int64_t src_frame_stride, int src_pitch, int w, int h, uint8_t* dst,
                           int64_t dst_frame_stride, int dst_pitch, int line_parity, int ss, int ds);
 
+// sn_packed.hip: packed 4:2:2 (one plane of Y, U and V; packing = sn::Packing of sn_surface_layout.h: 1 YUYV, 2 UYVY, 3 v210)
+// <-> a Y plane of w x h samples and a U and a V plane of w / 2 x h.  line_parity as above (the pack writes every line).
+// ss: the unpack shifts every 16-bit word it reads down; ds: the pack shifts every sample up (MSB-aligned words: Y210 / Y212).
+// v210 packs sample & 0x3FF and zero fields for pixels at or beyond w.  One side is never written.
+hipError_t launch_unpack(hipStream_t s, int packing, int bytes, int nframes, const uint8_t* pk, int64_t pk_frame_stride, int pk_pitch, int w, int h,
+                         uint8_t* y, int64_t y_frame_stride, int y_pitch, uint8_t* u, int64_t u_frame_stride, int u_pitch, uint8_t* v,
+                         int64_t v_frame_stride, int v_pitch, int line_parity, int ss);
+hipError_t launch_pack(hipStream_t s, int packing, int bytes, int nframes, const uint8_t* y, int64_t y_frame_stride, int y_pitch, const uint8_t* u,
+                       int64_t u_frame_stride, int u_pitch, const uint8_t* v, int64_t v_frame_stride, int v_pitch, int w, int h, uint8_t* pk,
+                       int64_t pk_frame_stride, int pk_pitch, int ds);
+
 // sn_pool_kernels.hip: the three-kernel path over the HBM-resident pool (every format).
 hipError_t launch_assemble(hipStream_t s, const PlaneArgs& p, int bytes, int nframes);
 hipError_t launch_pool_plane(hipStream_t s, const PlaneArgs& p, const PoolArgs& pool, int bytes,

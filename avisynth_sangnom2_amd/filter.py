@@ -49,6 +49,7 @@ _FORMATS = {
     "YUV420P12": dict(bytes=2, bits=12, planes=3, subw=1, subh=1),
     "YUV420P16": dict(bytes=2, bits=16, planes=3, subw=1, subh=1),
     "YUV422P8": dict(bytes=1, bits=8, planes=3, subw=1, subh=0),
+    "YUV422P10": dict(bytes=2, bits=10, planes=3, subw=1, subh=0), "YUV422P12": dict(bytes=2, bits=12, planes=3, subw=1, subh=0),
     "YUV444P8": dict(bytes=1, bits=8, planes=3), "YUV444P16": dict(bytes=2, bits=16, planes=3),
     "YUV444PS": dict(bytes=4, bits=32, planes=3), "YUV420PS": dict(bytes=4, bits=32, planes=3, subw=1, subh=1),
     "YUV422PS": dict(bytes=4, bits=32, planes=3, subw=1, subh=0),
@@ -60,10 +61,31 @@ def clip_format(name: str, width: int, height: int) -> ClipFormat:
     return ClipFormat(width=width, height=height, **_FORMATS[name])
 
 
-def _surfaces_of(planes, shape_of, nplanes, B, what, msb=False):
+def _packed_surface_of(t, shape_of, B, what, packed, msb):
+    """sn_surfaces of ONE device tensor that holds a packed 4:2:2 batch: [N, H, 2 W] of the sample type for "yuyv" / "uyvy",
+    [N, H, 4 ceil(W / 6)] int32 for "v210"."""
+    if (packed, bool(msb)) not in capi.PACKED_LAYOUTS:
+        raise ValueError(f"{what}: packed must be 'yuyv', 'uyvy' or 'v210' (v210 has no MSB form)")
+    if isinstance(t, (list, tuple)):
+        if len(t) != 1:
+            raise ValueError(f"{what}: a packed surface is ONE tensor")
+        t = t[0]
+    H, W = shape_of(0)
+    v210 = packed == "v210"
+    want, size = ((H, 4 * ((W + 5) // 6)), 4) if v210 else ((H, 2 * W), B)
+    if t.dim() != 3 or tuple(t.shape[1:]) != want:
+        raise ValueError(f"{what}: shape {tuple(t.shape)}, expected (N,) + {want}")
+    if t.element_size() != size or not t.is_cuda or t.stride(-1) != 1:
+        raise ValueError(f"{what}: a device-resident tensor of {'int32' if v210 else 'the sample type'} with contiguous rows expected")
+    return capi.surfaces(capi.PACKED_LAYOUTS[(packed, bool(msb))], [t.data_ptr()], [t.stride(1) * size], [t.stride(0) * size]), t.shape[0]
+
+
+def _surfaces_of(planes, shape_of, nplanes, B, what, msb=False, packed=None):
     """sn_surfaces of device tensors: the planar tensors process_batch takes ([N, H_p, W_p] each), or two tensors
     [Y [N, H, W], UV [N, Hc, Wc, 2]] for a semi-planar surface (NV12, P010 / P016, NV16, NV24; UV[..., 0] is U).
-    msb: 16-bit words with the sample in the high bits (SN_LAYOUT_*_MSB)."""
+    msb: 16-bit words with the sample in the high bits (SN_LAYOUT_*_MSB).  packed: "yuyv", "uyvy" or "v210" -- one tensor."""
+    if packed is not None:
+        return _packed_surface_of(planes, shape_of, B, what, packed, msb)
     planes = list(planes)
     semi = len(planes) == 2 and planes[1].dim() == 4
     if not semi and len(planes) < nplanes:
@@ -312,14 +334,16 @@ class SangNom2:
         self._check(self._lib.sn_process_device_strided(self._h, N, sp, sfs, spi, dp, dfs, dpi, par))
         return dst
 
-    def process_surfaces(self, src, dst, parity=None, src_msb=False, dst_msb=False):
+    def process_surfaces(self, src, dst, parity=None, src_msb=False, dst_msb=False, src_packed=None, dst_packed=None):
         """process_batch for decoder and encoder surfaces (sn_process_device_surfaces): each of src and dst is either the
         planar tensors process_batch takes or [Y [N, H, W], UV [N, Hc, Wc, 2]], independently.  src_msb / dst_msb: that
         side's 16-bit words hold the sample in their high bits (P010 on a 10-bit clip, P012 on a 12-bit one); the result is
-        the clip's own, aligned as dst_msb says.  Asynchronous on the context's stream (the first call that needs scratch
+        the clip's own, aligned as dst_msb says.  src_packed / dst_packed ("yuyv", "uyvy", "v210"; 4:2:2 clips): that side is
+        ONE tensor of packed rows -- [N, H, 2 W] of the sample type (YUY2 / UYVY; Y210 / Y212 with the _msb flag), or
+        [N, H, 4 ceil(W / 6)] int32 for v210.  Asynchronous on the context's stream (the first call that needs scratch
         allocates it)."""
-        s, N = _surfaces_of(src, self.plane_shape_in, self.nplanes, self.clip.bytes, "src", src_msb)
-        d, Nd = _surfaces_of(dst, self.plane_shape_out, self.nplanes, self.clip.bytes, "dst", dst_msb)
+        s, N = _surfaces_of(src, self.plane_shape_in, self.nplanes, self.clip.bytes, "src", src_msb, src_packed)
+        d, Nd = _surfaces_of(dst, self.plane_shape_out, self.nplanes, self.clip.bytes, "dst", dst_msb, dst_packed)
         if N != Nd:
             raise ValueError("src and dst must carry the same number of frames")
         par = None if parity is None else (ctypes.c_int32 * N)(*[int(x) for x in parity])
@@ -465,12 +489,12 @@ class SangNomAA(_AAContext):
         self._check(self._lib.sn_aa_process_device_strided(self._h, N, sp, sfs, spi, dp, dfs, dpi, par))
         return dst
 
-    def process_surfaces(self, src, dst, parity=None, src_msb=False, dst_msb=False):
+    def process_surfaces(self, src, dst, parity=None, src_msb=False, dst_msb=False, src_packed=None, dst_packed=None):
         """process_batch for decoder and encoder surfaces (sn_aa_process_device_surfaces): each of src and dst is either
         the planar tensors or [Y [N, H, W], UV [N, Hc, Wc, 2]] (dh: dst is [Y [N, 2 H, 2 W], UV [N, 2 Hc, 2 Wc, 2]]).
-        src_msb / dst_msb: as for SangNom2.process_surfaces."""
-        s, N = _surfaces_of(src, self.plane_shape, self.nplanes, self.clip.bytes, "src", src_msb)
-        d, Nd = _surfaces_of(dst, self.plane_shape_out, self.nplanes, self.clip.bytes, "dst", dst_msb)
+        src_msb / dst_msb, src_packed / dst_packed: as for SangNom2.process_surfaces (dh: a packed dst has rows for 2 W)."""
+        s, N = _surfaces_of(src, self.plane_shape, self.nplanes, self.clip.bytes, "src", src_msb, src_packed)
+        d, Nd = _surfaces_of(dst, self.plane_shape_out, self.nplanes, self.clip.bytes, "dst", dst_msb, dst_packed)
         if N != Nd:
             raise ValueError("src and dst must carry the same number of frames")
         par = None if parity is None else (ctypes.c_int32 * N)(*[int(x) for x in parity])

@@ -409,8 +409,53 @@ int sn_aa_collect_host(sn_aa_context* ctx, int32_t slot, void* const dst[3], con
  * writes planes twice as wide and twice as high: 2 * (2 * chroma width) * bytes_per_sample).  SN_ERR_UNSUPPORTED:
  * SN_LAYOUT_SEMIPLANAR on a context with num_planes == 1 or bytes_per_sample == 4 (no such surface exists); an _MSB
  * layout on a context with bytes_per_sample != 2 (the text names layout).  A refused call queues nothing and leaves the
- * context usable. */
-enum { SN_LAYOUT_PLANAR = 0, SN_LAYOUT_SEMIPLANAR = 1, SN_LAYOUT_PLANAR_MSB = 2, SN_LAYOUT_SEMIPLANAR_MSB = 3 };
+ * context usable.
+ *
+ * Packed 4:2:2 -- what SDI / HDMI capture and uncompressed intermediates hand over: ONE plane that holds Y, U and V.
+ *   SN_LAYOUT_PACKED_YUYV      Y0 U0 Y1 V0 ..., samples of the context's type (YUY2 on an 8-bit context, Y216 on a 16-bit one)
+ *   SN_LAYOUT_PACKED_UYVY      U0 Y0 V0 Y1 ... (UYVY; v216 on a 16-bit context)
+ *   SN_LAYOUT_PACKED_YUYV_MSB  as PACKED_YUYV, 16-bit words with the sample in the high bits (Y210 on a 10-bit context, Y212
+ *                              on a 12-bit one); the shift is 16 - bits_per_sample as for the other _MSB layouts
+ *   SN_LAYOUT_PACKED_UYVY_MSB  as PACKED_UYVY, MSB-aligned
+ *   SN_LAYOUT_PACKED_V210      v210, 10-bit contexts only: blocks of 16 bytes, four little-endian 32-bit words for six pixels,
+ *                              three 10-bit fields per word at bits 0-9, 10-19 and 20-29:
+ *                                word 0 = U0 | Y0 << 10 | V0 << 20      word 1 = Y1 | U1 << 10 | Y2 << 20
+ *                                word 2 = V1 | Y3 << 10 | U2 << 20      word 3 = Y4 | V2 << 10 | Y5 << 20
+ *                              The width is even, so a partial last block holds 2 or 4 pixels.  On input bits 30-31 of every
+ *                              word and the fields of pixels >= width are ignored; on output every field is sample & 0x3FF,
+ *                              bits 30-31 are zero and the fields of pixels >= width are zero.  (The filter does not clamp: an
+ *                              interpolated sample above 1023 loses its high bits, as in an MSB destination.)
+ * (Values 4..7 are not layouts.)  plane[0] / pitch[0] / frame_stride[0] describe the surface; plane[1] and plane[2] must be
+ * NULL (SN_ERR_INVALID_ARG names the field), their pitches and strides are ignored.  A row of luma width w -- the side's own:
+ * the anti-aliasing call's dh destination is 2 w wide -- is 2 * w * bytes_per_sample bytes for YUYV / UYVY and 16 * ceil(w / 6)
+ * for v210; pitch[0] below that is SN_ERR_INVALID_ARG naming pitch[0].  Base, pitch and frame stride are multiples of the sample
+ * size, for v210 of 4 (the conventional v210 pitch, a multiple of 128, is accepted and not required); surfaces whose base,
+ * pitch and frame stride are multiples of 16 move 16 bytes per access.  The context must be 4:2:2 with integer samples
+ * (num_planes == 3, sub_w == 1, sub_h == 0, bytes_per_sample 1 or 2), with bytes_per_sample == 2 for the _MSB forms and
+ * bits_per_sample == 10 for v210; anything else is SN_ERR_UNSUPPORTED with "layout" in the text.
+ * One rule: the destination holds, bit for bit, what the planar call gives on the unpacked planes (MSB words shifted down,
+ * v210 fields extracted), packed as the destination's layout says (MSB shift up, v210 mask) -- in every configuration the
+ * context accepts and in both calls.  The two sides are independent: packed pairs with planar, semi-planar (NV16) and the
+ * other packed layouts in either direction.  Bytes of a destination row beyond the row size, and everything between rows,
+ * are never written; the source is never written.
+ * A packed source is unpacked into planar scratch (the lines the passes keep; every line with dh, in the anti-aliasing call and
+ * when a plane is only copied), the passes run there, and a packed destination is packed from planar scratch behind them, all
+ * lines.  A plane that is not processed never reaches a pass: it goes from the unpacked source to the destination.  A packed
+ * source frame counts once in split_frames, a packed destination frame once in merged_frames; copied_frames keeps its meaning.
+ * Scratch per frame of a call with a packed side, pitches rounded up to 256 bytes (R(x) = x rounded up to 256; w, h the
+ * source's luma geometry, W, H the destination's, B = bytes_per_sample):
+ *     source packed, MSB-aligned or semi-planar:   2 * R(w / 2 * B) * h   (U and V in)
+ *     source packed or MSB-aligned:                + R(w * B) * h         (Y in)
+ *     destination packed or semi-planar:           2 * R(W / 2 * B) * H   (U and V out)
+ *     destination packed:                          + R(W * B) * H         (Y out)
+ * for min(max_batch, what a sixteenth of the budget holds, at least 1) frames, as above.  A context whose need grows gives
+ * back what it holds and takes the union of what it held and what it needs now; the calls without a packed side ask for what
+ * they always did. */
+enum {
+    SN_LAYOUT_PLANAR = 0, SN_LAYOUT_SEMIPLANAR = 1, SN_LAYOUT_PLANAR_MSB = 2, SN_LAYOUT_SEMIPLANAR_MSB = 3,
+    SN_LAYOUT_PACKED_YUYV = 8, SN_LAYOUT_PACKED_UYVY = 9, SN_LAYOUT_PACKED_YUYV_MSB = 10, SN_LAYOUT_PACKED_UYVY_MSB = 11,
+    SN_LAYOUT_PACKED_V210 = 12
+};
 typedef struct sn_surfaces {
     int32_t struct_size;      /* = sizeof(sn_surfaces)                                        */
     int32_t layout;           /* SN_LAYOUT_*                                                 */

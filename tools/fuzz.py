@@ -5,6 +5,7 @@ configurations run with opt=1 (the SSE2 arithmetic, against tests/sse2_model.py)
 Wide 16-bit and float configurations (3872 .. 8192 columns) draw sn_options.column_parts.
 Device batches of three-plane 8 / 16-bit clips draw the layout of each side: planar, or semi-planar (a UV plane; sn_process_device_surfaces).
 Device batches of 9..15-bit clips also draw each side's alignment: LSB, or MSB (P010 / P012: the sample in the high bits, random low bits below it).
+Device batches of 4:2:2 8 / 16-bit clips draw a packed layout for each side as well (YUYV / UYVY, their MSB forms, v210 on 10-bit clips; junk where a source may carry it).
 usage: python tools/fuzz.py [--seconds 120] [--seed 1]"""
 import argparse
 import os
@@ -17,11 +18,12 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from avisynth_sangnom2_amd import ClipFormat, SangNom2, clip_format, synth  # noqa: E402
 from oracle.oracle import Config, Oracle  # noqa: E402
+from tests import packed_surface_cases as pc  # noqa: E402
 from tests import sse2_model as sm  # noqa: E402
 from tests.util import to_host  # noqa: E402
 
 FORMATS = ["Y8", "Y8", "Y8", "Y10", "Y16", "Y32", "YUV420P8", "YUV420P8", "YUV420P16", "YUV422P8", "YUV444P8", "YUV444PS", "YUV420PS", "YUV420P10",
-           "YUV420P12"]
+           "YUV420P12", "YUV422P10", "YUV422P10", "YUV422P12", "YUV422P16"]
 
 
 def cfg_of(clip, **kw):
@@ -41,6 +43,9 @@ def same(a, b):
     return np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
+CURRENT = [""]  # the configuration under way, for the report when a call raises
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=120.0)
@@ -50,7 +55,7 @@ def main():
     t_end = time.time() + a.seconds
     n = bad = 0
     stats = {"fused": 0, "pool": 0, "ring": 0, "host": 0, "batch": 0, "frames": 0, "pixels": 0, "banded_frames": 0, "band_fallbacks": 0, "chained_frames": 0,
-             "uv_sweep_configs": 0, "chain_redone": 0, "opt1": 0, "opt1_sweeps": 0, "part_frames": 0, "part_fallbacks": 0, "semi_sides": 0, "msb_sides": 0}
+             "uv_sweep_configs": 0, "chain_redone": 0, "opt1": 0, "opt1_sweeps": 0, "part_frames": 0, "part_fallbacks": 0, "semi_sides": 0, "msb_sides": 0, "packed_sides": 0}
     while time.time() < t_end:
         fmt = rng.choice(FORMATS)
         wide = rng.random() < 0.15
@@ -106,6 +111,7 @@ def main():
                     o = mk() if ext == "fresh" else per_plane.setdefault(p, mk())
                     outs.append(o([pl], parity[f])[0])
                 want.append(outs)
+        CURRENT[0] = f"{fmt} {w}x{h} {kw} ext={ext} way={way} nframes={nframes} opt={opt} sse2_sweeps={knob} column_parts={column_parts} pattern={pattern}"
         small = rng.choice([1, 0])  # SN_SMALL_SWEEP: the whole-plane sweeps, or auto mode's small-launch paths (bands, pool kernels)
         try:
             sweeps = rng.choice([0, 0, 0, 1])  # 8-bit 4:2:0: U and V as one sweep (default) or a sweep each
@@ -146,17 +152,39 @@ def main():
                     src = [src[0], torch.stack([src[1], src[2]], dim=-1).contiguous()]
                 if semi_out:
                     dst = [dst[0], torch.zeros(tuple(dst[1].shape) + (2,), dtype=dst[1].dtype, device=dev)]
+                # 4:2:2 8 / 16-bit clips: each side may be ONE packed plane instead (tests/packed_surface_cases.py has the numpy model)
+                packed_in = packed_out = None
+                if clip.planes == 3 and (clip.subw, clip.subh) == (1, 0) and clip.bytes < 4:
+                    kinds = ["yuyv", "uyvy"] + (["yuyv_msb", "uyvy_msb"] if clip.bytes == 2 else []) + (["v210", "v210"] if clip.bits == 10 else [])
+                    packed_in, packed_out = (rng.choice(kinds) if rng.random() < 0.5 else None for _ in range(2))
+                pview = {1: np.uint8, 2: np.int16, 4: np.int32}
+                if packed_in:
+                    a = np.stack(pc.pack_frames(packed_in, clip, frames, source=True, seed=rng.randint(0, 1 << 20)))
+                    src, semi_in, msb_in = torch.from_numpy(a.view(pview[a.dtype.itemsize])).to(dev), False, pc.is_msb(packed_in)
+                if packed_out:
+                    oh, ow = flt.plane_shape_out(0)
+                    shape = (nframes, oh, 4 * pc.v210_blocks(ow)) if packed_out == "v210" else (nframes, oh, 2 * ow)
+                    dst = torch.zeros(shape, dtype=torch.int32 if packed_out == "v210" else {1: torch.uint8, 2: torch.int16}[clip.bytes], device=dev)
+                    semi_out, msb_out = False, pc.is_msb(packed_out)
                 stats["semi_sides"] += int(semi_in) + int(semi_out)
                 stats["msb_sides"] += int(msb_in) + int(msb_out)
+                stats["packed_sides"] += int(bool(packed_in)) + int(bool(packed_out))
                 torch.cuda.synchronize()
-                if semi_in or semi_out or msb_in or msb_out or rng.random() < 0.25:
-                    flt.process_surfaces(src, dst, parity=parity, src_msb=msb_in, dst_msb=msb_out)
+                if semi_in or semi_out or msb_in or msb_out or packed_in or packed_out or rng.random() < 0.25:
+                    flt.process_surfaces(src, dst, parity=parity, src_msb=msb_in, dst_msb=msb_out, src_packed=packed_in and pc.order_of(packed_in),
+                                         dst_packed=packed_out and pc.order_of(packed_out))
                 else:
                     flt.process_batch(src, dst, parity=parity)
                 flt.synchronize()
-                if semi_out:
+                if packed_out:  # both sides of the comparison as planar LSB planes of the output's size, the bits a packed word drops gone
+                    oclip = clip_format(fmt, ow, oh)
+                    got = pc.unpack_frames(packed_out, oclip, list(to_host(dst).view(pc.packed_dtype(packed_out, clip))))
+                    want = pc.unpack_frames(packed_out, oclip, pc.pack_frames(packed_out, oclip, want))
+                    msb_out = False
+                elif semi_out:
                     dst = [dst[0], dst[1][..., 0], dst[1][..., 1]]
-                got = [[to_host(dst[p][f]).view(clip.dtype) for p in range(clip.planes)] for f in range(nframes)]
+                if not packed_out:
+                    got = [[to_host(dst[p][f]).view(clip.dtype) for p in range(clip.planes)] for f in range(nframes)]
                 if msb_out:  # the rule: the LSB result shifted left inside its 16-bit word
                     want = [[(pl << np.uint16(shift)).astype(np.uint16) for pl in fr] for fr in want]
             else:
@@ -199,4 +227,8 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    try:
+        main()
+    except Exception:
+        print(f"fuzz: a call raised in configuration: {CURRENT[0]}", flush=True)
+        raise
