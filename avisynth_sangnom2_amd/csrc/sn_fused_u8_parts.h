@@ -1,5 +1,5 @@
 // sn_fused_u8_parts.h -- the pieces of the 8-bit fused sweeps that do not depend on the sweep's mode: a kept line in
-// packed form (two pixels per register), stage 1's operands, the 7-tap box with the line buffer's clamps, and stage 3 in
+// packed form (two pixels per register), stage 1's operands (and the plain sweep's vertical byte pairs), the 7-tap box with the line buffer's clamps, and stage 3 in
 // the byte domain.  Shared by sn_fused_u8_v3.hip (a register's halves = two column strips of one plane) and
 // sn_fused_u8_uv.hip (a register's halves = the same strip of the U pass and of the V pass of a 4:2:0 frame).
 // Reference semantics: /root/reference/src/SangNom2.cpp:25-34 (loadPixel), :60-65 (calculateSangNom), :74-124
@@ -39,6 +39,25 @@ struct WideLine {
     __device__ __forceinline__ unsigned F2(int j) const { return Fv[j] | (Fv[j + 1] << 8); }
     __device__ __forceinline__ unsigned B2(int j) const { return Bv[j] | (Bv[j + 1] << 8); }
 };
+
+// A WideLine with the VERTICAL PAIRS that stage 1 of the plain sweep reads (round 9).  For the kept line k,
+//   Z[h][i] = pixel (x0 - 3 + i) of strip h:  byte 0 = line k - 1, byte 1 = line k, bytes 2 and 3 = zero.
+// The seven pixel-difference buffers (every buffer but the two SangNom ones) put
+//   S[r] = O[r-1] + |c_r(x+d) - c_{r+1}(x-d)| + |c_{r+1}(x+d) - c_{r+2}(x-d)|      (d = -3 .. 3 by buffer, c_r = kept line r - 1)
+// into the box, and that is ONE v_sad_u8 per strip on two such pairs with O as the accumulator: the pair (r, r+1) of
+// column x + d against the pair (r+1, r+2) of column x - d -- the pairs of the row's line n and of its line nn.  The low
+// strip's sum goes into bits 0..15 (v_sad_u8), the high strip's on top of it into bits 16..31 (v_sad_hi_u8); a half is
+// at most 255 + 2 * 255 = 765, so nothing carries from one into the other.  Bytes 2 and 3 of every pair are zero and add
+// nothing.  A row brings one new line: its pairs are the previous line's moved down a byte with the new pixel on top
+// (pair_down, one v_perm_b32 per pair, 28 per row), written over the pairs of the line that has just left -- the two
+// sets swap roles like the two line registers do.
+// The dead-half invariant of box7 holds as before: a half that is not live loads zeros for every line, so its pairs are
+// zero and both SADs add zero there; its O is zero through key_mask; so S = O + 0 + 0 stays zero in every row.
+struct PairLine : WideLine {
+    unsigned Z[2][PXL + 6];
+};
+template <class LineT>
+constexpr bool kWideForm = std::is_base_of<WideLine, LineT>::value;
 
 struct RawHalf {  // left dword, own 8 bytes, right dword of one strip
     uint32_t l, m0, m1, r;
@@ -140,7 +159,7 @@ __device__ __forceinline__ void unpack(LineT& L, const Raw& q)
 #pragma unroll
         for (int j = 0; j < PXL; ++j) {
             const unsigned f = sg_sat(L.P[j + 2], L.P[j + 3], L.P[j + 4]), b = sg_sat(L.P[j + 4], L.P[j + 3], L.P[j + 2]);
-            if constexpr (std::is_same<LineT, WideLine>::value) {
+            if constexpr (kWideForm<LineT>) {
                 L.Fv[j] = f;
                 L.Bv[j] = b;
             } else {
@@ -172,13 +191,59 @@ __device__ __forceinline__ void unpack(LineT& L, const Raw& q)
     for (int j = 0; j < PXL; ++j) {
         const unsigned xf = T[j] + e[j + 1];  // 4 (a + b) + (b - c)
         const unsigned xb = T[j + 1] - e[j];  // 4 (b + c) + (b - a)
-        if constexpr (std::is_same<LineT, WideLine>::value) {
+        if constexpr (kWideForm<LineT>) {
             L.Fv[j] = __builtin_amdgcn_perm(0u, xf, 0x0c030c01u);
             L.Bv[j] = __builtin_amdgcn_perm(0u, xb, 0x0c030c01u);
         } else {
             L.FB[j] = __builtin_amdgcn_perm(xb, xf, 0x07030501u);  // F | B << 8 in each half
         }
     }
+}
+
+// byte 1 of a pair moves to byte 0, byte k of the new line's dword `raw` becomes byte 1; bytes 2 and 3 stay zero
+__device__ __forceinline__ unsigned pair_down(unsigned old, uint32_t raw, int k)
+{
+    return __builtin_amdgcn_perm(raw, old, 0x0c0c0401u + ((unsigned)k << 8));
+}
+// The pairs of the line in q (after clamp_edges(), so loadPixel's clamp is inherited) from those of the line above it.
+// `L.Z` and `above` are different registers: the line above is still the row's n.
+__device__ __forceinline__ void make_pairs(PairLine& L, const Raw& q, const unsigned (&above)[2][PXL + 6])
+{
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            L.Z[h][k] = pair_down(above[h][k], q.h[h].l, k + 1);
+            L.Z[h][PXL + 3 + k] = pair_down(above[h][PXL + 3 + k], q.h[h].r, k);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            L.Z[h][3 + k] = pair_down(above[h][3 + k], q.h[h].m0, k);
+            L.Z[h][7 + k] = pair_down(above[h][7 + k], q.h[h].m1, k);
+        }
+    }
+}
+// The plane's last pool row has no line pair below it: S = O + |c_r(x+d) - c_{r+1}(x-d)| alone.  The same two SADs give it
+// on pairs whose byte 1 is zero: `n` keeps its upper pixels only, `nn` (the line register that is free by then) gets n's
+// lower pixels in byte 0.  Once per plane.
+__device__ __forceinline__ void last_pairs(PairLine& n, PairLine& nn)
+{
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int i = 0; i < PXL + 6; ++i) {
+            nn.Z[h][i] = n.Z[h][i] >> 8;
+            n.Z[h][i] &= 0xffu;
+        }
+}
+// S of a pixel-difference buffer (BUF = 0, 1, 2, 4, 6, 7, 8) at packed position j from the state O = O[r-1]: see PairLine
+template <int BUF>
+__device__ __forceinline__ unsigned sad_pairs_sum(const PairLine& n, const PairLine& nn, int j, unsigned o)
+{
+    static_assert(BUF != 3 && BUF != 5, "the SangNom buffers have no byte pairs");
+    constexpr int d = BUF < 3 ? BUF - 3 : BUF == 4 ? 0 : BUF - 5;  // cost_operands: c.P[i + d] against n.P[i - d]
+    const int a = j + 3 + d, b = j + 3 - d;
+    return __builtin_amdgcn_sad_hi_u8(n.Z[1][a], nn.Z[1][b], __builtin_amdgcn_sad_u8(n.Z[0][a], nn.Z[0][b], o));
 }
 
 // Stage 1, buffer BUF, packed position j, pair (c, n): the two values whose difference is the cost; Buffers enum of

@@ -15,7 +15,18 @@
 //     instructions for all eight windows (box7, sn_fused_u8_parts.h: windows 3 and 4 from two shared three-term sums, then
 //     one v_sub_u32_dpp and one v_add3 per window walking outwards on both sides); key = (B & 0x0ff00ff0) | code
 //     (v_and_or), O = key >> 4 as a PACKED shift (the code falls off both halves) and A' = O + U + V (v_add3), three per
-//     register; and the ladder's minimum over the keys, which takes TWO buffers' keys per instruction -- an even buffer
+//     register;
+//   * the whole-plane kPlain sweep (sad_pairs(): not its bands, no other mode) runs the seven pixel-difference buffers
+//     -- every buffer but 3 and 5, the SangNom differences -- in another form: their state is O[r-1] itself, and
+//     S = O[r-1] + D[r] + D[r+1] is ONE v_sad_u8 (low strip) and ONE v_sad_hi_u8 (high strip) on vertical pixel pairs
+//     (PairLine, sn_fused_u8_parts.h: byte 0 = the upper line's pixel, byte 1 = the lower line's; the pair (r, r+1) of
+//     column x + d against the pair (r+1, r+2) of column x - d), two per register where U, V and S took three, and no
+//     A' after the box.  The pairs are per strip (56 registers for the two lines where the packed windows took 28) and
+//     cost one v_perm_b32 per pair and row; the packed windows are still cut for the SangNom values and die with the
+//     unpack.  The first row starts from O[0] = 0; the plane's last row, which has no line pair below it, runs the same
+//     step on pairs whose lower pixels are masked to zero (last_pairs, once per plane).  Buffers 3 and 5 keep A = O + D.
+//     The seam mailbox copies state registers whatever they mean, and both sides of a seam change together;
+//   * the ladder's minimum over the keys, which takes TWO buffers' keys per instruction -- an even buffer
 //     hands its keys on, the odd one after it folds kmin = min(kmin, held, key) with v_pk_minimum3_f16 (keys are below
 //     0x1000 per half, where f16 patterns order like integers: pk_min3_keys, sn_fused_v3_common.h), the ninth buffer with
 //     v_pk_min_u16 -- five per register and row.  On gfx950 every packed, DPP and three-operand form issues in the same
@@ -139,18 +150,39 @@ struct RowCtx {  // what a row needs besides the lines
 #define SN_CHROMA_WIDE 1
 #endif
 __host__ __device__ constexpr bool wide_lines(int mode) { return !has_pools(mode) || (mode == kLumaSpill && SN_LUMA_WIDE) || (chroma_mode(mode) && SN_CHROMA_WIDE); }
-template <int MODE>
-using LineOf = typename std::conditional<wide_lines(MODE), WideLine, Line>::type;
+// SAD: stage 1 and the vertical sum of the seven pixel-difference buffers as two byte SADs on vertical pairs (PairLine,
+// sn_fused_u8_parts.h): the plain sweep of a whole plane.  Bands, kPadded and the pool-coupled sweeps keep the form below.
+#ifndef SN_PLAIN_SAD
+#define SN_PLAIN_SAD 1
+#endif
+__host__ __device__ constexpr bool sad_pairs(int mode, bool band) { return SN_PLAIN_SAD && mode == kPlain && !band; }
+template <int MODE, bool SAD = false>
+using LineOf = typename std::conditional<SAD, PairLine, typename std::conditional<wide_lines(MODE), WideLine, Line>::type>::type;
 
 // S1: the costs of row r+1 come from the lines (n, nn); otherwise they are zero (kPlain /
 // kLumaSpill: row bh is never written) or the previous pass's values (kChroma).
 // STORE: the smoothed row goes to pool_out (lanes / rows that keep nothing carry an out-of-range voffset).
-template <int BUF, int MODE, bool S1, bool STORE, int ARITH = 0>
-__device__ __forceinline__ void buffer_step(unsigned (&A)[PXL], unsigned (&kmin)[PXL], unsigned (&held)[PXL], const LineOf<MODE>& n, const LineOf<MODE>& nn,
-                                            const LaneRole& role, const PoolIO& io, const RowCtx& rc,
+template <int BUF, int MODE, bool S1, bool STORE, int ARITH = 0, bool SAD = false>
+__device__ __forceinline__ void buffer_step(unsigned (&A)[PXL], unsigned (&kmin)[PXL], unsigned (&held)[PXL], const LineOf<MODE, SAD>& n,
+                                            const LineOf<MODE, SAD>& nn, const LaneRole& role, const PoolIO& io, const RowCtx& rc,
                                             PoolIO::RawPair& stale)
 {
     unsigned D[PXL], S[PXL], Bx[PXL], O[PXL];
+    if constexpr (SAD && BUF != 3 && BUF != 5) {
+        // The state is O[r-1] itself, and both line pairs' costs enter with it in two SADs (sad_pairs_sum): two
+        // instructions per register where U, V and S = A + U + V took three, and no A' = O + U + V after the box.  The
+        // plane's last row (S1 = false) runs the same step on pairs whose lower pixels are zero (last_pairs).
+#pragma unroll
+        for (int j = 0; j < PXL; ++j) S[j] = sad_pairs_sum<BUF>(n, nn, j, A[j]);
+        box7(S, Bx, role);
+#pragma unroll
+        for (int j = 0; j < PXL; ++j) {
+            const unsigned key = and_or(box_sat<ARITH>(Bx[j]), role.key_mask, rank_of<BUF, MODE>());
+            A[j] = pk_lshr4(key);
+            fold_key<BUF>(kmin[j], held[j], key);
+        }
+        return;
+    }
     if constexpr ((MODE == kPlain || MODE == kLumaSpill) && S1) {
         // A plane on its own never needs the cost itself: |x - y| = (x -sat y) + (y -sat x), so S = A + U + V and
         // A' = O + U + V are one three-operand add each -- two saturating subtracts and two v_add3 where maximum,
@@ -286,9 +318,9 @@ __device__ __forceinline__ void unpark_raw(const Parked<NT, RB>& pk, int tid, in
 }
 
 // S3: the row has an interpolated line (stage 3); kChroma sweeps one extra row without one.
-template <int MODE, bool S1, bool S3, bool STORE, int NT, int ARITH = 0>
-__device__ __forceinline__ Out row_step(unsigned (&A)[reg_buffers(MODE)][PXL], const Parked<NT, reg_buffers(MODE)>& pk, int tid, const LineOf<MODE>& n,
-                                        const LineOf<MODE>& nn, const LaneRole& role, unsigned thr_key, const PoolIO& io,
+template <int MODE, bool S1, bool S3, bool STORE, int NT, int ARITH = 0, bool SAD = false>
+__device__ __forceinline__ Out row_step(unsigned (&A)[reg_buffers(MODE)][PXL], const Parked<NT, reg_buffers(MODE)>& pk, int tid, const LineOf<MODE, SAD>& n,
+                                        const LineOf<MODE, SAD>& nn, const LaneRole& role, unsigned thr_key, const PoolIO& io,
                                         const RowCtx& rc)
 {
     unsigned kmin[PXL], held[PXL];  // held: an even buffer's keys on their way to the next buffer's minimum (fold_key)
@@ -305,11 +337,11 @@ __device__ __forceinline__ Out row_step(unsigned (&A)[reg_buffers(MODE)][PXL], c
         constexpr int B = decltype(buf)::value;
         PoolIO::RawPair& st = (B & 1) ? st1 : st0;
         if constexpr (B < reg_buffers(MODE)) {
-            buffer_step<B, MODE, S1, STORE, ARITH>(A[B], kmin, held, n, nn, role, io, rc, st);
+            buffer_step<B, MODE, S1, STORE, ARITH, SAD>(A[B], kmin, held, n, nn, role, io, rc, st);
         } else {
             unsigned t[PXL];
             load_A(pk, tid, B, t);
-            buffer_step<B, MODE, S1, STORE, ARITH>(t, kmin, held, n, nn, role, io, rc, st);
+            buffer_step<B, MODE, S1, STORE, ARITH, SAD>(t, kmin, held, n, nn, role, io, rc, st);
             store_A(pk, tid, B, t);
         }
     };
@@ -396,6 +428,8 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args 
     const int f = f_raw < a.nframes ? f_raw : a.nframes - 1;
     const int tid = (int)threadIdx.x - sub * (NW * 64);
     constexpr int kRegBuffers = reg_buffers(MODE);
+    constexpr bool kSad = sad_pairs(MODE, BAND);
+    using LineT = LineOf<MODE, kSad>;
     Parked<NW * 64, kRegBuffers> parked;
     parked.v = reinterpret_cast<uint4*>(lds_raw + sub * lds_bytes(NW, MODE));
     parked.a = parked.v + parked_line_slots(MODE) * NW * 64;
@@ -552,7 +586,7 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args 
     const unsigned thr_key = (unsigned)((a.thr + 1) << 4) * 0x00010001u;
 
     // a band copies the kept lines ra .. rb (the top band line 0 as well)
-    LineOf<MODE> L0, L1;
+    LineT L0, L1;
     Raw q0 = load_raw(src_line + (r0 - 1) * src_step);
     Raw q1 = nk > 1 ? load_raw(src_line + r0 * src_step) : q0;
     // The third line is fetched HERE, before the first stores, so that on entering the row loop the loads in flight have
@@ -567,8 +601,13 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args 
     if (nk > 1) keep(dst_line + r0 * dst_step, q1, r0 == ra && r0 <= nr);
     {
         const Raw f0 = clamp_edges(q0, role), f1 = clamp_edges(q1, role);
-        unpack<LineOf<MODE>, ARITH>(L0, f0);
-        unpack<LineOf<MODE>, ARITH>(L1, f1);
+        unpack<LineT, ARITH>(L0, f0);
+        unpack<LineT, ARITH>(L1, f1);
+        if constexpr (kSad) {  // L1's pairs are (line r0 - 1, line r0); nothing reads the upper half of L0's
+            const unsigned none[2][PXL + 6] = {};
+            make_pairs(L0, f0, none);
+            make_pairs(L1, f1, L0.Z);
+        }
         RawLine R;
         make_raw(R, f0, L0);
         park_raw(parked, tid, (r0 - 1) % 3, R);  // K[r0 - 1]: c of row r0
@@ -577,13 +616,17 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args 
     }
 
     // A[1] = O[0] + P[1] = P[1] (pool row 0 is never written: zero); P[1] = stage-1 costs of the first
-    // line pair, and outside the chroma region (kChroma) what the previous pass left in row 1
+    // line pair, and outside the chroma region (kChroma) what the previous pass left in row 1.  The pixel-difference
+    // buffers of the SAD form keep O[r-1] alone: O[0] = 0.
     unsigned A[kRegBuffers][PXL];
     const bool first_lo = chroma_mode(MODE) && a.rows_in >= r0 && in_cone(r0, a.cone_in, 0);
     const bool first_hi = chroma_mode(MODE) && a.rows_in >= r0 && in_cone(r0, a.cone_in, 1);
     auto init_A = [&](auto buf, unsigned (&Ab)[PXL]) {
         constexpr int B = decltype(buf)::value;
-        if constexpr (chroma_mode(MODE)) {
+        if constexpr (kSad && B != 3 && B != 5) {
+#pragma unroll
+            for (int j = 0; j < PXL; ++j) Ab[j] = 0u;
+        } else if constexpr (chroma_mode(MODE)) {
             io.load(B, r0, first_lo ? io.v_lo : kOutOfRange, first_hi ? io.v_hi : kOutOfRange, Ab);
             if (r0 <= nr) {
 #pragma unroll
@@ -698,7 +741,7 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args 
     // interpolated line).
     TurnTaking turns;
     turns.init(a.turn_shift);
-    auto step = [&](int r, LineOf<MODE>& n, LineOf<MODE>& nn, auto s1_tag, auto s3_tag, auto store_tag, auto pos_tag,
+    auto step = [&](int r, LineT& n, LineT& nn, auto s1_tag, auto s3_tag, auto store_tag, auto pos_tag,
                     const Blk& bk) __attribute__((always_inline)) {
         constexpr bool HAS_NEXT = decltype(s1_tag)::value;
         constexpr bool S3 = decltype(s3_tag)::value;
@@ -718,7 +761,8 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args 
             asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
             SN_RT(0);  // [0] the wait for the prefetched line
 #endif
-            unpack<LineOf<MODE>, ARITH>(nn, fq);
+            unpack<LineT, ARITH>(nn, fq);
+            if constexpr (kSad) make_pairs(nn, fq, n.Z);  // over the pairs of the line that left with the previous row
             RawLine R;
             make_raw(R, fq, nn);
             park_raw(parked, tid, slot_nn, R);  // K[r + 1]: n of the next row, c of the one after
@@ -728,6 +772,8 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args 
         if constexpr (HAS_NEXT) {
             if (r + 2 <= nr) qnext = load_raw(src_next);  // prefetch K[r+2]
             src_next += src_step;
+        } else if constexpr (kSad) {
+            last_pairs(n, nn);  // the plane's last row: no line pair below it
         }
         SN_RT(1);  // [1] unpack, windows, park, kept-line store, prefetch issue
         if constexpr (POS < 0) {
@@ -753,7 +799,7 @@ __global__ void __launch_bounds__(NW * group_of(NW) * 64, 2) k_fused_u8_v3(Args 
             rc.any_out = __builtin_amdgcn_readfirstlane(__any((rc.vout != kOutOfRange) | (rc.vout_hi != kOutOfRange)) ? 1 : 0) != 0;
         }
         SN_RT(3);  // [3] ghost refresh (every fifth row) and row set-up
-        const Out o = row_step<MODE, HAS_NEXT, S3, STORE, NW * 64, ARITH>(A, parked, tid, n, nn, role, thr_key, io, rc);
+        const Out o = row_step<MODE, HAS_NEXT, S3, STORE, NW * 64, ARITH, kSad>(A, parked, tid, n, nn, role, thr_key, io, rc);
         if constexpr (S3) put(out_row, o);  // stored at once: nothing is carried into the next row
         SN_RT(4);  // [4] nine buffer steps + stage 3 + output store
         out_row += dst_step;

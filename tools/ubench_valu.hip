@@ -198,6 +198,22 @@ KIND(pk_minimum3_f16, O_PKMIN3F16)
               X8(O_PKMAX(10), O_PKMIN3F16(11), O_SUB(12), O_ADD(13), O_ANDOR(14), O_AND(15), O_LSHR(16), O_OR(17)) \
               X8(O_ADD(10), O_AND(11), O_BFI(12), O_MUL24(13), O_LSHR(14), O_ADDDPP(15), O_ADD(16), O_AND(17))
 DEFK(sweepmix_min3f16, SW32M SW32M SW32M SW32M)
+// Round 9: stage 1 and the vertical sum as two byte SADs (v_sad_u8 into the low half, v_sad_hi_u8 on top of it into the
+// high half).  v_sad_u8 is in the first table; v_sad_hi_u8 is new.  The mixes are a buffer step of today's row per packed
+// register (box: add3 and sub_dpp; key: and_or, packed shift, three-input minimum) with ONE instruction in four a byte
+// SAD: the low form alone, the high form alone, and the pair as the kernel would issue it.
+#define O_SADHIU8(n) "v_sad_hi_u8 v" STR(n) ", v" STR(n) ", v18, v19"
+#define O_PKLSHR4(n) "v_pk_lshrrev_b16 v" STR(n) ", 4, v" STR(n)
+KIND(sad_hi_u8, O_SADHIU8)
+#define SW8SAD(SA, SB) X8(SA(10), SB(11), O_ADD3(12), O_ADDDPP(13), O_ADD3(14), O_ANDOR(15), O_PKLSHR4(16), O_PKMIN3F16(17))
+#define SW8REF X8(O_PKSUBC(10), O_PKSUBC(11), O_ADD3(12), O_ADDDPP(13), O_ADD3(14), O_ANDOR(15), O_PKLSHR4(16), O_PKMIN3F16(17))
+DEFK(stepmix_pk_sub, R16(SW8REF))
+DEFK(stepmix_sad_u8, R16(SW8SAD(O_SADU8, O_SADU8)))
+DEFK(stepmix_sad_hi_u8, R16(SW8SAD(O_SADHIU8, O_SADHIU8)))
+DEFK(stepmix_sad_pair, R16(SW8SAD(O_SADU8, O_SADHIU8)))
+// the pair as ONE dependent chain per register (the high form accumulates onto the low form's result)
+#define SADPAIR8 X8(O_SADU8(10), O_SADHIU8(10), O_SADU8(11), O_SADHIU8(11), O_SADU8(12), O_SADHIU8(12), O_SADU8(13), O_SADHIU8(13))
+DEFK(sad_pair_chain, R16(SADPAIR8))
 
 typedef void (*kern_t)(unsigned long long*, int);
 struct Entry {
@@ -227,6 +243,9 @@ int main(int argc, char** argv)
         E3(add_e64_sgpr) E3(add_sgpr)
         {"mix 6 fast 2 salu", k_mix_f6salu2_ind},
         E3(pk_minimum3_f16) {"sweep mix, pk_minimum3_f16 for pk_min", k_sweepmix_min3f16},
+        E3(sad_hi_u8) {"sad_u8 + sad_hi_u8 chained", k_sad_pair_chain},
+        {"step mix, 2 pk_sub in 8", k_stepmix_pk_sub}, {"step mix, 2 sad_u8 in 8", k_stepmix_sad_u8},
+        {"step mix, 2 sad_hi_u8 in 8", k_stepmix_sad_hi_u8}, {"step mix, sad_u8 + sad_hi_u8 in 8", k_stepmix_sad_pair},
     };
     // arguments: [--waves 1,2,4] [--iters N] [--rounds R] substrings of the names to run
     std::vector<int> wlist = {1, 2, 3, 4, 8};

@@ -168,6 +168,8 @@
 #define O_MOV64(n) "v_mov_b64 v[" STR(n) ":11], v[18:19]"
 #define O_LSHLADD64(n) "v_lshl_add_u64 v[10:11], v[10:11], 3, v[18:19]"
 #define O_PKADDU16(n) "v_pk_add_u16 v" STR(n) ", v" STR(n) ", v18"
+#define O_SADU8(n) "v_sad_u8 v" STR(n) ", v" STR(n) ", v18, v19"
+#define O_SADHIU8(n) "v_sad_hi_u8 v" STR(n) ", v" STR(n) ", v18, v19"
 
 // eight different fast opcodes
 #define FM X8(O_ADD(10), O_AND(11), O_SUB(12), O_LSHR(13), O_OR(14), O_ADD(15), O_AND(16), O_SUB(17))
@@ -235,6 +237,14 @@ DEFK(x8_ds_swizzle, R16(FM_X(O_DSSWZ)) "s_waitcnt lgkmcnt(0)\n\t")
 DEFK(x8_waitcnt, R16(FM_X(O_WAITL)))
 DEFK(x8_cmp_vcc, R16(FM_X(O_CMPLT)))
 DEFK(x8_add_co, R16(FM_X(O_ADDCO)))
+DEFK(x8_sad_u8, R16(FM_X(O_SADU8)))
+DEFK(x8_sad_hi_u8, R16(FM_X(O_SADHIU8)))
+// one byte SAD in four of a SLOW stream (the sweep's row is all slow forms): does it stay at 4.06?
+#define S8_X(OP) X8(O_PKMIN(10), O_BFI(11), O_PKMAX(12), OP(13), O_PKMIN(14), O_BFI(15), O_PKMAX(16), OP(17))
+DEFK(s4_pk_min, R16(S8_X(O_PKMIN)))
+DEFK(s4_sad_u8, R16(S8_X(O_SADU8)))
+DEFK(s4_sad_hi_u8, R16(S8_X(O_SADHIU8)))
+DEFK(s4_min3_u16, R16(S8_X(O_MIN3U16)))
 
 // (4) classes of further opcodes (independent chains, all eight accumulators)
 #define CLASS(NAME, OP) DEFK(c_##NAME, R16(IND8(OP)))
@@ -249,7 +259,7 @@ CLASS(floor_f32, O_FLOORF) CLASS(trunc_f32, O_TRUNCF) CLASS(fract_f32, O_FRACTF)
 CLASS(cvt_u32_f32, O_CVTU32F32) CLASS(pk_add_f16, O_PKADDF16) CLASS(pk_fma_f16, O_PKFMAF16) CLASS(add_f16, O_ADDF16)
 CLASS(fma_f16, O_FMAF16) CLASS(max_f16, O_MAXF16) CLASS(dot4_u32_u8, O_DOT4) CLASS(dot2_u32_u16, O_DOT2U16)
 CLASS(msad_u8, O_MSAD) CLASS(mul_lo_u32, O_MULLOU32) CLASS(and_sgpr, O_ANDSG) CLASS(and_inline, O_ANDINL) CLASS(min_u16, O_MINU16)
-CLASS(pk_add_u16, O_PKADDU16) CLASS(bitop3, O_BITOP3) CLASS(xor, O_XOR)
+CLASS(pk_add_u16, O_PKADDU16) CLASS(bitop3, O_BITOP3) CLASS(xor, O_XOR) CLASS(sad_u8, O_SADU8) CLASS(sad_hi_u8, O_SADHIU8)
 DEFK(c_pk_fma_f32, R16(R8("v_pk_fma_f32 v[10:11], v[10:11], v[18:19], v[18:19]\n\t")))
 DEFK(c_pk_add_f32, R16(R8("v_pk_add_f32 v[10:11], v[10:11], v[18:19]\n\t")))
 DEFK(c_pk_mul_f32, R16(R8("v_pk_mul_f32 v[10:11], v[10:11], v[18:19]\n\t")))
@@ -282,7 +292,8 @@ int main(int argc, char** argv)
         E(x8_dpp_wave, 128) E(x8_dpp_row, 128) E(x8_dpp_quad, 128) E(x8_bfi, 128) E(x8_bitop3, 128) E(x8_fma, 128) E(x8_lshl, 128)
         E(x8_add_sgpr, 128) E(x8_and_sgpr, 128) E(x8_add_literal, 128) E(x8_and_inline, 128) E(x8_min_u16, 128) E(x8_s_nop, 128)
         E(x8_v_nop, 128) E(x8_salu, 128) E(x8_ds_read, 128) E(x8_ds_write, 128) E(x8_ds_bpermute, 128) E(x8_ds_swizzle, 128)
-        E(x8_waitcnt, 128) E(x8_cmp_vcc, 128) E(x8_add_co, 128)
+        E(x8_waitcnt, 128) E(x8_cmp_vcc, 128) E(x8_add_co, 128) E(x8_sad_u8, 128) E(x8_sad_hi_u8, 128)
+        E(s4_pk_min, 128) E(s4_sad_u8, 128) E(s4_sad_hi_u8, 128) E(s4_min3_u16, 128)
         EC(lshl_add) EC(lshl_or) EC(add_lshl) EC(or3) EC(xad) EC(mad_u32_u24) EC(mad_u16) EC(add_u16) EC(lshr_b16) EC(ashr_i16)
         EC(pk_lshr_b16) EC(pk_sub_u16) EC(pk_mul_lo_u16) EC(min3_u16) EC(max3_u32) EC(med3_u32) EC(add_co) EC(sub_co)
         EC(cmp_lt_u32_vcc) EC(cmp_lt_u32_sgpr) EC(cmp_lt_u16_vcc) EC(sub_f32) EC(mul_f32) EC(min_f32) EC(add_f32_e64_abs)
@@ -290,7 +301,7 @@ int main(int argc, char** argv)
         EC(trunc_f32) EC(fract_f32) EC(cvt_f32_u32) EC(cvt_u32_f32) EC(pk_add_f16) EC(pk_fma_f16) EC(add_f16) EC(fma_f16)
         EC(max_f16) EC(dot4_u32_u8) EC(dot2_u32_u16) EC(msad_u8) EC(mul_lo_u32) EC(and_sgpr) EC(and_inline)
         EC(min_u16) EC(pk_add_u16) EC(bitop3) EC(xor) EC(pk_fma_f32) EC(pk_add_f32) EC(pk_mul_f32) EC(mov_b64) EC(lshl_add_u64)
-        EC(swap_b32) EC(accvgpr_write) EC(accvgpr_read) EC(accvgpr_mov)
+        EC(swap_b32) EC(accvgpr_write) EC(accvgpr_read) EC(accvgpr_mov) EC(sad_u8) EC(sad_hi_u8)
     };
     std::vector<int> wlist = {1, 2, 4};
     int total = 512000, rounds = 4;
