@@ -556,13 +556,14 @@ static int ensure_parts(Context* c, int nseams)
     return SN_OK;
 }
 
-// ... and the pool slots the redo of a failed frame runs on
+// ... and the pool slots the redo of a failed frame runs on -- or, a plane marked for parts that is never cut (no
+// interpolated row: plan_parts), the pool path that serves it in every launch (run_group)
 static int ensure_parts_scratch(Context* c)
 {
     int nseams = 0;
     for (int p = 0; p < c->nplanes(); ++p) {
         PartsPlan pl;
-        if (!plan_parts(c, p, pl)) continue;
+        if (!plan_parts(c, p, pl) && !c->plane_parts[p]) continue;
         nseams = pl.n - 1 > nseams ? pl.n - 1 : nseams;
         const int rc = ensure_pool(c, c->isolated ? p : 0);
         if (rc != SN_OK) return rc;
@@ -1496,6 +1497,11 @@ static int run_group(Context* c, hipStream_t st, int slot0, int n, const void* c
             g.plan[p].n = 0;
         }
     }
+    // Creation marks a plane for column parts by its width alone (plane_parts), and plan_parts cuts only planes with a row to
+    // interpolate.  A marked plane without a plan has no whole-plane sweep to fall back on -- it is wider than any instance --
+    // and nothing to interpolate either: the pool path's assemble is all it needs, and part_frames does not count it.
+    for (int p = 0; p < c->nplanes(); ++p)
+        if (g.fused[p] && c->plane_parts[p] && g.plan[p].n == 0) g.fused[p] = false;
     if (g.nbands == 0)
         for (int p = 0; p < c->nplanes(); ++p) SN_HIP(c, g.plane_in(p));
     // The reference smooths the whole luma-sized pool in every pass (SangNom2.cpp:126-159).  A plane of fewer lines reads

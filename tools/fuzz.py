@@ -159,8 +159,8 @@ def main():
                     packed_in, packed_out = (rng.choice(kinds) if rng.random() < 0.5 else None for _ in range(2))
                 pview = {1: np.uint8, 2: np.int16, 4: np.int32}
                 if packed_in:
-                    a = np.stack(pc.pack_frames(packed_in, clip, frames, source=True, seed=rng.randint(0, 1 << 20)))
-                    src, semi_in, msb_in = torch.from_numpy(a.view(pview[a.dtype.itemsize])).to(dev), False, pc.is_msb(packed_in)
+                    rows = np.stack(pc.pack_frames(packed_in, clip, frames, source=True, seed=rng.randint(0, 1 << 20)))  # (not `a`: the arguments)
+                    src, semi_in, msb_in = torch.from_numpy(rows.view(pview[rows.dtype.itemsize])).to(dev), False, pc.is_msb(packed_in)
                 if packed_out:
                     oh, ow = flt.plane_shape_out(0)
                     shape = (nframes, oh, 4 * pc.v210_blocks(ow)) if packed_out == "v210" else (nframes, oh, 2 * ow)
