@@ -32,7 +32,15 @@ EXPORTS = (
     "sn_aa_host_slots", "sn_aa_submit_host", "sn_aa_collect_host",
     "sn_get_parts_info", "sn_aa_get_parts_info", "sn_debug_set_column_parts",
     "sn_process_device_surfaces", "sn_aa_process_device_surfaces", "sn_get_surface_info", "sn_aa_get_surface_info",
+    "sn_aa_get_reduce", "sn_reduce_device",
 )
+# ... and the ones whose names end in a digit
+EXPORTS_NUMBERED = ("sn_aa_create_ex2",)
+
+# sn_aa_options.reduce: the anti-aliasing call with dh returns the frame at source size (sangnom_hip.h has the arithmetic)
+SN_AA_REDUCE_NONE, SN_AA_REDUCE_TENT, SN_AA_REDUCE_HALFBAND = 0, 1, 2
+REDUCE_KERNELS = {0: SN_AA_REDUCE_NONE, None: SN_AA_REDUCE_NONE, False: SN_AA_REDUCE_NONE, "none": SN_AA_REDUCE_NONE,
+                  "tent": SN_AA_REDUCE_TENT, 1: SN_AA_REDUCE_TENT, "halfband": SN_AA_REDUCE_HALFBAND, 2: SN_AA_REDUCE_HALFBAND}
 
 # sn_surfaces.layout: planar Y, U, V or Y plus one plane of U,V pairs (NV12, P010 / P016, NV16, NV24); _MSB: 16-bit words
 # with the sample in the high bits (P010 on a 10-bit context, P012 on a 12-bit one)
@@ -68,6 +76,17 @@ class SnPolicy(ctypes.Structure):
 class SnOptions(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_int32), ("arithmetic", ctypes.c_int32), ("column_parts", ctypes.c_int32),
                 ("reserved", ctypes.c_int32 * 5)]
+
+
+class SnAAOptions(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_int32), ("reduce", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6)]
+
+
+def aa_options(reduce=0) -> "SnAAOptions":
+    """sn_aa_options: reduce = 0, "tent" (1) or "halfband" (2)."""
+    if reduce not in REDUCE_KERNELS:
+        raise ValueError("reduce must be 0, 'tent' or 'halfband'")
+    return SnAAOptions(struct_size=ctypes.sizeof(SnAAOptions), reduce=REDUCE_KERNELS[reduce])
 
 
 class SnPartsInfo(ctypes.Structure):
@@ -170,6 +189,10 @@ def load():
     L.sn_create_with_policy.argtypes = [ctypes.POINTER(SnConfig), ctypes.POINTER(SnPolicy), ctypes.POINTER(vp)]
     L.sn_create_ex.argtypes = [ctypes.POINTER(SnConfig), ctypes.POINTER(SnPolicy), ctypes.POINTER(SnOptions), ctypes.POINTER(vp)]
     L.sn_aa_create_ex.argtypes = [ctypes.POINTER(SnConfig), ctypes.POINTER(SnPolicy), ctypes.POINTER(SnOptions), ctypes.POINTER(vp)]
+    L.sn_aa_create_ex2.argtypes = [ctypes.POINTER(SnConfig), ctypes.POINTER(SnPolicy), ctypes.POINTER(SnOptions), ctypes.POINTER(SnAAOptions),
+                                   ctypes.POINTER(vp)]
+    L.sn_aa_get_reduce.argtypes = [vp]
+    L.sn_reduce_device.argtypes = [vp, i32, i32, vp, i64, i32, i32, i32, i32, i32, vp, i64, i32]
     L.sn_get_arithmetic.argtypes = [vp]
     L.sn_get_policy.argtypes = [vp, ctypes.POINTER(SnPolicy)]
     L.sn_set_policy.argtypes = [vp, ctypes.POINTER(SnPolicy)]

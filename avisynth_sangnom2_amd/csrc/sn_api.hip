@@ -2642,6 +2642,25 @@ int sn_turn_device(sn_context* h, int32_t direction, int32_t nframes, const void
     return SN_OK;
 }
 
+int sn_reduce_device(sn_context* h, int32_t kernel, int32_t nframes, const void* src, int64_t sfs, int32_t sp, int32_t width, int32_t height,
+                     int32_t ox, int32_t oy, void* dst, int64_t dfs, int32_t dp)
+{
+    Context* c = reinterpret_cast<Context*>(h);
+    if (!c) return sn::fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    const int B = c->cfg.bytes_per_sample;
+    if (!src || !dst || nframes < 0 || width <= 0 || height <= 0 || width > INT32_MAX / 8 || height > INT32_MAX / 2)
+        return sn::fail(c, SN_ERR_INVALID_ARG, "sn_reduce_device: bad pointer or size");
+    if (kernel != SN_AA_REDUCE_TENT && kernel != SN_AA_REDUCE_HALFBAND)
+        return sn::fail(c, SN_ERR_INVALID_ARG, "sn_reduce_device: kernel must be 1 (tent) or 2 (half-band)");
+    if (ox < 0 || ox > 1 || oy < 0 || oy > 1) return sn::fail(c, SN_ERR_INVALID_ARG, "sn_reduce_device: ox and oy must be 0 or 1");
+    if (sp < 2 * width * B || dp < width * B || sp % B || dp % B || sfs % B || dfs % B || (uintptr_t)src % B || (uintptr_t)dst % B)
+        return sn::fail(c, SN_ERR_INVALID_ARG, "sn_reduce_device: pitch smaller than the row or misaligned");
+    SN_HIP(c, hipSetDevice(c->device));
+    SN_HIP(c, sn::launch_reduce(c->stream, B, c->cfg.bits_per_sample, kernel, nframes, static_cast<const uint8_t*>(src), sfs, sp, width, height, ox, oy,
+                                static_cast<uint8_t*>(dst), dfs, dp));
+    return SN_OK;
+}
+
 int sn_synchronize(sn_context* h)
 {
     Context* c = reinterpret_cast<Context*>(h);
@@ -2820,6 +2839,9 @@ int sn_debug_read_coupled_rows(sn_context* h, int32_t which, void* host_dst, siz
 // With cfg.dh both passes double the height: the idiom enlarges by two in both directions.  The first pass's output is
 // then twice as high as the turned clip, the second pass's input twice as wide as the clip and its output (the
 // destination) twice as wide and twice as high; without dh every one of these geometries is the clip's or the turned one.
+// With a reduction (sn_aa_options.reduce, dh only) the second pass writes a fourth intermediate E in its own geometry
+// (ow x oh) and sn_reduce.hip brings it to the destination, which has the clip's geometry again (dstw x dsth): nine plane
+// sizes of intermediates per processed plane and frame instead of five.
 struct sn_aa_context {
     sn_config cfg{};
     sn_context* first = nullptr;   // the turned clip
@@ -2832,16 +2854,21 @@ struct sn_aa_context {
     int w[3] = {0, 0, 0}, h[3] = {0, 0, 0};  // clip geometry per plane
     int pitch[3] = {0, 0, 0}, tpitch[3] = {0, 0, 0};
     int64_t cbytes[3] = {0, 0, 0}, tbytes[3] = {0, 0, 0};  // one frame of a plane: clip geometry / turned
-    int ow[3] = {0, 0, 0}, oh[3] = {0, 0, 0};              // the destination's geometry per plane (dh: 2w x 2h)
+    int ow[3] = {0, 0, 0}, oh[3] = {0, 0, 0};              // the second pass's output per plane (dh: 2w x 2h)
     int opitch[3] = {0, 0, 0};
     int64_t obytes[3] = {0, 0, 0};
     int64_t u1bytes[3] = {0, 0, 0};                        // the first pass's output: tpitch x ow lines
     int t2pitch[3] = {0, 0, 0};                            // the second pass's input: ow wide, h high
     int64_t t2bytes[3] = {0, 0, 0};
+    int reduce = SN_AA_REDUCE_NONE;                        // dh only: the second pass's output goes through sn_reduce.hip on its way out
+    int dstw[3] = {0, 0, 0}, dsth[3] = {0, 0, 0};          // the destination's geometry per plane: ow x oh, with reduce w x h
+    int dstpitch[3] = {0, 0, 0};                           // ... of the library's own buffers of that geometry (host groups)
+    int64_t dstbytes[3] = {0, 0, 0};
     int cap = 0;                                       // frames the intermediates hold (a chunk)
     uint8_t* d_t1[3] = {nullptr, nullptr, nullptr};   // turned: input of the first pass (only its kept lines are written; dh: every line)
     uint8_t* d_u1[3] = {nullptr, nullptr, nullptr};   // turned: its output (dh: twice as high)
     uint8_t* d_t2[3] = {nullptr, nullptr, nullptr};   // turned back: input of the second pass (kept lines only; dh: every line, twice as wide)
+    uint8_t* d_e[3] = {nullptr, nullptr, nullptr};    // reduce: the second pass's output, opitch x oh
     // host frames: `per_group` slots form a group whose frames one batch works on; the ring's groups, then one group of
     // one slot for the synchronous call
     struct Slot {
@@ -2911,16 +2938,16 @@ static int aa_ensure_intermediates(sn_aa_context* a, int frames)
     if (frames <= a->cap) return SN_OK;
     int64_t per_frame = 0;
     for (int p = 0; p < a->planes; ++p)
-        if (a->process[p]) per_frame += a->tbytes[p] + a->u1bytes[p] + a->t2bytes[p];
+        if (a->process[p]) per_frame += a->tbytes[p] + a->u1bytes[p] + a->t2bytes[p] + (a->reduce ? a->obytes[p] : 0);
     const int64_t fit = per_frame > 0 ? scratch_budget(reinterpret_cast<Context*>(a->first)) / per_frame : frames;
     const int cap = (int)(fit < 1 ? 1 : fit < frames ? fit : frames);
     if (cap <= a->cap) return SN_OK;
     SN_AA_HIP(hipStreamSynchronize(a->stream));
     for (int p = 0; p < a->planes; ++p) {
         if (!a->process[p]) continue;  // copied from source to destination: no turn, no pass, no intermediate
-        const size_t nb[3] = {(size_t)a->tbytes[p] * cap, (size_t)a->u1bytes[p] * cap, (size_t)a->t2bytes[p] * cap};
-        uint8_t** q[3] = {&a->d_t1[p], &a->d_u1[p], &a->d_t2[p]};
-        for (int k = 0; k < 3; ++k) {
+        const size_t nb[4] = {(size_t)a->tbytes[p] * cap, (size_t)a->u1bytes[p] * cap, (size_t)a->t2bytes[p] * cap, (size_t)a->obytes[p] * cap};
+        uint8_t** q[4] = {&a->d_t1[p], &a->d_u1[p], &a->d_t2[p], &a->d_e[p]};
+        for (int k = 0; k < (a->reduce ? 4 : 3); ++k) {
             if (*q[k]) SN_AA_HIP(hipFree(*q[k]));
             *q[k] = nullptr;
             SN_AA_HIP(hipMalloc(reinterpret_cast<void**>(q[k]), nb[k]));
@@ -2942,7 +2969,7 @@ void sn_aa_destroy(sn_aa_context* a)
     if (a->second) sn_destroy(a->second);
     if (a->first) sn_destroy(a->first);  // owns the stream unless the caller gave one
     for (int p = 0; p < 3; ++p)
-        for (uint8_t* q : {a->d_t1[p], a->d_u1[p], a->d_t2[p]})
+        for (uint8_t* q : {a->d_t1[p], a->d_u1[p], a->d_t2[p], a->d_e[p]})
             if (q) (void)hipFree(q);
     for (uint8_t* q : {a->uv.in[0], a->uv.in[1], a->uv.out[0], a->uv.out[1], a->uv.y, a->uv.yo})
         if (q) (void)hipFree(q);
@@ -2958,6 +2985,11 @@ int sn_aa_create_with_policy(const sn_config* cfg, const sn_policy* policy, sn_a
 
 int sn_aa_create_ex(const sn_config* cfg, const sn_policy* policy, const sn_options* options, sn_aa_context** out)
 {
+    return sn_aa_create_ex2(cfg, policy, options, nullptr, out);
+}
+
+int sn_aa_create_ex2(const sn_config* cfg, const sn_policy* policy, const sn_options* options, const sn_aa_options* aa_options, sn_aa_context** out)
+{
     auto fail_aa = [](sn_aa_context* a, int code, const std::string& msg) {
         g_aa_error = msg;
         if (a) sn_aa_destroy(a);
@@ -2968,9 +3000,20 @@ int sn_aa_create_ex(const sn_config* cfg, const sn_policy* policy, const sn_opti
     if (cfg->struct_size != (int32_t)sizeof(sn_config)) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_config.struct_size mismatch");
     if (cfg->max_batch < 0) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "max_batch must be >= 0");
     if (cfg->host_depth < 0 || cfg->host_depth > 256) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "host_depth must be 0..256");
+    int reduce = SN_AA_REDUCE_NONE;
+    if (aa_options) {
+        if (aa_options->struct_size != (int32_t)sizeof(sn_aa_options)) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_aa_options.struct_size mismatch");
+        if (aa_options->reduce < SN_AA_REDUCE_NONE || aa_options->reduce > SN_AA_REDUCE_HALFBAND)
+            return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_aa_options.reduce must be 0 (none), 1 (tent) or 2 (half-band)");
+        for (int32_t r : aa_options->reserved)
+            if (r) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_aa_options.reserved must be zero");
+        reduce = aa_options->reduce;
+    }
+    if (reduce && !cfg->dh) return fail_aa(nullptr, SN_ERR_CONFIG, "SangNomAA: reduce needs dh=true");
     sn_aa_context* a = new (std::nothrow) sn_aa_context();
     if (!a) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "out of host memory");
     a->cfg = *cfg;
+    a->reduce = reduce;
     a->max_batch = cfg->max_batch > 1 ? cfg->max_batch : 1;
     // the ring: two groups, so that one group uploads while the other is worked on; a group's frames are one batch
     a->depth = cfg->host_depth > 0 ? cfg->host_depth : 4;
@@ -3018,6 +3061,10 @@ int sn_aa_create_ex(const sn_config* cfg, const sn_policy* policy, const sn_opti
         a->u1bytes[p] = (int64_t)a->tpitch[p] * a->ow[p];
         a->t2pitch[p] = a->opitch[p];
         a->t2bytes[p] = (int64_t)a->t2pitch[p] * a->h[p];
+        a->dstw[p] = reduce ? a->w[p] : a->ow[p];
+        a->dsth[p] = reduce ? a->h[p] : a->oh[p];
+        a->dstpitch[p] = reduce ? a->pitch[p] : a->opitch[p];
+        a->dstbytes[p] = reduce ? a->cbytes[p] : a->obytes[p];
     }
     if (int rc2 = aa_ensure_intermediates(a, a->max_batch)) return fail_aa(a, rc2, a->err);
     *out = a;
@@ -3077,7 +3124,23 @@ static int aa_run(sn_aa_context* a, int n, const void* const src[3], const int64
         if (int rc = turns(1)) return rc;
         void* d2[3] = {nullptr, nullptr, nullptr};
         for (int p = 0; p < a->planes; ++p) d2[p] = static_cast<uint8_t*>(dst[p]) + (int64_t)f0 * dfs[p];
-        SN_AA_SN(a->second, run_batch(c2, st, 0, m, s2, a->t2bytes, a->t2pitch, d2, dfs, dp, par));
+        if (!a->reduce) {
+            SN_AA_SN(a->second, run_batch(c2, st, 0, m, s2, a->t2bytes, a->t2pitch, d2, dfs, dp, par));
+            continue;
+        }
+        // reduce (dh: every plane is processed): the second pass fills E, the reduction writes the destination -- one launch
+        // per run of frames with the same field offset, which is where the source samples lie in E
+        void* e2[3] = {a->d_e[0], a->d_e[1], a->d_e[2]};
+        SN_AA_SN(a->second, run_batch(c2, st, 0, m, s2, a->t2bytes, a->t2pitch, e2, a->obytes, a->opitch, par));
+        for (int g0 = 0; g0 < m;) {
+            const int off = field_offset(c2, par ? par[g0] : 1);
+            int g1 = g0 + 1;
+            while (g1 < m && field_offset(c2, par ? par[g1] : 1) == off) ++g1;
+            for (int p = 0; p < a->planes; ++p)
+                SN_AA_HIP(sn::launch_reduce(st, B, a->cfg.bits_per_sample, a->reduce, g1 - g0, a->d_e[p] + g0 * a->obytes[p], a->obytes[p], a->opitch[p],
+                                            a->w[p], a->h[p], 1 - off, off, static_cast<uint8_t*>(d2[p]) + (int64_t)g0 * dfs[p], dfs[p], dp[p]));
+            g0 = g1;
+        }
     }
     return SN_OK;
 }
@@ -3091,7 +3154,7 @@ int sn_aa_process_device_strided(sn_aa_context* a, int32_t nframes, const void* 
     if (!src || !sfs || !sp || !dst || !dfs || !dp) return aa_fail(a, SN_ERR_INVALID_ARG, "plane / stride array is NULL");
     const int B = a->cfg.bytes_per_sample;
     for (int p = 0; p < a->planes; ++p) {
-        if (!src[p] || !dst[p] || sp[p] < a->w[p] * B || dp[p] < a->ow[p] * B)
+        if (!src[p] || !dst[p] || sp[p] < a->w[p] * B || dp[p] < a->dstw[p] * B)
             return aa_fail(a, SN_ERR_INVALID_ARG, "plane pointer is NULL or pitch smaller than the row");
         if (sp[p] % B || dp[p] % B || sfs[p] % B || dfs[p] % B || (uintptr_t)src[p] % B || (uintptr_t)dst[p] % B)
             return aa_fail(a, SN_ERR_INVALID_ARG, "plane pointer / pitch / frame stride not aligned to the sample size");
@@ -3136,7 +3199,7 @@ int sn_aa_process_device_surfaces(sn_aa_context* a, int32_t nframes, const sn_su
     g.planes = a->planes;
     g.sub_w = a->cfg.sub_w, g.sub_h = a->cfg.sub_h;
     g.max_batch = a->max_batch;
-    for (int p = 0; p < g.planes; ++p) g.w_in[p] = a->w[p], g.h_in[p] = a->h[p], g.w_out[p] = a->ow[p], g.h_out[p] = a->oh[p];
+    for (int p = 0; p < g.planes; ++p) g.w_in[p] = a->w[p], g.h_in[p] = a->h[p], g.w_out[p] = a->dstw[p], g.h_out[p] = a->dsth[p];
     g.luma_processed = a->process[0];
     g.chroma_processed = g.planes < 3 || a->process[1];
     g.all_lines = true;  // a turn reads whole source rows, whichever destination lines it writes
@@ -3174,6 +3237,8 @@ int sn_aa_synchronize(sn_aa_context* a)
 
 void* sn_aa_get_stream(sn_aa_context* a) { return a ? reinterpret_cast<void*>(a->stream) : nullptr; }
 
+int sn_aa_get_reduce(sn_aa_context* a) { return a ? a->reduce : -1; }
+
 int sn_aa_get_info(sn_aa_context* a, int32_t pass, sn_info* info)
 {
     if (!a) return aa_fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
@@ -3205,7 +3270,7 @@ static int aa_ensure_group(sn_aa_context* a, int gi, int n)
     sn_aa_context::Group& g = a->groups[(size_t)gi];
     if (g.n) return SN_OK;
     for (int p = 0; p < a->planes; ++p) {
-        const size_t nb = (size_t)a->cbytes[p] * n, onb = (size_t)a->obytes[p] * n;
+        const size_t nb = (size_t)a->cbytes[p] * n, onb = (size_t)a->dstbytes[p] * n;
         // a plane that is not processed never visits the device: its staging carries it from submission to collection
         SN_AA_HIP(hipHostMalloc(reinterpret_cast<void**>(&g.h_src[p]), nb, hipHostMallocDefault));
         if (!a->process[p]) continue;
@@ -3235,7 +3300,7 @@ static int aa_check_host_planes(sn_aa_context* a, const void* const ptr[3], cons
 {
     if (!ptr || !pitch) return aa_fail(a, SN_ERR_INVALID_ARG, "plane array is NULL");
     for (int p = 0; p < a->planes; ++p)
-        if (!ptr[p] || pitch[p] < (out ? a->ow[p] : a->w[p]) * a->cfg.bytes_per_sample)
+        if (!ptr[p] || pitch[p] < (out ? a->dstw[p] : a->w[p]) * a->cfg.bytes_per_sample)
             return aa_fail(a, SN_ERR_INVALID_ARG, "plane pointer is NULL or pitch smaller than the row");
     return SN_OK;
 }
@@ -3260,7 +3325,7 @@ static int aa_stage(sn_aa_context* a, sn_aa_context::Group& g, int k, const void
         }
         direct[p] = sn::plane_is_pinned(src[p], sp[p], a->w[p] * B, a->h[p]);
         if (!direct[p]) jobs[nj++] = {g.h_src[p] + k * a->cbytes[p], static_cast<const uint8_t*>(src[p]), a->pitch[p], sp[p], a->w[p] * B, a->h[p]};
-        if (dst && sn::plane_is_pinned(dst[p], dp[p], a->ow[p] * B, a->oh[p])) sl.out[p] = dst[p], sl.out_pitch[p] = dp[p];
+        if (dst && sn::plane_is_pinned(dst[p], dp[p], a->dstw[p] * B, a->dsth[p])) sl.out[p] = dst[p], sl.out_pitch[p] = dp[p];
     }
     if (nj) a->copier->run(jobs, nj);
     for (int p = 0; p < a->planes; ++p) {
@@ -3290,18 +3355,18 @@ static int aa_launch(sn_aa_context* a, sn_aa_context::Group& g)
     for (int p = 0; p < a->planes; ++p) {
         any = any || a->process[p];
         s3[p] = a->process[p] ? g.d_src[p] + g.lo * a->cbytes[p] : g.h_src[p];  // (not processed: never read on the device)
-        d3[p] = a->process[p] ? g.d_out[p] + g.lo * a->obytes[p] : g.h_src[p];
+        d3[p] = a->process[p] ? g.d_out[p] + g.lo * a->dstbytes[p] : g.h_src[p];
     }
     if (any)
-        if (int rc = aa_run(a, n, s3, a->cbytes, a->pitch, d3, a->obytes, a->opitch, par.data())) return rc;
+        if (int rc = aa_run(a, n, s3, a->cbytes, a->pitch, d3, a->dstbytes, a->dstpitch, par.data())) return rc;
     SN_AA_HIP(hipEventRecord(g.swept, a->stream));
     SN_AA_HIP(hipStreamWaitEvent(a->down, g.swept, 0));
     for (int k = g.lo; k < g.hi; ++k) {
         sn_aa_context::Slot& sl = g.slot[(size_t)k];
         for (int p = 0; p < a->planes; ++p) {
             if (!a->process[p]) continue;
-            SN_AA_HIP(hipMemcpy2DAsync(sl.out[p] ? sl.out[p] : g.h_dst[p] + k * a->obytes[p], sl.out[p] ? (size_t)sl.out_pitch[p] : (size_t)a->opitch[p],
-                                       g.d_out[p] + k * a->obytes[p], a->opitch[p], (size_t)a->ow[p] * B, a->oh[p], hipMemcpyDeviceToHost, a->down));
+            SN_AA_HIP(hipMemcpy2DAsync(sl.out[p] ? sl.out[p] : g.h_dst[p] + k * a->dstbytes[p], sl.out[p] ? (size_t)sl.out_pitch[p] : (size_t)a->dstpitch[p],
+                                       g.d_out[p] + k * a->dstbytes[p], a->dstpitch[p], (size_t)a->dstw[p] * B, a->dsth[p], hipMemcpyDeviceToHost, a->down));
         }
         sl.state = Context::kInFlight;
     }
@@ -3349,7 +3414,7 @@ static int aa_finish(sn_aa_context* a, sn_aa_context::Group& g, int k, void* con
         if (a->process[p] ? sl.out[p] == dst[p] : sl.copied[p]) continue;  // already there
         // (a plane that is not processed has the clip's geometry on both sides: there is none with dh)
         if (a->process[p])
-            jobs[nj++] = {static_cast<uint8_t*>(dst[p]), g.h_dst[p] + k * a->obytes[p], dp[p], a->opitch[p], a->ow[p] * B, a->oh[p]};
+            jobs[nj++] = {static_cast<uint8_t*>(dst[p]), g.h_dst[p] + k * a->dstbytes[p], dp[p], a->dstpitch[p], a->dstw[p] * B, a->dsth[p]};
         else
             jobs[nj++] = {static_cast<uint8_t*>(dst[p]), g.h_src[p] + k * a->cbytes[p], dp[p], a->pitch[p], a->w[p] * B, a->h[p]};
     }

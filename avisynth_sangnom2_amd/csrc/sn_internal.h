@@ -71,6 +71,11 @@ struct Context;
 hipError_t launch_turn(hipStream_t s, int bytes, int right, int nframes, const uint8_t* src, int64_t src_frame_stride, int src_pitch, int w,
                        int h, uint8_t* dst, int64_t dst_frame_stride, int dst_pitch, int line_parity = -1);
 
+// sn_reduce.hip: the 2w x 2h plane of the anti-aliasing call with dh back to w x h (of dst): kernel 1 = tent [1 2 1],
+// 2 = half-band [-1 0 9 16 9 0 -1], centred on src[2y + oy][2x + ox], edges clamped; integer results clamped to `bits`
+hipError_t launch_reduce(hipStream_t s, int bytes, int bits, int kernel, int nframes, const uint8_t* src, int64_t src_frame_stride, int src_pitch,
+                         int w, int h, int ox, int oy, uint8_t* dst, int64_t dst_frame_stride, int dst_pitch);
+
 // sn_uv.hip: semi-planar chroma (a UV plane of U,V sample pairs: NV12 / P016 / NV16 / NV24) <-> a U and a V plane of cw x h
 // samples each.  line_parity 0 / 1: only the lines of that parity are read and written (the lines the pass that follows
 // keeps), < 0: all of them.  One side is never written: split reads uv, merge reads u and v.

@@ -302,6 +302,17 @@ class SangNom2:
                                              dst.data_ptr(), dst.stride(0) * B, dst.stride(1) * B))
         return dst
 
+    def reduce(self, src, dst, kernel, ox: int, oy: int):
+        """sn_reduce_device: src [N, 2 H, 2 W] -> dst [N, H, W] (torch tensors on the device) by kernel "tent" | "halfband",
+        centred on src[2y + oy][2x + ox].  Asynchronous on the context's stream."""
+        B = self.clip.bytes
+        N, H, W = dst.shape
+        if tuple(src.shape) != (N, 2 * H, 2 * W) or src.stride(2) != 1 or dst.stride(2) != 1 or src.element_size() != B or dst.element_size() != B:
+            raise ValueError("reduce: src must be [N, 2 H, 2 W] for dst [N, H, W], both x-contiguous and of the clip's sample type")
+        self._check(self._lib.sn_reduce_device(self._h, capi.REDUCE_KERNELS.get(kernel, kernel), N, src.data_ptr(), src.stride(0) * B, src.stride(1) * B,
+                                               W, H, int(ox), int(oy), dst.data_ptr(), dst.stride(0) * B, dst.stride(1) * B))
+        return dst
+
     def get_frame_device(self, src, dst, parity: int = 1):
         """Device planes: torch tensors [H, W] on this context's GPU.  Asynchronous."""
         return self.process_batch([s.unsqueeze(0) for s in src], [d.unsqueeze(0) for d in dst], [parity])
@@ -384,15 +395,19 @@ class _AAContext:
     """An sn_aa_context: the anti-aliasing idiom TurnLeft().SangNom2(...).TurnRight().SangNom2(...) as one call of the
     library.  Not a function of the reference; the result is what that script gives with it.
     dh=True: both passes with dh=true, enlargement by two in both directions; every plane is processed (luma / chroma are
-    ignored, as in the reference) and every destination plane is twice as wide and twice as high as its source plane."""
+    ignored, as in the reference) and every destination plane is twice as wide and twice as high as its source plane.
+    reduce="tent" | "halfband" (with dh): the enlarged frame is reduced on the device by that kernel, centred on the source
+    samples (sangnom_hip.h has the arithmetic), and every destination plane has the source plane's shape again."""
 
     def __init__(self, clip: ClipFormat, order: int = 1, aa: int = 48, aac: int = 0, luma: bool = True, chroma: bool = True,
                  device: int = 0, isolated_planes: bool = False, fresh_pool: bool = False, opt: int = -1, max_batch: int = 1,
-                 host_depth: int = 0, stream: int | None = None, dh: bool = False, column_parts: int = 0, **policy_kw):
+                 host_depth: int = 0, stream: int | None = None, dh: bool = False, column_parts: int = 0, reduce=0, **policy_kw):
         if opt < -1 or opt > 1:
             raise SangNomError(capi.SN_ERR_CONFIG, "SangNom2: opt must be between -1..2.")  # sic, SangNom2.cpp:420
         self.clip = clip
         self.dh = bool(dh)
+        aopts = capi.aa_options(reduce)  # reduce="tent" | "halfband" (dh only): the frame comes back at source size
+        self.reduce = aopts.reduce
         self.max_batch = max_batch
         self._lib = capi.load()
         cfg = capi.SnConfig(
@@ -403,7 +418,7 @@ class _AAContext:
         self._h = ctypes.c_void_p()
         pol = capi.policy(**{k: policy_kw.get(k) for k in ("small_launches", "chain", "copy_threads", "scratch_budget_mb", "chroma_sweeps", "sse2_sweeps")})
         opts = capi.options(capi.arithmetic_of_opt(opt), column_parts=column_parts)
-        rc = self._lib.sn_aa_create_ex(ctypes.byref(cfg), ctypes.byref(pol), ctypes.byref(opts), ctypes.byref(self._h))
+        rc = self._lib.sn_aa_create_ex2(ctypes.byref(cfg), ctypes.byref(pol), ctypes.byref(opts), ctypes.byref(aopts), ctypes.byref(self._h))
         if rc != capi.SN_OK:
             self._h = None
             raise SangNomError(rc, self._lib.sn_aa_last_error(None).decode())
@@ -417,7 +432,7 @@ class _AAContext:
 
     def plane_shape_out(self, p: int):
         h, w = self.plane_shape(p)
-        return (2 * h, 2 * w) if self.dh else (h, w)
+        return (2 * h, 2 * w) if self.dh and not self.reduce else (h, w)
 
     def close(self):
         if getattr(self, "_h", None):

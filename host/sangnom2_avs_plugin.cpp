@@ -101,7 +101,8 @@ AVSValue __cdecl Create_SangNom2HIP(AVSValue args, void*, IScriptEnvironment* en
 
 // SangNomAA(clip, order, aa, aac): TurnLeft().SangNom2(order, aa, aac).TurnRight().SangNom2(order, aa, aac) with the frame
 // staying on the device between the passes (sangnom::AAFilter).  dh=true: both passes with dh=true, the clip comes out
-// twice as wide and twice as high.
+// twice as wide and twice as high; with reduce=1 (tent) or 2 (half-band) on top of it the enlarged frame is reduced on the
+// device and the clip keeps its size: a drop-in anti-aliaser.  Reduce without dh: "SangNomAA: reduce needs dh=true".
 class SangNomAA : public GenericVideoFilter {
     sangnom::AAFilter<AvsHost> impl_;
 
@@ -128,6 +129,7 @@ AVSValue __cdecl Create_SangNomAA(AVSValue args, void*, IScriptEnvironment* env)
     a.fresh = args[9].AsBool(false);
     a.lookahead = args[10].AsInt(-1);
     a.dh = args[11].AsBool(false);
+    a.reduce = args[12].AsInt(0);
     return new SangNomAA(args[0].AsClip(), a, env);
 }
 
@@ -151,7 +153,7 @@ extern "C" __declspec(dllexport) const char* __stdcall AvisynthPluginInit3(IScri
     env->AddFunction("SangNom", "c[order]i[aa]i[opt]i", Create_SangNom, 0);                                        // :482
     env->AddFunction("SangNom2HIP", "c[order]i[aa]i[aac]i[threads]i[dh]b[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i[device]i",
                      Create_SangNom2HIP, 0);
-    env->AddFunction("SangNomAA", "c[order]i[aa]i[aac]i[device]i[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i[dh]b", Create_SangNomAA, 0);
+    env->AddFunction("SangNomAA", "c[order]i[aa]i[aac]i[device]i[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i[dh]b[reduce]i", Create_SangNomAA, 0);
     return "SangNom2";
 }
 #endif  // SN_HAVE_AVISYNTH

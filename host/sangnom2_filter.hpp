@@ -38,6 +38,7 @@ struct Args {  // SangNom2(clip, order, aa, aac, threads, dh, luma, chroma, opt)
     int lookahead = -1;  // frames in flight behind GetFrame; -1: $SANGNOM_LOOKAHEAD or 1 (synchronous)
     bool isolated = false;  // extension: every plane filtered as a Y clip of its own (sn_config.isolated_planes)
     bool fresh = false;     // extension: ... and every frame by a new instance (sn_config.fresh_pool)
+    int reduce = 0;         // SangNomAA only, with dh: SN_AA_REDUCE_TENT / SN_AA_REDUCE_HALFBAND, the frame comes back at source size
     int column_parts = -1;  // sn_options.column_parts (16-bit / float planes wider than 3840 in column parts); -1: $SANGNOM_COLUMN_PARTS or 0
     sn_policy policy{};     // scheduling only (sangnom_hip.h); zeros = the defaults
 };
@@ -241,6 +242,9 @@ private:
 // With Args::dh both passes run with dh=true: TurnLeft().SangNom2(dh=true).TurnRight().SangNom2(dh=true), enlargement by
 // two in both directions.  The filter's clip is then twice as wide and twice as high, every plane is processed (luma /
 // chroma are ignored, as in the reference), and the alpha of a YUVA clip fills a 2 x 2 block per source sample.
+// With Args::reduce (1 tent, 2 half-band; needs dh) the library reduces the enlarged frame on the device, centred on the
+// source samples (sangnom_hip.h, "Anti-aliasing at source size"): the filter's clip is the source's again -- a drop-in
+// anti-aliaser --, a frame of source size comes down, and the alpha passes through 1:1.
 template <class Host>
 class AAFilter {
 public:
@@ -258,6 +262,8 @@ public:
         if (a.order < 0 || a.order > 2) env->ThrowError("%s: order must be between 0..2.", name);
         if (a.aa < 0 || a.aa > 128) env->ThrowError("%s: aa must be between 0..128.", name);
         if (a.aac < 0 || a.aac > 128) env->ThrowError("%s: aac must be between 0..128.", name);
+        if (a.reduce < 0 || a.reduce > 2) env->ThrowError("%s: reduce must be between 0..2.", name);
+        if (a.reduce && !a.dh) env->ThrowError("%s: reduce needs dh=true", name);
         sn_config c{};
         c.struct_size = (int32_t)sizeof c;
         c.width = Host::Width(vi_);
@@ -289,8 +295,12 @@ public:
         opts.struct_size = (int32_t)sizeof opts;
         opts.arithmetic = a.opt == 1 ? SN_ARITH_SSE2 : SN_ARITH_CXX;
         opts.column_parts = column_parts_of(a);
-        if (sn_aa_create_ex(&c, &pol, &opts, &ctx_) != SN_OK) env->ThrowError("%s: %s", name, sn_aa_last_error(nullptr));
-        if (a.dh) {  // each pass doubles the height of what it is given: the clip comes out twice as wide and twice as high
+        sn_aa_options aopts{};
+        aopts.struct_size = (int32_t)sizeof aopts;
+        aopts.reduce = a.reduce;
+        if (sn_aa_create_ex2(&c, &pol, &opts, &aopts, &ctx_) != SN_OK) env->ThrowError("%s: %s", name, sn_aa_last_error(nullptr));
+        enlarged_ = a.dh && !a.reduce;
+        if (enlarged_) {  // each pass doubles the height of what it is given: the clip comes out twice as wide and twice as high
             Host::SetWidth(vi_, Host::Width(vi_) * 2);
             Host::SetHeight(vi_, Host::Height(vi_) * 2);
         }
@@ -345,7 +355,7 @@ private:
         if (!alpha_) return;
         const size_t B = (size_t)Host::ComponentSize(vi_);
         const size_t row = (size_t)Host::Width(vi_) * B;
-        if (!args_.dh) {
+        if (!enlarged_) {
             for (int y = 0; y < Host::Height(vi_); ++y)
                 std::memcpy(Host::WritePtr(dst, 3) + (size_t)y * Host::Pitch(dst, 3), Host::ReadPtr(src, 3) + (size_t)y * Host::Pitch(src, 3), row);
             return;
@@ -411,6 +421,7 @@ private:
     sn_aa_context* ctx_ = nullptr;
     int planes_ = 1;
     bool alpha_ = false;
+    bool enlarged_ = false;  // dh without reduce: the clip is twice as wide and twice as high
 };
 
 // Legacy SangNom(clip, order, aa, opt): order 0/1/2 = bottom/top/double-rate is remapped to

@@ -4,9 +4,10 @@
 // offers the same filter to VapourSynth scripts through the C ABI of include/sangnom_hip.h:
 //     core.sangnomhip.SangNom(clip, order=1, dh=False, aa=48, aac=0, luma=True, chroma=True,
 //                             isolated=False, fresh=False)
-//     core.sangnomhip.SangNomAA(clip, order=1, aa=48, aac=0, luma=True, chroma=True, isolated=False, fresh=False, dh=False)
+//     core.sangnomhip.SangNomAA(clip, order=1, aa=48, aac=0, luma=True, chroma=True, isolated=False, fresh=False, dh=False, reduce=0)
 // SangNomAA is the anti-aliasing idiom (a quarter turn, SangNom, the turn back, SangNom) as one call of the library
-// (sn_aa_process_host); with dh=True both passes double the height: the clip comes out twice as wide and twice as high.
+// (sn_aa_process_host); with dh=True both passes double the height: the clip comes out twice as wide and twice as high;
+// with reduce=1 (tent) or 2 (half-band) on top of dh the library reduces it on the device and the clip keeps its size.
 // It needs the VapourSynth SDK header VapourSynth4.h, a third-party file that is not part of this repository or
 // of the build image: without it this file compiles to nothing, so it has NOT been compiled or run here
 // (INTEGRATION.md says so).  With the SDK:  make -C host VS_INCLUDE_DIR=<dir of VapourSynth4.h>.
@@ -132,10 +133,14 @@ void VS_CC sangnomCreate(const VSMap* in, VSMap* out, void* userData, VSCore* co
     char msg[256];
     if (sn_validate(&c, msg, sizeof msg) != SN_OK) return fail(bare(msg));
     // SangNomAA: the turned clip and, with dh, the clip twice as wide are validated by the creation itself
-    if (aa ? sn_aa_create(&c, &d->aa) != SN_OK : sn_create(&c, &d->ctx) != SN_OK) return fail(bare(aa ? sn_aa_last_error(nullptr) : sn_last_error(nullptr)));
+    sn_aa_options ao{};
+    ao.struct_size = (int32_t)sizeof ao;
+    ao.reduce = aa ? geti("reduce", 0) : 0;
+    if (ao.reduce && !c.dh) return fail("reduce needs dh=true");
+    if (aa ? sn_aa_create_ex2(&c, nullptr, nullptr, &ao, &d->aa) != SN_OK : sn_create(&c, &d->ctx) != SN_OK) return fail(bare(aa ? sn_aa_last_error(nullptr) : sn_last_error(nullptr)));
     d->planes = c.num_planes;
-    if (c.dh) d->vi.height *= 2;
-    if (c.dh && aa) d->vi.width *= 2;  // both passes double the height of what they are given
+    if (c.dh && !ao.reduce) d->vi.height *= 2;
+    if (c.dh && aa && !ao.reduce) d->vi.width *= 2;  // both passes double the height of what they are given
     // The context keeps the reference's per-instance state (scratch pool, frame order), so frames are served one at
     // a time in request order: fmFrameState.  With fresh=True every frame is independent, but the context is still
     // not re-entrant (one stream, one staging area), hence the mutex above rather than a parallel mode.
@@ -154,7 +159,7 @@ VS_EXTERNAL_API(void) VapourSynthPluginInit2(VSPlugin* plugin, const VSPLUGINAPI
                              "clip:vnode;", sangnomCreate, nullptr, plugin);
     static int aa_tag = 1;
     vspapi->registerFunction("SangNomAA",
-                             "clip:vnode;order:int:opt;aa:int:opt;aac:int:opt;luma:int:opt;chroma:int:opt;isolated:int:opt;fresh:int:opt;dh:int:opt;",
+                             "clip:vnode;order:int:opt;aa:int:opt;aac:int:opt;luma:int:opt;chroma:int:opt;isolated:int:opt;fresh:int:opt;dh:int:opt;reduce:int:opt;",
                              "clip:vnode;", sangnomCreate, &aa_tag, plugin);
 }
 #endif  // SN_HAVE_VAPOURSYNTH

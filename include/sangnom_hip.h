@@ -298,6 +298,16 @@ int sn_turn_device(sn_context* ctx, int32_t direction, int32_t nframes, const vo
                    int32_t src_pitch, int32_t width, int32_t height, void* dst, int64_t dst_frame_stride,
                    int32_t dst_pitch);
 
+/* The reduction of the anti-aliasing call (below: "Anti-aliasing at source size", which defines the arithmetic) on its
+ * own, for pipelines that keep frames on the device, like sn_turn_device: `nframes` planes of 2 width x 2 height samples
+ * to width x height, centred on src[2y + oy][2x + ox], on the context's stream.  Sample type and bit depth (the clamp)
+ * come from the context.  kernel: SN_AA_REDUCE_TENT or SN_AA_REDUCE_HALFBAND; ox, oy: 0 or 1; src_pitch >= 2 width
+ * samples, dst_pitch >= width samples; pointers, pitches and frame strides multiples of the sample size (multiples of 16
+ * on a side: 16 bytes per lane and access on that side).  Nothing beyond width samples of a destination row is written. */
+int sn_reduce_device(sn_context* ctx, int32_t kernel, int32_t nframes, const void* src, int64_t src_frame_stride, int32_t src_pitch,
+                     int32_t width, int32_t height /* of dst; src is 2 width x 2 height */, int32_t ox, int32_t oy, void* dst,
+                     int64_t dst_frame_stride, int32_t dst_pitch);
+
 /* The anti-aliasing idiom TurnLeft().SangNom2(order, aa, aac).TurnRight().SangNom2(order, aa, aac) as ONE call with
  * host planes (README.md:3 of the reference: "mainly used in anti-aliasing scripts"): the frame
  * crosses PCIe once each way and stays on the device between the two passes (two filter instances -- one for the
@@ -322,11 +332,49 @@ int sn_turn_device(sn_context* ctx, int32_t direction, int32_t nframes, const vo
  * whole turns, and the intermediates per processed plane and frame are the turned source, the first pass's output
  * (twice that) and the second pass's input (twice that again, up to pitch rounding): five plane sizes against three
  * without dh, counted against sn_policy.scratch_budget_mb in the same way.  On the host path a whole source frame goes
- * up and a frame four times its size comes down; nothing of it can be copied on the host. */
+ * up and a frame four times its size comes down; nothing of it can be copied on the host.
+ *
+ * Anti-aliasing at source size (sn_aa_create_ex2 with sn_aa_options.reduce != 0; needs cfg.dh = 1, otherwise SN_ERR_CONFIG
+ * "reduce needs dh"): both passes run exactly as above (sn_aa_get_info(ctx, 1) still reports the 2 width clip), their
+ * 2W x 2H result E stays in an intermediate of the library (nine plane sizes with reduce, counted against
+ * scratch_budget_mb like the others) and a reduction kernel writes the destination.  Every destination plane, pitch check
+ * and frame stride of EVERY sn_aa_* entry point then describes the source geometry W_p x H_p (a packed or semi-planar dst
+ * has rows for W), and on the host path a frame of the source's size comes down.  No counterpart in the reference (it has
+ * no resampler); the arithmetic is defined here, exactly:
+ *   `off` is the kept-field offset of the frame: 0 for order 1, 1 for order 2, parity ? 0 : 1 for order 0.  The source
+ *   sample (x, y) reappears untouched at E[2y + oy][2x + ox] with oy = off and ox = 1 - off.  The reduction is a symmetric
+ *   odd filter centred on that position, so the result has no sub-pixel shift; coordinates outside E are clamped to the edge.
+ *     SN_AA_REDUCE_TENT = 1:     taps k = [1 2 1], shift s = 2 per direction.
+ *     SN_AA_REDUCE_HALFBAND = 2: taps k = [-1 0 9 16 9 0 -1], shift s = 5 per direction (the sharper one).
+ *   Let r be the radius (1 or 3), X = 2x + ox, Y = 2y + oy, cx(i) = clamp(i, 0, 2W-1) and cy(j) = clamp(j, 0, 2H-1).
+ *   Integer samples (8..16 bit), all sums in signed 32-bit:
+ *     h[j] = sum_i k[i] * E[cy(Y+j-r)][cx(X+i-r)]
+ *     v    = sum_j k[j] * h[j]
+ *     out  = clamp((v + (1 << (2s-1))) >> 2s, 0, 2^bits_per_sample - 1) with an arithmetic shift.
+ *   |v| <= 36*36*65535 fits in 32 bits.  The clamp is to the clip's range, not the container's: a reduced 10-bit plane is
+ *   always valid in an MSB or v210 destination.  For the tent kernel only the upper clamp can act, when E itself is out of range.
+ *   Float samples: one rounding per written operation, in this order, with no contraction:
+ *     tent:      h = (a[-1] + a[+1]) + (a[0] + a[0]);  v = (h[-1] + h[+1]) + (h[0] + h[0]);  out = v * 0.0625f
+ *     half-band: h = ((a[-1] + a[+1]) * 9.0f + a[0] * 16.0f) - (a[-3] + a[+3]);  v is the same expression over h[-3..3];
+ *                out = v * 0.0009765625f
+ *   No clamp.
+ *   The same reduction follows both arithmetics (sn_options.arithmetic); only E differs.  Every plane is reduced, because dh
+ *   forces every plane through both passes. */
+enum { SN_AA_REDUCE_NONE = 0, SN_AA_REDUCE_TENT = 1, SN_AA_REDUCE_HALFBAND = 2 };
+typedef struct sn_aa_options {
+    int32_t struct_size; /* sizeof(sn_aa_options) */
+    int32_t reduce;      /* SN_AA_REDUCE_* */
+    int32_t reserved[6]; /* zero */
+} sn_aa_options;         /* 32 bytes */
 typedef struct sn_aa_context sn_aa_context;
 int sn_aa_create(const sn_config* cfg, sn_aa_context** out);
 int sn_aa_create_with_policy(const sn_config* cfg, const sn_policy* policy /* NULL = defaults; both passes */, sn_aa_context** out);
 int sn_aa_create_ex(const sn_config* cfg, const sn_policy* policy, const sn_options* options /* both passes */, sn_aa_context** out);
+/* sn_aa_create_ex is sn_aa_create_ex2 with aa_options = NULL (the defaults: no reduction).  A bad struct_size, a reduce
+ * outside 0..2 or a non-zero reserved word: SN_ERR_INVALID_ARG, naming the field. */
+int sn_aa_create_ex2(const sn_config* cfg, const sn_policy* policy, const sn_options* options, const sn_aa_options* aa_options /* NULL = defaults */,
+                     sn_aa_context** out);
+int sn_aa_get_reduce(sn_aa_context* ctx); /* SN_AA_REDUCE_* of a live context; -1 for NULL */
 int sn_aa_process_host(sn_aa_context* ctx, const void* const src[3], const int32_t src_pitch[3], void* const dst[3],
                        const int32_t dst_pitch[3], int32_t parity);
 const char* sn_aa_last_error(const sn_aa_context* ctx); /* ctx == NULL: last failed sn_aa_create on this thread */

@@ -3,8 +3,12 @@
 the turn kernel alone; with --host, frames from pageable host memory: the synchronous call (SangNomAAHost.get_frame)
 against the ring at --depth.  --dh: the enlargement form (both passes with dh=true, destinations twice as wide and twice
 as high); --dh --composed: the same idiom composed by hand from two SangNom2(dh=True) contexts and SangNom2.turn on one
-stream, the way a caller had to build it before the call took dh.
-usage: python tools/aa_bench.py [--frames 512] [--fresh 1] [--fmt Y8] [--size 3840x2160] [--dh [--composed]] [--host [--depth 8]]"""
+stream, the way a caller had to build it before the call took dh.  --reduce tent|halfband (implies --dh): the enlarged
+frame is reduced on the device, destinations of source size (device batches and --host).  --reduce-bw: the reduce kernel
+alone (sn_reduce_device, both tap sets) against the turn kernel on the same 2W x 2H planes, alternating, --size being the
+SOURCE size; any of Y8 / Y16 / Y32.
+usage: python tools/aa_bench.py [--frames 512] [--fresh 1] [--fmt Y8] [--size 3840x2160] [--dh [--composed]] [--reduce K] [--host [--depth 8]]
+       python tools/aa_bench.py --reduce-bw [--fmt Y16] [--size 1920x1080] [--frames 64]"""
 import argparse
 import json
 import os
@@ -30,11 +34,13 @@ def host_rates(clip, a):
     up = sum(s[0] * s[1] for s in shapes) * clip.bytes
     if a.dh:
         out["dh"] = True
-        out["pcie_bytes_per_frame_up"], out["pcie_bytes_per_frame_down"] = up, 4 * up
+        out["pcie_bytes_per_frame_up"], out["pcie_bytes_per_frame_down"] = up, up if a.reduce else 4 * up
+        if a.reduce:
+            out["reduce"] = a.reduce
     else:
         out["pcie_bytes_per_frame_each_way"] = up
-    dh_kw = dict(dh=True) if a.dh else {}
-    oshapes = [(2 * s[0], 2 * s[1]) if a.dh else s for s in shapes]
+    dh_kw = dict(dh=True, **(dict(reduce=a.reduce) if a.reduce else {})) if a.dh else {}
+    oshapes = [(2 * s[0], 2 * s[1]) if a.dh and not a.reduce else s for s in shapes]
     with SangNomAAHost(clip, aac=48 if clip.planes > 1 else 0, fresh_pool=bool(a.fresh), **dh_kw) as flt:
         for i in range(3):
             flt.get_frame(frames[i])
@@ -95,6 +101,38 @@ def composed_dh_rate(clip, a, src, dst):
         return round(N * reps / (time.perf_counter() - t0), 1)
 
 
+def reduce_bandwidth(clip, a):
+    """sn_reduce_device against sn_turn_device on the same planes E (2W x 2H, distinct frames), alternating: median seconds
+    per launch of --frames frames; reduce moves 5 W H B bytes per frame (4 read, 1 written), the turn 8 W H B."""
+    dev = torch.device("cuda:0")
+    N, W, H, B = a.frames, clip.width, clip.height, clip.bytes
+    dt = {1: torch.uint8, 2: torch.int16, 4: torch.float32}[B]
+    E = torch.randint(0, 256, (N, 2 * H, 2 * W * B), device=dev, dtype=torch.uint8).view(dt) if B != 4 else torch.rand((N, 2 * H, 2 * W), device=dev)
+    turned = torch.empty((N, 2 * W, 2 * H), device=dev, dtype=dt)
+    small = torch.empty((N, H, W), device=dev, dtype=dt)
+    out = {"clip": f"{a.fmt} source {W}x{H}, E {2 * W}x{2 * H}", "frames": N, "E_bytes": N * 4 * W * H * B}
+    with SangNom2(clip, max_batch=1) as flt:
+        runs = {"turn": lambda: flt.turn(E, turned, 1), "tent": lambda: flt.reduce(E, small, "tent", 1, 0),
+                "halfband": lambda: flt.reduce(E, small, "halfband", 1, 0)}
+        times = {k: [] for k in runs}
+        torch.cuda.synchronize()
+        for r in range(a.reps + 1):
+            for k, fn in runs.items():
+                flt.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                flt.synchronize()
+                if r:
+                    times[k].append(time.perf_counter() - t0)
+        for k, t in times.items():
+            t.sort()
+            moved = (8 if k == "turn" else 5) * N * W * H * B
+            out[k + "_ms"] = round(1e3 * t[len(t) // 2], 3)
+            out[k + "_GBps"] = round(moved / t[len(t) // 2] / 1e9, 1)
+            out[k + "_GBps_min_max"] = [round(moved / t[-1] / 1e9, 1), round(moved / t[0] / 1e9, 1)]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=512)
@@ -105,13 +143,21 @@ def main():
     ap.add_argument("--depth", type=int, default=8, help="--host: slots of the ring")
     ap.add_argument("--dh", action="store_true", help="both passes with dh=true: enlargement by two in both directions")
     ap.add_argument("--composed", action="store_true", help="--dh, device-resident: two SangNom2(dh=True) contexts and SangNom2.turn by hand")
+    ap.add_argument("--reduce", choices=["tent", "halfband"], help="with dh: reduce the enlarged frame on the device (implies --dh)")
+    ap.add_argument("--reduce-bw", action="store_true", help="the reduce kernel alone against the turn kernel on the same planes")
+    ap.add_argument("--reps", type=int, default=9, help="--reduce-bw: timed launches per kernel")
     a = ap.parse_args()
     w, h = [int(x) for x in a.size.split("x")]
     clip = clip_format(a.fmt, w, h)
+    if a.reduce:
+        a.dh = True
+    if a.reduce_bw:
+        print(json.dumps(reduce_bandwidth(clip, a)))
+        return
     if clip.bytes != 1:
         sys.exit("aa_bench: 8-bit formats only")
-    if a.composed and (not a.dh or a.host):
-        sys.exit("aa_bench: --composed goes with --dh, device-resident")
+    if a.composed and (not a.dh or a.host or a.reduce):
+        sys.exit("aa_bench: --composed goes with --dh, device-resident, without --reduce")
     if a.host:
         print(json.dumps(host_rates(clip, a)))
         return
@@ -119,16 +165,19 @@ def main():
     N = a.frames
     src = [torch.randint(0, 256, (N, h >> (clip.subh if p else 0), w >> (clip.subw if p else 0)), device=dev, dtype=torch.uint8)
            for p in range(clip.planes)]
-    k = 2 if a.dh else 1
+    k = 2 if a.dh and not a.reduce else 1
     dst = [torch.empty((N, k * s.shape[1], k * s.shape[2]), device=dev, dtype=torch.uint8) for s in src]
     out = {"clip": f"{a.fmt} {w}x{h}", "frames": N, "fresh_pool": bool(a.fresh)}
     if a.dh:
         out["dh"] = True
+    if a.reduce:
+        out["reduce"] = a.reduce
     if a.composed:
         out["composed_fps"] = composed_dh_rate(clip, a, src, dst)
         print(json.dumps(out))
         return
-    with SangNomAA(clip, max_batch=N, fresh_pool=bool(a.fresh), aac=48 if clip.planes > 1 else 0, **(dict(dh=True) if a.dh else {})) as aa:
+    with SangNomAA(clip, max_batch=N, fresh_pool=bool(a.fresh), aac=48 if clip.planes > 1 else 0, **(dict(dh=True) if a.dh else {}),
+                   **(dict(reduce=a.reduce) if a.reduce else {})) as aa:
         torch.cuda.synchronize()
         for _ in range(2):
             aa.process_batch(src, dst)
