@@ -32,10 +32,10 @@ EXPORTS = (
     "sn_aa_host_slots", "sn_aa_submit_host", "sn_aa_collect_host",
     "sn_get_parts_info", "sn_aa_get_parts_info", "sn_debug_set_column_parts",
     "sn_process_device_surfaces", "sn_aa_process_device_surfaces", "sn_get_surface_info", "sn_aa_get_surface_info",
-    "sn_aa_get_reduce", "sn_reduce_device",
+    "sn_aa_get_reduce", "sn_reduce_device", "sn_aa_get_mask", "sn_mask_merge_device",
 )
 # ... and the ones whose names end in a digit
-EXPORTS_NUMBERED = ("sn_aa_create_ex2",)
+EXPORTS_NUMBERED = ("sn_aa_create_ex2", "sn_aa_create_ex3")
 
 # sn_aa_options.reduce: the anti-aliasing call with dh returns the frame at source size (sangnom_hip.h has the arithmetic)
 SN_AA_REDUCE_NONE, SN_AA_REDUCE_TENT, SN_AA_REDUCE_HALFBAND = 0, 1, 2
@@ -87,6 +87,23 @@ def aa_options(reduce=0) -> "SnAAOptions":
     if reduce not in REDUCE_KERNELS:
         raise ValueError("reduce must be 0, 'tent' or 'halfband'")
     return SnAAOptions(struct_size=ctypes.sizeof(SnAAOptions), reduce=REDUCE_KERNELS[reduce])
+
+
+# sn_aa_mask.kind: the call's result is merged into the source through an edge mask of the source (sangnom_hip.h, "Edge mask")
+SN_AA_MASK_NONE, SN_AA_MASK_SOBEL = 0, 1
+
+
+class SnAAMask(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_int32), ("kind", ctypes.c_int32), ("lo", ctypes.c_int32), ("hi", ctypes.c_int32),
+                ("expand", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
+def aa_mask(mask=None, expand=1) -> "SnAAMask":
+    """sn_aa_mask: mask = None (no mask) or (lo, hi) in 8-bit scale; expand = 0 or 1.  The library checks the values."""
+    if mask is None:
+        return SnAAMask(struct_size=ctypes.sizeof(SnAAMask), kind=SN_AA_MASK_NONE)
+    lo, hi = mask
+    return SnAAMask(struct_size=ctypes.sizeof(SnAAMask), kind=SN_AA_MASK_SOBEL, lo=int(lo), hi=int(hi), expand=int(expand))
 
 
 class SnPartsInfo(ctypes.Structure):
@@ -191,6 +208,10 @@ def load():
     L.sn_aa_create_ex.argtypes = [ctypes.POINTER(SnConfig), ctypes.POINTER(SnPolicy), ctypes.POINTER(SnOptions), ctypes.POINTER(vp)]
     L.sn_aa_create_ex2.argtypes = [ctypes.POINTER(SnConfig), ctypes.POINTER(SnPolicy), ctypes.POINTER(SnOptions), ctypes.POINTER(SnAAOptions),
                                    ctypes.POINTER(vp)]
+    L.sn_aa_create_ex3.argtypes = [ctypes.POINTER(SnConfig), ctypes.POINTER(SnPolicy), ctypes.POINTER(SnOptions), ctypes.POINTER(SnAAOptions),
+                                   ctypes.POINTER(SnAAMask), ctypes.POINTER(vp)]
+    L.sn_aa_get_mask.argtypes = [vp, ctypes.POINTER(SnAAMask)]
+    L.sn_mask_merge_device.argtypes = [vp, ctypes.POINTER(SnAAMask), i32, vp, i64, i32, vp, i64, i32, i32, i32, vp, i64, i32]
     L.sn_aa_get_reduce.argtypes = [vp]
     L.sn_reduce_device.argtypes = [vp, i32, i32, vp, i64, i32, i32, i32, i32, i32, vp, i64, i32]
     L.sn_get_arithmetic.argtypes = [vp]

@@ -2661,6 +2661,42 @@ int sn_reduce_device(sn_context* h, int32_t kernel, int32_t nframes, const void*
     return SN_OK;
 }
 
+// sn_aa_mask as sn_aa_create_ex3 and sn_mask_merge_device take it: empty when it is fine, otherwise the message, naming the field
+static std::string mask_problem(const sn_aa_mask* m)
+{
+    if (m->struct_size != (int32_t)sizeof(sn_aa_mask)) return "sn_aa_mask.struct_size mismatch";
+    if (m->kind < SN_AA_MASK_NONE || m->kind > SN_AA_MASK_SOBEL) return "sn_aa_mask.kind must be 0 (none) or 1 (Sobel)";
+    if (m->kind == SN_AA_MASK_NONE) return "";
+    if (m->lo < 0 || m->lo > 255) return "sn_aa_mask.lo must be 0..255";
+    if (m->hi < 0 || m->hi > 255) return "sn_aa_mask.hi must be 0..255";
+    if (m->lo > m->hi) return "sn_aa_mask.lo must not be above sn_aa_mask.hi";
+    if (m->expand < 0 || m->expand > 1) return "sn_aa_mask.expand must be 0 or 1";
+    for (int32_t r : m->reserved)
+        if (r) return "sn_aa_mask.reserved must be zero";
+    return "";
+}
+
+int sn_mask_merge_device(sn_context* h, const sn_aa_mask* mask, int32_t nframes, const void* src, int64_t sfs, int32_t sp, const void* aa, int64_t afs,
+                         int32_t ap, int32_t width, int32_t height, void* dst, int64_t dfs, int32_t dp)
+{
+    Context* c = reinterpret_cast<Context*>(h);
+    if (!c) return sn::fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    const int B = c->cfg.bytes_per_sample;
+    if (!mask) return sn::fail(c, SN_ERR_INVALID_ARG, "sn_mask_merge_device: mask is NULL");
+    const std::string problem = mask_problem(mask);
+    if (!problem.empty()) return sn::fail(c, SN_ERR_INVALID_ARG, ("sn_mask_merge_device: " + problem).c_str());
+    if (mask->kind != SN_AA_MASK_SOBEL) return sn::fail(c, SN_ERR_INVALID_ARG, "sn_mask_merge_device: sn_aa_mask.kind must be 1 (Sobel)");
+    if (!src || !dst || nframes < 0 || width <= 0 || height <= 0 || width > INT32_MAX / 8 || height > INT32_MAX / 2)
+        return sn::fail(c, SN_ERR_INVALID_ARG, "sn_mask_merge_device: bad pointer or size");
+    if (sp < width * B || dp < width * B || sp % B || dp % B || sfs % B || dfs % B || (uintptr_t)src % B || (uintptr_t)dst % B ||
+        (aa && (ap < width * B || ap % B || afs % B || (uintptr_t)aa % B)))
+        return sn::fail(c, SN_ERR_INVALID_ARG, "sn_mask_merge_device: pitch smaller than the row or misaligned");
+    SN_HIP(c, hipSetDevice(c->device));
+    SN_HIP(c, sn::launch_mask_merge(c->stream, B, c->cfg.bits_per_sample, mask->lo, mask->hi, mask->expand, nframes, static_cast<const uint8_t*>(src), sfs, sp,
+                                    static_cast<const uint8_t*>(aa), afs, ap, width, height, static_cast<uint8_t*>(dst), dfs, dp));
+    return SN_OK;
+}
+
 int sn_synchronize(sn_context* h)
 {
     Context* c = reinterpret_cast<Context*>(h);
@@ -2861,6 +2897,7 @@ struct sn_aa_context {
     int t2pitch[3] = {0, 0, 0};                            // the second pass's input: ow wide, h high
     int64_t t2bytes[3] = {0, 0, 0};
     int reduce = SN_AA_REDUCE_NONE;                        // dh only: the second pass's output goes through sn_reduce.hip on its way out
+    sn_aa_mask mask{};                                     // kind != 0: the result is merged into the source through an edge mask (sn_mask.hip), last
     int dstw[3] = {0, 0, 0}, dsth[3] = {0, 0, 0};          // the destination's geometry per plane: ow x oh, with reduce w x h
     int dstpitch[3] = {0, 0, 0};                           // ... of the library's own buffers of that geometry (host groups)
     int64_t dstbytes[3] = {0, 0, 0};
@@ -2990,6 +3027,12 @@ int sn_aa_create_ex(const sn_config* cfg, const sn_policy* policy, const sn_opti
 
 int sn_aa_create_ex2(const sn_config* cfg, const sn_policy* policy, const sn_options* options, const sn_aa_options* aa_options, sn_aa_context** out)
 {
+    return sn_aa_create_ex3(cfg, policy, options, aa_options, nullptr, out);
+}
+
+int sn_aa_create_ex3(const sn_config* cfg, const sn_policy* policy, const sn_options* options, const sn_aa_options* aa_options, const sn_aa_mask* mask,
+                     sn_aa_context** out)
+{
     auto fail_aa = [](sn_aa_context* a, int code, const std::string& msg) {
         g_aa_error = msg;
         if (a) sn_aa_destroy(a);
@@ -3010,10 +3053,20 @@ int sn_aa_create_ex2(const sn_config* cfg, const sn_policy* policy, const sn_opt
         reduce = aa_options->reduce;
     }
     if (reduce && !cfg->dh) return fail_aa(nullptr, SN_ERR_CONFIG, "SangNomAA: reduce needs dh=true");
+    sn_aa_mask use_mask{};
+    use_mask.struct_size = (int32_t)sizeof(sn_aa_mask);
+    if (mask) {
+        const std::string problem = mask_problem(mask);
+        if (!problem.empty()) return fail_aa(nullptr, SN_ERR_INVALID_ARG, problem);
+        if (mask->kind != SN_AA_MASK_NONE) use_mask = *mask;
+    }
+    if (use_mask.kind && cfg->dh && !reduce)
+        return fail_aa(nullptr, SN_ERR_CONFIG, "SangNomAA: mask needs the frame at source size (dh=false, or dh=true with reduce)");
     sn_aa_context* a = new (std::nothrow) sn_aa_context();
     if (!a) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "out of host memory");
     a->cfg = *cfg;
     a->reduce = reduce;
+    a->mask = use_mask;
     a->max_batch = cfg->max_batch > 1 ? cfg->max_batch : 1;
     // the ring: two groups, so that one group uploads while the other is worked on; a group's frames are one batch
     a->depth = cfg->host_depth > 0 ? cfg->host_depth : 4;
@@ -3124,8 +3177,20 @@ static int aa_run(sn_aa_context* a, int n, const void* const src[3], const int64
         if (int rc = turns(1)) return rc;
         void* d2[3] = {nullptr, nullptr, nullptr};
         for (int p = 0; p < a->planes; ++p) d2[p] = static_cast<uint8_t*>(dst[p]) + (int64_t)f0 * dfs[p];
+        // the edge mask, last: the chunk's result is merged into the source through the source's own mask, in place on the
+        // destination (which has the source's size: creation has seen to it); one launch per processed plane
+        auto masked = [&]() -> int {
+            for (int p = 0; p < a->planes && a->mask.kind; ++p) {
+                if (!a->process[p]) continue;
+                SN_AA_HIP(sn::launch_mask_merge(st, B, a->cfg.bits_per_sample, a->mask.lo, a->mask.hi, a->mask.expand, m,
+                                                static_cast<const uint8_t*>(src[p]) + (int64_t)f0 * sfs[p], sfs[p], sp[p], static_cast<const uint8_t*>(d2[p]),
+                                                dfs[p], dp[p], a->w[p], a->h[p], static_cast<uint8_t*>(d2[p]), dfs[p], dp[p]));
+            }
+            return SN_OK;
+        };
         if (!a->reduce) {
             SN_AA_SN(a->second, run_batch(c2, st, 0, m, s2, a->t2bytes, a->t2pitch, d2, dfs, dp, par));
+            if (int rc = masked()) return rc;
             continue;
         }
         // reduce (dh: every plane is processed): the second pass fills E, the reduction writes the destination -- one launch
@@ -3141,6 +3206,7 @@ static int aa_run(sn_aa_context* a, int n, const void* const src[3], const int64
                                             a->w[p], a->h[p], 1 - off, off, static_cast<uint8_t*>(d2[p]) + (int64_t)g0 * dfs[p], dfs[p], dp[p]));
             g0 = g1;
         }
+        if (int rc = masked()) return rc;
     }
     return SN_OK;
 }
@@ -3238,6 +3304,14 @@ int sn_aa_synchronize(sn_aa_context* a)
 void* sn_aa_get_stream(sn_aa_context* a) { return a ? reinterpret_cast<void*>(a->stream) : nullptr; }
 
 int sn_aa_get_reduce(sn_aa_context* a) { return a ? a->reduce : -1; }
+
+int sn_aa_get_mask(sn_aa_context* a, sn_aa_mask* out)
+{
+    if (!a) return aa_fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    if (!out || out->struct_size != (int32_t)sizeof(sn_aa_mask)) return aa_fail(a, SN_ERR_INVALID_ARG, "out is NULL or sn_aa_mask.struct_size mismatch");
+    *out = a->mask;
+    return SN_OK;
+}
 
 int sn_aa_get_info(sn_aa_context* a, int32_t pass, sn_info* info)
 {

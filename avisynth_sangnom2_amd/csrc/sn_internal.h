@@ -76,6 +76,13 @@ hipError_t launch_turn(hipStream_t s, int bytes, int right, int nframes, const u
 hipError_t launch_reduce(hipStream_t s, int bytes, int bits, int kernel, int nframes, const uint8_t* src, int64_t src_frame_stride, int src_pitch,
                          int w, int h, int ox, int oy, uint8_t* dst, int64_t dst_frame_stride, int dst_pitch);
 
+// sn_mask.hip: the edge mask of the anti-aliasing call.  A Sobel mask of src (w x h; lo, hi in 8-bit scale, expand 0 / 1:
+// sangnom_hip.h has the arithmetic) merges aa into src: dst = src where the mask is 0, aa where it is 256.  aa == nullptr:
+// dst is the mask itself.  dst may be the plane aa lies in (same base, pitch and frame stride); src must not overlap dst.
+hipError_t launch_mask_merge(hipStream_t s, int bytes, int bits, int lo, int hi, int expand, int nframes, const uint8_t* src, int64_t src_frame_stride,
+                             int src_pitch, const uint8_t* aa, int64_t aa_frame_stride, int aa_pitch, int w, int h, uint8_t* dst,
+                             int64_t dst_frame_stride, int dst_pitch);
+
 // sn_uv.hip: semi-planar chroma (a UV plane of U,V sample pairs: NV12 / P016 / NV16 / NV24) <-> a U and a V plane of cw x h
 // samples each.  line_parity 0 / 1: only the lines of that parity are read and written (the lines the pass that follows
 // keeps), < 0: all of them.  One side is never written: split reads uv, merge reads u and v.

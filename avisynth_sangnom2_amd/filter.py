@@ -313,6 +313,21 @@ class SangNom2:
                                                W, H, int(ox), int(oy), dst.data_ptr(), dst.stride(0) * B, dst.stride(1) * B))
         return dst
 
+    def mask_merge(self, src, aa, dst, lo: int, hi: int, expand: int = 1):
+        """sn_mask_merge_device: the Sobel edge mask of src [N, H, W] (lo, hi in 8-bit scale, expand 0 | 1) merges aa into src:
+        dst = src where the mask is 0, aa where it is 256.  aa=None: dst is the mask itself.  dst may be aa.  Torch tensors
+        on the device; asynchronous on the context's stream."""
+        B = self.clip.bytes
+        N, H, W = dst.shape
+        for t in (src, dst) + (() if aa is None else (aa,)):
+            if tuple(t.shape) != (N, H, W) or t.stride(2) != 1 or t.element_size() != B:
+                raise ValueError("mask_merge: src, aa and dst must be [N, H, W], x-contiguous and of the clip's sample type")
+        m = capi.aa_mask((lo, hi), expand)
+        a_ptr, a_fs, a_p = (None, 0, 0) if aa is None else (aa.data_ptr(), aa.stride(0) * B, aa.stride(1) * B)
+        self._check(self._lib.sn_mask_merge_device(self._h, ctypes.byref(m), N, src.data_ptr(), src.stride(0) * B, src.stride(1) * B, a_ptr, a_fs, a_p,
+                                                   W, H, dst.data_ptr(), dst.stride(0) * B, dst.stride(1) * B))
+        return dst
+
     def get_frame_device(self, src, dst, parity: int = 1):
         """Device planes: torch tensors [H, W] on this context's GPU.  Asynchronous."""
         return self.process_batch([s.unsqueeze(0) for s in src], [d.unsqueeze(0) for d in dst], [parity])
@@ -397,17 +412,21 @@ class _AAContext:
     dh=True: both passes with dh=true, enlargement by two in both directions; every plane is processed (luma / chroma are
     ignored, as in the reference) and every destination plane is twice as wide and twice as high as its source plane.
     reduce="tent" | "halfband" (with dh): the enlarged frame is reduced on the device by that kernel, centred on the source
-    samples (sangnom_hip.h has the arithmetic), and every destination plane has the source plane's shape again."""
+    samples (sangnom_hip.h has the arithmetic), and every destination plane has the source plane's shape again.
+    mask=(lo, hi), mask_expand=0 | 1 (without dh, or with dh and reduce): the result is merged into the source through a Sobel
+    edge mask of the source (sangnom_hip.h, "Edge mask"): flat areas and texture keep the source's samples."""
 
     def __init__(self, clip: ClipFormat, order: int = 1, aa: int = 48, aac: int = 0, luma: bool = True, chroma: bool = True,
                  device: int = 0, isolated_planes: bool = False, fresh_pool: bool = False, opt: int = -1, max_batch: int = 1,
-                 host_depth: int = 0, stream: int | None = None, dh: bool = False, column_parts: int = 0, reduce=0, **policy_kw):
+                 host_depth: int = 0, stream: int | None = None, dh: bool = False, column_parts: int = 0, reduce=0, mask=None, mask_expand: int = 1,
+                 **policy_kw):
         if opt < -1 or opt > 1:
             raise SangNomError(capi.SN_ERR_CONFIG, "SangNom2: opt must be between -1..2.")  # sic, SangNom2.cpp:420
         self.clip = clip
         self.dh = bool(dh)
         aopts = capi.aa_options(reduce)  # reduce="tent" | "halfband" (dh only): the frame comes back at source size
         self.reduce = aopts.reduce
+        amask = capi.aa_mask(mask, mask_expand)  # mask=(lo, hi): the result goes into the source through the source's edge mask
         self.max_batch = max_batch
         self._lib = capi.load()
         cfg = capi.SnConfig(
@@ -418,7 +437,8 @@ class _AAContext:
         self._h = ctypes.c_void_p()
         pol = capi.policy(**{k: policy_kw.get(k) for k in ("small_launches", "chain", "copy_threads", "scratch_budget_mb", "chroma_sweeps", "sse2_sweeps")})
         opts = capi.options(capi.arithmetic_of_opt(opt), column_parts=column_parts)
-        rc = self._lib.sn_aa_create_ex2(ctypes.byref(cfg), ctypes.byref(pol), ctypes.byref(opts), ctypes.byref(aopts), ctypes.byref(self._h))
+        rc = self._lib.sn_aa_create_ex3(ctypes.byref(cfg), ctypes.byref(pol), ctypes.byref(opts), ctypes.byref(aopts), ctypes.byref(amask),
+                                        ctypes.byref(self._h))
         if rc != capi.SN_OK:
             self._h = None
             raise SangNomError(rc, self._lib.sn_aa_last_error(None).decode())
@@ -460,6 +480,12 @@ class _AAContext:
 
     def stream_handle(self) -> int:
         return self._lib.sn_aa_get_stream(self._h)
+
+    def mask(self) -> capi.SnAAMask:
+        """sn_aa_get_mask: the edge mask of this context (kind 0 when there is none)."""
+        m = capi.SnAAMask(struct_size=ctypes.sizeof(capi.SnAAMask))
+        self._check(self._lib.sn_aa_get_mask(self._h, ctypes.byref(m)))
+        return m
 
     def info(self, pass_: int) -> capi.SnInfo:
         """sn_get_info of one of the two filter instances: 0 the turned clip's, 1 the clip's."""

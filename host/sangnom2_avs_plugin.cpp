@@ -103,6 +103,9 @@ AVSValue __cdecl Create_SangNom2HIP(AVSValue args, void*, IScriptEnvironment* en
 // staying on the device between the passes (sangnom::AAFilter).  dh=true: both passes with dh=true, the clip comes out
 // twice as wide and twice as high; with reduce=1 (tent) or 2 (half-band) on top of it the enlarged frame is reduced on the
 // device and the clip keeps its size: a drop-in anti-aliaser.  Reduce without dh: "SangNomAA: reduce needs dh=true".
+// mask=true (at source size: no dh, or dh with reduce): the result is merged into the source through a Sobel edge mask of the
+// source, thresholds mlo <= mhi (0..255, defaults 8 and 32) and mexpand (0 | 1, default 1); the defaults are starting values
+// that nobody has tuned on real footage.
 class SangNomAA : public GenericVideoFilter {
     sangnom::AAFilter<AvsHost> impl_;
 
@@ -130,6 +133,10 @@ AVSValue __cdecl Create_SangNomAA(AVSValue args, void*, IScriptEnvironment* env)
     a.lookahead = args[10].AsInt(-1);
     a.dh = args[11].AsBool(false);
     a.reduce = args[12].AsInt(0);
+    a.mask = args[13].AsBool(false);
+    a.mask_lo = args[14].AsInt(8);
+    a.mask_hi = args[15].AsInt(32);
+    a.mask_expand = args[16].AsInt(1);
     return new SangNomAA(args[0].AsClip(), a, env);
 }
 
@@ -153,7 +160,8 @@ extern "C" __declspec(dllexport) const char* __stdcall AvisynthPluginInit3(IScri
     env->AddFunction("SangNom", "c[order]i[aa]i[opt]i", Create_SangNom, 0);                                        // :482
     env->AddFunction("SangNom2HIP", "c[order]i[aa]i[aac]i[threads]i[dh]b[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i[device]i",
                      Create_SangNom2HIP, 0);
-    env->AddFunction("SangNomAA", "c[order]i[aa]i[aac]i[device]i[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i[dh]b[reduce]i", Create_SangNomAA, 0);
+    env->AddFunction("SangNomAA", "c[order]i[aa]i[aac]i[device]i[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i[dh]b[reduce]i[mask]b[mlo]i[mhi]i[mexpand]i",
+                     Create_SangNomAA, 0);
     return "SangNom2";
 }
 #endif  // SN_HAVE_AVISYNTH

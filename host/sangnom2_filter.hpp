@@ -39,6 +39,8 @@ struct Args {  // SangNom2(clip, order, aa, aac, threads, dh, luma, chroma, opt)
     bool isolated = false;  // extension: every plane filtered as a Y clip of its own (sn_config.isolated_planes)
     bool fresh = false;     // extension: ... and every frame by a new instance (sn_config.fresh_pool)
     int reduce = 0;         // SangNomAA only, with dh: SN_AA_REDUCE_TENT / SN_AA_REDUCE_HALFBAND, the frame comes back at source size
+    bool mask = false;      // SangNomAA only, at source size: the result is merged into the source through the source's Sobel edge mask
+    int mask_lo = 8, mask_hi = 32, mask_expand = 1;  // ... sn_aa_mask.lo / hi / expand; starting values, not tuned on real footage
     int column_parts = -1;  // sn_options.column_parts (16-bit / float planes wider than 3840 in column parts); -1: $SANGNOM_COLUMN_PARTS or 0
     sn_policy policy{};     // scheduling only (sangnom_hip.h); zeros = the defaults
 };
@@ -245,6 +247,9 @@ private:
 // With Args::reduce (1 tent, 2 half-band; needs dh) the library reduces the enlarged frame on the device, centred on the
 // source samples (sangnom_hip.h, "Anti-aliasing at source size"): the filter's clip is the source's again -- a drop-in
 // anti-aliaser --, a frame of source size comes down, and the alpha passes through 1:1.
+// With Args::mask (the clip at source size: no dh, or dh with reduce) the library merges the result into the source through
+// a Sobel edge mask of the source (sangnom_hip.h, "Edge mask"; mask_lo <= mask_hi in 0..255, mask_expand 0 or 1), which is
+// what the anti-aliasing scripts do behind the filter: flat areas and texture keep the source's samples.
 template <class Host>
 class AAFilter {
 public:
@@ -264,6 +269,13 @@ public:
         if (a.aac < 0 || a.aac > 128) env->ThrowError("%s: aac must be between 0..128.", name);
         if (a.reduce < 0 || a.reduce > 2) env->ThrowError("%s: reduce must be between 0..2.", name);
         if (a.reduce && !a.dh) env->ThrowError("%s: reduce needs dh=true", name);
+        if (a.mask) {
+            if (a.mask_lo < 0 || a.mask_lo > 255) env->ThrowError("%s: sn_aa_mask.lo must be 0..255", name);
+            if (a.mask_hi < 0 || a.mask_hi > 255) env->ThrowError("%s: sn_aa_mask.hi must be 0..255", name);
+            if (a.mask_lo > a.mask_hi) env->ThrowError("%s: sn_aa_mask.lo must not be above sn_aa_mask.hi", name);
+            if (a.mask_expand < 0 || a.mask_expand > 1) env->ThrowError("%s: sn_aa_mask.expand must be 0 or 1", name);
+            if (a.dh && !a.reduce) env->ThrowError("%s: mask needs the frame at source size (dh=false, or dh=true with reduce)", name);
+        }
         sn_config c{};
         c.struct_size = (int32_t)sizeof c;
         c.width = Host::Width(vi_);
@@ -298,7 +310,11 @@ public:
         sn_aa_options aopts{};
         aopts.struct_size = (int32_t)sizeof aopts;
         aopts.reduce = a.reduce;
-        if (sn_aa_create_ex2(&c, &pol, &opts, &aopts, &ctx_) != SN_OK) env->ThrowError("%s: %s", name, sn_aa_last_error(nullptr));
+        sn_aa_mask mask{};
+        mask.struct_size = (int32_t)sizeof mask;
+        mask.kind = a.mask ? SN_AA_MASK_SOBEL : SN_AA_MASK_NONE;
+        mask.lo = a.mask_lo, mask.hi = a.mask_hi, mask.expand = a.mask_expand;
+        if (sn_aa_create_ex3(&c, &pol, &opts, &aopts, &mask, &ctx_) != SN_OK) env->ThrowError("%s: %s", name, sn_aa_last_error(nullptr));
         enlarged_ = a.dh && !a.reduce;
         if (enlarged_) {  // each pass doubles the height of what it is given: the clip comes out twice as wide and twice as high
             Host::SetWidth(vi_, Host::Width(vi_) * 2);

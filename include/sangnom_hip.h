@@ -308,6 +308,30 @@ int sn_reduce_device(sn_context* ctx, int32_t kernel, int32_t nframes, const voi
                      int32_t width, int32_t height /* of dst; src is 2 width x 2 height */, int32_t ox, int32_t oy, void* dst,
                      int64_t dst_frame_stride, int32_t dst_pitch);
 
+/* The edge mask of the anti-aliasing call (below: "Edge mask", which defines the arithmetic).  kind SN_AA_MASK_SOBEL: lo <= hi
+ * in 0..255 (8-bit scale, like aa), expand 0 or 1.  The defaults the plugins offer (lo 8, hi 32, expand 1) are a starting
+ * point: nobody has tuned them on real footage. */
+enum { SN_AA_MASK_NONE = 0, SN_AA_MASK_SOBEL = 1 };
+typedef struct sn_aa_mask {
+    int32_t struct_size; /* sizeof(sn_aa_mask) */
+    int32_t kind;        /* SN_AA_MASK_*; with SN_AA_MASK_NONE the fields below are ignored */
+    int32_t lo, hi;      /* e <= lo keeps the source, e >= hi takes the result */
+    int32_t expand;      /* 1: the mask is its own maximum over 3 x 3 */
+    int32_t reserved[3]; /* zero */
+} sn_aa_mask;            /* 32 bytes */
+
+/* The mask and the merge on their own, for pipelines that keep frames on the device and for tuning thresholds: `nframes`
+ * planes of width x height samples on the context's stream; sample type and bit depth come from the context.  The mask is
+ * built from src; dst = src where it is 0, aa where it is 256, the blend between (see "Edge mask").  aa == NULL: dst is the
+ * mask itself, integers (m * (2^bits - 1) + 128) >> 8, float (float)m * 0.00390625f.  mask->kind must be SN_AA_MASK_SOBEL;
+ * the struct is checked as sn_aa_create_ex3 checks it.  dst may be the very plane aa lies in (same base, pitch and frame
+ * stride: each sample of aa is read by the thread that overwrites it); src must not overlap dst.  Pitches >= width samples;
+ * pointers, pitches and frame strides multiples of the sample size (multiples of 16 on a side: 16 bytes per lane and access on
+ * that side).  Nothing beyond width samples of a destination row is written.  A refused call queues nothing. */
+int sn_mask_merge_device(sn_context* ctx, const sn_aa_mask* mask, int32_t nframes, const void* src, int64_t src_frame_stride, int32_t src_pitch,
+                         const void* aa /* NULL: write the mask */, int64_t aa_frame_stride, int32_t aa_pitch, int32_t width, int32_t height,
+                         void* dst, int64_t dst_frame_stride, int32_t dst_pitch);
+
 /* The anti-aliasing idiom TurnLeft().SangNom2(order, aa, aac).TurnRight().SangNom2(order, aa, aac) as ONE call with
  * host planes (README.md:3 of the reference: "mainly used in anti-aliasing scripts"): the frame
  * crosses PCIe once each way and stays on the device between the two passes (two filter instances -- one for the
@@ -359,7 +383,36 @@ int sn_reduce_device(sn_context* ctx, int32_t kernel, int32_t nframes, const voi
  *                out = v * 0.0009765625f
  *   No clamp.
  *   The same reduction follows both arithmetics (sn_options.arithmetic); only E differs.  Every plane is reduced, because dh
- *   forces every plane through both passes. */
+ *   forces every plane through both passes.
+ *
+ * Edge mask (sn_aa_create_ex3 with mask->kind = SN_AA_MASK_SOBEL): what every anti-aliasing script built on SangNom does
+ * behind the filter.  An edge mask is built from the SOURCE plane and the call's result is merged into the source through
+ * it, in place on the destination behind the last step: flat areas and texture keep the source's samples untouched.  The
+ * destination must have the source's size: dh = 0, or dh = 1 with a reduction; otherwise SN_ERR_CONFIG "SangNomAA: mask
+ * needs the frame at source size (dh=false, or dh=true with reduce)", before a device is touched.  No scratch is added and
+ * neither pass changes; source and destination must not overlap (already the rule).  The mask is computed per processed
+ * plane from that plane's own source, with the same lo, hi, expand for every plane (subsampled chroma gets no luma-derived
+ * mask).  Planes that are not processed are copied as without a mask.  Without dh the kept lines of the result are copies
+ * of the source, so the merge leaves them as they are.  Neither the reference nor masktools defines these pixels; the
+ * arithmetic is the library's own, exactly:
+ *   S is the source plane (W x H), R the call's result for it, S(y, x) = S[clamp(y, 0, H-1)][clamp(x, 0, W-1)].
+ *   Integer samples (8..16 bit), all in signed 32-bit:
+ *     gx = (S(y-1,x+1) + 2 S(y,x+1) + S(y+1,x+1)) - (S(y-1,x-1) + 2 S(y,x-1) + S(y+1,x-1))
+ *     gy = (S(y+1,x-1) + 2 S(y+1,x) + S(y+1,x+1)) - (S(y-1,x-1) + 2 S(y-1,x) + S(y-1,x+1))
+ *     e  = (|gx| + |gy|) >> 2                  (a step of height d across a straight edge gives e = d)
+ *     Tlo = lo << (bits_per_sample - 8),  Thi = hi << (bits_per_sample - 8)
+ *     m0 = 0 if e <= Tlo;  256 else if e >= Thi;  else ((e - Tlo) * 256) / (Thi - Tlo)  (floor; the product is below 2^24)
+ *     m  = m0 with expand = 0;  the maximum of m0 over the 3 x 3 neighbourhood (clamped coordinates) with expand = 1
+ *     out = (S * (256 - m) + R * m + 128) >> 8
+ *   m = 0 gives S exactly and m = 256 gives R exactly; no clamp is needed.
+ *   Float samples: one rounding per written operation, no contraction:
+ *     col(dx) = (S(y-1,x+dx) + S(y+1,x+dx)) + (S(y,x+dx) + S(y,x+dx));  row(dy) = (S(y+dy,x-1) + S(y+dy,x+1)) + (S(y+dy,x) + S(y+dy,x))
+ *     gx = col(+1) - col(-1);  gy = row(+1) - row(-1);  e = (|gx| + |gy|) * 0.25f
+ *     Tlo = (float)lo / 255.0f,  Thi = (float)hi / 255.0f,  k = 256.0f / (Thi - Tlo): single precision, computed on the host
+ *       (k only when hi > lo)
+ *     m0 = 0 if !(e > Tlo) (a NaN keeps the source);  256 else if e >= Thi;  else min(256, (int)((e - Tlo) * k)) (truncation)
+ *     m as above
+ *     out = S if m == 0;  R if m == 256;  else S + (R - S) * ((float)m * 0.00390625f) */
 enum { SN_AA_REDUCE_NONE = 0, SN_AA_REDUCE_TENT = 1, SN_AA_REDUCE_HALFBAND = 2 };
 typedef struct sn_aa_options {
     int32_t struct_size; /* sizeof(sn_aa_options) */
@@ -375,6 +428,12 @@ int sn_aa_create_ex(const sn_config* cfg, const sn_policy* policy, const sn_opti
 int sn_aa_create_ex2(const sn_config* cfg, const sn_policy* policy, const sn_options* options, const sn_aa_options* aa_options /* NULL = defaults */,
                      sn_aa_context** out);
 int sn_aa_get_reduce(sn_aa_context* ctx); /* SN_AA_REDUCE_* of a live context; -1 for NULL */
+/* sn_aa_create_ex2 is sn_aa_create_ex3 with mask = NULL (no mask).  A bad struct_size, a kind outside 0..1, lo or hi outside
+ * 0..255, lo > hi, an expand outside 0..1 or a non-zero reserved word: SN_ERR_INVALID_ARG, naming the field; with kind =
+ * SN_AA_MASK_NONE only struct_size and kind are looked at. */
+int sn_aa_create_ex3(const sn_config* cfg, const sn_policy* policy, const sn_options* options, const sn_aa_options* aa_options /* NULL = defaults */,
+                     const sn_aa_mask* mask /* NULL = none */, sn_aa_context** out);
+int sn_aa_get_mask(sn_aa_context* ctx, sn_aa_mask* out /* struct_size set by the caller */); /* kind 0 when there is none */
 int sn_aa_process_host(sn_aa_context* ctx, const void* const src[3], const int32_t src_pitch[3], void* const dst[3],
                        const int32_t dst_pitch[3], int32_t parity);
 const char* sn_aa_last_error(const sn_aa_context* ctx); /* ctx == NULL: last failed sn_aa_create on this thread */

@@ -6,9 +6,14 @@ as high); --dh --composed: the same idiom composed by hand from two SangNom2(dh=
 stream, the way a caller had to build it before the call took dh.  --reduce tent|halfband (implies --dh): the enlarged
 frame is reduced on the device, destinations of source size (device batches and --host).  --reduce-bw: the reduce kernel
 alone (sn_reduce_device, both tap sets) against the turn kernel on the same 2W x 2H planes, alternating, --size being the
-SOURCE size; any of Y8 / Y16 / Y32.
+SOURCE size; any of Y8 / Y16 / Y32.  --mask lo,hi[,expand] (at source size: without --dh, or with --reduce): the call with
+the edge mask next to the call without it, in one run (device batches and --host).  --mask-bw: the mask kernel alone
+(sn_mask_merge_device, on noise -- every sample of the result is read -- and on a constant plane -- none is) against the
+half-band reduce kernel that writes the same plane, alternating; any of Y8 / Y16 / Y32.
 usage: python tools/aa_bench.py [--frames 512] [--fresh 1] [--fmt Y8] [--size 3840x2160] [--dh [--composed]] [--reduce K] [--host [--depth 8]]
-       python tools/aa_bench.py --reduce-bw [--fmt Y16] [--size 1920x1080] [--frames 64]"""
+       python tools/aa_bench.py --reduce-bw [--fmt Y16] [--size 1920x1080] [--frames 64]
+       python tools/aa_bench.py --mask 8,32,1 [--reduce halfband] [--size 1920x1080] [--host]
+       python tools/aa_bench.py --mask-bw [--fmt Y16] [--size 3840x2160] [--frames 32]"""
 import argparse
 import json
 import os
@@ -23,7 +28,7 @@ import numpy as np  # noqa: E402
 from avisynth_sangnom2_amd import ClipFormat, SangNom2, SangNomAA, SangNomAAHost, clip_format  # noqa: E402
 
 
-def host_rates(clip, a):
+def host_rates(clip, a, mask_kw=None):
     """Frames from pageable host memory, every result collected into pageable memory: frames/s of the synchronous call and
     of the ring with as many frames in flight as it holds.  A whole frame crosses PCIe each way."""
     rng = np.random.default_rng(1)
@@ -40,6 +45,7 @@ def host_rates(clip, a):
     else:
         out["pcie_bytes_per_frame_each_way"] = up
     dh_kw = dict(dh=True, **(dict(reduce=a.reduce) if a.reduce else {})) if a.dh else {}
+    dh_kw.update(mask_kw or {})
     oshapes = [(2 * s[0], 2 * s[1]) if a.dh and not a.reduce else s for s in shapes]
     with SangNomAAHost(clip, aac=48 if clip.planes > 1 else 0, fresh_pool=bool(a.fresh), **dh_kw) as flt:
         for i in range(3):
@@ -133,6 +139,48 @@ def reduce_bandwidth(clip, a):
     return out
 
 
+def mask_bandwidth(clip, a):
+    """sn_mask_merge_device (in place on the result, as the call uses it; expand 0 and 1) against the half-band sn_reduce_device
+    that writes the same W x H plane, alternating: median seconds per launch of --frames frames.  The merge moves 3 W H B bytes
+    per frame on noise (S and R read, dst written) and 2 W H B on a constant plane (R is not read where the mask is empty),
+    the reduction 5 W H B."""
+    dev = torch.device("cuda:0")
+    N, W, H, B = a.frames, clip.width, clip.height, clip.bytes
+    dt = {1: torch.uint8, 2: torch.int16, 4: torch.float32}[B]
+
+    def noise(h, w):
+        if B == 4:
+            return torch.rand((N, h, w), device=dev)
+        hi = 1 << clip.bits
+        return torch.randint(0, hi, (N, h, w), device=dev, dtype=torch.int32).to(dt)
+    E, S, R = noise(2 * H, 2 * W), noise(H, W), noise(H, W)
+    flat = torch.full((N, H, W), 0.3 if B == 4 else 77, device=dev, dtype=dt)
+    small = torch.empty((N, H, W), device=dev, dtype=dt)
+    lo, hi, _ = a.mask_values
+    out = {"clip": f"{a.fmt} {W}x{H}", "frames": N, "plane_bytes": N * W * H * B, "mask": [lo, hi]}
+    with SangNom2(clip, max_batch=1) as flt:
+        runs = {"halfband": (5, lambda: flt.reduce(E, small, "halfband", 1, 0)),
+                "mask0_noise": (3, lambda: flt.mask_merge(S, R, R, lo, hi, 0)), "mask1_noise": (3, lambda: flt.mask_merge(S, R, R, lo, hi, 1)),
+                "mask1_flat": (2, lambda: flt.mask_merge(flat, R, R, lo, hi, 1)), "mask1_only": (2, lambda: flt.mask_merge(S, None, small, lo, hi, 1))}
+        times = {k: [] for k in runs}
+        torch.cuda.synchronize()
+        for r in range(a.reps + 1):
+            for k, (_, fn) in runs.items():
+                flt.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                flt.synchronize()
+                if r:
+                    times[k].append(time.perf_counter() - t0)
+        for k, t in times.items():
+            t.sort()
+            moved = runs[k][0] * N * W * H * B
+            out[k + "_us_per_frame"] = round(1e6 * t[len(t) // 2] / N, 2)
+            out[k + "_GBps"] = round(moved / t[len(t) // 2] / 1e9, 1)
+            out[k + "_us_min_max"] = [round(1e6 * t[0] / N, 2), round(1e6 * t[-1] / N, 2)]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=512)
@@ -145,8 +193,12 @@ def main():
     ap.add_argument("--composed", action="store_true", help="--dh, device-resident: two SangNom2(dh=True) contexts and SangNom2.turn by hand")
     ap.add_argument("--reduce", choices=["tent", "halfband"], help="with dh: reduce the enlarged frame on the device (implies --dh)")
     ap.add_argument("--reduce-bw", action="store_true", help="the reduce kernel alone against the turn kernel on the same planes")
-    ap.add_argument("--reps", type=int, default=9, help="--reduce-bw: timed launches per kernel")
+    ap.add_argument("--reps", type=int, default=9, help="--reduce-bw, --mask-bw: timed launches per kernel")
+    ap.add_argument("--mask", help="lo,hi[,expand]: the call with the edge mask next to the call without it (at source size)")
+    ap.add_argument("--mask-bw", action="store_true", help="the mask kernel alone against the half-band reduce kernel on the same plane")
     a = ap.parse_args()
+    a.mask_values = ([int(x) for x in a.mask.split(",")] + [1])[:3] if a.mask else [8, 32, 1]
+    mask_kw = dict(mask=tuple(a.mask_values[:2]), mask_expand=a.mask_values[2]) if a.mask else None
     w, h = [int(x) for x in a.size.split("x")]
     clip = clip_format(a.fmt, w, h)
     if a.reduce:
@@ -154,12 +206,22 @@ def main():
     if a.reduce_bw:
         print(json.dumps(reduce_bandwidth(clip, a)))
         return
+    if a.mask_bw:
+        print(json.dumps(mask_bandwidth(clip, a)))
+        return
     if clip.bytes != 1:
         sys.exit("aa_bench: 8-bit formats only")
+    if a.mask and ((a.dh and not a.reduce) or a.composed):
+        sys.exit("aa_bench: --mask needs the frame at source size: without --dh, or with --reduce")
     if a.composed and (not a.dh or a.host or a.reduce):
         sys.exit("aa_bench: --composed goes with --dh, device-resident, without --reduce")
     if a.host:
-        print(json.dumps(host_rates(clip, a)))
+        out = host_rates(clip, a)
+        if a.mask:
+            masked = host_rates(clip, a, mask_kw)
+            out["mask"] = a.mask_values
+            out.update({"mask_" + k: masked[k] for k in ("sync_fps", "ring_fps") if k in masked})
+        print(json.dumps(out))
         return
     dev = torch.device("cuda:0")
     N = a.frames
@@ -176,18 +238,22 @@ def main():
         out["composed_fps"] = composed_dh_rate(clip, a, src, dst)
         print(json.dumps(out))
         return
-    with SangNomAA(clip, max_batch=N, fresh_pool=bool(a.fresh), aac=48 if clip.planes > 1 else 0, **(dict(dh=True) if a.dh else {}),
-                   **(dict(reduce=a.reduce) if a.reduce else {})) as aa:
-        torch.cuda.synchronize()
-        for _ in range(2):
-            aa.process_batch(src, dst)
-        aa.synchronize()
-        t0 = time.perf_counter()
-        reps = 5
-        for _ in range(reps):
-            aa.process_batch(src, dst)
-        aa.synchronize()
-        out["aa_fps"] = round(N * reps / (time.perf_counter() - t0), 1)
+    reps = 5
+    for key, kw in [("aa_fps", {})] + ([("aa_mask_fps", mask_kw)] if a.mask else []):
+        with SangNomAA(clip, max_batch=N, fresh_pool=bool(a.fresh), aac=48 if clip.planes > 1 else 0, **(dict(dh=True) if a.dh else {}),
+                       **(dict(reduce=a.reduce) if a.reduce else {}), **kw) as aa:
+            torch.cuda.synchronize()
+            for _ in range(2):
+                aa.process_batch(src, dst)
+            aa.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                aa.process_batch(src, dst)
+            aa.synchronize()
+            out[key] = round(N * reps / (time.perf_counter() - t0), 1)
+    if a.mask:
+        out["mask"] = a.mask_values
+        out["mask_us_per_frame"] = round(1e6 / out["aa_mask_fps"] - 1e6 / out["aa_fps"], 2)
     with SangNom2(clip, max_batch=N) as flt:
         t = torch.empty((N, w, h), device=dev, dtype=torch.uint8)
         torch.cuda.synchronize()
