@@ -17,6 +17,7 @@
 #include "sn_copier.h"
 #include "sn_sweep_args.h"
 #include "sn_surface_layout.h"
+#include "sn_surface_plan.h"
 #include "sn_internal.h"
 
 constexpr int kSyncChunks = 4;  // chunks of rows a pageable plane of the synchronous call is staged in
@@ -27,14 +28,13 @@ namespace sn {
 // frames in the source's chroma geometry (a semi-planar source is split into it, the planes of an MSB-aligned one are shifted
 // into it) and in the destination's (merged from it); and, for an MSB-aligned source only, its luma shifted down.
 struct UvScratch {
-    uint8_t* in[2] = {nullptr, nullptr};   // full height; a split writes the lines the pass keeps, the rest stays 0xA5
-    uint8_t* out[2] = {nullptr, nullptr};  // full height, every line written by the pass
-    uint8_t* y = nullptr;                  // luma of an MSB-aligned or packed source, LSB-aligned: as `in`
-    uint8_t* yo = nullptr;                 // luma a packed destination is packed from: as `out`
-    int cap = 0;                           // frames (0: not allocated yet)
-    int pitch_in = 0, pitch_out = 0, pitch_y = 0, pitch_yo = 0;
-    int64_t in_bytes = 0, out_bytes = 0, y_bytes = 0, yo_bytes = 0;  // one frame of one plane
-    int64_t bytes = 0;                     // all of it
+    // every part: a view of `cap` frames, its frame stride one frame of the plane (base nullptr: the part is not allocated)
+    PlaneViewW in[2];   // full height; a split writes the lines the pass keeps, the rest stays 0xA5
+    PlaneViewW out[2];  // full height, every line written by the pass
+    PlaneViewW y;       // luma of an MSB-aligned or packed source, LSB-aligned: as `in`
+    PlaneViewW yo;      // luma a packed destination is packed from: as `out`
+    int cap = 0;        // frames (0: not allocated yet)
+    int64_t bytes = 0;  // all of it
     int64_t split_frames = 0, merged_frames = 0, copied_frames = 0;  // sn_surface_info
 };
 
@@ -373,8 +373,8 @@ void sn_destroy(sn_context* h)
         if (c->plane_pool[p].base) (void)hipFree(c->plane_pool[p].base);
     for (int i = 0; i < 2; ++i)
         if (c->fpool[i]) (void)hipFree(c->fpool[i]);
-    for (uint8_t* q : {c->uv.in[0], c->uv.in[1], c->uv.out[0], c->uv.out[1], c->uv.y, c->uv.yo})
-        if (q) (void)hipFree(q);
+    for (const sn::PlaneViewW& q : {c->uv.in[0], c->uv.in[1], c->uv.out[0], c->uv.out[1], c->uv.y, c->uv.yo})
+        if (q.base) (void)hipFree(q.base);
     if (c->gate.in) (void)hipStreamSynchronize(c->gate.in);
     if (c->gate.out) (void)hipStreamSynchronize(c->gate.out);
     for (int p = 0; p < 3; ++p) {
@@ -1713,10 +1713,9 @@ static int run_batch(Context* c, hipStream_t st, int slot0, int nframes, const v
     int planes[3] = {0, 0, 0};
     const int pn = slot0 == 0 ? chain_planes(c, planes) : 0;
     while (f < nframes) {
-        const int off = field_offset(c, parity ? parity[f] : 1);
-        int g = f + 1;
-        if (c->history_free || pn)
-            while (g < nframes && field_offset(c, parity ? parity[g] : 1) == off) ++g;
+        const sn::FieldRun run = sn::field_run(parity, f, nframes, [c](int par) { return field_offset(c, par); }, c->history_free || pn);
+        const int off = run.offset;
+        int g = run.end;
         // (a single frame with two or three processed planes is a chain too: its passes follow each other rows apart)
         int rc = !c->history_free && (g - f) * pn > 1 ? run_chain(c, st, g - f, src, sfs, sp, dst, dfs, dp, f, off, planes, pn)
                                                : run_group(c, st, slot0, g - f, src, sfs, sp, dst, dfs, dp, f, off);
@@ -1775,6 +1774,8 @@ struct SurfaceSide {  // a checked sn_surfaces
     uint8_t* p[3] = {nullptr, nullptr, nullptr};
     int32_t pitch[3] = {0, 0, 0};
     int64_t fs[3] = {0, 0, 0};
+    sn::PlaneViewW view(int q) const { return sn::PlaneViewW{p[q], fs[q], pitch[q]}; }
+    sn::PlanSide plan_side() const { return sn::PlanSide{semi, packing, shift}; }
 };
 
 // the description on its own: SN_OK, or the code and the text that names the field
@@ -1824,78 +1825,57 @@ static int surface_side(const char* name, const sn_surfaces* s, const int w[3], 
     return SN_OK;
 }
 
-// What a call needs of the scratch.  Without a packed side: the chroma planes (both geometries, as ever) when processed chroma
-// passes through a semi-planar side or comes from an MSB-aligned source; the luma plane when processed luma comes from an
-// MSB-aligned source.  With a packed side (surface_walk_packed): the source's planes where they are not planar LSB-aligned
-// planes already, the destination's where the passes cannot write them in place (sangnom_hip.h has the table).
-struct SurfaceNeeds {
-    bool in = false, out = false;  // U and V in the source's / the destination's geometry
-    bool y = false, yo = false;    // luma likewise
-};
-
-static SurfaceNeeds surface_needs(const SurfaceGeometry& g, const SurfaceSide& src, const SurfaceSide& dst)
+static sn::SurfacePlan surface_plan_of(const SurfaceGeometry& g, const SurfaceSide& src, const SurfaceSide& dst)
 {
-    SurfaceNeeds n;
-    if (src.packing || dst.packing) {
-        n.in = src.packing || src.semi || src.shift != 0;
-        n.y = src.packing || src.shift != 0;
-        n.out = dst.packing || dst.semi;
-        n.yo = dst.packing != 0;
-        return n;
-    }
-    n.in = n.out = g.planes >= 3 && g.chroma_processed && (src.semi || dst.semi || src.shift != 0);
-    n.y = g.luma_processed && src.shift != 0;
-    return n;
+    return sn::surface_plan(src.plan_side(), dst.plan_side(), g.planes, g.luma_processed, g.chroma_processed, g.all_lines);
 }
 
 static void surface_scratch_free(sn::UvScratch& S)
 {
-    for (uint8_t** q : {&S.in[0], &S.in[1], &S.out[0], &S.out[1], &S.y, &S.yo}) {
-        if (*q) (void)hipFree(*q);
-        *q = nullptr;
+    for (sn::PlaneViewW* q : {&S.in[0], &S.in[1], &S.out[0], &S.out[1], &S.y, &S.yo}) {
+        if (q->base) (void)hipFree(q->base);
+        *q = sn::PlaneViewW{};
     }
     S.cap = 0;
     S.bytes = 0;
 }
 
 // The scratch, once per part: for min(max_batch, what a sixteenth of the budget holds, at least 1) frames (sangnom_hip.h).
-// Allocated before anything of the call is queued; the stream is drained so that whichever stream comes first finds it filled.
-// A context that holds some parts and now needs another gives back what it holds and takes the union, so that the sum obeys
-// the rule; calls without an MSB-aligned source or a packed side never ask for luma and allocate what they always did.
-static hipError_t surface_scratch(sn::UvScratch& S, hipStream_t st, const SurfaceGeometry& g, int64_t budget, SurfaceNeeds need)
+// `need` is the plan's (sn_surface_plan.h; sangnom_hip.h has the table).  Allocated before anything of the call is queued; the
+// stream is drained so that whichever stream comes first finds it filled.  A context that holds some parts and now needs another
+// gives back what it holds and takes the union, so that the sum obeys the rule; calls without an MSB-aligned source or a packed
+// side never ask for luma and allocate what they always did.
+static hipError_t surface_scratch(sn::UvScratch& S, hipStream_t st, const SurfaceGeometry& g, int64_t budget, sn::SurfaceNeeds need)
 {
-    if ((!need.in || S.in[0]) && (!need.out || S.out[0]) && (!need.y || S.y) && (!need.yo || S.yo)) return hipSuccess;
-    need.in = need.in || S.in[0];
-    need.out = need.out || S.out[0];
-    need.y = need.y || S.y;
-    need.yo = need.yo || S.yo;
+    if ((!need.in || S.in[0].base) && (!need.out || S.out[0].base) && (!need.y || S.y.base) && (!need.yo || S.yo.base)) return hipSuccess;
+    need.in = need.in || S.in[0].base;
+    need.out = need.out || S.out[0].base;
+    need.y = need.y || S.y.base;
+    need.yo = need.yo || S.yo.base;
     hipError_t e = hipStreamSynchronize(st);  // (what an earlier call queued may still read the part that goes)
     if (e != hipSuccess) return e;
     surface_scratch_free(S);
-    S.pitch_in = (g.w_in[1] * g.B + 255) & ~255;
-    S.pitch_out = (g.w_out[1] * g.B + 255) & ~255;
-    S.pitch_y = (g.w_in[0] * g.B + 255) & ~255;
-    S.pitch_yo = (g.w_out[0] * g.B + 255) & ~255;
-    S.in_bytes = (int64_t)S.pitch_in * g.h_in[1];
-    S.out_bytes = (int64_t)S.pitch_out * g.h_out[1];
-    S.y_bytes = (int64_t)S.pitch_y * g.h_in[0];
-    S.yo_bytes = (int64_t)S.pitch_yo * g.h_out[0];
-    const int64_t per_frame = (need.in ? 2 * S.in_bytes : 0) + (need.out ? 2 * S.out_bytes : 0) + (need.y ? S.y_bytes : 0) + (need.yo ? S.yo_bytes : 0);
+    // one frame of a part: w samples a row, the pitch rounded up to 256 bytes
+    auto part = [&](int w, int h) {
+        const int32_t pitch = (w * g.B + 255) & ~255;
+        return sn::PlaneViewW{nullptr, (int64_t)pitch * h, pitch};
+    };
+    const sn::PlaneViewW in = part(g.w_in[1], g.h_in[1]), out = part(g.w_out[1], g.h_out[1]), y = part(g.w_in[0], g.h_in[0]), yo = part(g.w_out[0], g.h_out[0]);
+    const int64_t per_frame = (need.in ? 2 * in.fs : 0) + (need.out ? 2 * out.fs : 0) + (need.y ? y.fs : 0) + (need.yo ? yo.fs : 0);
     const int64_t fit = budget / 16 / per_frame;
     const int cap = (int)(fit < 1 ? 1 : fit < g.max_batch ? fit : g.max_batch);
+    // a split writes only the lines its pass keeps: a pass that read another line of a source part would read the 0xA5 pattern
+    auto take = [&](sn::PlaneViewW& q, const sn::PlaneViewW& shape, bool fill) {
+        q = shape;
+        e = hipMalloc(reinterpret_cast<void**>(&q.base), (size_t)q.fs * cap);
+        if (e == hipSuccess && fill) e = hipMemsetAsync(q.base, 0xA5, (size_t)q.fs * cap, st);
+    };
     for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-        if (need.in) {
-            e = hipMalloc(reinterpret_cast<void**>(&S.in[k]), (size_t)S.in_bytes * cap);
-            // a split writes only the lines its pass keeps: a pass that read another line would read this pattern
-            if (e == hipSuccess) e = hipMemsetAsync(S.in[k], 0xA5, (size_t)S.in_bytes * cap, st);
-        }
-        if (need.out && e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&S.out[k]), (size_t)S.out_bytes * cap);
+        if (need.in) take(S.in[k], in, true);
+        if (need.out && e == hipSuccess) take(S.out[k], out, false);
     }
-    if (need.y && e == hipSuccess) {
-        e = hipMalloc(reinterpret_cast<void**>(&S.y), (size_t)S.y_bytes * cap);
-        if (e == hipSuccess) e = hipMemsetAsync(S.y, 0xA5, (size_t)S.y_bytes * cap, st);
-    }
-    if (need.yo && e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&S.yo), (size_t)S.yo_bytes * cap);
+    if (need.y && e == hipSuccess) take(S.y, y, true);
+    if (need.yo && e == hipSuccess) take(S.yo, yo, false);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(st);
@@ -1907,24 +1887,21 @@ static hipError_t surface_scratch(sn::UvScratch& S, hipStream_t st, const Surfac
     return hipSuccess;
 }
 
-struct SurfacePasses {  // the call's passes on planar planes: `m` frames, pointers at the first of them
+struct SurfacePasses {  // the call's passes on planar planes: `m` frames, the views at the first of them
     void* self;
-    int (*run)(void* self, int m, const void* const s[3], const int64_t sfs[3], const int32_t sp[3], void* const d[3], const int64_t dfs[3],
-               const int32_t dp[3], const int32_t* parity);
+    int (*run)(void* self, int m, const sn::PlaneView s[3], const sn::PlaneViewW d[3], const int32_t* parity);
     int (*offset)(void* self, int parity);  // the field offset of a frame (unless all_lines)
 };
 
-static int surface_walk_packed(sn::UvScratch& S, hipStream_t st, const SurfaceGeometry& g, int n, const SurfaceSide& src, const SurfaceSide& dst,
-                               const int32_t* parity, const SurfacePasses& passes, std::string& msg);
-
+// Executes a plan (sn_surface_plan.h, which decides every launch): the planes that go from source to destination once, then
+// per chunk of what the scratch holds the source as planar LSB-aligned planes, the call's passes on them, and the destination
+// finished from where the passes -- or, for a plane that is not processed, the source's planar form -- left each plane.
+// MSB-aligned sides (shift ss of the source, ds of the destination): the passes see LSB-aligned planes; samples are shifted down
+// on their way in and up on their way out, or where the passes wrote them.
 // A HIP error of the walk itself comes back as SN_ERR_HIP with its text in msg; an error of the passes leaves msg empty (the
-// context holds the text).  A call with a packed side is surface_walk_packed's.
-// MSB-aligned sides (shift ss of the source, ds of the destination): the passes see LSB-aligned planes.  The source's planes
-// go through scratch, shifted down on the way (chroma inside the split when it is semi-planar); the passes write LSB-aligned
-// samples into the destination's planes (or the chroma scratch a merge reads), which are then shifted up where they lie (inside
-// the merge for a UV plane).  A plane that is not processed goes from src to dst as (x >> ss) << ds, once, before the chunks.
-static int surface_walk(sn::UvScratch& S, hipStream_t st, const SurfaceGeometry& g, int n, const SurfaceSide& src, const SurfaceSide& dst,
-                        const int32_t* parity, const SurfacePasses& passes, std::string& msg)
+// context holds the text).
+static int surface_walk(sn::UvScratch& S, hipStream_t st, const SurfaceGeometry& g, const sn::SurfacePlan& P, int n, const SurfaceSide& src,
+                        const SurfaceSide& dst, const int32_t* parity, const SurfacePasses& passes, std::string& msg)
 {
 #define SN_UV_HIP(call)                                                      \
     do {                                                                     \
@@ -1934,204 +1911,72 @@ static int surface_walk(sn::UvScratch& S, hipStream_t st, const SurfaceGeometry&
             return SN_ERR_HIP;                                               \
         }                                                                    \
     } while (0)
-    if (src.packing || dst.packing) return surface_walk_packed(S, st, g, n, src, dst, parity, passes, msg);
-    const int B = g.B, ss = src.shift, ds = dst.shift;
-    const bool msb = ss != 0 || ds != 0, chroma = g.planes >= 3;
-    const SurfaceNeeds need = surface_needs(g, src, dst);
-    const void* s[3];
-    void* d[3];
-    int64_t sfs[3], dfs[3];
-    int32_t sp[3], dp[3];
-    if (chroma && !g.chroma_processed) {
-        // never through a pass and never through scratch: one copy of the UV plane, or one conversion from src to dst
-        const int cw = g.w_in[1], h = g.h_in[1];
-        if (src.semi && dst.semi && !msb) {
-            for (int f = 0; f < n; ++f)
-                SN_UV_HIP(hipMemcpy2DAsync(dst.p[1] + f * dst.fs[1], (size_t)dst.pitch[1], src.p[1] + f * src.fs[1], (size_t)src.pitch[1],
-                                           (size_t)2 * cw * B, (size_t)h, hipMemcpyDeviceToDevice, st));
-        } else if (src.semi && dst.semi) {  // the UV plane as a plane of 2 cw samples (ss == ds: only the low bits go)
-            SN_UV_HIP(sn::launch_shift16(st, n, src.p[1], src.fs[1], src.pitch[1], 2 * cw, h, dst.p[1], dst.fs[1], dst.pitch[1], -1, ss, ds));
-        } else if (src.semi) {
-            SN_UV_HIP(sn::launch_uv_split(st, B, n, src.p[1], src.fs[1], src.pitch[1], cw, h, dst.p[1], dst.fs[1], dst.pitch[1], dst.p[2], dst.fs[2],
-                                          dst.pitch[2], -1, ss, ds));
-        } else if (dst.semi) {
-            SN_UV_HIP(sn::launch_uv_merge(st, B, n, src.p[1], src.fs[1], src.pitch[1], src.p[2], src.fs[2], src.pitch[2], cw, h, dst.p[1], dst.fs[1],
-                                          dst.pitch[1], ss, ds));
-        } else {  // planar on both sides, one of them MSB-aligned
-            for (int p = 1; p < 3; ++p)
-                SN_UV_HIP(sn::launch_shift16(st, n, src.p[p], src.fs[p], src.pitch[p], cw, h, dst.p[p], dst.fs[p], dst.pitch[p], -1, ss, ds));
+    using View = sn::PlaneViewW;
+    const int B = g.B;
+    // one step of the plan: m frames from `from` to `to` (the step's stage says which planes those are), planes of w x h
+    auto step = [&](const sn::PlanStep& s, const View from[3], const View to[3], int m, const int w[3], const int h[3], int lines, int ss, int ds) -> int {
+        const int p = s.plane, pw = s.uv_row ? 2 * w[p] : w[p];
+        switch (s.op) {
+        case sn::kOpShift16: SN_UV_HIP(sn::launch_shift16(st, m, from[p], pw, h[p], to[p], lines, ss, ds)); break;
+        case sn::kOpUvSplit: SN_UV_HIP(sn::launch_uv_split(st, B, m, from[1], w[1], h[1], to[1], to[2], lines, ss, ds)); break;
+        case sn::kOpUvMerge: SN_UV_HIP(sn::launch_uv_merge(st, B, m, from[1], from[2], w[1], h[1], to[1], ss, ds)); break;
+        case sn::kOpUnpack: SN_UV_HIP(sn::launch_unpack(st, src.packing, B, m, from[0], w[0], h[0], to[0], to[1], to[2], lines, ss)); break;
+        case sn::kOpPack: SN_UV_HIP(sn::launch_pack(st, dst.packing, B, m, from[0], from[1], from[2], w[0], h[0], to[0], ds)); break;
+        default:
+            if (s.op == sn::kOpCopyOrShift16 && B == 2) {
+                SN_UV_HIP(sn::launch_shift16(st, m, from[p], pw, h[p], to[p], lines, ss, ds));
+                break;
+            }
+            for (int f = 0; f < m; ++f)
+                SN_UV_HIP(hipMemcpy2DAsync(to[p].at(f).base, (size_t)to[p].pitch, from[p].at(f).base, (size_t)from[p].pitch, (size_t)pw * B, (size_t)h[p],
+                                           hipMemcpyDeviceToDevice, st));
         }
-        S.copied_frames += n;
-    }
-    if (msb && !g.luma_processed)  // (the caller has told its passes: luma_elsewhere)
-        SN_UV_HIP(sn::launch_shift16(st, n, src.p[0], src.fs[0], src.pitch[0], g.w_in[0], g.h_in[0], dst.p[0], dst.fs[0], dst.pitch[0], -1, ss, ds));
-    const int cap = need.in || need.y ? S.cap : n;
+        return SN_OK;
+    };
+    // a plane of the plan at frame f0 of the call: scratch holds the chunk, so its frame 0 is frame f0
+    auto at = [&](const sn::PlaneRef& r, int64_t f0) -> View {
+        switch (r.buf) {
+        case sn::kBufIn: return S.in[r.idx];
+        case sn::kBufOut: return S.out[r.idx];
+        case sn::kBufY: return S.y;
+        case sn::kBufYo: return S.yo;
+        case sn::kBufDst: return dst.view(r.idx).at(f0);
+        default: return src.view(r.idx).at(f0);
+        }
+    };
+    const int ss = src.shift, ds = dst.shift;
+    const View sv[3] = {src.view(0), src.view(1), src.view(2)}, dv[3] = {dst.view(0), dst.view(1), dst.view(2)};
+    for (int i = 0; i < P.nonce; ++i)
+        if (int rc = step(P.once[i], sv, dv, n, g.w_in, g.h_in, -1, ss, ds)) return rc;
+    if (P.count_copied == sn::kCountPerCall) S.copied_frames += n;
+    const int cap = P.chunked ? S.cap : n;
     for (int f0 = 0; f0 < n; f0 += cap) {
         const int m = n - f0 < cap ? n - f0 : cap;
         const int32_t* par = parity ? parity + f0 : nullptr;
-        for (int p = 0; p < 3; ++p) {
-            // planes the passes leave alone (a Y clip's chroma, chroma that is not processed), and the third of a semi-planar
-            // side until its scratch replaces it below: their pointers only have to be there
-            const bool real = p < g.planes && (p == 0 || g.chroma_processed);
-            const int q = !real ? 0 : src.semi && p == 2 ? 1 : p, r = !real ? 0 : dst.semi && p == 2 ? 1 : p;
-            s[p] = src.p[q] + (int64_t)f0 * src.fs[q], sfs[p] = src.fs[q], sp[p] = src.pitch[q];
-            d[p] = dst.p[r] + (int64_t)f0 * dst.fs[r], dfs[p] = dst.fs[r], dp[p] = dst.pitch[r];
+        View rd[3], wr[3], res[3], sf[3], df[3], to[3];
+        for (int p = 0; p < 3; ++p) rd[p] = at(P.read[p], f0), wr[p] = at(P.write[p], f0), res[p] = at(P.result[p], f0), df[p] = dv[p].at(f0);
+        // the source: the lines the passes keep, one launch per run of frames with the same field offset (field_run, as run_batch
+        // cuts them), or every line and the chunk in one run
+        for (int g0 = 0; g0 < m && P.nsource;) {
+            sn::FieldRun run{m, -1};
+            if (!P.source_all_lines) run = sn::field_run(par, g0, m, [&](int parity_of_frame) { return passes.offset(passes.self, parity_of_frame); });
+            for (int p = 0; p < 3; ++p) sf[p] = sv[p].at(f0 + g0), to[p] = rd[p].at(g0);
+            for (int i = 0; i < P.nsource; ++i)
+                if (int rc = step(P.source[i], sf, to, run.end - g0, g.w_in, g.h_in, run.offset, ss, 0)) return rc;
+            g0 = run.end;
         }
-        // the lines the pass keeps: one launch per run of frames with the same field offset, as run_batch cuts them
-        for (int g0 = 0; g0 < m && (need.y || (need.in && (src.semi || ss != 0)));) {
-            int g1 = m, lines = -1;
-            if (!g.all_lines) {
-                lines = passes.offset(passes.self, par ? par[g0] : 1);
-                for (g1 = g0 + 1; g1 < m && passes.offset(passes.self, par ? par[g1] : 1) == lines;) ++g1;
-            }
-            if (need.y)
-                SN_UV_HIP(sn::launch_shift16(st, g1 - g0, src.p[0] + (f0 + g0) * src.fs[0], src.fs[0], src.pitch[0], g.w_in[0], g.h_in[0],
-                                             S.y + g0 * S.y_bytes, S.y_bytes, S.pitch_y, lines, ss, 0));
-            if (need.in && src.semi) {
-                SN_UV_HIP(sn::launch_uv_split(st, B, g1 - g0, src.p[1] + (f0 + g0) * src.fs[1], src.fs[1], src.pitch[1], g.w_in[1], g.h_in[1],
-                                              S.in[0] + g0 * S.in_bytes, S.in_bytes, S.pitch_in, S.in[1] + g0 * S.in_bytes, S.in_bytes, S.pitch_in, lines, ss, 0));
-            } else if (need.in && ss != 0) {
-                for (int k = 0; k < 2; ++k)
-                    SN_UV_HIP(sn::launch_shift16(st, g1 - g0, src.p[1 + k] + (f0 + g0) * src.fs[1 + k], src.fs[1 + k], src.pitch[1 + k], g.w_in[1], g.h_in[1],
-                                                 S.in[k] + g0 * S.in_bytes, S.in_bytes, S.pitch_in, lines, ss, 0));
-            }
-            g0 = g1;
-        }
-        if (need.y) s[0] = S.y, sfs[0] = S.y_bytes, sp[0] = S.pitch_y;
-        if (need.in && (src.semi || ss != 0)) {
-            for (int k = 0; k < 2; ++k) s[1 + k] = S.in[k], sfs[1 + k] = S.in_bytes, sp[1 + k] = S.pitch_in;
-            if (src.semi) S.split_frames += m;
-        }
-        if (need.in && dst.semi)
-            for (int k = 0; k < 2; ++k) d[1 + k] = S.out[k], dfs[1 + k] = S.out_bytes, dp[1 + k] = S.pitch_out;
-        const int rc = passes.run(passes.self, m, s, sfs, sp, d, dfs, dp, par);
-        if (rc != SN_OK) return rc;
-        if (need.in && dst.semi) {
-            SN_UV_HIP(sn::launch_uv_merge(st, B, m, S.out[0], S.out_bytes, S.pitch_out, S.out[1], S.out_bytes, S.pitch_out, g.w_out[1], g.h_out[1],
-                                          dst.p[1] + (int64_t)f0 * dst.fs[1], dst.fs[1], dst.pitch[1], 0, ds));
-            S.merged_frames += m;
-        }
-        // the planes the passes wrote straight into an MSB-aligned destination: shifted up where they lie
-        for (int p = 0; p < g.planes && p < 3 && ds != 0; ++p) {
-            if (p == 0 ? !g.luma_processed : (!g.chroma_processed || dst.semi)) continue;
-            uint8_t* const q = dst.p[p] + (int64_t)f0 * dst.fs[p];
-            SN_UV_HIP(sn::launch_shift16(st, m, q, dst.fs[p], dst.pitch[p], g.w_out[p], g.h_out[p], q, dst.fs[p], dst.pitch[p], -1, 0, ds));
-        }
+        if (P.count_split == sn::kCountPerChunk) S.split_frames += m;
+        const sn::PlaneView rdc[3] = {rd[0], rd[1], rd[2]};
+        if (int rc = passes.run(passes.self, m, rdc, wr, par)) return rc;
+        for (int i = 0; i < P.nafter; ++i)
+            if (int rc = step(P.after[i], res, df, m, g.w_out, g.h_out, -1, 0, ds)) return rc;
+        if (P.count_merged == sn::kCountPerChunk) S.merged_frames += m;
+        if (P.count_copied == sn::kCountPerChunk) S.copied_frames += m;
     }
     return SN_OK;
 #undef SN_UV_HIP
 }
 
-// A call with a packed side (SN_LAYOUT_PACKED_*: one plane of Y, U and V).  Per chunk: the source becomes three planar LSB-aligned
-// planes -- a packed source unpacked into the scratch (MSB words shifted down inside the unpack), another one as surface_walk has
-// it --, the passes run on them into the destination's planes or, for a packed or semi-planar destination, into the output
-// scratch, and a packed destination is packed from there (MSB shift and v210 mask inside the pack), all lines.  A plane that is
-// not processed never reaches a pass (the caller has told its passes: luma_elsewhere; chroma_elsewhere): every line of the source
-// is made planar, and the plane goes from there to the destination -- read by the pack, or converted as in surface_walk.
-static int surface_walk_packed(sn::UvScratch& S, hipStream_t st, const SurfaceGeometry& g, int n, const SurfaceSide& src, const SurfaceSide& dst,
-                               const int32_t* parity, const SurfacePasses& passes, std::string& msg)
-{
-#define SN_UV_HIP(call)                                                      \
-    do {                                                                     \
-        hipError_t e_ = (call);                                              \
-        if (e_ != hipSuccess) {                                              \
-            msg = std::string(#call " failed: ") + hipGetErrorString(e_);    \
-            return SN_ERR_HIP;                                               \
-        }                                                                    \
-    } while (0)
-    const int B = g.B, ss = src.shift, ds = dst.shift;
-    const bool lp = g.luma_processed, cp = g.chroma_processed;
-    const bool every_line = g.all_lines || !lp || !cp;
-    const bool y_scratch = src.packing || ss != 0, c_scratch = src.packing || src.semi || ss != 0;
-    for (int f0 = 0; f0 < n; f0 += S.cap) {
-        const int m = n - f0 < S.cap ? n - f0 : S.cap;
-        const int32_t* par = parity ? parity + f0 : nullptr;
-        // ---- the source as planar LSB-aligned planes: one launch per run of frames with the same field offset
-        for (int g0 = 0; g0 < m && (y_scratch || c_scratch);) {
-            int g1 = m, lines = -1;
-            if (!every_line) {
-                lines = passes.offset(passes.self, par ? par[g0] : 1);
-                for (g1 = g0 + 1; g1 < m && passes.offset(passes.self, par ? par[g1] : 1) == lines;) ++g1;
-            }
-            const int k = g1 - g0;
-            const int64_t f = f0 + g0;
-            if (src.packing) {
-                SN_UV_HIP(sn::launch_unpack(st, src.packing, B, k, src.p[0] + f * src.fs[0], src.fs[0], src.pitch[0], g.w_in[0], g.h_in[0],
-                                            S.y + g0 * S.y_bytes, S.y_bytes, S.pitch_y, S.in[0] + g0 * S.in_bytes, S.in_bytes, S.pitch_in,
-                                            S.in[1] + g0 * S.in_bytes, S.in_bytes, S.pitch_in, lines, ss));
-            } else {
-                if (y_scratch)
-                    SN_UV_HIP(sn::launch_shift16(st, k, src.p[0] + f * src.fs[0], src.fs[0], src.pitch[0], g.w_in[0], g.h_in[0], S.y + g0 * S.y_bytes,
-                                                 S.y_bytes, S.pitch_y, lines, ss, 0));
-                if (src.semi) {
-                    SN_UV_HIP(sn::launch_uv_split(st, B, k, src.p[1] + f * src.fs[1], src.fs[1], src.pitch[1], g.w_in[1], g.h_in[1], S.in[0] + g0 * S.in_bytes,
-                                                  S.in_bytes, S.pitch_in, S.in[1] + g0 * S.in_bytes, S.in_bytes, S.pitch_in, lines, ss, 0));
-                } else if (c_scratch) {
-                    for (int c = 0; c < 2; ++c)
-                        SN_UV_HIP(sn::launch_shift16(st, k, src.p[1 + c] + f * src.fs[1 + c], src.fs[1 + c], src.pitch[1 + c], g.w_in[1], g.h_in[1],
-                                                     S.in[c] + g0 * S.in_bytes, S.in_bytes, S.pitch_in, lines, ss, 0));
-                }
-            }
-            g0 = g1;
-        }
-        if (src.packing || src.semi) S.split_frames += m;
-        const void* s[3];
-        void* d[3];
-        int64_t sfs[3], dfs[3];
-        int32_t sp[3], dp[3];
-        for (int p = 0; p < 3; ++p) {
-            if (p == 0 ? y_scratch : c_scratch) {
-                s[p] = p == 0 ? S.y : S.in[p - 1], sfs[p] = p == 0 ? S.y_bytes : S.in_bytes, sp[p] = p == 0 ? S.pitch_y : S.pitch_in;
-            } else {
-                s[p] = src.p[p] + (int64_t)f0 * src.fs[p], sfs[p] = src.fs[p], sp[p] = src.pitch[p];
-            }
-            if (dst.packing || (dst.semi && p > 0)) {
-                d[p] = p == 0 ? S.yo : S.out[p - 1], dfs[p] = p == 0 ? S.yo_bytes : S.out_bytes, dp[p] = p == 0 ? S.pitch_yo : S.pitch_out;
-            } else {
-                d[p] = dst.p[p] + (int64_t)f0 * dst.fs[p], dfs[p] = dst.fs[p], dp[p] = dst.pitch[p];
-            }
-        }
-        // ---- the passes
-        const int rc = passes.run(passes.self, m, s, sfs, sp, d, dfs, dp, par);
-        if (rc != SN_OK) return rc;
-        // ---- the destination.  A plane that is not processed has the source's geometry and is read where the source's lies.
-        const uint8_t* o[3];
-        int64_t ofs[3];
-        int32_t op[3];
-        for (int p = 0; p < 3; ++p) {
-            const bool processed = p == 0 ? lp : cp;
-            o[p] = static_cast<const uint8_t*>(processed ? d[p] : s[p]), ofs[p] = processed ? dfs[p] : sfs[p], op[p] = processed ? dp[p] : sp[p];
-        }
-        if (dst.packing) {
-            SN_UV_HIP(sn::launch_pack(st, dst.packing, B, m, o[0], ofs[0], op[0], o[1], ofs[1], op[1], o[2], ofs[2], op[2], g.w_out[0], g.h_out[0],
-                                      dst.p[0] + (int64_t)f0 * dst.fs[0], dst.fs[0], dst.pitch[0], ds));
-            S.merged_frames += m;
-        } else {
-            for (int p = 0; p < 3; ++p) {
-                if (dst.semi && p > 0) continue;
-                const bool processed = p == 0 ? lp : cp;
-                uint8_t* const q = dst.p[p] + (int64_t)f0 * dst.fs[p];
-                if (processed && ds != 0) {  // shifted up where the passes wrote it
-                    SN_UV_HIP(sn::launch_shift16(st, m, q, dst.fs[p], dst.pitch[p], g.w_out[p], g.h_out[p], q, dst.fs[p], dst.pitch[p], -1, 0, ds));
-                } else if (!processed && B == 2) {
-                    SN_UV_HIP(sn::launch_shift16(st, m, o[p], ofs[p], op[p], g.w_out[p], g.h_out[p], q, dst.fs[p], dst.pitch[p], -1, 0, ds));
-                } else if (!processed) {
-                    for (int f = 0; f < m; ++f)
-                        SN_UV_HIP(hipMemcpy2DAsync(q + f * dst.fs[p], (size_t)dst.pitch[p], o[p] + f * ofs[p], (size_t)op[p], (size_t)g.w_out[p] * B,
-                                                   (size_t)g.h_out[p], hipMemcpyDeviceToDevice, st));
-                }
-            }
-            if (dst.semi) {
-                SN_UV_HIP(sn::launch_uv_merge(st, B, m, o[1], ofs[1], op[1], o[2], ofs[2], op[2], g.w_out[1], g.h_out[1], dst.p[1] + (int64_t)f0 * dst.fs[1],
-                                              dst.fs[1], dst.pitch[1], 0, ds));
-                S.merged_frames += m;
-            }
-        }
-        if (!cp) S.copied_frames += m;
-    }
-    return SN_OK;
-#undef SN_UV_HIP
-}
 
 static int surface_info(const sn::UvScratch& S, sn_surface_info* info)
 {
@@ -2146,14 +1991,29 @@ static int surface_info(const sn::UvScratch& S, sn_surface_info* info)
 
 static int sn_surface_offset(void* self, int parity) { return field_offset(static_cast<Context*>(self), parity); }
 
-static int sn_surface_run(void* self, int m, const void* const s[3], const int64_t sfs[3], const int32_t sp[3], void* const d[3], const int64_t dfs[3],
-                          const int32_t dp[3], const int32_t* parity)
+// plane views as the arrays run_batch and the ABI take
+struct PlaneArrays {
+    const void* s[3];
+    void* d[3];
+    int64_t sfs[3], dfs[3];
+    int32_t sp[3], dp[3];
+    PlaneArrays(const sn::PlaneView sv[3], const sn::PlaneViewW dv[3])
+    {
+        for (int p = 0; p < 3; ++p) {
+            s[p] = sv[p].base, sfs[p] = sv[p].fs, sp[p] = sv[p].pitch;
+            d[p] = dv[p].base, dfs[p] = dv[p].fs, dp[p] = dv[p].pitch;
+        }
+    }
+};
+
+static int sn_surface_run(void* self, int m, const sn::PlaneView sv[3], const sn::PlaneViewW dv[3], const int32_t* parity)
 {
     Context* c = static_cast<Context*>(self);
+    const PlaneArrays a(sv, dv);
     // chroma that is not processed has gone from src to dst already: launch_assemble leaves those planes alone
     // (PlaneArgs::copied_elsewhere) and copies a luma plane that is not processed either, as in the planar call
     c->chroma_elsewhere = !(c->cfg.dh || c->process[1]);
-    const int rc = run_batch(c, c->stream, 0, m, s, sfs, sp, d, dfs, dp, parity);
+    const int rc = run_batch(c, c->stream, 0, m, a.s, a.sfs, a.sp, a.d, a.dfs, a.dp, parity);
     c->chroma_elsewhere = false;
     return rc;
 }
@@ -2186,10 +2046,11 @@ int sn_process_device_surfaces(sn_context* h, int32_t nframes, const sn_surfaces
     if (rc != SN_OK) return sn::fail(c, rc, "%s", msg.c_str());
     if (nframes == 0) return SN_OK;
     SN_HIP(c, hipSetDevice(c->device));
-    SN_HIP(c, surface_scratch(c->uv, c->stream, g, scratch_budget(c), surface_needs(g, ss, ds)));
+    const sn::SurfacePlan plan = surface_plan_of(g, ss, ds);
+    SN_HIP(c, surface_scratch(c->uv, c->stream, g, scratch_budget(c), plan.need));
     const SurfacePasses passes{c, sn_surface_run, sn_surface_offset};
     c->luma_elsewhere = (ss.shift != 0 || ds.shift != 0 || ss.packing || ds.packing) && !g.luma_processed;
-    rc = surface_walk(c->uv, c->stream, g, nframes, ss, ds, parity, passes, msg);
+    rc = surface_walk(c->uv, c->stream, g, plan, nframes, ss, ds, parity, passes, msg);
     c->luma_elsewhere = false;
     if (rc != SN_OK && !msg.empty()) return sn::fail(c, rc, "%s", msg.c_str());
     return rc;
@@ -2637,8 +2498,8 @@ int sn_turn_device(sn_context* h, int32_t direction, int32_t nframes, const void
     if (sp < width * B || dp < height * B || sp % B || dp % B || (uintptr_t)src % B || (uintptr_t)dst % B)
         return sn::fail(c, SN_ERR_INVALID_ARG, "sn_turn_device: pitch smaller than the row or misaligned");
     SN_HIP(c, hipSetDevice(c->device));
-    SN_HIP(c, sn::launch_turn(c->stream, B, direction > 0 ? 1 : 0, nframes, static_cast<const uint8_t*>(src), sfs, sp, width, height,
-                              static_cast<uint8_t*>(dst), dfs, dp));
+    SN_HIP(c, sn::launch_turn(c->stream, B, direction > 0 ? 1 : 0, nframes, sn::PlaneView{static_cast<const uint8_t*>(src), sfs, sp}, width, height,
+                              sn::PlaneViewW{static_cast<uint8_t*>(dst), dfs, dp}));
     return SN_OK;
 }
 
@@ -2656,8 +2517,8 @@ int sn_reduce_device(sn_context* h, int32_t kernel, int32_t nframes, const void*
     if (sp < 2 * width * B || dp < width * B || sp % B || dp % B || sfs % B || dfs % B || (uintptr_t)src % B || (uintptr_t)dst % B)
         return sn::fail(c, SN_ERR_INVALID_ARG, "sn_reduce_device: pitch smaller than the row or misaligned");
     SN_HIP(c, hipSetDevice(c->device));
-    SN_HIP(c, sn::launch_reduce(c->stream, B, c->cfg.bits_per_sample, kernel, nframes, static_cast<const uint8_t*>(src), sfs, sp, width, height, ox, oy,
-                                static_cast<uint8_t*>(dst), dfs, dp));
+    SN_HIP(c, sn::launch_reduce(c->stream, B, c->cfg.bits_per_sample, kernel, nframes, sn::PlaneView{static_cast<const uint8_t*>(src), sfs, sp}, width,
+                                height, ox, oy, sn::PlaneViewW{static_cast<uint8_t*>(dst), dfs, dp}));
     return SN_OK;
 }
 
@@ -2692,8 +2553,9 @@ int sn_mask_merge_device(sn_context* h, const sn_aa_mask* mask, int32_t nframes,
         (aa && (ap < width * B || ap % B || afs % B || (uintptr_t)aa % B)))
         return sn::fail(c, SN_ERR_INVALID_ARG, "sn_mask_merge_device: pitch smaller than the row or misaligned");
     SN_HIP(c, hipSetDevice(c->device));
-    SN_HIP(c, sn::launch_mask_merge(c->stream, B, c->cfg.bits_per_sample, mask->lo, mask->hi, mask->expand, nframes, static_cast<const uint8_t*>(src), sfs, sp,
-                                    static_cast<const uint8_t*>(aa), afs, ap, width, height, static_cast<uint8_t*>(dst), dfs, dp));
+    SN_HIP(c, sn::launch_mask_merge(c->stream, B, c->cfg.bits_per_sample, mask->lo, mask->hi, mask->expand, nframes,
+                                    sn::PlaneView{static_cast<const uint8_t*>(src), sfs, sp}, sn::PlaneView{static_cast<const uint8_t*>(aa), afs, ap}, width,
+                                    height, sn::PlaneViewW{static_cast<uint8_t*>(dst), dfs, dp}));
     return SN_OK;
 }
 
@@ -3008,8 +2870,8 @@ void sn_aa_destroy(sn_aa_context* a)
     for (int p = 0; p < 3; ++p)
         for (uint8_t* q : {a->d_t1[p], a->d_u1[p], a->d_t2[p], a->d_e[p]})
             if (q) (void)hipFree(q);
-    for (uint8_t* q : {a->uv.in[0], a->uv.in[1], a->uv.out[0], a->uv.out[1], a->uv.y, a->uv.yo})
-        if (q) (void)hipFree(q);
+    for (const sn::PlaneViewW& q : {a->uv.in[0], a->uv.in[1], a->uv.out[0], a->uv.out[1], a->uv.y, a->uv.yo})
+        if (q.base) (void)hipFree(q.base);
     for (auto& g : a->groups) aa_free_group(g);
     for (hipStream_t st : {a->up, a->down})
         if (st) (void)hipStreamDestroy(st);
@@ -3125,50 +2987,42 @@ int sn_aa_create_ex3(const sn_config* cfg, const sn_policy* policy, const sn_opt
 }
 
 // Frames [0, n) of a strided device batch through both passes, on the call's stream.
-static int aa_run(sn_aa_context* a, int n, const void* const src[3], const int64_t sfs[3], const int32_t sp[3], void* const dst[3],
-                  const int64_t dfs[3], const int32_t dp[3], const int32_t* parity)
+static int aa_run(sn_aa_context* a, int n, const sn::PlaneView src[3], const sn::PlaneViewW dst[3], const int32_t* parity)
 {
     Context* c1 = reinterpret_cast<Context*>(a->first);
     Context* c2 = reinterpret_cast<Context*>(a->second);
     const int B = a->cfg.bytes_per_sample;
     hipStream_t st = a->stream;
+    // the intermediates of a chunk: the turned source, the first pass's output, that turned back, the second pass's output of a reduce
+    sn::PlaneViewW t1[3], u1[3], t2[3], e[3];
+    for (int p = 0; p < 3; ++p) {
+        t1[p] = sn::PlaneViewW{a->d_t1[p], a->tbytes[p], a->tpitch[p]}, u1[p] = sn::PlaneViewW{a->d_u1[p], a->u1bytes[p], a->tpitch[p]};
+        t2[p] = sn::PlaneViewW{a->d_t2[p], a->t2bytes[p], a->t2pitch[p]}, e[p] = sn::PlaneViewW{a->d_e[p], a->obytes[p], a->opitch[p]};
+    }
     // planes that are not processed are never touched by the passes (copies_elsewhere): their pointers only have to be there
-    const void* s1[3] = {src[0], src[1], src[2]};
-    void* d1[3] = {dst[0], dst[1], dst[2]};
-    const void* s2[3] = {src[0], src[1], src[2]};
+    const void* s1[3] = {src[0].base, src[1].base, src[2].base};
+    void* d1[3] = {dst[0].base, dst[1].base, dst[2].base};
+    const void* s2[3] = {src[0].base, src[1].base, src[2].base};
+    const PlaneArrays out(src, dst);  // (the destination's frame strides and pitches as run_batch takes them)
     for (int p = 0; p < a->planes; ++p)
         if (a->process[p]) s1[p] = a->d_t1[p], d1[p] = a->d_u1[p], s2[p] = a->d_t2[p];
     for (int f0 = 0; f0 < n; f0 += a->cap) {
         const int m = n - f0 < a->cap ? n - f0 : a->cap;
         const int32_t* par = parity ? parity + f0 : nullptr;
-        // a turn writes the lines its pass keeps: one launch per run of frames with the same field offset, as run_batch cuts them;
-        // a dh pass reads every line of its source: the whole form, one launch for the chunk
+        // a turn writes the lines its pass keeps: one launch per run of frames with the same field offset (field_run, as run_batch
+        // cuts them); a dh pass reads every line of its source: the whole form, one launch for the chunk
         auto turns = [&](int right) -> int {
-            if (a->cfg.dh) {
-                for (int p = 0; p < a->planes; ++p) {  // dh forces every plane
-                    if (!right)
-                        SN_AA_HIP(sn::launch_turn(st, B, 0, m, static_cast<const uint8_t*>(src[p]) + (int64_t)f0 * sfs[p], sfs[p], sp[p], a->w[p], a->h[p],
-                                                  a->d_t1[p], a->tbytes[p], a->tpitch[p], -1));
-                    else
-                        SN_AA_HIP(sn::launch_turn(st, B, 1, m, a->d_u1[p], a->u1bytes[p], a->tpitch[p], a->h[p], a->ow[p], a->d_t2[p], a->t2bytes[p],
-                                                  a->t2pitch[p], -1));
-                }
-                return SN_OK;
-            }
             for (int g0 = 0; g0 < m;) {
-                const int off = field_offset(c1, par ? par[g0] : 1);
-                int g1 = g0 + 1;
-                while (g1 < m && field_offset(c1, par ? par[g1] : 1) == off) ++g1;
+                sn::FieldRun run{m, -1};
+                if (!a->cfg.dh) run = sn::field_run(par, g0, m, [c1](int q) { return field_offset(c1, q); });
                 for (int p = 0; p < a->planes; ++p) {
-                    if (!a->process[p]) continue;
+                    if (!a->process[p]) continue;  // (dh forces every plane)
                     if (!right)  // TurnLeft: the clip's plane -> h wide, w high
-                        SN_AA_HIP(sn::launch_turn(st, B, 0, g1 - g0, static_cast<const uint8_t*>(src[p]) + (int64_t)(f0 + g0) * sfs[p], sfs[p], sp[p],
-                                                  a->w[p], a->h[p], a->d_t1[p] + g0 * a->tbytes[p], a->tbytes[p], a->tpitch[p], off));
+                        SN_AA_HIP(sn::launch_turn(st, B, 0, run.end - g0, src[p].at(f0 + g0), a->w[p], a->h[p], t1[p].at(g0), run.offset));
                     else  // TurnRight of the first pass's output
-                        SN_AA_HIP(sn::launch_turn(st, B, 1, g1 - g0, a->d_u1[p] + g0 * a->u1bytes[p], a->u1bytes[p], a->tpitch[p], a->h[p], a->ow[p],
-                                                  a->d_t2[p] + g0 * a->t2bytes[p], a->t2bytes[p], a->t2pitch[p], off));
+                        SN_AA_HIP(sn::launch_turn(st, B, 1, run.end - g0, u1[p].at(g0), a->h[p], a->ow[p], t2[p].at(g0), run.offset));
                 }
-                g0 = g1;
+                g0 = run.end;
             }
             return SN_OK;
         };
@@ -3176,20 +3030,19 @@ static int aa_run(sn_aa_context* a, int n, const void* const src[3], const int64
         SN_AA_SN(a->first, run_batch(c1, st, 0, m, s1, a->tbytes, a->tpitch, d1, a->u1bytes, a->tpitch, par));
         if (int rc = turns(1)) return rc;
         void* d2[3] = {nullptr, nullptr, nullptr};
-        for (int p = 0; p < a->planes; ++p) d2[p] = static_cast<uint8_t*>(dst[p]) + (int64_t)f0 * dfs[p];
+        for (int p = 0; p < a->planes; ++p) d2[p] = dst[p].at(f0).base;
         // the edge mask, last: the chunk's result is merged into the source through the source's own mask, in place on the
         // destination (which has the source's size: creation has seen to it); one launch per processed plane
         auto masked = [&]() -> int {
             for (int p = 0; p < a->planes && a->mask.kind; ++p) {
                 if (!a->process[p]) continue;
-                SN_AA_HIP(sn::launch_mask_merge(st, B, a->cfg.bits_per_sample, a->mask.lo, a->mask.hi, a->mask.expand, m,
-                                                static_cast<const uint8_t*>(src[p]) + (int64_t)f0 * sfs[p], sfs[p], sp[p], static_cast<const uint8_t*>(d2[p]),
-                                                dfs[p], dp[p], a->w[p], a->h[p], static_cast<uint8_t*>(d2[p]), dfs[p], dp[p]));
+                SN_AA_HIP(sn::launch_mask_merge(st, B, a->cfg.bits_per_sample, a->mask.lo, a->mask.hi, a->mask.expand, m, src[p].at(f0), dst[p].at(f0),
+                                                a->w[p], a->h[p], dst[p].at(f0)));
             }
             return SN_OK;
         };
         if (!a->reduce) {
-            SN_AA_SN(a->second, run_batch(c2, st, 0, m, s2, a->t2bytes, a->t2pitch, d2, dfs, dp, par));
+            SN_AA_SN(a->second, run_batch(c2, st, 0, m, s2, a->t2bytes, a->t2pitch, d2, out.dfs, out.dp, par));
             if (int rc = masked()) return rc;
             continue;
         }
@@ -3198,16 +3051,33 @@ static int aa_run(sn_aa_context* a, int n, const void* const src[3], const int64
         void* e2[3] = {a->d_e[0], a->d_e[1], a->d_e[2]};
         SN_AA_SN(a->second, run_batch(c2, st, 0, m, s2, a->t2bytes, a->t2pitch, e2, a->obytes, a->opitch, par));
         for (int g0 = 0; g0 < m;) {
-            const int off = field_offset(c2, par ? par[g0] : 1);
-            int g1 = g0 + 1;
-            while (g1 < m && field_offset(c2, par ? par[g1] : 1) == off) ++g1;
+            const sn::FieldRun run = sn::field_run(par, g0, m, [c2](int q) { return field_offset(c2, q); });
             for (int p = 0; p < a->planes; ++p)
-                SN_AA_HIP(sn::launch_reduce(st, B, a->cfg.bits_per_sample, a->reduce, g1 - g0, a->d_e[p] + g0 * a->obytes[p], a->obytes[p], a->opitch[p],
-                                            a->w[p], a->h[p], 1 - off, off, static_cast<uint8_t*>(d2[p]) + (int64_t)g0 * dfs[p], dfs[p], dp[p]));
-            g0 = g1;
+                SN_AA_HIP(sn::launch_reduce(st, B, a->cfg.bits_per_sample, a->reduce, run.end - g0, e[p].at(g0), a->w[p], a->h[p], 1 - run.offset, run.offset,
+                                            dst[p].at(f0 + g0)));
+            g0 = run.end;
         }
         if (int rc = masked()) return rc;
     }
+    return SN_OK;
+}
+
+// the plane arrays of the ABI as views (planes the clip does not have: empty)
+static void plane_views(int planes, const void* const src[3], const int64_t sfs[3], const int32_t sp[3], void* const dst[3], const int64_t dfs[3],
+                        const int32_t dp[3], sn::PlaneView sv[3], sn::PlaneViewW dv[3])
+{
+    for (int p = 0; p < planes; ++p) {
+        sv[p] = sn::PlaneView{static_cast<const uint8_t*>(src[p]), sfs[p], sp[p]};
+        dv[p] = sn::PlaneViewW{static_cast<uint8_t*>(dst[p]), dfs[p], dp[p]};
+    }
+}
+
+// a plane that is not processed: source to destination, once; no turn and no pass
+static int aa_copy_plane(sn_aa_context* a, int p, int n, const sn::PlaneView& s, const sn::PlaneViewW& d)
+{
+    for (int f = 0; f < n; ++f)
+        SN_AA_HIP(hipMemcpy2DAsync(d.at(f).base, (size_t)d.pitch, s.at(f).base, (size_t)s.pitch, (size_t)a->w[p] * a->cfg.bytes_per_sample, a->h[p],
+                                   hipMemcpyDeviceToDevice, a->stream));
     return SN_OK;
 }
 
@@ -3227,26 +3097,23 @@ int sn_aa_process_device_strided(sn_aa_context* a, int32_t nframes, const void* 
     }
     if (nframes == 0) return SN_OK;
     SN_AA_HIP(hipSetDevice(a->cfg.device));
-    // a plane that is not processed: source to destination, once; no turn and no pass
-    for (int p = 0; p < a->planes; ++p) {
-        if (a->process[p]) continue;
-        for (int f = 0; f < nframes; ++f)
-            SN_AA_HIP(hipMemcpy2DAsync(static_cast<uint8_t*>(dst[p]) + f * dfs[p], (size_t)dp[p], static_cast<const uint8_t*>(src[p]) + f * sfs[p],
-                                       (size_t)sp[p], (size_t)a->w[p] * B, a->h[p], hipMemcpyDeviceToDevice, a->stream));
-    }
-    return aa_run(a, nframes, src, sfs, sp, dst, dfs, dp, parity);
+    sn::PlaneView sv[3];
+    sn::PlaneViewW dv[3];
+    plane_views(a->planes, src, sfs, sp, dst, dfs, dp, sv, dv);
+    for (int p = 0; p < a->planes; ++p)
+        if (!a->process[p])
+            if (int rc = aa_copy_plane(a, p, nframes, sv[p], dv[p])) return rc;
+    return aa_run(a, nframes, sv, dv, parity);
 }
 
-static int aa_surface_run(void* self, int m, const void* const s[3], const int64_t sfs[3], const int32_t sp[3], void* const d[3], const int64_t dfs[3],
-                          const int32_t dp[3], const int32_t* parity)
+static int aa_surface_run(void* self, int m, const sn::PlaneView s[3], const sn::PlaneViewW d[3], const int32_t* parity)
 {
     sn_aa_context* a = static_cast<sn_aa_context*>(self);
     if (!a->process[0] && !a->luma_elsewhere)  // luma that is not processed: source to destination, once (chroma: surface_walk)
-        for (int f = 0; f < m; ++f)
-            SN_AA_HIP(hipMemcpy2DAsync(static_cast<uint8_t*>(d[0]) + f * dfs[0], (size_t)dp[0], static_cast<const uint8_t*>(s[0]) + f * sfs[0],
-                                       (size_t)sp[0], (size_t)a->w[0] * a->cfg.bytes_per_sample, a->h[0], hipMemcpyDeviceToDevice, a->stream));
-    return aa_run(a, m, s, sfs, sp, d, dfs, dp, parity);
+        if (int rc = aa_copy_plane(a, 0, m, s[0], d[0])) return rc;
+    return aa_run(a, m, s, d, parity);
 }
+
 
 int sn_aa_process_device_surfaces(sn_aa_context* a, int32_t nframes, const sn_surfaces* src, const sn_surfaces* dst, const int32_t* parity)
 {
@@ -3275,10 +3142,11 @@ int sn_aa_process_device_surfaces(sn_aa_context* a, int32_t nframes, const sn_su
     if (rc != SN_OK) return aa_fail(a, rc, msg);
     if (nframes == 0) return SN_OK;
     SN_AA_HIP(hipSetDevice(a->cfg.device));
-    SN_AA_HIP(surface_scratch(a->uv, a->stream, g, scratch_budget(reinterpret_cast<Context*>(a->first)), surface_needs(g, ss, ds)));
+    const sn::SurfacePlan plan = surface_plan_of(g, ss, ds);
+    SN_AA_HIP(surface_scratch(a->uv, a->stream, g, scratch_budget(reinterpret_cast<Context*>(a->first)), plan.need));
     const SurfacePasses passes{a, aa_surface_run, nullptr};
     a->luma_elsewhere = (ss.shift != 0 || ds.shift != 0 || ss.packing || ds.packing) && !g.luma_processed;
-    rc = surface_walk(a->uv, a->stream, g, nframes, ss, ds, parity, passes, msg);
+    rc = surface_walk(a->uv, a->stream, g, plan, nframes, ss, ds, parity, passes, msg);
     a->luma_elsewhere = false;
     if (rc != SN_OK && !msg.empty()) return aa_fail(a, rc, msg);
     return rc;
@@ -3431,8 +3299,11 @@ static int aa_launch(sn_aa_context* a, sn_aa_context::Group& g)
         s3[p] = a->process[p] ? g.d_src[p] + g.lo * a->cbytes[p] : g.h_src[p];  // (not processed: never read on the device)
         d3[p] = a->process[p] ? g.d_out[p] + g.lo * a->dstbytes[p] : g.h_src[p];
     }
+    sn::PlaneView sv[3];
+    sn::PlaneViewW dv[3];
+    plane_views(a->planes, s3, a->cbytes, a->pitch, d3, a->dstbytes, a->dstpitch, sv, dv);
     if (any)
-        if (int rc = aa_run(a, n, s3, a->cbytes, a->pitch, d3, a->dstbytes, a->dstpitch, par.data())) return rc;
+        if (int rc = aa_run(a, n, sv, dv, par.data())) return rc;
     SN_AA_HIP(hipEventRecord(g.swept, a->stream));
     SN_AA_HIP(hipStreamWaitEvent(a->down, g.swept, 0));
     for (int k = g.lo; k < g.hi; ++k) {

@@ -66,46 +66,53 @@ struct ChainArgs {
 
 struct Context;
 
+// A plane of a strided batch: frame f starts at base + f * fs, its rows are `pitch` bytes apart.  PlaneView is read-only,
+// PlaneViewW writable (and readable: it converts).
+struct PlaneView {
+    const uint8_t* base = nullptr;
+    int64_t fs = 0;     // bytes
+    int32_t pitch = 0;  // bytes
+    PlaneView at(int64_t frame) const { return PlaneView{base + frame * fs, fs, pitch}; }
+};
+struct PlaneViewW {
+    uint8_t* base = nullptr;
+    int64_t fs = 0;
+    int32_t pitch = 0;
+    PlaneViewW at(int64_t frame) const { return PlaneViewW{base + frame * fs, fs, pitch}; }
+    operator PlaneView() const { return PlaneView{base, fs, pitch}; }
+};
+
 // sn_turn.hip: quarter turn of a plane (right = clockwise), for device-resident anti-aliasing pipelines;
 // line_parity 0 / 1: only the destination lines of that parity are written, < 0: all of them
-hipError_t launch_turn(hipStream_t s, int bytes, int right, int nframes, const uint8_t* src, int64_t src_frame_stride, int src_pitch, int w,
-                       int h, uint8_t* dst, int64_t dst_frame_stride, int dst_pitch, int line_parity = -1);
+hipError_t launch_turn(hipStream_t s, int bytes, int right, int nframes, PlaneView src, int w, int h, PlaneViewW dst, int line_parity = -1);
 
 // sn_reduce.hip: the 2w x 2h plane of the anti-aliasing call with dh back to w x h (of dst): kernel 1 = tent [1 2 1],
 // 2 = half-band [-1 0 9 16 9 0 -1], centred on src[2y + oy][2x + ox], edges clamped; integer results clamped to `bits`
-hipError_t launch_reduce(hipStream_t s, int bytes, int bits, int kernel, int nframes, const uint8_t* src, int64_t src_frame_stride, int src_pitch,
-                         int w, int h, int ox, int oy, uint8_t* dst, int64_t dst_frame_stride, int dst_pitch);
+hipError_t launch_reduce(hipStream_t s, int bytes, int bits, int kernel, int nframes, PlaneView src, int w, int h, int ox, int oy, PlaneViewW dst);
 
 // sn_mask.hip: the edge mask of the anti-aliasing call.  A Sobel mask of src (w x h; lo, hi in 8-bit scale, expand 0 / 1:
-// sangnom_hip.h has the arithmetic) merges aa into src: dst = src where the mask is 0, aa where it is 256.  aa == nullptr:
+// sangnom_hip.h has the arithmetic) merges aa into src: dst = src where the mask is 0, aa where it is 256.  aa.base == nullptr:
 // dst is the mask itself.  dst may be the plane aa lies in (same base, pitch and frame stride); src must not overlap dst.
-hipError_t launch_mask_merge(hipStream_t s, int bytes, int bits, int lo, int hi, int expand, int nframes, const uint8_t* src, int64_t src_frame_stride,
-                             int src_pitch, const uint8_t* aa, int64_t aa_frame_stride, int aa_pitch, int w, int h, uint8_t* dst,
-                             int64_t dst_frame_stride, int dst_pitch);
+hipError_t launch_mask_merge(hipStream_t s, int bytes, int bits, int lo, int hi, int expand, int nframes, PlaneView src, PlaneView aa, int w, int h,
+                             PlaneViewW dst);
 
 // sn_uv.hip: semi-planar chroma (a UV plane of U,V sample pairs: NV12 / P016 / NV16 / NV24) <-> a U and a V plane of cw x h
 // samples each.  line_parity 0 / 1: only the lines of that parity are read and written (the lines the pass that follows
 // keeps), < 0: all of them.  One side is never written: split reads uv, merge reads u and v.
 // ss / ds (16-bit samples only): every sample goes through (x >> ss) << ds on its way (MSB-aligned sides: P010 / P012).
-hipError_t launch_uv_split(hipStream_t s, int bytes, int nframes, const uint8_t* uv, int64_t uv_frame_stride, int uv_pitch, int cw, int h,
-                           uint8_t* u, int64_t u_frame_stride, int u_pitch, uint8_t* v, int64_t v_frame_stride, int v_pitch, int line_parity = -1,
-                           int ss = 0, int ds = 0);
-hipError_t launch_uv_merge(hipStream_t s, int bytes, int nframes, const uint8_t* u, int64_t u_frame_stride, int u_pitch, const uint8_t* v,
-                           int64_t v_frame_stride, int v_pitch, int cw, int h, uint8_t* uv, int64_t uv_frame_stride, int uv_pitch, int ss = 0, int ds = 0);
+hipError_t launch_uv_split(hipStream_t s, int bytes, int nframes, PlaneView uv, int cw, int h, PlaneViewW u, PlaneViewW v, int line_parity = -1, int ss = 0,
+                           int ds = 0);
+hipError_t launch_uv_merge(hipStream_t s, int bytes, int nframes, PlaneView u, PlaneView v, int cw, int h, PlaneViewW uv, int ss = 0, int ds = 0);
 // ... and one plane of w x h 16-bit words on its own: dst = (src >> ss) << ds, the same line_parity; src == dst is allowed
-hipError_t launch_shift16(hipStream_t s, int nframes, const uint8_t* src, int64_t src_frame_stride, int src_pitch, int w, int h, uint8_t* dst,
-                          int64_t dst_frame_stride, int dst_pitch, int line_parity, int ss, int ds);
+hipError_t launch_shift16(hipStream_t s, int nframes, PlaneView src, int w, int h, PlaneViewW dst, int line_parity, int ss, int ds);
 
 // sn_packed.hip: packed 4:2:2 (one plane of Y, U and V; packing = sn::Packing of sn_surface_layout.h: 1 YUYV, 2 UYVY, 3 v210)
 // <-> a Y plane of w x h samples and a U and a V plane of w / 2 x h.  line_parity as above (the pack writes every line).
 // ss: the unpack shifts every 16-bit word it reads down; ds: the pack shifts every sample up (MSB-aligned words: Y210 / Y212).
 // v210 packs sample & 0x3FF and zero fields for pixels at or beyond w.  One side is never written.
-hipError_t launch_unpack(hipStream_t s, int packing, int bytes, int nframes, const uint8_t* pk, int64_t pk_frame_stride, int pk_pitch, int w, int h,
-                         uint8_t* y, int64_t y_frame_stride, int y_pitch, uint8_t* u, int64_t u_frame_stride, int u_pitch, uint8_t* v,
-                         int64_t v_frame_stride, int v_pitch, int line_parity, int ss);
-hipError_t launch_pack(hipStream_t s, int packing, int bytes, int nframes, const uint8_t* y, int64_t y_frame_stride, int y_pitch, const uint8_t* u,
-                       int64_t u_frame_stride, int u_pitch, const uint8_t* v, int64_t v_frame_stride, int v_pitch, int w, int h, uint8_t* pk,
-                       int64_t pk_frame_stride, int pk_pitch, int ds);
+hipError_t launch_unpack(hipStream_t s, int packing, int bytes, int nframes, PlaneView pk, int w, int h, PlaneViewW y, PlaneViewW u, PlaneViewW v,
+                         int line_parity, int ss);
+hipError_t launch_pack(hipStream_t s, int packing, int bytes, int nframes, PlaneView y, PlaneView u, PlaneView v, int w, int h, PlaneViewW pk, int ds);
 
 // sn_pool_kernels.hip: the three-kernel path over the HBM-resident pool (every format).
 hipError_t launch_assemble(hipStream_t s, const PlaneArgs& p, int bytes, int nframes);

@@ -266,9 +266,13 @@ static void mask_launch(hipStream_t st, int expand, int nframes, const uint8_t* 
         hipLaunchKernelGGL((k_mask_merge<T, 0>), grid, dim3(256), 0, st, src, sfs, spitch, aa, afs, apitch, dst, dfs, dpitch, w, h, t, maxv, src16, aa16, dst16);
 }
 
-hipError_t launch_mask_merge(hipStream_t st, int bytes, int bits, int lo, int hi, int expand, int nframes, const uint8_t* src, int64_t sfs, int spitch,
-                             const uint8_t* aa, int64_t afs, int apitch, int w, int h, uint8_t* dst, int64_t dfs, int dpitch)
+hipError_t launch_mask_merge(hipStream_t st, int bytes, int bits, int lo, int hi, int expand, int nframes, PlaneView s, PlaneView a, int w, int h,
+                             PlaneViewW d)
 {
+    const uint8_t *const src = s.base, *const aa = a.base;
+    uint8_t* const dst = d.base;
+    const int64_t sfs = s.fs, afs = a.fs, dfs = d.fs;
+    const int spitch = s.pitch, apitch = a.pitch, dpitch = d.pitch;
     if (nframes <= 0 || w <= 0 || h <= 0) return hipSuccess;
     if (lo < 0 || hi > 255 || lo > hi || expand < 0 || expand > 1) return hipErrorInvalidValue;
     const int src16 = (uintptr_t)src % 16 == 0 && spitch % 16 == 0 && sfs % 16 == 0;

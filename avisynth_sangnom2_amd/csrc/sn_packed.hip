@@ -311,18 +311,17 @@ static hipError_t launch_packed(hipStream_t st, bool pack, int packing, int byte
     return hipGetLastError();
 }
 
-hipError_t launch_unpack(hipStream_t st, int packing, int bytes, int nframes, const uint8_t* pk, int64_t pk_fs, int pk_pitch, int w, int h, uint8_t* y,
-                         int64_t y_fs, int y_pitch, uint8_t* u, int64_t u_fs, int u_pitch, uint8_t* v, int64_t v_fs, int v_pitch, int line_parity, int ss)
+static PkPlane pk_plane(const PlaneView& p) { return PkPlane{const_cast<uint8_t*>(p.base), p.fs, p.pitch}; }
+
+hipError_t launch_unpack(hipStream_t st, int packing, int bytes, int nframes, PlaneView pk, int w, int h, PlaneViewW y, PlaneViewW u, PlaneViewW v,
+                         int line_parity, int ss)
 {
-    return launch_packed(st, false, packing, bytes, nframes, PkPlane{const_cast<uint8_t*>(pk), pk_fs, pk_pitch}, PkPlane{y, y_fs, y_pitch},
-                         PkPlane{u, u_fs, u_pitch}, PkPlane{v, v_fs, v_pitch}, w, h, line_parity, ss, 0);
+    return launch_packed(st, false, packing, bytes, nframes, pk_plane(pk), pk_plane(y), pk_plane(u), pk_plane(v), w, h, line_parity, ss, 0);
 }
 
-hipError_t launch_pack(hipStream_t st, int packing, int bytes, int nframes, const uint8_t* y, int64_t y_fs, int y_pitch, const uint8_t* u, int64_t u_fs,
-                       int u_pitch, const uint8_t* v, int64_t v_fs, int v_pitch, int w, int h, uint8_t* pk, int64_t pk_fs, int pk_pitch, int ds)
+hipError_t launch_pack(hipStream_t st, int packing, int bytes, int nframes, PlaneView y, PlaneView u, PlaneView v, int w, int h, PlaneViewW pk, int ds)
 {
-    return launch_packed(st, true, packing, bytes, nframes, PkPlane{pk, pk_fs, pk_pitch}, PkPlane{const_cast<uint8_t*>(y), y_fs, y_pitch},
-                         PkPlane{const_cast<uint8_t*>(u), u_fs, u_pitch}, PkPlane{const_cast<uint8_t*>(v), v_fs, v_pitch}, w, h, -1, 0, ds);
+    return launch_packed(st, true, packing, bytes, nframes, pk_plane(pk), pk_plane(y), pk_plane(u), pk_plane(v), w, h, -1, 0, ds);
 }
 
 }  // namespace sn

@@ -149,9 +149,12 @@ static void reduce_launch(hipStream_t st, int kernel, int nframes, const uint8_t
         hipLaunchKernelGGL((k_reduce<T, 2>), grid, dim3(256), 0, st, src, sfs, spitch, w, h, ox, oy, dst, dfs, dpitch, maxv, src16, dst16);
 }
 
-hipError_t launch_reduce(hipStream_t st, int bytes, int bits, int kernel, int nframes, const uint8_t* src, int64_t sfs, int spitch, int w, int h, int ox,
-                         int oy, uint8_t* dst, int64_t dfs, int dpitch)
+hipError_t launch_reduce(hipStream_t st, int bytes, int bits, int kernel, int nframes, PlaneView s, int w, int h, int ox, int oy, PlaneViewW d)
 {
+    const uint8_t* const src = s.base;
+    uint8_t* const dst = d.base;
+    const int64_t sfs = s.fs, dfs = d.fs;
+    const int spitch = s.pitch, dpitch = d.pitch;
     if (nframes <= 0 || w <= 0 || h <= 0) return hipSuccess;
     if (kernel != 1 && kernel != 2) return hipErrorInvalidValue;
     const int src16 = (uintptr_t)src % 16 == 0 && spitch % 16 == 0 && sfs % 16 == 0;

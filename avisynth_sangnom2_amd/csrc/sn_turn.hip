@@ -79,9 +79,12 @@ __global__ void __launch_bounds__(256) k_turn(const uint8_t* src, int64_t sfs, i
     }
 }
 
-hipError_t launch_turn(hipStream_t st, int bytes, int right, int nframes, const uint8_t* src, int64_t sfs, int spitch, int w, int h, uint8_t* dst,
-                       int64_t dfs, int dpitch, int line_parity)
+hipError_t launch_turn(hipStream_t st, int bytes, int right, int nframes, PlaneView s, int w, int h, PlaneViewW d, int line_parity)
 {
+    const uint8_t* const src = s.base;
+    uint8_t* const dst = d.base;
+    const int64_t sfs = s.fs, dfs = d.fs;
+    const int spitch = s.pitch, dpitch = d.pitch;
     if (nframes <= 0 || w <= 0 || h <= 0) return hipSuccess;
     dim3 grid((w + kTile - 1) / kTile, (h + kTile - 1) / kTile, nframes), block(256);
     const int per = 4 / bytes;  // samples per dword: the turned tile must start on a dword of the destination row

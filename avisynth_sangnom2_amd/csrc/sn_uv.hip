@@ -184,29 +184,26 @@ static hipError_t launch_uv(hipStream_t st, bool merge, int bytes, int nframes, 
     return hipGetLastError();
 }
 
-hipError_t launch_uv_split(hipStream_t st, int bytes, int nframes, const uint8_t* uv, int64_t uv_fs, int uv_pitch, int cw, int h, uint8_t* u,
-                           int64_t u_fs, int u_pitch, uint8_t* v, int64_t v_fs, int v_pitch, int line_parity, int ss, int ds)
+static UvPlane uv_plane(const PlaneView& p) { return UvPlane{const_cast<uint8_t*>(p.base), p.fs, p.pitch}; }
+
+hipError_t launch_uv_split(hipStream_t st, int bytes, int nframes, PlaneView uv, int cw, int h, PlaneViewW u, PlaneViewW v, int line_parity, int ss, int ds)
 {
-    return launch_uv(st, false, bytes, nframes, UvPlane{const_cast<uint8_t*>(uv), uv_fs, uv_pitch}, UvPlane{u, u_fs, u_pitch}, UvPlane{v, v_fs, v_pitch}, cw,
-                     h, line_parity, ss, ds);
+    return launch_uv(st, false, bytes, nframes, uv_plane(uv), uv_plane(u), uv_plane(v), cw, h, line_parity, ss, ds);
 }
 
-hipError_t launch_uv_merge(hipStream_t st, int bytes, int nframes, const uint8_t* u, int64_t u_fs, int u_pitch, const uint8_t* v, int64_t v_fs,
-                           int v_pitch, int cw, int h, uint8_t* uv, int64_t uv_fs, int uv_pitch, int ss, int ds)
+hipError_t launch_uv_merge(hipStream_t st, int bytes, int nframes, PlaneView u, PlaneView v, int cw, int h, PlaneViewW uv, int ss, int ds)
 {
-    return launch_uv(st, true, bytes, nframes, UvPlane{uv, uv_fs, uv_pitch}, UvPlane{const_cast<uint8_t*>(u), u_fs, u_pitch},
-                     UvPlane{const_cast<uint8_t*>(v), v_fs, v_pitch}, cw, h, -1, ss, ds);
+    return launch_uv(st, true, bytes, nframes, uv_plane(uv), uv_plane(u), uv_plane(v), cw, h, -1, ss, ds);
 }
 
-hipError_t launch_shift16(hipStream_t st, int nframes, const uint8_t* src, int64_t src_fs, int src_pitch, int w, int h, uint8_t* dst, int64_t dst_fs,
-                          int dst_pitch, int line_parity, int ss, int ds)
+hipError_t launch_shift16(hipStream_t st, int nframes, PlaneView src, int w, int h, PlaneViewW dst, int line_parity, int ss, int ds)
 {
     if (nframes <= 0 || w <= 0 || h <= 0) return hipSuccess;
     if (ss < 0 || ss > 15 || ds < 0 || ds > 15) return hipErrorInvalidValue;
     const int row0 = line_parity < 0 ? 0 : line_parity & 1, rstep = line_parity < 0 ? 1 : 2;
     const int nrows = (h - row0 + rstep - 1) / rstep;
     if (nrows <= 0) return hipSuccess;
-    const UvPlane s{const_cast<uint8_t*>(src), src_fs, src_pitch}, d{dst, dst_fs, dst_pitch};
+    const UvPlane s = uv_plane(src), d = uv_plane(dst);
     const int vec_ok = uv_aligned(s) && uv_aligned(d) ? 1 : 0;
     hipLaunchKernelGGL(k_shift16, uv_grid(vec_ok, w, 8, nrows, nframes), dim3(kUvLanes, kUvRows), 0, st, s, d, w, row0, rstep, nrows, nframes, vec_ok, ss, ds);
     return hipGetLastError();
