@@ -70,7 +70,7 @@ RECORDED = {
 
 
 def _packed(side):
-    return side in ("yuyv", "yuyv_msb", "v210")
+    return side in pc.LAYOUTS
 
 
 def _rows(clip, frames, side, source):
@@ -79,19 +79,19 @@ def _rows(clip, frames, side, source):
         return [np.stack(pc.pack_frames(side, clip, frames, source=source))]
     s = mc.shift_of(clip) if side.endswith("_msb") else 0
     words = (mc.msb_source(frames, s) if source else mc.up(frames, s)) if s else frames
-    if side.startswith("nv16"):
+    if side.startswith("nv"):  # nv16, nv16_msb; nv12
         return [np.stack([fr[0] for fr in words]), np.stack([sc.uv_rows(fr[1], fr[2]) for fr in words])]
     return [np.stack([fr[p] for fr in words]) for p in range(3)]
 
 
 def _up(a):
     import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view({2: np.int16, 4: np.int32}[a.dtype.itemsize])).pin_memory().to(sg._dev())
+    return torch.from_numpy(np.ascontiguousarray(a).view({1: np.uint8, 2: np.int16, 4: np.int32}[a.dtype.itemsize])).pin_memory().to(sg._dev())
 
 
 def _tensors(side, rows):
     """Device tensors over `rows` as process_surfaces takes that side: the UV plane of a semi-planar side as [N, H, Wc, 2]."""
-    if side.startswith("nv16"):
+    if side.startswith("nv"):
         return [rows[0], rows[1].unflatten(2, (rows[1].shape[2] // 2, 2))]
     return rows[0] if _packed(side) else rows
 
@@ -102,7 +102,7 @@ def _guarded(want):
     full, views = [], []
     for a in want:
         n, h, r = a.shape
-        t = torch.empty((n, h, r + GUARD_BYTES // a.dtype.itemsize), dtype={2: torch.int16, 4: torch.int32}[a.dtype.itemsize], device=sg._dev())
+        t = torch.empty((n, h, r + GUARD_BYTES // a.dtype.itemsize), dtype={1: torch.uint8, 2: torch.int16, 4: torch.int32}[a.dtype.itemsize], device=sg._dev())
         t.view(torch.uint8).fill_(GUARD)
         full.append(t)
         views.append(t[:, :, :r])
@@ -110,7 +110,7 @@ def _guarded(want):
 
 
 def _keywords(side):
-    return dict(msb=side.endswith("_msb"), packed=("yuyv" if side.startswith("yuyv") else "v210") if _packed(side) else None)
+    return dict(msb=side.endswith("_msb"), packed=pc.order_of(side) if _packed(side) else None)
 
 
 def walk(name):
