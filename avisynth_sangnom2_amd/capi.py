@@ -33,9 +33,10 @@ EXPORTS = (
     "sn_get_parts_info", "sn_aa_get_parts_info", "sn_debug_set_column_parts",
     "sn_process_device_surfaces", "sn_aa_process_device_surfaces", "sn_get_surface_info", "sn_aa_get_surface_info",
     "sn_aa_get_reduce", "sn_reduce_device", "sn_aa_get_mask", "sn_mask_merge_device",
+    "sn_aa_get_mask_ex", "sn_mask_merge_luma_device",
 )
 # ... and the ones whose names end in a digit
-EXPORTS_NUMBERED = ("sn_aa_create_ex2", "sn_aa_create_ex3")
+EXPORTS_NUMBERED = ("sn_aa_create_ex2", "sn_aa_create_ex3", "sn_aa_create_ex4")
 
 # sn_aa_options.reduce: the anti-aliasing call with dh returns the frame at source size (sangnom_hip.h has the arithmetic)
 SN_AA_REDUCE_NONE, SN_AA_REDUCE_TENT, SN_AA_REDUCE_HALFBAND = 0, 1, 2
@@ -104,6 +105,22 @@ def aa_mask(mask=None, expand=1) -> "SnAAMask":
         return SnAAMask(struct_size=ctypes.sizeof(SnAAMask), kind=SN_AA_MASK_NONE)
     lo, hi = mask
     return SnAAMask(struct_size=ctypes.sizeof(SnAAMask), kind=SN_AA_MASK_SOBEL, lo=int(lo), hi=int(hi), expand=int(expand))
+
+
+# sn_aa_mask_ex.chroma: which mask merges chroma -- the chroma plane's own, or the source luma plane's reduced to chroma's geometry
+SN_AA_MASK_CHROMA_OWN, SN_AA_MASK_CHROMA_LUMA = 0, 1
+MASK_CHROMA = {"own": SN_AA_MASK_CHROMA_OWN, "luma": SN_AA_MASK_CHROMA_LUMA}
+
+
+class SnAAMaskEx(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_int32), ("chroma", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6)]
+
+
+def aa_mask_ex(chroma="own") -> "SnAAMaskEx":
+    """sn_aa_mask_ex: chroma = "own" (every plane through its own mask) or "luma" (chroma through the luma plane's mask)."""
+    if not isinstance(chroma, str) or chroma not in MASK_CHROMA:
+        raise ValueError("mask_chroma must be 'own' or 'luma'")
+    return SnAAMaskEx(struct_size=ctypes.sizeof(SnAAMaskEx), chroma=MASK_CHROMA[chroma])
 
 
 class SnPartsInfo(ctypes.Structure):
@@ -211,6 +228,11 @@ def load():
     L.sn_aa_create_ex3.argtypes = [ctypes.POINTER(SnConfig), ctypes.POINTER(SnPolicy), ctypes.POINTER(SnOptions), ctypes.POINTER(SnAAOptions),
                                    ctypes.POINTER(SnAAMask), ctypes.POINTER(vp)]
     L.sn_aa_get_mask.argtypes = [vp, ctypes.POINTER(SnAAMask)]
+    L.sn_aa_create_ex4.argtypes = [ctypes.POINTER(SnConfig), ctypes.POINTER(SnPolicy), ctypes.POINTER(SnOptions), ctypes.POINTER(SnAAOptions),
+                                   ctypes.POINTER(SnAAMask), ctypes.POINTER(SnAAMaskEx), ctypes.POINTER(vp)]
+    L.sn_aa_get_mask_ex.argtypes = [vp, ctypes.POINTER(SnAAMaskEx)]
+    L.sn_mask_merge_luma_device.argtypes = [vp, ctypes.POINTER(SnAAMask), i32, vp, i64, i32, i32, i32, p3v, p3l, p3i, p3v, p3l, p3i, i32, i32,
+                                            p3v, p3l, p3i]
     L.sn_mask_merge_device.argtypes = [vp, ctypes.POINTER(SnAAMask), i32, vp, i64, i32, vp, i64, i32, i32, i32, vp, i64, i32]
     L.sn_aa_get_reduce.argtypes = [vp]
     L.sn_reduce_device.argtypes = [vp, i32, i32, vp, i64, i32, i32, i32, i32, i32, vp, i64, i32]

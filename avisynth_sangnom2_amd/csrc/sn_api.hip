@@ -2559,6 +2559,45 @@ int sn_mask_merge_device(sn_context* h, const sn_aa_mask* mask, int32_t nframes,
     return SN_OK;
 }
 
+int sn_mask_merge_luma_device(sn_context* h, const sn_aa_mask* mask, int32_t nframes, const void* luma, int64_t lfs, int32_t lp, int32_t sub_w, int32_t sub_h,
+                              const void* const src[2], const int64_t sfs[2], const int32_t sp[2], const void* const aa[2], const int64_t afs[2],
+                              const int32_t ap[2], int32_t width, int32_t height, void* const dst[2], const int64_t dfs[2], const int32_t dp[2])
+{
+    Context* c = reinterpret_cast<Context*>(h);
+    if (!c) return sn::fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    const int B = c->cfg.bytes_per_sample;
+    if (!mask) return sn::fail(c, SN_ERR_INVALID_ARG, "sn_mask_merge_luma_device: mask is NULL");
+    const std::string problem = mask_problem(mask);
+    if (!problem.empty()) return sn::fail(c, SN_ERR_INVALID_ARG, ("sn_mask_merge_luma_device: " + problem).c_str());
+    if (mask->kind != SN_AA_MASK_SOBEL) return sn::fail(c, SN_ERR_INVALID_ARG, "sn_mask_merge_luma_device: sn_aa_mask.kind must be 1 (Sobel)");
+    if (sub_w < 0 || sub_w > 2 || sub_h < 0 || sub_h > 2) return sn::fail(c, SN_ERR_INVALID_ARG, "sn_mask_merge_luma_device: sub_w and sub_h must be 0..2");
+    if (!luma || !src || !sfs || !sp || !dst || !dfs || !dp || !src[0] || !dst[0] || nframes < 0 || width <= 0 || height <= 0 ||
+        width > INT32_MAX / 32 || height > INT32_MAX / 8)
+        return sn::fail(c, SN_ERR_INVALID_ARG, "sn_mask_merge_luma_device: bad pointer or size");
+    const int planes = src[1] ? 2 : 1;
+    const bool merge = aa && aa[0];
+    if (merge && (!afs || !ap)) return sn::fail(c, SN_ERR_INVALID_ARG, "sn_mask_merge_luma_device: bad pointer or size");
+    if (planes == 1 ? dst[1] || (aa && aa[1]) : !dst[1] || (aa && !aa[0] != !aa[1]))
+        return sn::fail(c, SN_ERR_INVALID_ARG, "sn_mask_merge_luma_device: src[1], aa[1] and dst[1] must be given together (aa: all planes or none)");
+    bool bad = lp < (width << sub_w) * B || lp % B || lfs % B || (uintptr_t)luma % B;
+    for (int p = 0; p < planes; ++p) {
+        bad = bad || sp[p] < width * B || dp[p] < width * B || sp[p] % B || dp[p] % B || sfs[p] % B || dfs[p] % B || (uintptr_t)src[p] % B ||
+              (uintptr_t)dst[p] % B || (merge && (ap[p] < width * B || ap[p] % B || afs[p] % B || (uintptr_t)aa[p] % B));
+    }
+    if (bad) return sn::fail(c, SN_ERR_INVALID_ARG, "sn_mask_merge_luma_device: pitch smaller than the row or misaligned");
+    sn::PlaneView s[2], a[2];
+    sn::PlaneViewW d[2];
+    for (int p = 0; p < planes; ++p) {
+        s[p] = sn::PlaneView{static_cast<const uint8_t*>(src[p]), sfs[p], sp[p]};
+        if (merge) a[p] = sn::PlaneView{static_cast<const uint8_t*>(aa[p]), afs[p], ap[p]};
+        d[p] = sn::PlaneViewW{static_cast<uint8_t*>(dst[p]), dfs[p], dp[p]};
+    }
+    SN_HIP(c, hipSetDevice(c->device));
+    SN_HIP(c, sn::launch_mask_merge_luma(c->stream, B, c->cfg.bits_per_sample, mask->lo, mask->hi, mask->expand, nframes,
+                                         sn::PlaneView{static_cast<const uint8_t*>(luma), lfs, lp}, sub_w, sub_h, planes, s, a, width, height, d));
+    return SN_OK;
+}
+
 int sn_synchronize(sn_context* h)
 {
     Context* c = reinterpret_cast<Context*>(h);
@@ -2760,6 +2799,7 @@ struct sn_aa_context {
     int64_t t2bytes[3] = {0, 0, 0};
     int reduce = SN_AA_REDUCE_NONE;                        // dh only: the second pass's output goes through sn_reduce.hip on its way out
     sn_aa_mask mask{};                                     // kind != 0: the result is merged into the source through an edge mask (sn_mask.hip), last
+    int mask_chroma = SN_AA_MASK_CHROMA_OWN;               // ... SN_AA_MASK_CHROMA_LUMA: planes 1 and 2 through the source luma plane's mask
     int dstw[3] = {0, 0, 0}, dsth[3] = {0, 0, 0};          // the destination's geometry per plane: ow x oh, with reduce w x h
     int dstpitch[3] = {0, 0, 0};                           // ... of the library's own buffers of that geometry (host groups)
     int64_t dstbytes[3] = {0, 0, 0};
@@ -2895,6 +2935,12 @@ int sn_aa_create_ex2(const sn_config* cfg, const sn_policy* policy, const sn_opt
 int sn_aa_create_ex3(const sn_config* cfg, const sn_policy* policy, const sn_options* options, const sn_aa_options* aa_options, const sn_aa_mask* mask,
                      sn_aa_context** out)
 {
+    return sn_aa_create_ex4(cfg, policy, options, aa_options, mask, nullptr, out);
+}
+
+int sn_aa_create_ex4(const sn_config* cfg, const sn_policy* policy, const sn_options* options, const sn_aa_options* aa_options, const sn_aa_mask* mask,
+                     const sn_aa_mask_ex* mask_ex, sn_aa_context** out)
+{
     auto fail_aa = [](sn_aa_context* a, int code, const std::string& msg) {
         g_aa_error = msg;
         if (a) sn_aa_destroy(a);
@@ -2924,11 +2970,26 @@ int sn_aa_create_ex3(const sn_config* cfg, const sn_policy* policy, const sn_opt
     }
     if (use_mask.kind && cfg->dh && !reduce)
         return fail_aa(nullptr, SN_ERR_CONFIG, "SangNomAA: mask needs the frame at source size (dh=false, or dh=true with reduce)");
+    int mask_chroma = SN_AA_MASK_CHROMA_OWN;
+    if (mask_ex) {
+        if (mask_ex->struct_size != (int32_t)sizeof(sn_aa_mask_ex)) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_aa_mask_ex.struct_size mismatch");
+        if (use_mask.kind) {  // without a mask the fields below are ignored
+            if (mask_ex->chroma < SN_AA_MASK_CHROMA_OWN || mask_ex->chroma > SN_AA_MASK_CHROMA_LUMA)
+                return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_aa_mask_ex.chroma must be 0 (own) or 1 (luma)");
+            for (int32_t r : mask_ex->reserved)
+                if (r) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_aa_mask_ex.reserved must be zero");
+            mask_chroma = mask_ex->chroma;
+        }
+    }
+    // the source luma plane reaches the device only where it is processed (the host routes upload no other plane)
+    if (mask_chroma == SN_AA_MASK_CHROMA_LUMA && cfg->num_planes >= 3 && !cfg->dh && !cfg->luma && cfg->chroma)
+        return fail_aa(nullptr, SN_ERR_CONFIG, "SangNomAA: a luma-derived chroma mask needs luma processed (luma=true)");
     sn_aa_context* a = new (std::nothrow) sn_aa_context();
     if (!a) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "out of host memory");
     a->cfg = *cfg;
     a->reduce = reduce;
     a->mask = use_mask;
+    a->mask_chroma = mask_chroma;
     a->max_batch = cfg->max_batch > 1 ? cfg->max_batch : 1;
     // the ring: two groups, so that one group uploads while the other is worked on; a group's frames are one batch
     a->depth = cfg->host_depth > 0 ? cfg->host_depth : 4;
@@ -3034,7 +3095,15 @@ static int aa_run(sn_aa_context* a, int n, const sn::PlaneView src[3], const sn:
         // the edge mask, last: the chunk's result is merged into the source through the source's own mask, in place on the
         // destination (which has the source's size: creation has seen to it); one launch per processed plane
         auto masked = [&]() -> int {
-            for (int p = 0; p < a->planes && a->mask.kind; ++p) {
+            // chroma through the source luma plane's mask: U and V in one launch
+            const bool by_luma = a->mask.kind && a->mask_chroma == SN_AA_MASK_CHROMA_LUMA && a->planes == 3 && a->process[1];
+            if (by_luma) {
+                const sn::PlaneView cs[2] = {src[1].at(f0), src[2].at(f0)}, ca[2] = {dst[1].at(f0), dst[2].at(f0)};
+                const sn::PlaneViewW cd[2] = {dst[1].at(f0), dst[2].at(f0)};
+                SN_AA_HIP(sn::launch_mask_merge_luma(st, B, a->cfg.bits_per_sample, a->mask.lo, a->mask.hi, a->mask.expand, m, src[0].at(f0), a->cfg.sub_w,
+                                                     a->cfg.sub_h, 2, cs, ca, a->w[1], a->h[1], cd));
+            }
+            for (int p = 0; p < (by_luma ? 1 : a->planes) && a->mask.kind; ++p) {
                 if (!a->process[p]) continue;
                 SN_AA_HIP(sn::launch_mask_merge(st, B, a->cfg.bits_per_sample, a->mask.lo, a->mask.hi, a->mask.expand, m, src[p].at(f0), dst[p].at(f0),
                                                 a->w[p], a->h[p], dst[p].at(f0)));
@@ -3178,6 +3247,17 @@ int sn_aa_get_mask(sn_aa_context* a, sn_aa_mask* out)
     if (!a) return aa_fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
     if (!out || out->struct_size != (int32_t)sizeof(sn_aa_mask)) return aa_fail(a, SN_ERR_INVALID_ARG, "out is NULL or sn_aa_mask.struct_size mismatch");
     *out = a->mask;
+    return SN_OK;
+}
+
+int sn_aa_get_mask_ex(sn_aa_context* a, sn_aa_mask_ex* out)
+{
+    if (!a) return aa_fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    if (!out || out->struct_size != (int32_t)sizeof(sn_aa_mask_ex))
+        return aa_fail(a, SN_ERR_INVALID_ARG, "out is NULL or sn_aa_mask_ex.struct_size mismatch");
+    *out = sn_aa_mask_ex{};
+    out->struct_size = (int32_t)sizeof(sn_aa_mask_ex);
+    out->chroma = a->mask_chroma;
     return SN_OK;
 }
 

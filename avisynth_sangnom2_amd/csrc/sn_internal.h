@@ -95,6 +95,11 @@ hipError_t launch_reduce(hipStream_t s, int bytes, int bits, int kernel, int nfr
 // dst is the mask itself.  dst may be the plane aa lies in (same base, pitch and frame stride); src must not overlap dst.
 hipError_t launch_mask_merge(hipStream_t s, int bytes, int bits, int lo, int hi, int expand, int nframes, PlaneView src, PlaneView aa, int w, int h,
                              PlaneViewW dst);
+// ... and `planes` (1 or 2) chroma planes of w x h merged through the mask of the luma plane above them, (w << sub_w) x
+// (h << sub_h), reduced to chroma's geometry by the block mean (sangnom_hip.h, "Edge mask": mc).  aa[p].base == nullptr (all
+// planes or none): dst is the reduced mask.  dst[p] may be the plane aa[p] lies in; luma and src must not overlap dst.
+hipError_t launch_mask_merge_luma(hipStream_t s, int bytes, int bits, int lo, int hi, int expand, int nframes, PlaneView luma, int sub_w, int sub_h,
+                                  int planes, const PlaneView src[2], const PlaneView aa[2], int w, int h, const PlaneViewW dst[2]);
 
 // sn_uv.hip: semi-planar chroma (a UV plane of U,V sample pairs: NV12 / P016 / NV16 / NV24) <-> a U and a V plane of cw x h
 // samples each.  line_parity 0 / 1: only the lines of that parity are read and written (the lines the pass that follows

@@ -328,6 +328,36 @@ class SangNom2:
                                                    W, H, dst.data_ptr(), dst.stride(0) * B, dst.stride(1) * B))
         return dst
 
+    def mask_merge_luma(self, luma, src, aa, dst, lo: int, hi: int, expand: int = 1, sub_w: int = 1, sub_h: int = 1):
+        """sn_mask_merge_luma_device: the Sobel edge mask of luma [N, H << sub_h, W << sub_w], reduced to chroma's geometry
+        by the block mean, merges aa into src.  src, aa and dst are one tensor [N, H, W] or a pair of them (U and V in one
+        launch); aa=None: dst is the reduced mask itself.  dst may be aa.  Torch tensors on the device; asynchronous on the
+        context's stream."""
+        B = self.clip.bytes
+        as_pair = lambda t: list(t) if isinstance(t, (list, tuple)) else [t]
+        s, d = as_pair(src), as_pair(dst)
+        a = None if aa is None else as_pair(aa)
+        N, H, W = d[0].shape
+        if len(s) not in (1, 2) or len(d) != len(s) or (a is not None and len(a) != len(s)):
+            raise ValueError("mask_merge_luma: src, aa and dst must be one tensor each or pairs of the same length")
+        for t in s + d + (a or []):
+            if tuple(t.shape) != (N, H, W) or t.stride(2) != 1 or t.element_size() != B:
+                raise ValueError("mask_merge_luma: src, aa and dst must be [N, H, W], x-contiguous and of the clip's sample type")
+        if tuple(luma.shape) != (N, H << sub_h, W << sub_w) or luma.stride(2) != 1 or luma.element_size() != B:
+            raise ValueError("mask_merge_luma: luma must be [N, H << sub_h, W << sub_w], x-contiguous and of the clip's sample type")
+
+        def arrays(ts):
+            ptr, fs, pitch = (ctypes.c_void_p * 2)(), (ctypes.c_int64 * 2)(), (ctypes.c_int32 * 2)()
+            for p, t in enumerate(ts):
+                ptr[p], fs[p], pitch[p] = t.data_ptr(), t.stride(0) * B, t.stride(1) * B
+            return ptr, fs, pitch
+        m = capi.aa_mask((lo, hi), expand)
+        sa, da = arrays(s), arrays(d)
+        aaa = (None, None, None) if a is None else arrays(a)
+        self._check(self._lib.sn_mask_merge_luma_device(self._h, ctypes.byref(m), N, luma.data_ptr(), luma.stride(0) * B, luma.stride(1) * B,
+                                                        int(sub_w), int(sub_h), *sa, *aaa, W, H, *da))
+        return dst
+
     def get_frame_device(self, src, dst, parity: int = 1):
         """Device planes: torch tensors [H, W] on this context's GPU.  Asynchronous."""
         return self.process_batch([s.unsqueeze(0) for s in src], [d.unsqueeze(0) for d in dst], [parity])
@@ -414,12 +444,14 @@ class _AAContext:
     reduce="tent" | "halfband" (with dh): the enlarged frame is reduced on the device by that kernel, centred on the source
     samples (sangnom_hip.h has the arithmetic), and every destination plane has the source plane's shape again.
     mask=(lo, hi), mask_expand=0 | 1 (without dh, or with dh and reduce): the result is merged into the source through a Sobel
-    edge mask of the source (sangnom_hip.h, "Edge mask"): flat areas and texture keep the source's samples."""
+    edge mask of the source (sangnom_hip.h, "Edge mask"): flat areas and texture keep the source's samples.
+    mask_chroma="own" | "luma": every processed plane through its own mask (the default), or chroma through the mask of the
+    source luma plane reduced to chroma's geometry, as anti-aliasing scripts do."""
 
     def __init__(self, clip: ClipFormat, order: int = 1, aa: int = 48, aac: int = 0, luma: bool = True, chroma: bool = True,
                  device: int = 0, isolated_planes: bool = False, fresh_pool: bool = False, opt: int = -1, max_batch: int = 1,
                  host_depth: int = 0, stream: int | None = None, dh: bool = False, column_parts: int = 0, reduce=0, mask=None, mask_expand: int = 1,
-                 **policy_kw):
+                 mask_chroma="own", **policy_kw):
         if opt < -1 or opt > 1:
             raise SangNomError(capi.SN_ERR_CONFIG, "SangNom2: opt must be between -1..2.")  # sic, SangNom2.cpp:420
         self.clip = clip
@@ -427,6 +459,7 @@ class _AAContext:
         aopts = capi.aa_options(reduce)  # reduce="tent" | "halfband" (dh only): the frame comes back at source size
         self.reduce = aopts.reduce
         amask = capi.aa_mask(mask, mask_expand)  # mask=(lo, hi): the result goes into the source through the source's edge mask
+        amask_ex = capi.aa_mask_ex(mask_chroma)
         self.max_batch = max_batch
         self._lib = capi.load()
         cfg = capi.SnConfig(
@@ -437,8 +470,8 @@ class _AAContext:
         self._h = ctypes.c_void_p()
         pol = capi.policy(**{k: policy_kw.get(k) for k in ("small_launches", "chain", "copy_threads", "scratch_budget_mb", "chroma_sweeps", "sse2_sweeps")})
         opts = capi.options(capi.arithmetic_of_opt(opt), column_parts=column_parts)
-        rc = self._lib.sn_aa_create_ex3(ctypes.byref(cfg), ctypes.byref(pol), ctypes.byref(opts), ctypes.byref(aopts), ctypes.byref(amask),
-                                        ctypes.byref(self._h))
+        rc = self._lib.sn_aa_create_ex4(ctypes.byref(cfg), ctypes.byref(pol), ctypes.byref(opts), ctypes.byref(aopts), ctypes.byref(amask),
+                                        ctypes.byref(amask_ex), ctypes.byref(self._h))
         if rc != capi.SN_OK:
             self._h = None
             raise SangNomError(rc, self._lib.sn_aa_last_error(None).decode())
@@ -485,6 +518,13 @@ class _AAContext:
         """sn_aa_get_mask: the edge mask of this context (kind 0 when there is none)."""
         m = capi.SnAAMask(struct_size=ctypes.sizeof(capi.SnAAMask))
         self._check(self._lib.sn_aa_get_mask(self._h, ctypes.byref(m)))
+        return m
+
+    @property
+    def mask_ex(self) -> capi.SnAAMaskEx:
+        """sn_aa_get_mask_ex: which mask merges chroma in this context."""
+        m = capi.SnAAMaskEx(struct_size=ctypes.sizeof(capi.SnAAMaskEx))
+        self._check(self._lib.sn_aa_get_mask_ex(self._h, ctypes.byref(m)))
         return m
 
     def info(self, pass_: int) -> capi.SnInfo:

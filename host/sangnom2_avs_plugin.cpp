@@ -105,7 +105,8 @@ AVSValue __cdecl Create_SangNom2HIP(AVSValue args, void*, IScriptEnvironment* en
 // device and the clip keeps its size: a drop-in anti-aliaser.  Reduce without dh: "SangNomAA: reduce needs dh=true".
 // mask=true (at source size: no dh, or dh with reduce): the result is merged into the source through a Sobel edge mask of the
 // source, thresholds mlo <= mhi (0..255, defaults 8 and 32) and mexpand (0 | 1, default 1); the defaults are starting values
-// that nobody has tuned on real footage.
+// that nobody has tuned on real footage.  mluma=true: chroma is merged through the luma plane's mask (reduced to chroma's
+// geometry) instead of its own, as anti-aliasing scripts do; needs luma=true.
 class SangNomAA : public GenericVideoFilter {
     sangnom::AAFilter<AvsHost> impl_;
 
@@ -137,6 +138,7 @@ AVSValue __cdecl Create_SangNomAA(AVSValue args, void*, IScriptEnvironment* env)
     a.mask_lo = args[14].AsInt(8);
     a.mask_hi = args[15].AsInt(32);
     a.mask_expand = args[16].AsInt(1);
+    a.mask_luma = args[17].AsBool(false);
     return new SangNomAA(args[0].AsClip(), a, env);
 }
 
@@ -160,7 +162,7 @@ extern "C" __declspec(dllexport) const char* __stdcall AvisynthPluginInit3(IScri
     env->AddFunction("SangNom", "c[order]i[aa]i[opt]i", Create_SangNom, 0);                                        // :482
     env->AddFunction("SangNom2HIP", "c[order]i[aa]i[aac]i[threads]i[dh]b[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i[device]i",
                      Create_SangNom2HIP, 0);
-    env->AddFunction("SangNomAA", "c[order]i[aa]i[aac]i[device]i[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i[dh]b[reduce]i[mask]b[mlo]i[mhi]i[mexpand]i",
+    env->AddFunction("SangNomAA", "c[order]i[aa]i[aac]i[device]i[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i[dh]b[reduce]i[mask]b[mlo]i[mhi]i[mexpand]i[mluma]b",
                      Create_SangNomAA, 0);
     return "SangNom2";
 }

@@ -41,6 +41,7 @@ struct Args {  // SangNom2(clip, order, aa, aac, threads, dh, luma, chroma, opt)
     int reduce = 0;         // SangNomAA only, with dh: SN_AA_REDUCE_TENT / SN_AA_REDUCE_HALFBAND, the frame comes back at source size
     bool mask = false;      // SangNomAA only, at source size: the result is merged into the source through the source's Sobel edge mask
     int mask_lo = 8, mask_hi = 32, mask_expand = 1;  // ... sn_aa_mask.lo / hi / expand; starting values, not tuned on real footage
+    bool mask_luma = false;  // ... chroma through the source luma plane's mask (sn_aa_mask_ex.chroma = SN_AA_MASK_CHROMA_LUMA), as the scripts do
     int column_parts = -1;  // sn_options.column_parts (16-bit / float planes wider than 3840 in column parts); -1: $SANGNOM_COLUMN_PARTS or 0
     sn_policy policy{};     // scheduling only (sangnom_hip.h); zeros = the defaults
 };
@@ -249,7 +250,8 @@ private:
 // anti-aliaser --, a frame of source size comes down, and the alpha passes through 1:1.
 // With Args::mask (the clip at source size: no dh, or dh with reduce) the library merges the result into the source through
 // a Sobel edge mask of the source (sangnom_hip.h, "Edge mask"; mask_lo <= mask_hi in 0..255, mask_expand 0 or 1), which is
-// what the anti-aliasing scripts do behind the filter: flat areas and texture keep the source's samples.
+// what the anti-aliasing scripts do behind the filter: flat areas and texture keep the source's samples.  Args::mask_luma
+// merges chroma through the luma plane's mask reduced to chroma's geometry instead of chroma's own (needs luma processed).
 template <class Host>
 class AAFilter {
 public:
@@ -275,6 +277,8 @@ public:
             if (a.mask_lo > a.mask_hi) env->ThrowError("%s: sn_aa_mask.lo must not be above sn_aa_mask.hi", name);
             if (a.mask_expand < 0 || a.mask_expand > 1) env->ThrowError("%s: sn_aa_mask.expand must be 0 or 1", name);
             if (a.dh && !a.reduce) env->ThrowError("%s: mask needs the frame at source size (dh=false, or dh=true with reduce)", name);
+            if (a.mask_luma && Host::NumComponents(vi_) >= 3 && !a.dh && !a.luma && a.chroma)
+                env->ThrowError("%s: a luma-derived chroma mask needs luma processed (luma=true)", name);
         }
         sn_config c{};
         c.struct_size = (int32_t)sizeof c;
@@ -314,7 +318,10 @@ public:
         mask.struct_size = (int32_t)sizeof mask;
         mask.kind = a.mask ? SN_AA_MASK_SOBEL : SN_AA_MASK_NONE;
         mask.lo = a.mask_lo, mask.hi = a.mask_hi, mask.expand = a.mask_expand;
-        if (sn_aa_create_ex3(&c, &pol, &opts, &aopts, &mask, &ctx_) != SN_OK) env->ThrowError("%s: %s", name, sn_aa_last_error(nullptr));
+        sn_aa_mask_ex mask_ex{};
+        mask_ex.struct_size = (int32_t)sizeof mask_ex;
+        mask_ex.chroma = a.mask_luma ? SN_AA_MASK_CHROMA_LUMA : SN_AA_MASK_CHROMA_OWN;
+        if (sn_aa_create_ex4(&c, &pol, &opts, &aopts, &mask, &mask_ex, &ctx_) != SN_OK) env->ThrowError("%s: %s", name, sn_aa_last_error(nullptr));
         enlarged_ = a.dh && !a.reduce;
         if (enlarged_) {  // each pass doubles the height of what it is given: the clip comes out twice as wide and twice as high
             Host::SetWidth(vi_, Host::Width(vi_) * 2);

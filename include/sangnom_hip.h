@@ -332,6 +332,32 @@ int sn_mask_merge_device(sn_context* ctx, const sn_aa_mask* mask, int32_t nframe
                          const void* aa /* NULL: write the mask */, int64_t aa_frame_stride, int32_t aa_pitch, int32_t width, int32_t height,
                          void* dst, int64_t dst_frame_stride, int32_t dst_pitch);
 
+/* Which mask merges chroma in the anti-aliasing call (below: "Edge mask", the paragraph on mc).  SN_AA_MASK_CHROMA_OWN: every
+ * processed plane through the mask of its own source (the default, and what a context made without this struct does).
+ * SN_AA_MASK_CHROMA_LUMA: planes 1 and 2 through the mask of the source LUMA plane, reduced to chroma's geometry. */
+enum { SN_AA_MASK_CHROMA_OWN = 0, SN_AA_MASK_CHROMA_LUMA = 1 };
+typedef struct sn_aa_mask_ex {
+    int32_t struct_size; /* sizeof(sn_aa_mask_ex) */
+    int32_t chroma;      /* SN_AA_MASK_CHROMA_* */
+    int32_t reserved[6]; /* zero */
+} sn_aa_mask_ex;         /* 32 bytes */
+
+/* The luma-derived chroma merge on its own: `nframes` frames on the context's stream.  The mask m_L is built from `luma`,
+ * (width << sub_w) x (height << sub_h) samples, reduced to mc (see "Edge mask") and merges aa[p] into src[p] for one or two
+ * chroma planes of width x height samples in one launch: src[1] == NULL means one plane, and then dst[1] and aa[1] must be
+ * NULL too.  aa == NULL or every entry of it NULL: dst[p] is the reduced mask itself, integers (mc * (2^bits - 1) + 128) >> 8,
+ * float (float)mc * 0.00390625f; with two planes aa[0] and aa[1] are both given or both NULL.  sub_w, sub_h: 0..2.  mask is
+ * checked as sn_mask_merge_device checks it; sample type and bit depth come from the context.  dst[p] may be the very plane
+ * aa[p] lies in; luma and src must not overlap dst.  Pitches >= the row; pointers, pitches and frame strides multiples of the
+ * sample size (multiples of 16 on a side -- luma, or src, aa or dst of one plane: 16 bytes per lane and access on that side).
+ * Nothing beyond width samples of a destination row is written.  A refused call queues nothing. */
+int sn_mask_merge_luma_device(sn_context* ctx, const sn_aa_mask* mask, int32_t nframes, const void* luma, int64_t luma_frame_stride,
+                              int32_t luma_pitch, int32_t sub_w, int32_t sub_h, const void* const src[2], const int64_t src_frame_stride[2],
+                              const int32_t src_pitch[2], const void* const aa[2] /* NULL, or both entries NULL: write the mask */,
+                              const int64_t aa_frame_stride[2], const int32_t aa_pitch[2], int32_t width,
+                              int32_t height /* of a chroma plane; luma is (width << sub_w) x (height << sub_h) */, void* const dst[2],
+                              const int64_t dst_frame_stride[2], const int32_t dst_pitch[2]);
+
 /* The anti-aliasing idiom TurnLeft().SangNom2(order, aa, aac).TurnRight().SangNom2(order, aa, aac) as ONE call with
  * host planes (README.md:3 of the reference: "mainly used in anti-aliasing scripts"): the frame
  * crosses PCIe once each way and stays on the device between the two passes (two filter instances -- one for the
@@ -412,7 +438,24 @@ int sn_mask_merge_device(sn_context* ctx, const sn_aa_mask* mask, int32_t nframe
  *       (k only when hi > lo)
  *     m0 = 0 if !(e > Tlo) (a NaN keeps the source);  256 else if e >= Thi;  else min(256, (int)((e - Tlo) * k)) (truncation)
  *     m as above
- *     out = S if m == 0;  R if m == 256;  else S + (R - S) * ((float)m * 0.00390625f) */
+ *     out = S if m == 0;  R if m == 256;  else S + (R - S) * ((float)m * 0.00390625f)
+ *   Chroma through the luma plane's mask (sn_aa_create_ex4 with sn_aa_mask_ex.chroma = SN_AA_MASK_CHROMA_LUMA; opt-in): what
+ *   the scripts do that the mask was modelled on -- one mask from luma merges all three planes, chroma through the mask scaled
+ *   to chroma's geometry.  Plane 0 is merged as above.  L is the SOURCE luma plane, Wl x Hl, and m_L the m above computed on
+ *   L at luma resolution with the call's lo, hi, expand and the clip's bit depth (float: the float rules, NaN included).
+ *   For a chroma plane of W x H samples with Wl = W << sw and Hl = H << sh (sw, sh in 0..2) and n = sw + sh:
+ *     mc(y, x) = (sum_{j < 2^sh} sum_{i < 2^sw} m_L[(y << sh) + j][(x << sw) + i] + ((1 << n) >> 1)) >> n
+ *   all in signed 32-bit (the sum is at most 16 * 256); for n = 0, mc = m_L.  A block of zeros gives 0 exactly and a block of
+ *   256 gives 256 exactly, so "m = 0 gives S, m = 256 gives R" still holds.  out is the merge formula above (integer and
+ *   float) with S = the chroma source, R = the chroma result and m = mc.  Where the mask itself is written
+ *   (sn_mask_merge_luma_device with aa == NULL) it is mc through the rule of sn_mask_merge_device: integers
+ *   (mc * (2^bits - 1) + 128) >> 8, float (float)mc * 0.00390625f.  The block mean places a chroma sample at the centre of its
+ *   block of luma samples; for left-sited (MPEG-2) chroma that is a quarter of a luma pixel off horizontally.  No siting option
+ *   is offered.  These pixels are the library's own too: neither the reference nor masktools defines them.
+ *   Rules of the call: planes 1 and 2, where processed, are merged through mc; a Y clip accepts the option and it has no
+ *   effect; chroma = 0 without dh copies chroma as without a mask; cfg.luma == 0 without dh and with chroma != 0 is refused
+ *   before a device is touched, SN_ERR_CONFIG "SangNomAA: a luma-derived chroma mask needs luma processed (luma=true)" (the
+ *   host routes never upload a plane that is not processed).  No scratch is added and neither pass changes. */
 enum { SN_AA_REDUCE_NONE = 0, SN_AA_REDUCE_TENT = 1, SN_AA_REDUCE_HALFBAND = 2 };
 typedef struct sn_aa_options {
     int32_t struct_size; /* sizeof(sn_aa_options) */
@@ -434,6 +477,12 @@ int sn_aa_get_reduce(sn_aa_context* ctx); /* SN_AA_REDUCE_* of a live context; -
 int sn_aa_create_ex3(const sn_config* cfg, const sn_policy* policy, const sn_options* options, const sn_aa_options* aa_options /* NULL = defaults */,
                      const sn_aa_mask* mask /* NULL = none */, sn_aa_context** out);
 int sn_aa_get_mask(sn_aa_context* ctx, sn_aa_mask* out /* struct_size set by the caller */); /* kind 0 when there is none */
+/* sn_aa_create_ex3 is sn_aa_create_ex4 with mask_ex = NULL (the defaults: every plane through its own mask).  A bad
+ * struct_size, a chroma outside 0..1 or a non-zero reserved word: SN_ERR_INVALID_ARG, naming sn_aa_mask_ex.<field>; with
+ * mask == NULL or kind = SN_AA_MASK_NONE only struct_size of mask_ex is looked at. */
+int sn_aa_create_ex4(const sn_config* cfg, const sn_policy* policy, const sn_options* options, const sn_aa_options* aa_options /* NULL = defaults */,
+                     const sn_aa_mask* mask /* NULL = none */, const sn_aa_mask_ex* mask_ex /* NULL = defaults */, sn_aa_context** out);
+int sn_aa_get_mask_ex(sn_aa_context* ctx, sn_aa_mask_ex* out /* struct_size set by the caller */); /* chroma 0 when there is no mask */
 int sn_aa_process_host(sn_aa_context* ctx, const void* const src[3], const int32_t src_pitch[3], void* const dst[3],
                        const int32_t dst_pitch[3], int32_t parity);
 const char* sn_aa_last_error(const sn_aa_context* ctx); /* ctx == NULL: last failed sn_aa_create on this thread */

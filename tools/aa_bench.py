@@ -9,7 +9,9 @@ alone (sn_reduce_device, both tap sets) against the turn kernel on the same 2W x
 SOURCE size; any of Y8 / Y16 / Y32.  --mask lo,hi[,expand] (at source size: without --dh, or with --reduce): the call with
 the edge mask next to the call without it, in one run (device batches and --host).  --mask-bw: the mask kernel alone
 (sn_mask_merge_device, on noise -- every sample of the result is read -- and on a constant plane -- none is) against the
-half-band reduce kernel that writes the same plane, alternating; any of Y8 / Y16 / Y32.
+half-band reduce kernel that writes the same plane, alternating; any of Y8 / Y16 / Y32 -- and the luma-derived chroma merge
+of a 4:2:0 frame of that size (sn_mask_merge_luma_device: U and V in one launch, in two launches) against the two own-mask
+merges of the same chroma planes.  --mask-chroma luma (with --mask): the masked call merges chroma through luma's mask.
 usage: python tools/aa_bench.py [--frames 512] [--fresh 1] [--fmt Y8] [--size 3840x2160] [--dh [--composed]] [--reduce K] [--host [--depth 8]]
        python tools/aa_bench.py --reduce-bw [--fmt Y16] [--size 1920x1080] [--frames 64]
        python tools/aa_bench.py --mask 8,32,1 [--reduce halfband] [--size 1920x1080] [--host]
@@ -178,6 +180,44 @@ def mask_bandwidth(clip, a):
             out[k + "_us_per_frame"] = round(1e6 * t[len(t) // 2] / N, 2)
             out[k + "_GBps"] = round(moved / t[len(t) // 2] / 1e9, 1)
             out[k + "_us_min_max"] = [round(1e6 * t[0] / N, 2), round(1e6 * t[-1] / N, 2)]
+    out.update(luma_merge_times(clip, a, dev, dt, noise))
+    return out
+
+
+def luma_merge_times(clip, a, dev, dt, noise):
+    """The chroma merge of a 4:2:0 frame whose luma plane is --size, in place on the result as the call uses it, expand 1, on
+    noise: U and V through luma's mask in one launch (4 + 6 chroma-plane units of bytes: luma read, S and R read and dst
+    written twice), in two launches (14 units), and the two own-mask merges (6 units); alternating, microseconds per frame."""
+    N, W, H, B = a.frames, clip.width, clip.height, clip.bytes
+    lo, hi, _ = a.mask_values
+    L = noise(H, W)
+    S, R = [noise(H // 2, W // 2) for _ in range(2)], [noise(H // 2, W // 2) for _ in range(2)]
+    unit = N * (W // 2) * (H // 2) * B
+    out = {}
+    with SangNom2(clip, max_batch=1) as flt:
+        def two():
+            for p in range(2):
+                flt.mask_merge_luma(L, S[p], R[p], R[p], lo, hi, 1)
+
+        def own():
+            for p in range(2):
+                flt.mask_merge(S[p], R[p], R[p], lo, hi, 1)
+        runs = {"luma_uv_one_launch": (10, lambda: flt.mask_merge_luma(L, S, R, R, lo, hi, 1)), "luma_uv_two_launches": (14, two), "own_uv": (6, own)}
+        times = {k: [] for k in runs}
+        torch.cuda.synchronize()
+        for r in range(a.reps + 1):
+            for k, (_, fn) in runs.items():
+                flt.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                flt.synchronize()
+                if r:
+                    times[k].append(time.perf_counter() - t0)
+        for k, t in times.items():
+            t.sort()
+            out[k + "_us_per_frame"] = round(1e6 * t[len(t) // 2] / N, 2)
+            out[k + "_GBps"] = round(runs[k][0] * unit / t[len(t) // 2] / 1e9, 1)
+            out[k + "_us_min_max"] = [round(1e6 * t[0] / N, 2), round(1e6 * t[-1] / N, 2)]
     return out
 
 
@@ -195,10 +235,13 @@ def main():
     ap.add_argument("--reduce-bw", action="store_true", help="the reduce kernel alone against the turn kernel on the same planes")
     ap.add_argument("--reps", type=int, default=9, help="--reduce-bw, --mask-bw: timed launches per kernel")
     ap.add_argument("--mask", help="lo,hi[,expand]: the call with the edge mask next to the call without it (at source size)")
+    ap.add_argument("--mask-chroma", choices=["own", "luma"], default="own", help="--mask: which mask merges chroma (luma: the luma plane's, reduced)")
     ap.add_argument("--mask-bw", action="store_true", help="the mask kernel alone against the half-band reduce kernel on the same plane")
     a = ap.parse_args()
     a.mask_values = ([int(x) for x in a.mask.split(",")] + [1])[:3] if a.mask else [8, 32, 1]
     mask_kw = dict(mask=tuple(a.mask_values[:2]), mask_expand=a.mask_values[2]) if a.mask else None
+    if mask_kw and a.mask_chroma != "own":
+        mask_kw["mask_chroma"] = a.mask_chroma
     w, h = [int(x) for x in a.size.split("x")]
     clip = clip_format(a.fmt, w, h)
     if a.reduce:
@@ -253,6 +296,7 @@ def main():
             out[key] = round(N * reps / (time.perf_counter() - t0), 1)
     if a.mask:
         out["mask"] = a.mask_values
+        out["mask_chroma"] = a.mask_chroma
         out["mask_us_per_frame"] = round(1e6 / out["aa_mask_fps"] - 1e6 / out["aa_fps"], 2)
     with SangNom2(clip, max_batch=N) as flt:
         t = torch.empty((N, w, h), device=dev, dtype=torch.uint8)
