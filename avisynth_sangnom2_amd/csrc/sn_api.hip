@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "sn_copier.h"
+#include "sn_route.h"
 #include "sn_sweep_args.h"
 #include "sn_surface_layout.h"
 #include "sn_surface_plan.h"
@@ -38,54 +39,25 @@ struct UvScratch {
     int64_t split_frames = 0, merged_frames = 0, copied_frames = 0;  // sn_surface_info
 };
 
-struct Context {
-    sn_config cfg{};
+// What the clip's geometry decides is the plan (sn_route.h: c->bh, c->process[p], c->plane_fused[p], ...); the context adds the
+// device's side of it.
+struct Context : ClipPlan {
     sn_policy policy{};  // zeros = defaults (sangnom_hip.h)
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
     bool counted_live = false;  // this context is counted in g_live_contexts[device]
     int64_t uv_frames = 0;      // frames whose U and V passes ran as one sweep (sn_fused_u8_uv.hip)
-    bool uv_geometry = false;   // ... and whether this clip's geometry allows that (then only the luma -> U pool exists from the start)
-
-    int out_height = 0;  // vi.height after dh, SangNom2.cpp:284-285
-    int stride_e = 0;    // SangNom2.cpp:287
-    int bh = 0;          // SangNom2.cpp:288
-    float aaf[3] = {0, 0, 0};
-    bool process[3] = {true, true, true};
-    bool history_free = false;
     bool copies_elsewhere = false;  // a pass of sn_aa_*: planes that are not processed are copied by that call, once
     bool chroma_elsewhere = false;  // during a surface call: chroma that is not processed has gone from src to dst already
     bool luma_elsewhere = false;    // ... with an MSB-aligned side: so has luma that is not processed
-    bool use_fused = false;
-    int arith = SN_ARITH_CXX;  // sn_options.arithmetic, fixed for the context's life
-    // SN_ARITH_SSE2 on integer samples: the saturating instances of the pool kernels (float has one arithmetic)
-    bool saturating() const { return arith == SN_ARITH_SSE2 && cfg.bytes_per_sample < 4; }
-    // ... and which sweeps it uses there.  Every sweep has such instances, but by default (sn_policy.sse2_sweeps = 0) a
-    // context keeps the kernels of the release that introduced the arithmetic: sweeps for 8-bit planes on their own
-    // (plain, padded and row-band sweeps of sn_fused_u8_v3.hip), the pool kernels for the pool-coupled sweeps of subsampled
-    // chroma and for 9..16-bit clips.  sse2_sweeps = 1: whatever has sweeps in the default arithmetic
-    bool saturating_sweeps() const { return policy.sse2_sweeps == 1 || (cfg.bytes_per_sample == 1 && (isolated || !sn::fused_needs_pools(cfg))); }
-
-    PoolArgs pool{};  // allocated on first use when the fused kernels serve the configuration
-
-    // cfg.isolated_planes: every plane is its own filter instance (own pool geometry, own pool)
-    bool isolated = false;
-    PoolArgs plane_pool[3] = {};
-    bool plane_fused[3] = {false, false, false};
-    // cfg.fresh_pool: on top of that every frame starts from a zero-filled pool (planes narrower than their pool
-    // stride are swept over the whole stride with zero costs in the padding columns)
-    bool fresh = false;
-    bool plane_padded[3] = {false, false, false};
+    // (pool.base, plane_pool[p].base: allocated on first use when the fused kernels serve the configuration)
     int slots = 1;    // frames of a batch the pool path runs at once (1: frames in order on slot 0)
-
     int fslots = 1;   // frames per chunk of the fused 4:2:0 sweeps (each needs its two hand-off pools)
 
     // fused 8-bit path with subsampled chroma: two scratch pools per batch slot (sn_fused_u8_v3.hip, Mode)
-    bool fused420 = false;
     uint8_t* fpool[2] = {nullptr, nullptr};
     int64_t fpool_frame_bytes = 0;
-    int fpool_rows = 0;
 
     // the host ring (sn_submit_host / sn_collect_host): ring_groups x ring_per_group frame slots; a group's
     // frames are swept by one launch on the group's stream
@@ -145,7 +117,7 @@ struct Context {
 
     // row-band sweeps of small launches (sn_sweep_args.h): per scratch slot the bands' state
     // snapshots and the frame's flag; the verification counts failed frames in band_fallbacks_dev and mirrors the count
-    // into band_fallbacks, host memory the device can write (what the pause heuristic of band_count looks at)
+    // into band_fallbacks, host memory the device can write (what band_pause looks at)
     // the chain of a history-carrying stream (run_chain): a ring of pool slots, one per pass in flight
     uint8_t* chain_base = nullptr;
     int chain_slots = 0, chain_origin = 0;
@@ -162,16 +134,10 @@ struct Context {
     int64_t banded_frames = 0;
     int band_force = 0;           // sn_debug_set_bands: bands per frame (0 = choose), < 0 = never
     int band_warm = 0;            // rows of run-up (0 = the default of the sample type)
-    // content on which the check keeps failing (flat or periodic material) pays for the bands AND the pool path: after
-    // a failure the next launches go straight to the pool path, twice as many after every further one
-    int64_t band_fallbacks_seen = 0;
-    int band_pause = 0, band_pause_next = 0, band_good = 0;
+    FallbackPause band_pause;     // as of *band_fallbacks
 
     // column parts (sn_options.column_parts; sn_sweep_args.h, kParts): per scratch slot the frame's seam record and its
     // flag, the count of failed frames on the device and mirrored to host memory (the pause looks at the mirror)
-    bool parts_on = false;
-    bool plane_parts[3] = {false, false, false};  // the plane is too wide for one workgroup and is cut
-    bool parts_eligible = false;                  // ... and what sn_info.fused_eligible says of such a context
     int parts_force = 0, parts_ghost_force = 0;   // sn_debug_set_column_parts
     uint8_t* parts_rec = nullptr;
     int64_t parts_frame_bytes = 0;
@@ -180,13 +146,8 @@ struct Context {
     int64_t* parts_fallbacks = nullptr;
     int64_t* parts_fallbacks_dev = nullptr;
     int64_t part_frames = 0;
-    int64_t parts_fallbacks_seen = 0;
-    int parts_pause = 0, parts_pause_next = 0, parts_good = 0;
+    FallbackPause parts_pause;  // as of *parts_fallbacks
 
-    int plane_w(int p) const { return p == 0 ? cfg.width : cfg.width >> cfg.sub_w; }
-    int plane_h_in(int p) const { return p == 0 ? cfg.height : cfg.height >> cfg.sub_h; }
-    int plane_h_out(int p) const { return p == 0 ? out_height : out_height >> cfg.sub_h; }
-    int nplanes() const { return cfg.num_planes < 3 ? cfg.num_planes : 3; }
     double threshold(int p) const
     {
         switch (cfg.bytes_per_sample) {
@@ -283,24 +244,15 @@ static const char* structural_text(const sn_config& c)
     return nullptr;
 }
 
-// A frame's result cannot depend on earlier frames iff every pool cell that a pass reads was
-// written earlier in the same frame or is never written at all (rows 0 and bh).  See SURVEY.md
-// section 0.7 / 7-H2: needs stride_e == width, and for subsampled chroma a luma pass before it.
-static bool compute_history_free(const Context& c)
-{
-    if (c.stride_e != c.cfg.width) return false;
-    if (c.nplanes() == 1) return true;
-    const bool luma_pass = c.cfg.dh || c.cfg.luma;
-    const bool chroma_pass = c.cfg.dh || c.cfg.chroma;
-    if (!chroma_pass) return true;
-    if (c.cfg.sub_w == 0 && c.cfg.sub_h == 0) return true;  // chroma rewrites the whole pool
-    return luma_pass;
-}
-
 }  // namespace sn
 
 using sn::Context;
 using sn::Copier;
+using sn::KeptLines;
+using sn::PartsPlan;
+using sn::kMaxBands;
+using sn::kMaxBandSlots;
+using sn::kMaxParts;
 
 #ifdef SN_ABORT_TRACE  // diagnostic builds only (make EXTRA=-DSN_ABORT_TRACE): where did an abort() come from?
 #include <execinfo.h>
@@ -464,68 +416,6 @@ static int ensure_fpool(Context* c, int i)
     return SN_OK;
 }
 
-// Column parts (sn_options.column_parts): a 16-bit or float plane on its own that is too wide for one workgroup is cut into
-// 2 .. kMaxParts windows of at most kPartsWindow columns -- four waves, so that two workgroups share a compute unit as the
-// sweeps of narrower planes do.  Seams lie on multiples of 32; a window reaches at least kPartsGhost columns (rounded up to
-// 32) beyond each of its seams; all windows of a plane are equally wide, so that one launch sweeps them all (the narrower
-// ones are widened, away from the image edge or to both sides).  DESIGN.md 4.6 has the numbers behind the ghosts.
-constexpr int kMaxParts = sn::kMaxColumnParts;
-constexpr int kPartsWindow = (sn::v3c::kFirst + 3 * sn::v3c::kInner) * sn::v3c::PXL;  // 1936
-constexpr int kPartsGhost16 = 64, kPartsGhost32 = 96;
-struct PartsPlan {
-    int n = 0;
-    int win_w = 0;
-    int win_x[kMaxParts];
-    int seam[kMaxParts + 1];  // seam[k], k = 1 .. n - 1: the first own column of part k
-};
-static int parts_ghost(const Context* c) { return c->cfg.bytes_per_sample == 2 ? kPartsGhost16 : kPartsGhost32; }
-
-static bool plan_parts(const Context* c, int p, PartsPlan& pl)
-{
-    pl.n = 0;
-    const int B = c->cfg.bytes_per_sample;
-    if (!c->parts_on || B < 2 || c->fresh || p >= c->nplanes()) return false;
-    if (!(c->cfg.dh || c->process[p])) return false;
-    if (c->isolated ? c->plane_padded[p] : sn::fused_needs_pools(c->cfg)) return false;  // planes on their own only
-    const int w = c->plane_w(p);
-    if (w % 32 != 0 || c->plane_h_out(p) / 2 - 1 < 1) return false;
-    const int G = (parts_ghost(c) + 31) & ~31;
-    int P = c->parts_force;
-    if (P == 0) {
-        if (!sn::fused_parts_plane_eligible(B, w)) return false;
-        for (P = 2; P <= kMaxParts; ++P)
-            if ((((w + P - 1) / P + 31) & ~31) + 2 * G <= kPartsWindow) break;
-    }
-    if (P < 2 || P > kMaxParts) return false;
-    pl.seam[0] = 0;
-    pl.seam[P] = w;
-    for (int k = 1; k < P; ++k) pl.seam[k] = (int)(((int64_t)k * w / P + 16) & ~31);
-    int lo[kMaxParts], ww = 0;
-    for (int k = 0; k < P; ++k) {
-        if (pl.seam[k + 1] - pl.seam[k] < 32) return false;  // not wide enough to hold that many parts
-        lo[k] = k == 0 ? 0 : pl.seam[k] - G;
-        const int hi = k == P - 1 ? w : pl.seam[k + 1] + G;
-        if (lo[k] < 0 || hi > w) return false;
-        ww = hi - lo[k] > ww ? hi - lo[k] : ww;
-    }
-    if (sn::v3c::strips_for(ww / sn::v3c::PXL) > 8) return false;
-    pl.win_w = ww;
-    for (int k = 0; k < P; ++k) {  // every window as wide as the widest
-        const int hi = k == P - 1 ? w : pl.seam[k + 1] + G;
-        int x = lo[k] - (((ww - (hi - lo[k])) / 2) & ~31);
-        x = x < 0 ? 0 : x > w - ww ? w - ww : x;
-        pl.win_x[k] = x;
-    }
-    if (c->parts_ghost_force > 0) {  // the test hook: every seam that far from the end of the window left of it
-        for (int k = 1; k < P; ++k) {
-            pl.seam[k] = pl.win_x[k - 1] + pl.win_w - c->parts_ghost_force;
-            if (pl.seam[k] < pl.win_x[k] + 8 || pl.seam[k] <= pl.seam[k - 1]) return false;
-        }
-    }
-    pl.n = P;
-    return true;
-}
-
 // Seam records and flags for `nseams` seams per frame: allocated when the context is created (and by the test hook), never
 // inside a launch; counted against the scratch budget.
 static int ensure_parts(Context* c, int nseams)
@@ -563,7 +453,7 @@ static int ensure_parts_scratch(Context* c)
     int nseams = 0;
     for (int p = 0; p < c->nplanes(); ++p) {
         PartsPlan pl;
-        if (!plan_parts(c, p, pl) && !c->plane_parts[p]) continue;
+        if (!sn::plan_parts(*c, p, c->parts_force, c->parts_ghost_force, pl) && !c->plane_parts[p]) continue;
         nseams = pl.n - 1 > nseams ? pl.n - 1 : nseams;
         const int rc = ensure_pool(c, c->isolated ? p : 0);
         if (rc != SN_OK) return rc;
@@ -584,86 +474,12 @@ static int create_impl(const sn_config* cfg, Context* c)
     c->device = cfg->device;
     SN_HIP(c, hipSetDevice(c->device));
 
-    // constructor arithmetic, SangNom2.cpp:276-288
-    const int aa[3] = {cfg->aa, cfg->aac, cfg->aac};
-    for (int i = 0; i < c->nplanes(); ++i)
-        c->aaf[i] = cfg->bytes_per_sample < 4
-                        ? (aa[i] * 21.0f / 16.0f) * (float)(1 << (cfg->bits_per_sample - 8))
-                        : (aa[i] * 21.0f / 16.0f) / 256.0f;
-    c->process[0] = cfg->luma != 0;
-    c->process[1] = c->process[2] = cfg->chroma != 0;
-    c->out_height = cfg->dh ? cfg->height * 2 : cfg->height;
-    c->stride_e = (cfg->width + 31) & ~31;
-    c->bh = (c->out_height + 1) >> 1;
-    if (c->stride_e > 8192)
-        return sn::fail(c, SN_ERR_UNSUPPORTED, "width %d exceeds the supported maximum of 8192", cfg->width);
-    if (c->out_height / 2 > 65535)
-        return sn::fail(c, SN_ERR_UNSUPPORTED, "height %d exceeds the supported maximum", cfg->height);
-    c->history_free = sn::compute_history_free(*c);
-    c->fresh = cfg->fresh_pool != 0;
-    c->isolated = c->fresh || (cfg->isolated_planes != 0 && c->nplanes() > 1);
-
-    bool eligible = sn::fused_eligible(c->cfg);
-    if (c->isolated) {
-        // Every plane as its own Y clip: pool stride and height from the plane itself, nothing shared -- what a
-        // script gets from ExtractY/U/V -> SangNom2 -> CombinePlanes with the reference.  A plane is history-free
-        // iff its own width is a multiple of 32, and then the plain fused sweep serves it.
-        c->history_free = true;
-        eligible = true;
-        for (int p = 0; p < c->nplanes(); ++p) {
-            sn::PoolArgs& pool = c->plane_pool[p];
-            pool.stride_e = (c->plane_w(p) + 31) & ~31;
-            pool.bh = (c->plane_h_out(p) + 1) >> 1;
-            pool.slot_bytes = ((int64_t)sn::kBuffers * (pool.bh + 1) * pool.stride_e * cfg->bytes_per_sample + 255) & ~(int64_t)255;
-            if (!(cfg->dh || c->process[p])) continue;  // copied planes need nothing
-            if (pool.stride_e != c->plane_w(p) && !c->fresh) c->history_free = false;
-            c->plane_fused[p] = sn::fused_plane_eligible(cfg->bytes_per_sample, c->plane_w(p));
-            if (!c->plane_fused[p] && c->parts_on && !c->fresh && sn::fused_parts_plane_eligible(cfg->bytes_per_sample, c->plane_w(p)))
-                c->plane_fused[p] = c->plane_parts[p] = true;  // in column parts
-            if (c->fresh && !c->plane_fused[p] && sn::fused_padded_plane_eligible(cfg->bytes_per_sample, c->plane_w(p)))
-                c->plane_fused[p] = c->plane_padded[p] = true;
-            eligible = eligible && c->plane_fused[p];
-        }
+    // what the geometry decides, and what it refuses (sn_route.h)
+    {
+        sn::ClipPlan plan = sn::clip_plan(c->cfg, c->arith, c->parts_on, c->policy);
+        if (plan.refusal != SN_OK) return sn::fail(c, plan.refusal, "%s", plan.refusal_text.c_str());
+        static_cast<sn::ClipPlan&>(*c) = plan;
     }
-    if (!c->isolated && !eligible && c->parts_on && !sn::fused_needs_pools(c->cfg) &&
-        sn::fused_parts_plane_eligible(cfg->bytes_per_sample, cfg->width)) {
-        // Y and 4:4:4 (and clips whose subsampled chroma is only copied): every processed plane is as wide as the pool
-        eligible = true;
-        for (int p = 0; p < c->nplanes(); ++p) c->plane_parts[p] = (cfg->dh || c->process[p]) && c->plane_w(p) == cfg->width;
-    }
-    if (c->arith == SN_ARITH_SSE2) {
-        // The reference's SSE2 stage drivers read one vector to the left of the last full one, so its output is defined
-        // for planes of at least two vectors (src/SangNom2_SSE2.cpp:705-715): 32 / 16 / 8 samples.  Every processed plane.
-        const int least = 32 / cfg->bytes_per_sample;
-        for (int p = 0; p < c->nplanes(); ++p)
-            if ((cfg->dh || c->process[p]) && c->plane_w(p) < least)
-                return sn::fail(c, SN_ERR_UNSUPPORTED,
-                                "SN_ARITH_SSE2: plane %d is %d samples wide; the reference's SSE2 path is defined from %d samples (two vectors) on",
-                                p, c->plane_w(p), least);
-    }
-    if (c->saturating()) {
-        // Without sn_policy.sse2_sweeps only the 8-bit sweeps of planes on their own run in this arithmetic; every other
-        // integer plane runs on the pool kernels, and the context says so (sn_info.fused_eligible = 0).  DESIGN.md 4.5.
-        if (!c->saturating_sweeps()) {
-            if (cfg->mode == SN_MODE_FUSED)
-                return sn::fail(c, SN_ERR_UNSUPPORTED,
-                                "SN_MODE_FUSED requested but in SN_ARITH_SSE2 only 8-bit planes on their own have fused sweeps; "
-                                "this clip (%s) runs on the pool path in that mode",
-                                cfg->bytes_per_sample == 2 ? "9..16-bit samples" : "subsampled chroma sharing the luma pool");
-            eligible = false;
-            for (int p = 0; p < 3; ++p) c->plane_fused[p] = c->plane_padded[p] = c->plane_parts[p] = false;
-        }
-        c->pool.arith = SN_ARITH_SSE2;
-        for (int p = 0; p < 3; ++p) c->plane_pool[p].arith = SN_ARITH_SSE2;
-    }
-    if (cfg->mode == SN_MODE_FUSED && !eligible)
-        return sn::fail(c, SN_ERR_UNSUPPORTED, "SN_MODE_FUSED requested but this configuration is not eligible");
-    c->use_fused = eligible && cfg->mode != SN_MODE_POOL;
-    c->parts_eligible = eligible;
-
-    c->fused420 = c->use_fused && !c->isolated && sn::fused_needs_pools(c->cfg);
-    if (c->isolated && cfg->mode == SN_MODE_POOL)
-        for (int p = 0; p < 3; ++p) c->plane_fused[p] = false;
     if (cfg->stream) {
         c->stream = reinterpret_cast<hipStream_t>(cfg->stream);
     } else {
@@ -673,10 +489,6 @@ static int create_impl(const sn_config* cfg, Context* c)
 
     // Scratch is bounded: a batch larger than what scratch_budget() holds runs in chunks on the same slots
     // (only history-free configurations batch at all, and for them a slot's old content never matters).
-    c->pool.stride_e = c->stride_e;
-    c->pool.bh = c->bh;
-    c->pool.slot_bytes = (int64_t)sn::kBuffers * (c->bh + 1) * c->stride_e * cfg->bytes_per_sample;
-    c->pool.slot_bytes = (c->pool.slot_bytes + 255) & ~(int64_t)255;
     int rc = SN_OK;
     auto fit = [&](int64_t per_frame) {
         const int64_t n = scratch_budget(c) / per_frame;
@@ -686,7 +498,7 @@ static int create_impl(const sn_config* cfg, Context* c)
     c->slots = c->history_free ? fit(c->pool.slot_bytes) : 1;
     if (c->use_fused) {
         // the fused sweeps serve this configuration: the pool path only takes the launches that are too small to
-        // be worth a sweep (prefer_pool below), so a few slots are enough
+        // be worth a sweep (sn::prefer_pool), so a few slots are enough
         const int64_t cap = (4ll << 30) / c->pool.slot_bytes;
         const int small = (int)(cap < 1 ? 1 : cap > 64 ? 64 : cap);
         if (c->slots > small) c->slots = small;
@@ -699,20 +511,12 @@ static int create_impl(const sn_config* cfg, Context* c)
         }
     }
     if (c->fused420) {
-        // rows the chroma sweeps can reach: 1 .. min(nr_c + 2, bh - 1), plus row 0
-        const int nr_c = c->plane_h_out(1) / 2 - 1;
-        const int reach = nr_c + 2 < c->bh - 1 ? nr_c + 2 : c->bh - 1;
-        c->fpool_rows = reach + 1;
         c->fpool_frame_bytes = sn::sweep_pool_bytes(cfg->bytes_per_sample, cfg->width, c->fpool_rows);
         // a chunk is three launches of one workgroup per frame: whole rounds of resident workgroups
         // (two waves per SIMD, 256 CUs) leave no partly filled round at the end of each launch
         const int nw = sn::sweep_waves(cfg->bytes_per_sample, cfg->width);
         const int round = 256 * (8 / nw);
-        // 8-bit clips whose U and V passes run as one sweep (sn_fused_u8_uv.hip) need the luma -> U pool only; the U -> V pool of
-        // the two-sweep form is allocated when that form first runs (sn_policy.chroma_sweeps = 1, or a launch of planes the one
-        // sweep does not take)
-        c->uv_geometry = cfg->bytes_per_sample == 1 && c->plane_w(1) == c->plane_w(2) && c->plane_h_out(1) == c->plane_h_out(2) &&
-                         sn::fused_uv_ok(cfg->width, c->plane_w(1), c->plane_h_out(1) / 2, c->bh);
+        // (U and V as one sweep need the luma -> U pool only: ClipPlan::uv_geometry)
         const int npools = c->uv_geometry ? 1 : 2;
         c->fslots = fit(npools * c->fpool_frame_bytes);  // fused420 implies history-free (fused_eligible)
         if (c->fslots < round && scratch_budget_is_default(c)) {
@@ -733,12 +537,8 @@ static int create_impl(const sn_config* cfg, Context* c)
         }
     }
     if (c->plane_parts[0] || c->plane_parts[1] || c->plane_parts[2]) {
-        if (cfg->mode == SN_MODE_POOL) {
-            for (int p = 0; p < 3; ++p) c->plane_parts[p] = false;
-        } else {
-            rc = ensure_parts_scratch(c);
-            if (rc != SN_OK) return rc;
-        }
+        rc = ensure_parts_scratch(c);
+        if (rc != SN_OK) return rc;
     }
     SN_HIP(c, hipStreamSynchronize(c->stream));
     return SN_OK;
@@ -800,29 +600,6 @@ int sn_create_ex(const sn_config* cfg, const sn_policy* policy, const sn_options
     return SN_OK;
 }
 
-// GetFrame's field choice, SangNom2.cpp:336-341.
-static int field_offset(const Context* c, int parity)
-{
-    switch (c->cfg.order) {
-    case 0: return parity ? 0 : 1;
-    case 1: return 0;
-    default: return 1;
-    }
-}
-
-// Of a processed plane only the kept field is ever read (the other lines are the ones being interpolated,
-// SangNom2.cpp:361-366), so only those lines need to cross PCIe: line `first`, then every `step`-th, `rows` of them.  A
-// copied plane and a double-height clip (whose every line is kept) go as a whole.
-struct KeptLines {
-    int first, step, rows;
-};
-
-static KeptLines kept_lines(const Context* c, int p, int parity)
-{
-    if (c->cfg.dh || !c->process[p]) return {0, 1, c->plane_h_in(p)};
-    return {field_offset(c, parity), 2, c->plane_h_out(p) / 2};
-}
-
 // The host's copy threads (staging of the ring, kept lines of the synchronous call): sn_policy.copy_threads in all, the caller included.
 static void ensure_copier(Context* c)
 {
@@ -849,7 +626,7 @@ static int kept_line_jobs(const Context* c, int p, int parity, const void* src, 
         jobs[0] = {d, s, dp, sp, row, c->plane_h_in(p)};
         return 1;
     }
-    const int off = field_offset(c, parity), nk = c->plane_h_out(p) / 2, h_out = c->plane_h_out(p);
+    const int off = sn::field_offset(c->cfg.order, parity), nk = c->plane_h_out(p) / 2, h_out = c->plane_h_out(p);
     const int first = c->cfg.dh ? 0 : off, step = c->cfg.dh ? 1 : 2;  // kept line k in the source
     jobs[0] = {d + (size_t)off * dp, s + (size_t)first * sp, 2 * dp, step * sp, row, nk};
     if (off == 0) jobs[1] = {d + (size_t)(h_out - 1) * dp, s + (size_t)(first + step * (nk - 1)) * sp, dp, sp, row, 1};  // SangNom2.cpp:380-385
@@ -871,109 +648,6 @@ static int check_planes(Context* c, const void* const src[3], const int32_t sp[3
             return sn::fail(c, SN_ERR_INVALID_ARG, "plane %d pointer/pitch not aligned to the sample size", p);
     }
     return SN_OK;
-}
-
-// A fused sweep walks a plane row by row: its time hardly depends on how many frames the launch carries (up to a round of
-// resident workgroups) but it never takes less than rows x 2.6 - 4.7 us.  The pool path spreads ONE frame over the whole chip
-// and costs 13 - 33 ps per pool element and frame beyond that.  Both are exact, so in SN_MODE_AUTO a launch that is neither cut
-// into row bands (band_count) nor large goes to whichever this estimate says is faster.  Constants: fitted in round 4 to
-// tools/prefer_pool_calib.py (profiles/r4_prefer_pool.md: launches of 1 .. 128 device-resident frames through both paths, 1080p /
-// 2160p / 4320p, the three sample types, 4:2:0) -- round 1's had the pool path's fixed cost three times too high (stage 2 has
-// since moved to the strip kernels) and a row of a sweep that has its CU to itself 30 % too slow, which cancelled except at
-// 4320p, where launches of 16 .. 32 frames took the sweeps at up to twice the pool path's time.
-//   sweep: rows x t_row; t_row = 2.6 us (8-bit; 3.8 us for planes of more than eight strips: eight waves), 2.8 us (16-bit),
-//          4.3 us (float); the chroma planes of a coupled 4:2:0 clip sweep the luma-wide pool: 8-bit U and V as one sweep
-//          3.8 us per chroma row for both (1.9 us booked to each plane), otherwise 3.0 us (8-bit) / 3.15 us (16-bit) / 4.7 us
-//          (float) per row and plane
-//   pool : bh x (a + 0.036 us x ceil(stride / 1024)) + 60 us + n x stride x bh x per_elem per processed plane;
-//          a = 0.25 / 0.22 / 0.33 us, per_elem = 12.9 / 19.4 / 32.6 ps for 8-bit / 16-bit / float
-static bool prefer_pool(const Context* c, int n, int slot0)
-{
-    if (c->cfg.mode != SN_MODE_AUTO || !c->history_free || slot0 + n > c->slots) return false;
-    if (sweeps_always(c)) return false;  // SN_SMALL_SWEEP (the tests use it to reach the sweeps with small clips)
-    const int B = c->cfg.bytes_per_sample;
-    const double per_elem = B == 1 ? 12.9e-12 : B == 2 ? 19.4e-12 : 32.6e-12;
-    const double a_fix = B == 1 ? 0.25e-6 : B == 2 ? 0.22e-6 : 0.33e-6;
-    double fused = 0, pool = 0;
-    for (int p = 0; p < c->nplanes(); ++p) {
-        if (!(c->cfg.dh || c->process[p])) continue;
-        const bool own = c->isolated;  // own pool geometry per plane, else the luma-sized shared pool
-        const int stride = own ? c->plane_pool[p].stride_e : c->stride_e;
-        const int bh = own ? c->plane_pool[p].bh : c->bh;
-        const int rows = c->plane_h_out(p) / 2;
-        const bool coupled_chroma = c->fused420 && p > 0;
-        double t_row = B == 1 ? (stride > 3840 ? 3.8e-6 : 2.6e-6) : B == 2 ? 2.8e-6 : 4.3e-6;
-        if (coupled_chroma) t_row = B == 1 ? (c->uv_geometry && c->policy.chroma_sweeps == 0 ? 1.9e-6 : 3.0e-6) : B == 2 ? 3.15e-6 : 4.7e-6;
-        fused += rows * t_row;
-        const int cols_per_thread = (stride + 1023) / 1024;
-        // (a pass of the shared pool stops at the last row a later pass of this frame can still read: run_group's stop[])
-        const int bh_run = !own && rows + 2 < bh ? rows + 2 : bh;
-        pool += bh_run * (a_fix + 0.036e-6 * cols_per_thread) + 60e-6 + (double)n * stride * bh_run * per_elem;
-    }
-    return pool < fused;
-}
-
-// Row bands: a launch of a few frames -- a synchronous GetFrame, a short look-ahead -- cannot fill the
-// device with one workgroup per frame, so each frame is cut into bands of rows that start from a guessed state and are
-// verified afterwards (sn_sweep_args.h, sn_band.hip).  The run-up is what the guess needs to be forgotten on
-// ordinary content: 8-bit sums settle within 17-23 rows of noise, 16-bit within 30, float within 37.
-constexpr int kMaxBands = 128;
-constexpr int kMinBandRows = 8;
-
-static int band_warm_rows(const Context* c)
-{
-    if (c->band_warm > 0) return c->band_warm;
-    return c->cfg.bytes_per_sample == 1 ? 32 : c->cfg.bytes_per_sample == 2 ? 40 : 48;
-}
-
-constexpr int kMaxBandSlots = 192;  // launches of more frames than that fill the device without bands
-
-// Rows of the shortest processed plane if this context can cut small launches into bands at all, else 0.
-static int band_rows_available(const Context* c)
-{
-    if (c->plane_parts[0] || c->plane_parts[1] || c->plane_parts[2] || c->parts_force > 0) return 0;  // never combined with column parts
-    if (c->band_force < 0 || c->cfg.mode != SN_MODE_AUTO || !c->history_free) return 0;
-    if (c->isolated) {  // every processed plane must have the sweep for planes on their own (not the padded one)
-        for (int p = 0; p < c->nplanes(); ++p)
-            if ((c->cfg.dh || c->process[p]) && (!c->plane_fused[p] || c->plane_padded[p])) return 0;
-    } else if (!c->use_fused) {
-        return 0;
-    }
-    int nr_min = 1 << 30;
-    for (int p = 0; p < c->nplanes(); ++p)
-        if (c->cfg.dh || c->process[p]) nr_min = c->plane_h_out(p) / 2 - 1 < nr_min ? c->plane_h_out(p) / 2 - 1 : nr_min;
-    return nr_min == (1 << 30) || nr_min < 2 * kMinBandRows ? 0 : nr_min;
-}
-
-// Bands per frame for a launch of n frames on slots slot0.., 0 = do not cut.
-static int band_count(Context* c, int n, int slot0)
-{
-    const int nr_min = band_rows_available(c);
-    if (nr_min == 0) return 0;
-    if (slot0 + n > c->slots || slot0 + n > kMaxBandSlots) return 0;  // the fallback needs the frames' pool slots
-    if (c->band_force == 0 && sweeps_always(c)) return 0;  // whole-plane sweeps always (see prefer_pool)
-    int nb = c->band_force > 0 ? c->band_force : 512 / n;  // about two workgroups per CU in all
-    if (nb > nr_min / kMinBandRows) nb = nr_min / kMinBandRows;
-    if (nb > kMaxBands) nb = kMaxBands;
-    if (nb < (c->band_force > 0 ? 2 : 3)) return 0;  // a launch of hundreds of frames fills the device with whole-plane sweeps
-    if (c->band_force == 0 && nr_min / nb < band_warm_rows(c) / 4) nb = nr_min / (band_warm_rows(c) / 4);  // run-up <= 4 x own rows
-    if (nb < 2) return 0;
-    if (c->band_force == 0 && c->band_fallbacks) {
-        const int64_t seen = *c->band_fallbacks;  // as of the last banded launch that has finished
-        if (seen != c->band_fallbacks_seen) {
-            c->band_fallbacks_seen = seen;
-            c->band_pause_next = c->band_pause_next < 8 ? 8 : c->band_pause_next < 1024 ? 2 * c->band_pause_next : 1024;
-            c->band_pause = c->band_pause_next;
-            c->band_good = 0;
-        } else if (c->band_pause == 0 && ++c->band_good >= 64) {
-            c->band_pause_next = 0;
-        }
-        if (c->band_pause > 0) {
-            --c->band_pause;
-            return 0;
-        }
-    }
-    return nb;
 }
 
 // The chroma half of a small 4:2:0 launch as chains (run_group): three ring slots per frame -- the luma plane's smoothed
@@ -1013,15 +687,10 @@ static bool ensure_chroma_chains(Context* c, int slot0, int n, hipStream_t st)
 // The band fields of one sweep over pool rows 1 .. last, at most `want` bands.
 static void set_bands(const Context* c, sn::FusedPool& fp, int want, int last, int slot0, bool first)
 {
-    int nb = want < last / kMinBandRows ? want : last / kMinBandRows;
-    if (nb < 1) nb = 1;
-    fp.band_rows = (last + nb - 1) / nb;
-    fp.nbands = (last + fp.band_rows - 1) / fp.band_rows;
-    if (fp.nbands < 2) {  // a launcher takes one band as "not cut"; two bands of which the second is empty cannot happen
-        fp.band_rows = (last + 1) / 2;
-        fp.nbands = 2;
-    }
-    fp.band_warm = band_warm_rows(c);
+    const sn::BandGeometry bg = sn::band_geometry(want, last);
+    fp.band_rows = bg.band_rows;
+    fp.nbands = bg.nbands;
+    fp.band_warm = sn::band_warm_rows(c->cfg.bytes_per_sample, c->band_warm);
     fp.band_state = c->band_state + (int64_t)slot0 * c->band_words;
     fp.band_flags = c->band_flags + slot0;
     fp.band_reset = first ? 1 : 0;
@@ -1084,7 +753,7 @@ static int prepare_small_launch_scratch(Context* c)
     } else if (c->use_fused) {
         rc = ensure_pool(c);
     }
-    if (rc == SN_OK && band_rows_available(c) > 0) rc = ensure_bands(c);
+    if (rc == SN_OK && sn::band_rows_available(*c, c->band_force, c->parts_force) > 0) rc = ensure_bands(c);
     return rc;
 }
 
@@ -1106,7 +775,7 @@ static sn::PlaneArgs plane_args(const Context* c, int p, const void* const src[3
     a.dh = c->cfg.dh;
     a.enabled = (c->cfg.dh || c->process[p]) ? 1 : 0;
     a.copied_elsewhere = (c->copies_elsewhere || (p > 0 ? c->chroma_elsewhere : c->luma_elsewhere)) ? 1 : 0;
-    a.arith = c->saturating() ? SN_ARITH_SSE2 : SN_ARITH_CXX;  // (the sweeps; the pool kernels take PoolArgs::arith)
+    a.arith = c->saturating ? SN_ARITH_SSE2 : SN_ARITH_CXX;  // (the sweeps; the pool kernels take PoolArgs::arith)
     return a;
 }
 
@@ -1149,30 +818,6 @@ struct GroupLaunch {
         parts_counted = true;
     }
 };
-
-// Column parts pause after a launch with a failed frame, as the bands do (band_count); under SN_SMALL_AUTO a launch small
-// enough for row bands goes where it went before the option existed.  True: this launch's cut planes go to the pool path.
-static bool parts_to_pool(Context* c, int slot0, int n)
-{
-    bool to_pool = slot0 >= c->parts_slots || slot0 >= c->slots || !c->parts_rec;
-    if (c->cfg.mode == SN_MODE_AUTO && !sweeps_always(c) && 512 / n >= 3) to_pool = true;
-    if (!to_pool && c->parts_fallbacks) {
-        const int64_t seen = *c->parts_fallbacks;  // as of the last launch in parts that has finished
-        if (seen != c->parts_fallbacks_seen) {
-            c->parts_fallbacks_seen = seen;
-            c->parts_pause_next = c->parts_pause_next < 8 ? 8 : c->parts_pause_next < 1024 ? 2 * c->parts_pause_next : 1024;
-            c->parts_pause = c->parts_pause_next;
-            c->parts_good = 0;
-        } else if (c->parts_pause == 0 && ++c->parts_good >= 64) {
-            c->parts_pause_next = 0;
-        }
-        if (c->parts_pause > 0) {
-            --c->parts_pause;
-            to_pool = true;
-        }
-    }
-    return to_pool;
-}
 
 // One plane in column parts: a sweep per window, the check of the seams, and the pool path for the frames that fail it
 // (guarded launches, a chunk of pool slots at a time, that exit at once otherwise).  No k_assemble: kept lines are right
@@ -1423,7 +1068,7 @@ static int run_coupled(GroupLaunch& g)
     const sn::PlaneArgs* pa = g.pa;
     const int nr_c = c->plane_h_out(1) / 2 - 1;
     const int reach = c->fpool_rows - 1;
-    const int sweep_u = nr_c + 1 < c->bh - 1 ? nr_c + 1 : c->bh - 1;
+    const int sweep_u = sn::coupled_sweep_u(nr_c, c->bh);
     // 8-bit: U and V as ONE sweep (sn_fused_u8_uv.hip) -- only the luma -> U hand-off goes through a pool
     const bool one_chroma_sweep = c->uv_geometry && c->policy.chroma_sweeps == 0 && pa[1].enabled && pa[2].enabled && pa[1].h_in == pa[2].h_in;
     if (!one_chroma_sweep) {
@@ -1478,49 +1123,40 @@ static int run_group(Context* c, hipStream_t st, int slot0, int n, const void* c
     g.st = st;
     g.slot0 = slot0;
     g.n = n;
+    sn::LaunchInput in;
+    in.n = n;
+    in.slot0 = slot0;
     for (int p = 0; p < c->nplanes(); ++p) {
         g.pa[p] = plane_args(c, p, src, sfs, sp, dst, dfs, dp, f0, offset);
-        g.fused[p] = g.pa[p].enabled && (c->isolated ? c->plane_fused[p] : c->use_fused) && sn::fused_layout_ok(g.pa[p]);
+        in.layout_ok[p] = sn::fused_layout_ok(g.pa[p]);
     }
-    bool all_fused = true;
-    for (int p = 0; p < c->nplanes(); ++p) all_fused = all_fused && (g.fused[p] || !g.pa[p].enabled);
-    g.nbands = all_fused ? band_count(c, n, slot0) : 0;
-    if (g.nbands == 0 && prefer_pool(c, n, slot0))
-        for (int p = 0; p < 3; ++p) g.fused[p] = false;
-    // Column parts: which planes of this launch are cut
-    bool any_parts = false;
-    for (int p = 0; p < c->nplanes(); ++p) any_parts = (g.fused[p] && plan_parts(c, p, g.plan[p])) || any_parts;
-    if (any_parts && parts_to_pool(c, slot0, n)) {
-        // the planes that only the parts can sweep go to the pool path; forced parts of a narrower plane to its whole-plane sweep
-        for (int p = 0; p < c->nplanes(); ++p) {
-            if (g.plan[p].n > 0 && c->plane_parts[p]) g.fused[p] = false;
-            g.plan[p].n = 0;
-        }
+    in.sweeps_always = sweeps_always(c);
+    in.band_force = c->band_force;
+    in.band_warm = c->band_warm;
+    in.parts_force = c->parts_force;
+    in.parts_ghost_force = c->parts_ghost_force;
+    in.slots = c->slots;
+    in.parts_slots = c->parts_slots;
+    in.seam_record = c->parts_rec != nullptr;
+    in.chroma_sweeps = c->policy.chroma_sweeps;
+    // a launch that would be cut asks the pause of its kind first (and no other launch does: the pauses count launches)
+    const bool bands_paused = c->band_force == 0 && c->band_fallbacks && sn::launch_bands(*c, in) > 0 && c->band_pause.paused(*c->band_fallbacks);
+    sn::LaunchDecision d = sn::decide_launch(*c, in, bands_paused, false);
+    if (d.parts_cut && c->parts_fallbacks && c->parts_pause.paused(*c->parts_fallbacks)) d = sn::decide_launch(*c, in, bands_paused, true);
+    for (int p = 0; p < 3; ++p) {
+        g.fused[p] = d.fused[p];
+        g.plan[p] = d.plan[p];
+        g.stop[p] = d.stop[p];
     }
-    // Creation marks a plane for column parts by its width alone (plane_parts), and plan_parts cuts only planes with a row to
-    // interpolate.  A marked plane without a plan has no whole-plane sweep to fall back on -- it is wider than any instance --
-    // and nothing to interpolate either: the pool path's assemble is all it needs, and part_frames does not count it.
-    for (int p = 0; p < c->nplanes(); ++p)
-        if (g.fused[p] && c->plane_parts[p] && g.plan[p].n == 0) g.fused[p] = false;
+    g.nbands = d.nbands;
     if (g.nbands == 0)
         for (int p = 0; p < c->nplanes(); ++p) SN_HIP(c, g.plane_in(p));
-    // The reference smooths the whole luma-sized pool in every pass (SangNom2.cpp:126-159).  A plane of fewer lines reads
-    // back only rows 1 .. nr of it, and a later pass of this frame reads one row further than it smooths -- when nothing
-    // is carried into the next frame, rows beyond that are never looked at again and stage 2 of the pool path stops
-    // there (4:2:0: the two chroma passes take half the time).  SN_MODE_POOL keeps the full emulation, pool contents included.
-    if (c->history_free && c->cfg.mode != SN_MODE_POOL) {
-        int later = 0;
-        for (int p = c->nplanes() - 1; p >= 0; --p) {
-            if (!g.pa[p].enabled) continue;
-            const int own = g.pa[p].h_out / 2;  // rows 1 .. nr = own - 1
-            g.stop[p] = own > later + 1 ? own : later + 1;
-            later = g.stop[p];
-        }
+    switch (d.route) {
+    case sn::Route::kBandedPlanes: return run_banded_planes(g);
+    case sn::Route::kCoupled: return run_coupled(g);
+    case sn::Route::kCoupledBanded: return run_coupled_banded(g);
+    default: return run_planes(g);
     }
-    if (c->isolated) return g.nbands ? run_banded_planes(g) : run_planes(g);
-    if (c->fused420 && g.fused[0] && g.fused[1] && g.fused[2]) return g.nbands ? run_coupled_banded(g) : run_coupled(g);
-    if (g.nbands && !c->fused420) return run_banded_planes(g);
-    return run_planes(g);
 }
 
 // History-carrying clips, two passes or more of one field offset (several frames, or one frame with two or three processed
@@ -1541,19 +1177,10 @@ constexpr int kChainSlack = 2;  // rounds a workgroup's slots start later than l
 
 static int chain_planes(const Context* c, int planes[3])
 {
-    if (c->chain_slots < 0) return 0;
-    if (c->history_free || c->isolated || c->cfg.mode == SN_MODE_FUSED) return 0;
-    if (sn::pool_chain_lanes(c->cfg.bytes_per_sample, c->stride_e) < 2 || c->bh < 2) return 0;
-    if (c->policy.chain < 0) return 0;
+    if (c->chain_slots < 0 || c->policy.chain < 0) return 0;
     if (const char* e = test_env("SN_CHAIN"))
         if (atoi(e) == 0) return 0;
-    int pn = 0;
-    for (int p = 0; p < c->nplanes(); ++p) {
-        if (!(c->cfg.dh || c->process[p])) continue;
-        if (c->plane_w(p) % 8 != 0 || c->plane_h_out(p) / 2 - 1 >= c->bh || c->plane_h_out(p) / 2 - 1 < 1) return 0;
-        planes[pn++] = p;
-    }
-    return pn;
+    return sn::chain_planes(*c, sn::pool_chain_lanes(c->cfg.bytes_per_sample, c->stride_e), planes);
 }
 
 // The chain's ring of pool slots: one per pass in flight, sized for the launches this context can see (max_batch or the
@@ -1713,7 +1340,7 @@ static int run_batch(Context* c, hipStream_t st, int slot0, int nframes, const v
     int planes[3] = {0, 0, 0};
     const int pn = slot0 == 0 ? chain_planes(c, planes) : 0;
     while (f < nframes) {
-        const sn::FieldRun run = sn::field_run(parity, f, nframes, [c](int par) { return field_offset(c, par); }, c->history_free || pn);
+        const sn::FieldRun run = sn::field_run(parity, f, nframes, [c](int par) { return sn::field_offset(c->cfg.order, par); }, c->history_free || pn);
         const int off = run.offset;
         int g = run.end;
         // (a single frame with two or three processed planes is a chain too: its passes follow each other rows apart)
@@ -1989,7 +1616,7 @@ static int surface_info(const sn::UvScratch& S, sn_surface_info* info)
     return SN_OK;
 }
 
-static int sn_surface_offset(void* self, int parity) { return field_offset(static_cast<Context*>(self), parity); }
+static int sn_surface_offset(void* self, int parity) { return sn::field_offset(static_cast<Context*>(self)->cfg.order, parity); }
 
 // plane views as the arrays run_batch and the ABI take
 struct PlaneArrays {
@@ -2108,7 +1735,7 @@ int sn_process_host(sn_context* h, const void* const src[3], const int32_t sp[3]
             if (piped) SN_HIP(c, hipEventRecord(g.arrived[p], g.in));
             continue;
         }
-        const KeptLines kl = kept_lines(c, p, parity);
+        const KeptLines kl = sn::kept_lines(*c, p, parity);
         const uint8_t* from = static_cast<const uint8_t*>(src[p]) + (int64_t)kl.first * sp[p];
         size_t from_pitch = (size_t)kl.step * sp[p];
         if (!sn::plane_is_pinned(src[p], sp[p], c->plane_w(p) * B, c->plane_h_in(p))) {
@@ -2161,7 +1788,7 @@ int sn_process_host(sn_context* h, const void* const src[3], const int32_t sp[3]
             SN_HIP(c, hipStreamWaitEvent(g.out, g.done[p], 0));
         }
         // only the interpolated lines come back: offset + 1, offset + 3, ... (nr of them)
-        const int off = field_offset(c, parity), nr = c->plane_h_out(p) / 2 - 1;
+        const int off = sn::field_offset(c->cfg.order, parity), nr = c->plane_h_out(p) / 2 - 1;
         staged_back[p] = false;
         if ((c->cfg.dh || c->process[p]) && nr > 0) {
             hipStream_t so = piped ? g.out : c->stream;
@@ -2184,7 +1811,7 @@ int sn_process_host(sn_context* h, const void* const src[3], const int32_t sp[3]
     }
     for (int p = 0; p < c->nplanes(); ++p) {  // the staged planes: from the pinned staging into the caller's lines, chunk by chunk as they arrive
         if (!staged_back[p]) continue;
-        const int off = field_offset(c, parity), nr = c->plane_h_out(p) / 2 - 1;
+        const int off = sn::field_offset(c->cfg.order, parity), nr = c->plane_h_out(p) / 2 - 1;
         const int chunks = nr >= 4 * kSyncChunks ? kSyncChunks : 1;
         for (int k = 0; k < chunks; ++k) {
             const int y0 = (int)((int64_t)nr * k / chunks), y1 = (int)((int64_t)nr * (k + 1) / chunks);
@@ -2279,7 +1906,7 @@ static int launch_ring_group(Context* c, int gi)
             uint8_t* to = sd.direct[p] ? static_cast<uint8_t*>(sd.ptr[p]) : c->ring_pin_out[p] + (int64_t)(first + k) * c->ring_bytes_out[p];
             const int to_pitch = sd.direct[p] ? sd.pitch[p] : c->ring_pitch_out[p];
             if (sd.kept_on_host) {  // only the interpolated lines: offset + 1, offset + 3, ...
-                const int off = field_offset(c, c->slot_parity[first + k]), nr = c->plane_h_out(p) / 2 - 1;
+                const int off = sn::field_offset(c->cfg.order, c->slot_parity[first + k]), nr = c->plane_h_out(p) / 2 - 1;
                 if ((c->cfg.dh || c->process[p]) && nr > 0)
                     SN_HIP(c, hipMemcpy2DAsync(to + (int64_t)(off + 1) * to_pitch, (size_t)2 * to_pitch, from + (int64_t)(off + 1) * c->ring_pitch_out[p],
                                                (size_t)2 * c->ring_pitch_out[p], (size_t)c->plane_w(p) * B, nr, hipMemcpyDeviceToHost, g.stream));
@@ -2357,7 +1984,7 @@ static int submit_impl(sn_context* h, const void* const src[3], const int32_t sp
         if (!on_device[p]) continue;
         direct_in[p] = sn::plane_is_pinned(src[p], sp[p], c->plane_w(p) * B, c->plane_h_in(p));
         if (!direct_in[p]) {
-            const KeptLines kl = kept_lines(c, p, parity);  // only the lines that are read are staged ...
+            const KeptLines kl = sn::kept_lines(*c, p, parity);  // only the lines that are read are staged ...
             jobs[njobs++] = {c->ring_pin_in[p] + (int64_t)slot * c->ring_bytes_in[p] + (int64_t)kl.first * c->ring_pitch_in[p],
                              static_cast<const uint8_t*>(src[p]) + (int64_t)kl.first * sp[p], kl.step * c->ring_pitch_in[p], kl.step * sp[p],
                              c->plane_w(p) * B, kl.rows};
@@ -2367,7 +1994,7 @@ static int submit_impl(sn_context* h, const void* const src[3], const int32_t sp
     for (int p = 0; p < c->nplanes(); ++p) {
         if (!on_device[p]) continue;
         uint8_t* dev = c->ring_dev_in[p] + (int64_t)slot * c->ring_bytes_in[p];
-        const KeptLines kl = kept_lines(c, p, parity);  // ... and cross PCIe
+        const KeptLines kl = sn::kept_lines(*c, p, parity);  // ... and cross PCIe
         const uint8_t* from = direct_in[p] ? static_cast<const uint8_t*>(src[p]) : c->ring_pin_in[p] + (int64_t)slot * c->ring_bytes_in[p];
         const int from_pitch = direct_in[p] ? sp[p] : c->ring_pitch_in[p];
         if (kl.step == 1 && from_pitch == c->ring_pitch_in[p])  // every line, same pitch on both sides: one linear transfer
@@ -2631,7 +2258,7 @@ int sn_get_info(sn_context* h, sn_info* info)
     info->pool_stride = c->stride_e;
     info->pool_rows = c->bh + 1;
     info->fused_eligible = sn::fused_eligible(c->cfg) ? 1 : 0;
-    if (c->saturating() && !c->saturating_sweeps()) {
+    if (c->saturating && !c->saturating_sweeps) {
         info->fused_eligible = 0;  // SN_ARITH_SSE2 without sn_policy.sse2_sweeps: the pool path serves every plane
     } else if (c->isolated) {
         info->fused_eligible = 1;
@@ -2667,11 +2294,11 @@ int sn_get_parts_info(sn_context* h, sn_parts_info* info)
     bool any = false;
     for (int p = 0; p < 3; ++p) {
         PartsPlan pl;
-        const bool cut = p < c->nplanes() && (c->isolated ? c->plane_fused[p] : c->use_fused) && plan_parts(c, p, pl);
+        const bool cut = p < c->nplanes() && (c->isolated ? c->plane_fused[p] : c->use_fused) && sn::plan_parts(*c, p, c->parts_force, c->parts_ghost_force, pl);
         info->parts[p] = cut ? pl.n : 0;
         any = any || cut;
     }
-    info->ghost_columns = any ? (c->parts_ghost_force > 0 ? c->parts_ghost_force : parts_ghost(c)) : 0;
+    info->ghost_columns = any ? (c->parts_ghost_force > 0 ? c->parts_ghost_force : sn::parts_ghost(c->cfg.bytes_per_sample)) : 0;
     info->part_frames = c->part_frames;
     info->part_fallbacks = 0;
     if (c->parts_fallbacks_dev) {  // the device's own count (the host mirror may lag behind a launch with several failing frames)
@@ -2692,7 +2319,7 @@ int sn_debug_set_column_parts(sn_context* h, int32_t parts, int32_t ghost_column
     SN_HIP(c, hipSetDevice(c->device));
     c->parts_force = parts;
     c->parts_ghost_force = ghost_columns;
-    c->parts_pause = c->parts_pause_next = c->parts_good = 0;
+    c->parts_pause.forget();
     return ensure_parts_scratch(c);  // (allocates here, outside any launch)
 }
 
@@ -3075,7 +2702,7 @@ static int aa_run(sn_aa_context* a, int n, const sn::PlaneView src[3], const sn:
         auto turns = [&](int right) -> int {
             for (int g0 = 0; g0 < m;) {
                 sn::FieldRun run{m, -1};
-                if (!a->cfg.dh) run = sn::field_run(par, g0, m, [c1](int q) { return field_offset(c1, q); });
+                if (!a->cfg.dh) run = sn::field_run(par, g0, m, [c1](int q) { return sn::field_offset(c1->cfg.order, q); });
                 for (int p = 0; p < a->planes; ++p) {
                     if (!a->process[p]) continue;  // (dh forces every plane)
                     if (!right)  // TurnLeft: the clip's plane -> h wide, w high
@@ -3120,7 +2747,7 @@ static int aa_run(sn_aa_context* a, int n, const sn::PlaneView src[3], const sn:
         void* e2[3] = {a->d_e[0], a->d_e[1], a->d_e[2]};
         SN_AA_SN(a->second, run_batch(c2, st, 0, m, s2, a->t2bytes, a->t2pitch, e2, a->obytes, a->opitch, par));
         for (int g0 = 0; g0 < m;) {
-            const sn::FieldRun run = sn::field_run(par, g0, m, [c2](int q) { return field_offset(c2, q); });
+            const sn::FieldRun run = sn::field_run(par, g0, m, [c2](int q) { return sn::field_offset(c2->cfg.order, q); });
             for (int p = 0; p < a->planes; ++p)
                 SN_AA_HIP(sn::launch_reduce(st, B, a->cfg.bits_per_sample, a->reduce, run.end - g0, e[p].at(g0), a->w[p], a->h[p], 1 - run.offset, run.offset,
                                             dst[p].at(f0 + g0)));

@@ -1,32 +1,11 @@
-// sn_fused_select.hip -- which configurations the fused sweeps serve, and the sweeps' one entry point (host code only).
-//
-// A configuration is eligible when every plane fits one workgroup (width a multiple of 32; up to 7680 columns for
-// 8-bit, 3840 for 16-bit and float samples) and either every processed plane is as large as the pool (no pass can
-// see another pass's leftovers: SURVEY.md 0.7) or the chroma planes are subsampled AND luma is processed first --
-// then the sweeps couple the passes through hand-off pools; without a luma pass the chroma passes
-// would see the previous FRAME's leftovers, which only the pool path reproduces.
+// sn_fused_select.hip -- the sweeps' one entry point, the layout their addressing takes, and the hand-off pools' size and
+// layout (host code only).  Which configurations the sweeps serve is sn_route.h's.
 #include <stdint.h>
 #include <string.h>
 
-#include "sn_sweep_args.h"
+#include "sn_route.h"
 
 namespace sn {
-
-static bool chroma_subsampled_and_processed(const sn_config& c)
-{
-    const int np = c.num_planes < 3 ? c.num_planes : 3;
-    return np == 3 && (c.dh || c.chroma) && (c.sub_w != 0 || c.sub_h != 0);
-}
-
-bool fused_needs_pools(const sn_config& c) { return chroma_subsampled_and_processed(c); }
-
-bool sweep_plane_ok(int bytes_per_sample, int w) { return w % 32 == 0 && sweep_waves(bytes_per_sample, w) <= v3c::sweep_traits(bytes_per_sample).max_waves; }
-
-int sweep_waves(int bytes_per_sample, int sweep_w)
-{
-    const int nvw = v3c::strips_for(sweep_w / v3c::PXL);
-    return v3c::sweep_traits(bytes_per_sample).packed ? (nvw + 1) / 2 : nvw;
-}
 
 // a slot per thread and pool row: the eight columns of each strip the thread holds (two for 8-bit samples)
 static int slot_bytes(const v3c::SweepTraits& t) { return (t.packed ? 2 : 1) * v3c::PXL * t.bytes; }
@@ -68,31 +47,6 @@ hipError_t launch_sweep(hipStream_t st, int bytes_per_sample, const PlaneArgs& p
     if (bytes_per_sample == 4) return launch_sweep_f32(st, s, (float)threshold);
     if (bytes_per_sample == 2) return launch_sweep_u16(st, s);
     return launch_sweep_u8(st, s);
-}
-
-bool fused_plane_eligible(int bytes_per_sample, int w) { return sweep_plane_ok(bytes_per_sample, w); }
-
-bool fused_padded_plane_eligible(int bytes_per_sample, int w)
-{
-    if (w % 8 != 0) return false;  // the plane must end on a lane boundary (8 columns per lane)
-    return fused_plane_eligible(bytes_per_sample, (w + 31) & ~31);
-}
-
-bool fused_parts_plane_eligible(int bytes_per_sample, int w)
-{
-    if (bytes_per_sample != 2 && bytes_per_sample != 4) return false;
-    if (w % 32 != 0 || w > 8192) return false;
-    return !fused_plane_eligible(bytes_per_sample, w);
-}
-
-bool fused_eligible(const sn_config& c)
-{
-    if (!fused_plane_eligible(c.bytes_per_sample, c.width)) return false;
-    if (chroma_subsampled_and_processed(c)) {
-        if (!(c.dh || c.luma)) return false;
-        if ((c.width >> c.sub_w) % 8 != 0) return false;
-    }
-    return true;
 }
 
 // Pointer / pitch alignment the 8-byte vector accesses need, and the size the sweeps' addressing holds: they reach a plane

@@ -34,6 +34,7 @@
 
 #include "sn_fused_u8_parts.h"
 #include "sn_fused_v3_common.h"
+#include "sn_route.h"
 
 namespace sn {
 namespace uv {
@@ -41,8 +42,7 @@ namespace uv {
 using namespace v3c;
 using namespace v3;
 
-constexpr int kSkew = 2;       // steps the V pass runs behind the U pass
-constexpr int kMaxWaves = 8;   // strips of the luma-wide pool: 3840 columns
+// (kSkew, the steps the V pass runs behind the U pass, and kMaxWaves: sn_route.h, next to fused_uv_ok)
 constexpr unsigned kAll = 0xffffffffu;
 enum WaveClass { kR = 0, kRS = 1, kS = 2 };
 
@@ -658,18 +658,6 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused_u8_uv(Args a)
 }
 
 }  // namespace uv
-
-// Which subsampled geometries the one-sweep chroma passes take; everything else keeps the two chroma sweeps of
-// sn_fused_u8_v3.hip.  Both chroma planes processed and alike, the region a whole number of lanes, enough rows for the skew.
-// 4:2:0: the U pass has an extra row (nr_c + 1) and the V pass's last row finds it; 4:2:2: the pool ends with the chroma
-// planes' last row, the U pass has no extra row and V's last row takes nothing from it.
-bool fused_uv_ok(int sweep_w, int region_w, int nk_c, int bh)
-{
-    if (sweep_w % 32 != 0 || region_w % 8 != 0 || region_w <= 0 || region_w >= sweep_w) return false;
-    if (v3c::strips_for(sweep_w / v3c::PXL) > uv::kMaxWaves) return false;
-    const int nr = nk_c - 1;
-    return nr >= 2 * uv::kSkew + 2 && nr <= bh - 1;
-}
 
 hipError_t launch_fused_u8_uv(hipStream_t st, const PlaneArgs& pu, const PlaneArgs& pv, double thr_u, double thr_v, int nframes, const FusedPool& pool)
 {

@@ -132,16 +132,10 @@ hipError_t launch_pool_chain(hipStream_t s, const PoolArgs& pool, const ChainArg
 // after the guarded redo of a chain launch: *redone += (*fault != 0), and the running count into *host_mirror (host memory the device writes)
 hipError_t launch_chain_redo_count(hipStream_t s, const uint32_t* fault, uint32_t* redone, uint32_t* host_mirror);
 
-// sn_fused_select.hip: which configurations the fused sweeps serve.  A fused launch also does the plane's frame
-// assembly, so launch_assemble must not be called for a plane it serves.
-bool fused_eligible(const sn_config& c);
-// one plane of width w on its own (plain sweep): sample size and width within what the fused kernels take
-bool fused_plane_eligible(int bytes_per_sample, int w);
-// ... swept over its pool stride roundup(w, 32) with zero costs in the padding (fresh_pool)
-bool fused_padded_plane_eligible(int bytes_per_sample, int w);
-// ... too wide for one workgroup but served in column parts (sn_options.column_parts): 16-bit / float, w % 32 == 0, w <= 8192
-bool fused_parts_plane_eligible(int bytes_per_sample, int w);
-bool fused_needs_pools(const sn_config& c);  // subsampled chroma: luma / chroma sweeps coupled through scratch pools
+// Which configurations the fused sweeps serve: sn_route.h (fused_eligible, fused_*plane_eligible, fused_needs_pools,
+// sweep_plane_ok, sweep_waves, fused_uv_ok).  A fused launch also does the plane's frame assembly, so launch_assemble must
+// not be called for a plane it serves.
+// sn_fused_select.hip:
 // 8-byte alignment of bases, pitches and frame strides, and pitch * (rows + kFusedRowSlack) <= INT32_MAX on both sides
 constexpr int kFusedRowSlack = 16;
 bool fused_layout_ok(const PlaneArgs& p);
@@ -193,15 +187,12 @@ hipError_t launch_band_verify(hipStream_t s, const uint32_t* state, int threads,
 // sn_fused_select.hip: one sweep of `nframes` frames of plane p.  pool == nullptr: a plane on its own (kPlain); a launch the
 // kernels have no instance for is hipErrorInvalidValue (v3c::build_sweep)
 hipError_t launch_sweep(hipStream_t s, int bytes_per_sample, const PlaneArgs& p, double threshold, int nframes, const FusedPool* pool);
-bool sweep_plane_ok(int bytes_per_sample, int w);     // w within what one workgroup of the type's sweep takes (a multiple of 32)
-int sweep_waves(int bytes_per_sample, int sweep_w);   // waves of a workgroup that sweeps sweep_w columns
 int64_t sweep_pool_bytes(int bytes_per_sample, int sweep_w, int rows);  // one hand-off pool of one frame: [9][rows][threads] slots
 // host: scatter one hand-off pool (thread-slot layout) into [9][rows][sweep_w] samples (test hook)
 void sweep_pool_unpack(int bytes_per_sample, const uint32_t* raw, int sweep_w, int rows, void* out);
 // sn_fused_u8_uv.hip: the U and V passes of an 8-bit 4:2:0 frame as one sweep (U in the low halves of the registers, V in the
 // high halves two rows behind); `pool`: sweep_w, pool_in / frame_stride / pool_rows / rows_in = the luma sweep's hand-off
 // pool, sweep_rows = the U pass's last row.
-bool fused_uv_ok(int sweep_w, int region_w, int nk_c, int bh);
 hipError_t launch_fused_u8_uv(hipStream_t s, const PlaneArgs& pu, const PlaneArgs& pv, double thr_u, double thr_v, int nframes, const FusedPool& pool);
 #ifdef SN_EXPERIMENT_V4  // tools/experiments/sn_fused_u8_v4.hip (four waves per SIMD; slower: profiles/r2_v4_experiment.md)
 bool fused_v4_plane_ok(int w);

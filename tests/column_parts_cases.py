@@ -18,7 +18,7 @@ from oracle.oracle import Oracle
 from oracle.sangnom_numpy import NumpySangNom
 from tests.util import oracle_cfg
 
-GHOST = {1: 64, 2: 64, 4: 96}  # the library's ghost per sample size (sn_api.hip: kPartsGhost16 / kPartsGhost32); 8-bit: for the record
+GHOST = {1: 64, 2: 64, 4: 96}  # the library's ghost per sample size (sn_route.h: kPartsGhost16 / kPartsGhost32); 8-bit: for the record
 FORMATS = {"8-bit": (1, 8), "10-bit": (2, 10), "16-bit": (2, 16), "float": (4, 32)}
 CONVERGING = ("noise", "sine", "edges", "checker")  # what the GPU tests feed where no frame may take the fallback
 FIXED_POINT = "checker2"                            # never converges (8-bit, 16-bit, float): the natural fallback

@@ -4,15 +4,15 @@ device, tests/test_small_planes_cpu.py checks the table itself).  TEST INFRASTRU
 Which kernels serve a launch, and with what row counts, is decided on the host by a handful of rules over the planes' geometry.
 Each of them has a boundary at the lower end of the geometry -- a plane with no interpolated row, a pool of one row, a chroma
 plane too short for the one-sweep form -- and the tables below are derived from the rules so that every boundary has a case on
-each side.  The rules are restated ONCE here (test_small_planes_cpu.py holds each restatement against the library's own answer
-where one exists without a GPU):
+each side.  The rules live in csrc/sn_route.h and are restated ONCE here (test_small_planes_cpu.py puts every case of the tables
+to the header on a host compiler, tests/c/route_check.cpp, and holds each restatement against its answer):
 
   nr = h_out / 2 - 1              rows a plane interpolates (plan_parts and chain_planes ask for nr >= 1)
   bh = (h_out + 1) >> 1           rows of the luma-sized pool, row 0 not counted (pool_stage2_for: bh <= 1 has no stage 2;
                                   chain_planes asks for bh >= 2)
-  reach = min(nr_c + 2, bh - 1)   rows of the hand-off pool a coupled chroma sweep reaches (create_impl)
+  reach = min(nr_c + 2, bh - 1)   rows of the hand-off pool a coupled chroma sweep reaches (coupled_reach, clip_plan)
   nr_c >= 2 kSkew + 2             U and V as ONE sweep (fused_uv_ok; kSkew = 2, so nr_c >= 6)
-  nb <= nr / kMinBandRows         row bands of at least kMinBandRows = 8 rows, at least two of them (band_count, set_bands)
+  nb <= nr / kMinBandRows         row bands of at least kMinBandRows = 8 rows, at least two of them (band_count, band_geometry)
 
 A case is a tuple; its frames differ in content (noise, sine, edges, ...) and in parity.  Expected frames come from the C oracle,
 once per session; history-carrying clips (width not a multiple of 32) run against ONE oracle instance across their frames.
@@ -28,12 +28,12 @@ PATTERNS = ("noise", "sine", "edges")
 PARITIES = (1, 0, 1)
 
 # ---- the rules, restated ---------------------------------------------------------------------------------------------------------
-K_SKEW = 2                                 # sn_fused_u8_uv.hip
-MIN_BAND_ROWS = 8                          # sn_api.hip kMinBandRows
-BAND_WARM = {1: 32, 2: 40, 4: 48}          # sn_api.hip band_warm_rows: the default run-up per sample size
+K_SKEW = 2                                 # sn_route.h uv::kSkew
+MIN_BAND_ROWS = 8                          # sn_route.h kMinBandRows
+BAND_WARM = {1: 32, 2: 40, 4: 48}          # sn_route.h band_warm_rows: the default run-up per sample size
 MAX_SWEEP_WIDTH = {1: 7680, 2: 3840, 4: 3840}  # the widest whole-plane sweep (eight waves)
 MAX_WIDTH = 8192
-PARTS_GHOST = {2: 64, 4: 96}               # sn_api.hip kPartsGhost16 / kPartsGhost32
+PARTS_GHOST = {2: 64, 4: 96}               # sn_route.h kPartsGhost16 / kPartsGhost32
 
 
 def nr(h_out):

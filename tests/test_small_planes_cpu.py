@@ -1,10 +1,9 @@
 """The table of tests/small_plane_cases.py, checked without a GPU: every dispatch rule it is derived from has a case on each
-side, the restated rules are the library's (held against the headers on a host compiler and against the constants in the
-sources), the two CPU references agree bit for bit on every clip of the table, and the inputs can tell interpolation from line
+side, the restated rules are the library's (held against the answers of the headers on a host compiler), the two CPU
+references agree bit for bit on every clip of the table, and the inputs can tell interpolation from line
 doubling.
 """
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -198,28 +197,226 @@ def test_restated_pool_schedule_agrees_with_the_dispatch_header(tmp_path):
     assert set(lines) == {"none", "strided", "x8", "strips"}
 
 
-def _constant(path, pattern):
-    m = re.search(pattern, open(os.path.join(CSRC, path)).read())
-    assert m, (path, pattern)
-    return m.groups()
+MODES = {"auto": 0, "pool": 1, "fused": 2}  # SN_MODE_*
 
 
-def test_restated_constants_are_the_sources():
-    assert int(_constant("sn_fused_u8_uv.hip", r"constexpr int kSkew = (\d+);")[0]) == sp.K_SKEW
-    assert _constant("sn_fused_u8_uv.hip", r"return nr >= (2 \* uv::kSkew \+ 2) && nr <= bh - 1;")
-    assert int(_constant("sn_api.hip", r"constexpr int kMinBandRows = (\d+);")[0]) == sp.MIN_BAND_ROWS
-    assert _constant("sn_api.hip", r"nr_min < (2 \* kMinBandRows) \? 0 : nr_min")
-    assert _constant("sn_api.hip", r"if \(nb > nr_min / kMinBandRows\) nb = (nr_min / kMinBandRows);")
-    warm = _constant("sn_api.hip", r"return c->cfg\.bytes_per_sample == 1 \? (\d+) : c->cfg\.bytes_per_sample == 2 \? (\d+) : (\d+);")
-    assert tuple(int(v) for v in warm) == (sp.BAND_WARM[1], sp.BAND_WARM[2], sp.BAND_WARM[4])
-    ghost = _constant("sn_api.hip", r"constexpr int kPartsGhost16 = (\d+), kPartsGhost32 = (\d+);")
-    assert tuple(int(v) for v in ghost) == (sp.PARTS_GHOST[2], sp.PARTS_GHOST[4])
-    assert _constant("sn_api.hip", r"c->plane_h_out\(p\) / 2 - 1 (< 1)\) return false;")            # plan_parts
-    assert _constant("sn_api.hip", r"c->bh (< 2)\) return 0;")                                      # chain_planes
-    assert _constant("sn_api.hip", r"c->plane_h_out\(p\) / 2 - 1 >= c->bh \|\| c->plane_h_out\(p\) / 2 - 1 (< 1)\) return 0;")
-    assert _constant("sn_api.hip", r"const int reach = (nr_c \+ 2 < c->bh - 1 \? nr_c \+ 2 : c->bh - 1);")
-    assert _constant("sn_api.hip", r"c->bh = (\(c->out_height \+ 1\) >> 1);")
-    assert _constant("sn_pool_dispatch.h", r"if \(bh (<= 1)\) return \{PoolSchedule::kNone")
+def _route_query(fmt, w, h, kw=None, ckw=None, mode="auto", column_parts=0, **launch):
+    """One query of tests/c/route_check.cpp: the clip as SangNom2(clip, mode=..., column_parts=..., **kw, **ckw) describes it, and
+    a launch of n frames on slot 0 of a context with room for it (four pool slots, a seam record of four slots, the chain
+    kernels where sn_pool_kernels.hip has them: pools of 64 columns and more)."""
+    kw, ckw, clip = kw or {}, ckw or {}, clip_format(fmt, w, h)
+    la = dict(n=1, slot0=0, slots=4, parts_slots=4, seam_record=1, sweeps_always=0, band_force=0, band_warm=0, parts_force=0, ghost_force=0,
+              chroma_sweeps=0, chain_lanes=2 if sp.pool_stride(w) >= 64 else 0, bands_paused=0, parts_paused=0)
+    assert set(launch) <= set(la), launch
+    la.update(launch)
+    return [clip.bytes, clip.bits, clip.planes, clip.subw, clip.subh, w, h, int(bool(kw.get("dh"))), int(kw.get("luma", True)), int(kw.get("chroma", True)),
+            MODES[mode], int(bool(ckw.get("isolated_planes"))), int(bool(ckw.get("fresh_pool"))), 0, column_parts, 0] + list(la.values())
+
+
+def _route_answers(exe, queries):
+    r = subprocess.run([exe] + [str(v) for q in queries for v in q], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-1000:])
+    lines = r.stdout.split("\n")[:-1]
+    assert len(lines) == len(queries)
+    out = []
+    for line in lines:
+        head, _, text = line.partition(" text=")
+        a = {}
+        for k, v in (t.split("=") for t in head.split()):
+            if k == "route":
+                a[k] = v
+            elif "," in v:  # a list; of a parts plan, the windows as [first column, seam]
+                a[k] = [[int(x) for x in f.split(":")] if ":" in f else int(f) for f in v.split(",")]
+            else:
+                a[k] = int(v)
+        a["text"] = text
+        out.append(a)
+    return out
+
+
+PLANE = ("w", "h_out", "on", "fused", "padded", "parts", "sweep_ok", "pool_stride", "pool_bh")
+
+
+def _plane(a, p):
+    return dict(zip(PLANE, a[f"plane{p}"]))
+
+
+def test_restated_rules_agree_with_the_route_header(tmp_path):
+    """csrc/sn_route.h on a host compiler: every case of the tables is put to tests/c/route_check.cpp as the device test creates
+    and launches it, and every rule restated in small_plane_cases.py is held against the header's answer -- on both sides of its
+    boundary, which the tests of part 1 show the tables to stand on."""
+    exe = _compile(tmp_path, os.path.join(ROOT, "tests", "c", "route_check.cpp"), "route_check")
+    Q, checks = [], []
+
+    def ask(check, *a, **k):
+        Q.append(_route_query(*a, **k))
+        checks.append(check)
+
+    seen = {k: set() for k in ("nr", "bh", "reach", "uv", "bands", "warm", "sweep_ok", "marked", "chain", "ghost", "width")}
+
+    def common(a, fmt, w, h, kw):
+        """bh, nr-independent geometry and sweep_plane_ok / parts_marked's width half of every plane"""
+        clip, planes = clip_format(fmt, w, h), sp.planes_of(clip_format(fmt, w, h), kw)
+        assert a["refusal"] == 0 and a["bh"] == sp.bh(planes[0][1]) and a["stride_e"] == sp.pool_stride(w), (fmt, w, h, a)
+        seen["bh"].add(a["bh"] >= 2)
+        for p, (pw, ho, on) in enumerate(planes):
+            pl = _plane(a, p)
+            assert (pl["w"], pl["h_out"], pl["on"]) == (pw, ho, int(on)) and pl["sweep_ok"] == int(sp.sweep_plane_ok(clip.bytes, pw)), (fmt, w, h, p, pl)
+            seen["sweep_ok"].add(bool(pl["sweep_ok"]))
+        return clip, planes
+
+    def ghosts(a, p, B, ghost):
+        n, _, win_w, *parts = a[f"parts{p}"]
+        assert len(parts) == n >= 2
+        for k in range(1, n):  # the seam lies that far inside the window left of it and the window right of it
+            (x_l, _), (x_r, seam) = parts[k - 1], parts[k]
+            assert x_l + win_w - seam >= ghost and seam - x_r >= ghost, (p, k, parts, win_w)
+            seen["ghost"].add(min(x_l + win_w - seam, seam - x_r) == ghost)
+
+    def parts_case(fmt, w, h, kw, ckw):
+        def check(a):
+            clip, planes = common(a, fmt, w, h, kw)
+            iso = bool(ckw.get("isolated_planes"))
+            assert a["isolated"] == int(iso and clip.planes > 1) and a["parts_eligible"] == 1 and a["route"] == "planes" and a["nbands"] == 0
+            for p, (pw, ho, on) in enumerate(planes):
+                marked = on and sp.parts_marked(clip.bytes, pw) and (iso or pw == clip.width)
+                cut = marked and sp.nr(ho) >= 1
+                assert _plane(a, p)["parts"] == int(marked), (fmt, w, h, p)
+                assert (a[f"parts{p}"][0] >= 2, a[f"parts{p}"][1] >= 2) == (cut, cut), (fmt, w, h, p, a[f"parts{p}"])
+                assert a["fused"][p] == int(on and (cut or sp.sweep_plane_ok(clip.bytes, pw))), (fmt, w, h, p)
+                if on:
+                    seen["marked"].add(bool(marked))
+                if marked:
+                    seen["nr"].add(sp.nr(ho) >= 1)
+                if cut:
+                    ghosts(a, p, clip.bytes, sp.PARTS_GHOST[clip.bytes])
+            assert a["parts_cut"] == int(any(a[f"parts{p}"][0] for p in range(clip.planes)))
+        return check
+
+    for fmt, w, h, kw, ckw in sp.PARTS:
+        ask(parts_case(fmt, w, h, kw, ckw), fmt, w, h, kw, ckw, mode="fused", column_parts=1, n=3)
+
+    def forced_case(fmt, w, h, parts):
+        def check(a):
+            clip, _ = common(a, fmt, w, h, {})
+            assert _plane(a, 0)["parts"] == 0 and a["parts0"][:2] == [parts, parts] and a["fused"][0] == 1 and a["route"] == "planes", a
+            ghosts(a, 0, clip.bytes, sp.PARTS_GHOST[clip.bytes])
+            seen["marked"].add(bool(_plane(a, 0)["parts"]))  # the far side of parts_marked: a plane the whole-plane sweep takes
+        return check
+
+    for fmt, w, h, parts in sp.PARTS_FORCED:
+        ask(forced_case(fmt, w, h, parts), fmt, w, h, mode="fused", column_parts=1, n=3, parts_force=parts)
+        ask(lambda a: a["parts0"][:2] == [0, 0] or pytest.fail(str(a)), fmt, w, h, mode="fused", column_parts=1, n=3)
+
+    def wide_case(fmt, w, h, kw):
+        def check(a):
+            clip, planes = common(a, fmt, w, h, kw)
+            assert _plane(a, 0)["sweep_ok"] == 1 and a["use_fused"] == 1 and a["fused"][0] == 1 and (a["route"], a["nbands"]) == ("planes", 0), a
+            assert a["stop"][0] == planes[0][1] // 2
+        return check
+
+    for fmt, w, h, kw in sp.WIDE:
+        ask(wide_case(fmt, w, h, kw), fmt, w, h, kw, mode="fused", n=3)
+    for B, fmt in sp.Y.items():  # the other side: one column strip more
+        ask(lambda a, B=B: (_plane(a, 0)["sweep_ok"], a["use_fused"], _plane(a, 0)["parts"]) == (0, 0, 0) or pytest.fail(str(a)),
+            fmt, sp.MAX_SWEEP_WIDTH[B] + 32, 4)
+
+    def coupled_case(fmt, w, h, dh, table):
+        def check(a):
+            kw = dict(aac=48, dh=True) if dh else dict(aac=48)
+            clip, planes = common(a, fmt, w, h, kw)
+            nr_c, b = sp.nr(planes[1][1]), sp.bh(planes[0][1])
+            assert a["fused420"] == 1 and a["fpool_rows"] == sp.reach(nr_c, b) + 1 and a["reach"] == sp.reach(nr_c, b), (fmt, w, h, a)
+            assert a["route"] == "coupled" and a["fused"] == [1, 1, 1] and a["nbands"] == 0
+            assert a["uv_geometry"] == int(clip.bytes == 1 and sp.uv_rows_ok(nr_c, b)), (fmt, w, h, dh, a)
+            if table == "coupled":
+                seen["reach"].add("rows" if nr_c + 2 < b - 1 else "pool" if nr_c + 2 > b - 1 else "equal")
+            else:
+                seen["uv"].add(bool(a["uv_geometry"]))
+        return check
+
+    for fmt, w, h in sp.COUPLED:
+        ask(coupled_case(fmt, w, h, False, "coupled"), fmt, w, h, dict(aac=48), mode="fused", n=3)
+    for fmt, w, h, dh in sp.UV:
+        for cs in (0, 1):
+            ask(coupled_case(fmt, w, h, dh, "uv"), fmt, w, h, dict(aac=48, dh=True) if dh else dict(aac=48), mode="fused", chroma_sweeps=cs)
+
+    def bands_case(fmt, w, h, forced, warm):
+        def check(a):
+            clip, _ = common(a, fmt, w, h, {})
+            nb = sp.band_count(sp.nr(h), forced)
+            assert a["nbands"] == nb and a["route"] == ("banded_planes" if nb else "planes") and a["band_rows"] == (sp.nr(h) if nb else 0), (fmt, h, a)
+            assert a["warm"] == (warm or sp.BAND_WARM[clip.bytes])
+            seen["bands"].add(nb)
+            seen["warm"].add(warm)
+        return check
+
+    for fmt, w, h, forced in sp.BANDS:
+        for warm in sp.BAND_WARMS:
+            ask(bands_case(fmt, w, h, forced, warm), fmt, w, h, band_force=forced, band_warm=warm)
+
+    def chain_case(fmt, w, h, kw):
+        def check(a):
+            clip, planes = common(a, fmt, w, h, kw)
+            ok = sp.chain_ok(clip, kw)
+            assert a["history_free"] == 0 and (a["chain"] > 0) == ok and (not ok or a["chain"] == sum(on for _, _, on in planes)), (fmt, w, h, a)
+            assert a["use_fused"] == 0 and a["fused"] == [0, 0, 0] and a["stop"] == [0, 0, 0]
+            seen["chain"].add(ok)
+        return check
+
+    for fmt, w, h, kw in sp.CHAINS:
+        ask(chain_case(fmt, w, h, kw), fmt, w, h, kw, n=sp.CHAIN_FRAMES)
+
+    def pool_case(fmt, w, h):
+        def check(a):
+            common(a, fmt, w, h, {})
+            assert a["history_free"] == int(w % 32 == 0) and a["use_fused"] == 0 and a["fused"] == [0, 0, 0] and a["route"] == "planes"
+            assert a["stop"] == [0, 0, 0] and a["nbands"] == 0 and a["prefer_pool"] == 0  # the full emulation, pool contents included
+        return check
+
+    for fmt, w, h in sp.POOL:
+        ask(pool_case(fmt, w, h), fmt, w, h, mode="pool")
+
+    def narrow_case(fmt, w, h, fresh):
+        def check(a):
+            common(a, fmt, w, h, {})
+            padded = fresh and w % 8 == 0
+            pl = _plane(a, 0)
+            assert (a["history_free"], a["fresh"], a["isolated"], a["use_fused"]) == (int(fresh), int(fresh), int(fresh), int(padded)), (fmt, w, h, fresh, a)
+            assert (pl["padded"], pl["fused"], a["fused"][0]) == (int(padded), int(padded), int(padded)) and a["route"] == "planes" and a["nbands"] == 0
+            assert a["stride_e"] == 32 and (not fresh or (pl["pool_stride"], pl["pool_bh"]) == (32, sp.bh(h)))
+        return check
+
+    for fmt, w, h in sp.NARROW:
+        for fresh in (False, True):
+            ask(narrow_case(fmt, w, h, fresh), fmt, w, h, {}, dict(fresh_pool=True) if fresh else {}, sweeps_always=1)
+
+    def narrow_clip_case(fmt, w, h):
+        def check(a):
+            common(a, fmt, w, h, dict(aac=48))
+            assert a["use_fused"] == 0 and a["fused"] == [0, 0, 0] and a["route"] == "planes" and a["nbands"] == 0 and a["chain"] == 0, (fmt, w, h, a)
+        return check
+
+    for fmt, w, h in sp.NARROW_CLIPS:
+        ask(narrow_clip_case(fmt, w, h), fmt, w, h, dict(aac=48), sweeps_always=1)
+
+    def width_case(w):
+        def check(a):
+            assert (a["refusal"] == 0) == (w <= sp.MAX_WIDTH) and (w <= sp.MAX_WIDTH or a["text"] == f"width {w} exceeds the supported maximum of 8192"), a
+            seen["width"].add(w <= sp.MAX_WIDTH)
+        return check
+
+    for w in (sp.MAX_WIDTH, sp.MAX_WIDTH + 32):
+        ask(width_case(w), "Y8", w, 4)
+
+    answers = _route_answers(exe, Q)
+    for check, a in zip(checks, answers):
+        check(a)
+    assert len(Q) > 300
+    # every restated rule was asked on both sides of its boundary
+    for rule in ("nr", "bh", "uv", "sweep_ok", "marked", "chain", "ghost", "width"):
+        assert seen[rule] == {True, False}, (rule, seen[rule])
+    assert seen["reach"] == {"rows", "pool", "equal"} and seen["bands"] == {0, 2, 3} and seen["warm"] == {0, 1}
 
 
 # ---- 3. the references agree --------------------------------------------------------------------------------------------------------
