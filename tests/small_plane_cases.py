@@ -14,6 +14,9 @@ to the header on a host compiler, tests/c/route_check.cpp, and holds each restat
   nr_c >= 2 kSkew + 2             U and V as ONE sweep (fused_uv_ok; kSkew = 2, so nr_c >= 6)
   nb <= nr / kMinBandRows         row bands of at least kMinBandRows = 8 rows, at least two of them (band_count, band_geometry)
 
+clip_plan, band_count_auto and prefer_pool below restate creation's plan, auto mode's own band count and its estimate of the
+faster path for tests/config_space.py, whose CPU test holds them against the header for every launch of its table.
+
 A case is a tuple; its frames differ in content (noise, sine, edges, ...) and in parity.  Expected frames come from the C oracle,
 once per session; history-carrying clips (width not a multiple of 32) run against ONE oracle instance across their frames.
 """
@@ -101,13 +104,147 @@ def planes_of(clip, kw):
     return out
 
 
-def chain_ok(clip, kw):
-    """chain_planes: the batch of a history-carrying clip runs as a chain of passes."""
+def needs_pools(clip, kw):
+    """fused_needs_pools: subsampled chroma that is processed -- its passes share the luma-sized pool with the luma pass."""
+    return clip.planes == 3 and bool(kw.get("dh") or kw.get("chroma", True)) and (clip.subw != 0 or clip.subh != 0)
+
+
+def history_free(clip, kw):
+    """compute_history_free of a clip whose planes share one pool (not isolated_planes, not fresh_pool)."""
+    if clip.width % 32 != 0:
+        return False
+    if clip.planes == 1 or not needs_pools(clip, kw):
+        return True
+    return bool(kw.get("dh") or kw.get("luma", True))
+
+
+def chain_passes(clip, kw):
+    """chain_planes: passes per frame of the chain a history-carrying clip's launches run as, 0 = no chain."""
     planes = planes_of(clip, kw)
     b = bh(planes[0][1])
-    if clip.width % 32 == 0 or pool_stride(clip.width) < 64 or b < 2:
+    if history_free(clip, kw) or pool_stride(clip.width) < 64 or b < 2:
+        return 0
+    on = [(w, ho) for w, ho, o in planes if o]
+    return len(on) if all(w % 8 == 0 and 1 <= nr(ho) < b for w, ho in on) else 0
+
+
+def chain_ok(clip, kw):
+    """chain_planes: the batch of a history-carrying clip runs as a chain of passes."""
+    return chain_passes(clip, kw) > 0
+
+
+def uv_geometry(clip, kw):
+    """fused_uv_ok on the clip: the geometry allows U and V of an 8-bit frame as ONE sweep (at most eight strips: 3840 columns)."""
+    if clip.bytes != 1 or not needs_pools(clip, kw):
         return False
-    return all(w % 8 == 0 and 1 <= nr(ho) < b for w, ho, on in planes if on)
+    (w, ho, _), (wc, hc, _) = planes_of(clip, kw)[:2]
+    return w % 32 == 0 and wc % 8 == 0 and 0 < wc < w and strips_for(w // 8) <= 8 and uv_rows_ok(nr(hc), bh(ho))
+
+
+def clip_plan(clip, kw, ext="none", sse2=None, pool_mode=False, parts_on=False):
+    """sn_route.h clip_plan, as far as the routes need it: per plane (fused, padded, marked for column parts) and the clip's
+    flags.  ext: "none" | "isolated" | "fresh"; sse2: None (opt=0) or sn_policy.sse2_sweeps of an opt=1 context; pool_mode:
+    mode="pool"; parts_on: column_parts=1.  info_eligible: what sn_info.fused_eligible says of the context."""
+    B, planes, np_ = clip.bytes, planes_of(clip, kw), clip.planes
+    fresh = ext == "fresh"
+    isolated = fresh or (ext == "isolated" and np_ > 1)
+    pools = needs_pools(clip, kw)
+    sat = sse2 is not None and B < 4
+    sat_sweeps = sse2 == 1 or (B == 1 and (isolated or not pools))
+    cfg_eligible = sweep_plane_ok(B, clip.width) and (not pools or (bool(kw.get("dh") or kw.get("luma", True)) and planes[1][0] % 8 == 0))
+    padded_ok = lambda pw: pw % 8 == 0 and sweep_plane_ok(B, pool_stride(pw))  # noqa: E731  (fused_padded_plane_eligible)
+    fused, padded, marked = [False] * 3, [False] * 3, [False] * 3
+    eligible, hf = cfg_eligible, history_free(clip, kw)
+    if isolated:
+        eligible = True
+        hf = fresh or all(w % 32 == 0 for w, ho, on in planes if on)
+        for p, (pw, ho, on) in enumerate(planes):
+            if not on:
+                continue
+            fused[p] = sweep_plane_ok(B, pw)
+            if not fused[p] and parts_on and not fresh and parts_marked(B, pw):
+                fused[p] = marked[p] = True
+            if fresh and not fused[p] and padded_ok(pw):
+                fused[p] = padded[p] = True
+            eligible = eligible and fused[p]
+    elif not eligible and parts_on and not pools and parts_marked(B, clip.width):
+        eligible = True
+        marked = [on and pw == clip.width for pw, ho, on in planes] + [False] * (3 - np_)
+    info_eligible = cfg_eligible
+    if sat and not sat_sweeps:  # the pool kernels serve every plane in this arithmetic
+        eligible, info_eligible = False, False
+        fused, padded, marked = [False] * 3, [False] * 3, [False] * 3
+    elif isolated:
+        info_eligible = all(sweep_plane_ok(B, pw) or (fresh and padded_ok(pw)) for pw, ho, on in planes if on)
+    use_fused = eligible and not pool_mode
+    if pool_mode:  # the pool path serves every plane: nothing stays marked, and sn_info answers as for a clip without the option
+        marked = [False] * 3
+        if isolated:
+            fused = [False] * 3
+    if any(marked):
+        info_eligible = eligible
+    fused420 = use_fused and not isolated and pools
+    return dict(clip=clip, kw=kw, planes=planes, fresh=fresh, isolated=isolated, pools=pools, fused=fused, padded=padded, marked=marked,
+                use_fused=use_fused, fused420=fused420, uv=fused420 and uv_geometry(clip, kw), info_eligible=info_eligible, history_free=hf, sat=sat,
+                pool_mode=pool_mode)
+
+
+def sweeps_serve_all(plan):
+    """band_rows_available's condition on the planes: every processed plane has a whole-plane sweep (not the padded one)."""
+    if any(plan["marked"]) or plan["pool_mode"] or not plan["history_free"]:
+        return False
+    if plan["isolated"]:
+        return all(plan["fused"][p] and not plan["padded"][p] for p, (w, ho, on) in enumerate(plan["planes"]) if on)
+    return plan["use_fused"]
+
+
+def nr_min(plan):
+    return min(nr(ho) for w, ho, on in plan["planes"] if on)
+
+
+def band_count_auto(plan, n):
+    """band_count of an auto-mode launch of n frames without sn_debug_set_bands (its slots at hand): about 512 workgroups in
+    all, bands of at least kMinBandRows rows and of at least a quarter of the run-up, at least three bands by count."""
+    if not sweeps_serve_all(plan) or nr_min(plan) < 2 * MIN_BAND_ROWS:
+        return 0
+    nb = min(512 // n, nr_min(plan) // MIN_BAND_ROWS, 128)
+    if nb < 3:
+        return 0
+    quarter = BAND_WARM[plan["clip"].bytes] // 4
+    if nr_min(plan) // nb < quarter:
+        nb = nr_min(plan) // quarter
+    return nb if nb >= 2 else 0
+
+
+# sn_route.h prefer_pool's fitted constants, per sample size: seconds per pool element and frame, per pool row, per sweep row
+# (planes of more than 3840 columns: 8-bit only), per row of a coupled chroma sweep (8-bit: two sweeps; U and V as one: 1.9e-6)
+POOL_PER_ELEM = {1: 12.9e-12, 2: 19.4e-12, 4: 32.6e-12}
+POOL_PER_ROW = {1: 0.25e-6, 2: 0.22e-6, 4: 0.33e-6}
+SWEEP_ROW = {1: 2.6e-6, 2: 2.8e-6, 4: 4.3e-6}
+SWEEP_ROW_COUPLED = {1: 3.0e-6, 2: 3.15e-6, 4: 4.7e-6}
+
+
+def prefer_pool(plan, n, chroma_sweeps=0):
+    """prefer_pool for an auto-mode launch of n frames that is not cut into bands (policy SN_SMALL_AUTO, its slots at hand):
+    the estimate says the pool path is faster than the sweeps."""
+    if plan["pool_mode"] or not plan["history_free"]:
+        return False
+    B, planes = plan["clip"].bytes, plan["planes"]
+    fused = pool = 0.0
+    for p, (pw, ho, on) in enumerate(planes):
+        if not on:
+            continue
+        own = plan["isolated"]
+        stride = pool_stride(pw if own else planes[0][0])
+        b = bh(ho if own else planes[0][1])
+        rows = ho // 2
+        t_row = (3.8e-6 if stride > 3840 else SWEEP_ROW[1]) if B == 1 else SWEEP_ROW[B]
+        if plan["fused420"] and p > 0:
+            t_row = 1.9e-6 if B == 1 and plan["uv"] and chroma_sweeps == 0 else SWEEP_ROW_COUPLED[B]
+        fused += rows * t_row
+        b_run = rows + 2 if not own and rows + 2 < b else b
+        pool += b_run * (POOL_PER_ROW[B] + 0.036e-6 * ((stride + 1023) // 1024)) + 60e-6 + float(n) * stride * b_run * POOL_PER_ELEM[B]
+    return pool < fused
 
 
 # ---- the tables ------------------------------------------------------------------------------------------------------------------

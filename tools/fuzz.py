@@ -16,27 +16,13 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from avisynth_sangnom2_amd import ClipFormat, SangNom2, clip_format, synth  # noqa: E402
-from oracle.oracle import Config, Oracle  # noqa: E402
+from avisynth_sangnom2_amd import SangNom2, clip_format, synth  # noqa: E402
 from tests import packed_surface_cases as pc  # noqa: E402
-from tests import sse2_model as sm  # noqa: E402
+from tests.config_space import cfg_of, compose, reference  # noqa: E402,F401  (the reference's composition, shared with the covering table)
 from tests.util import to_host  # noqa: E402
 
 FORMATS = ["Y8", "Y8", "Y8", "Y10", "Y16", "Y32", "YUV420P8", "YUV420P8", "YUV420P16", "YUV422P8", "YUV444P8", "YUV444PS", "YUV420PS", "YUV420P10",
            "YUV420P12", "YUV422P10", "YUV422P10", "YUV422P12", "YUV422P16"]
-
-
-def cfg_of(clip, **kw):
-    return Config(width=clip.width, height=clip.height, bytes=clip.bytes, bits=clip.bits, planes=clip.planes, subw=clip.subw, subh=clip.subh, **kw)
-
-
-def reference(clip, opt, **kw):
-    """process(planes, parity) of one reference instance: the C oracle (opt=0) or the numpy model of the SSE2 path (opt=1)."""
-    if opt == 1:
-        m = sm.model_for(1, clip.width, clip.height, bytes=clip.bytes, bits=clip.bits, planes=clip.planes, subw=clip.subw, subh=clip.subh, **kw)
-        return lambda planes, parity: m.get_frame(planes, parity=parity)
-    o = Oracle(cfg_of(clip, **kw))
-    return lambda planes, parity: o.process(planes, parity=parity)
 
 
 def same(a, b):
@@ -94,23 +80,7 @@ def main():
         pattern = rng.choice(["noise", "noise", "checker", "edges", "sine"] + (["noise01", "noise01", "checker2"] if opt == 1 else []))
         frames = [synth.frame(clip, pattern, seed=rng.randint(0, 1 << 20)) for _ in range(nframes)]
         parity = [rng.randint(0, 1) for _ in range(nframes)]
-        # expected
-        if ext == "none":
-            ora = reference(clip, opt, **kw)
-            want = [ora(frames[f], parity[f]) for f in range(nframes)]
-        else:
-            per_plane = {}
-            want = []
-            for f in range(nframes):
-                outs = []
-                for p in range(clip.planes):
-                    pl = frames[f][p]
-                    yclip = ClipFormat(width=pl.shape[1], height=pl.shape[0], bytes=clip.bytes, bits=clip.bits)
-                    enabled = kw["luma"] if p == 0 else kw["chroma"]
-                    mk = lambda: reference(yclip, opt, order=kw["order"], aa=kw["aa"] if p == 0 else kw["aac"], dh=kw["dh"], luma=enabled)
-                    o = mk() if ext == "fresh" else per_plane.setdefault(p, mk())
-                    outs.append(o([pl], parity[f])[0])
-                want.append(outs)
+        want = compose(clip, frames, parity, kw, ext, opt)  # expected
         CURRENT[0] = f"{fmt} {w}x{h} {kw} ext={ext} way={way} nframes={nframes} opt={opt} sse2_sweeps={knob} column_parts={column_parts} pattern={pattern}"
         small = rng.choice([1, 0])  # SN_SMALL_SWEEP: the whole-plane sweeps, or auto mode's small-launch paths (bands, pool kernels)
         try:
