@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "sn_copier.h"
+#include "sn_pool_dispatch.h"
 #include "sn_route.h"
 #include "sn_sweep_args.h"
 #include "sn_surface_layout.h"

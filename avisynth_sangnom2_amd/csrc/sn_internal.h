@@ -123,8 +123,7 @@ hipError_t launch_pack(hipStream_t s, int packing, int bytes, int nframes, Plane
 hipError_t launch_assemble(hipStream_t s, const PlaneArgs& p, int bytes, int nframes);
 hipError_t launch_pool_plane(hipStream_t s, const PlaneArgs& p, const PoolArgs& pool, int bytes,
                              double threshold, int nframes, int slot0);
-int pool_chain_lanes(int bytes, int stride_e);  // passes one workgroup keeps in flight; 0: no chain for this pool
-int pool_chain_groups(int bytes, int stride_e, int want);  // workgroups per buffer the chain kernel can run for `want`
+// (pool_chain_lanes and pool_chain_groups, which pools a chain takes and over how many workgroups: sn_pool_dispatch.h)
 hipError_t launch_pool_prepare(hipStream_t s, const PlaneArgs& p, const PoolArgs& pool, int bytes, int nframes, int slot0);
 hipError_t launch_pool_finalize(hipStream_t s, const PlaneArgs& p, const PoolArgs& pool, int bytes, double threshold, int nframes,
                                 int slot0);

@@ -862,10 +862,7 @@ constexpr int kChainLag = 3;
 // chain runs twice as fast.  The halves are at different rows of different pool slots: each has its own pointers, fetch
 // ring, fresh-row count, and its loads, stores, ghost refresh and first-rows round are masked per half.  The mailbox is
 // indexed by the parity of the ROUND (both halves publish and receive at the same barrier), not of a pass's block.
-#ifndef SN_CHAIN8_THREADS
-#define SN_CHAIN8_THREADS 1024  // sixteen waves, four per SIMD: the two-pass body fits 128 registers (512 threads measured slower)
-#endif
-constexpr int kChain8Threads = SN_CHAIN8_THREADS;
+// (kChain8Threads, the workgroup of the two-pass body, is sn_pool_dispatch.h's: the chain rules below rest on it)
 
 // Round 3: SEVERAL workgroups per buffer (GROUPED).  One workgroup is bound by what its CU issues (profiles/r3_chain.md:
 // one VALU instruction per 4.7 cycles and SIMD where the instruction class's floor is 4.06), and a pass can only start
@@ -1644,13 +1641,7 @@ static hipError_t launch_pool_plane_t(hipStream_t st, const PlaneArgs& p, const 
 }
 
 // ---- the chain of a history-carrying stream: stage 1 of all passes, one stage 2, stage 3 of all passes ----
-int pool_chain_lanes(int bytes, int stride_e)
-{
-    if (stride_e < 64) return 0;
-    const int nw = v3c::strips_for(stride_e / 8);
-    if (bytes == 1) return nw <= kChain8Threads / 64 ? 2 * (kChain8Threads / 64 / nw) : 0;  // two passes per set of nw waves (k_smooth_u8_chain)
-    return nw <= kSmoothThreads / 128 ? kSmoothThreads / 64 / nw : 0;                     // at least two passes in flight
-}
+// pool_chain_lanes, chain_waves and pool_chain_groups are pure rules: sn_pool_dispatch.h
 
 template <class T, int A>
 static hipError_t launch_pool_prepare_t(hipStream_t st, const PlaneArgs& p, const PoolArgs& pool, int nframes, int slot0)
@@ -1691,24 +1682,6 @@ hipError_t launch_pool_finalize(hipStream_t st, const PlaneArgs& p, const PoolAr
     case 4: return launch_pool_finalize_t<float, 0>(st, p, pool, threshold, nframes, slot0);
     }
     return hipErrorInvalidValue;
-}
-
-// Workgroups per buffer a chain can be spread over (`want` or fewer).  8-bit: each gets 1 / groups of the sixteen waves
-// and needs at least one pair of passes (nw waves).  16-bit and float (one pass per wave): thirty-two waves in all, sixteen
-// per workgroup at most, and a workgroup needs a pass (nw waves).
-static int chain_waves(int bytes, int groups)
-{
-    const int all = bytes == 1 ? kChain8Threads / 64 : 2 * (kSmoothThreads / 64);
-    const int w = all / groups;
-    return w > kSmoothThreads / 64 ? kSmoothThreads / 64 : w;
-}
-int pool_chain_groups(int bytes, int stride_e, int want)
-{
-    if (want <= 1) return 1;
-    const int nw = v3c::strips_for(stride_e / 8);
-    int g = 1;
-    while (g * 2 <= want && g * 2 <= kChainMaxGroups && chain_waves(bytes, g * 2) >= nw) g *= 2;
-    return g;
 }
 
 __global__ void k_chain_redo_count(const uint32_t* fault, uint32_t* redone, uint32_t* host_mirror)

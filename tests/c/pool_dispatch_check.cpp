@@ -3,7 +3,16 @@
 // refuses strides above 8192) against boundaries written out by hand, and against the if-ladder the launcher had before the
 // rule was a function of its own -- restated below -- which also shows that the ladder's last branch, the kernels with NC
 // consecutive columns per thread (k_smooth<T, NC, A>, NC = 2, 4, 8), was never taken.
+//
+// The chain's rules of the same header -- pool_chain_lanes, chain_waves, pool_chain_groups -- against values written out by hand
+// on both sides of every boundary they have.
+//
+// `pool_dispatch_check query` reads lines of "bytes stride bh frames want" from stdin and prints, per line,
+// "schedule threads lds lds_attr lanes groups waves": pool_stage2_for(bytes, stride, bh, frames), pool_chain_lanes(bytes, stride),
+// pool_chain_groups(bytes, stride, want) and chain_waves(bytes, that answer) -- tests/test_pool_geometry_cpu.py holds the
+// restatement of tests/pool_geometry_cases.py against it.
 #include <stdio.h>
+#include <string.h>
 
 #include "sn_pool_dispatch.h"
 
@@ -70,8 +79,71 @@ static Old old_ladder(int bytes, int stride_e, int bh, int nframes)
     return {PoolSchedule::kNone, 0, 0, false, 0};
 }
 
-int main()
+static int query()
 {
+    static const char* const names[] = {"none", "strided", "x8", "strips", "refused"};
+    int bytes, se, bh, frames, want;
+    while (scanf("%d %d %d %d %d", &bytes, &se, &bh, &frames, &want) == 5) {
+        const PoolStage2 r = pool_stage2_for(bytes, se, bh, frames);
+        const int g = pool_chain_groups(bytes, se, want);
+        printf("%s %d %zu %d %d %d %d\n", names[(int)r.schedule], r.threads, r.lds, (int)r.lds_attr, pool_chain_lanes(bytes, se), g, chain_waves(bytes, g));
+    }
+    return 0;
+}
+
+// the chain's rules, by hand
+static void chain_rules()
+{
+    int bytes = 0, se = 0, bh = 0, frames = 0;
+    static_assert(kChain8Threads == 1024 && kSmoothThreads == 1024 && kChainMaxGroups == 8, "the values below are written for these");
+    // pool_chain_lanes.  Below 64 columns no chain, whatever the type
+    for (int b : {1, 2, 4}) {
+        bytes = b;
+        se = 32;
+        CHECK(pool_chain_lanes(b, 32) == 0);
+    }
+    // 8-bit: sixteen waves in sets of nw, two passes a set.  64 and 512 columns: one strip, 32 passes; 544: two strips, 16
+    CHECK(pool_chain_lanes(1, 64) == 32 && pool_chain_lanes(1, 512) == 32 && pool_chain_lanes(1, 544) == 16 && pool_chain_lanes(1, 960) == 16);
+    CHECK(pool_chain_lanes(1, 992) == 10 && pool_chain_lanes(1, 1472) == 8 && pool_chain_lanes(1, 1952) == 6);   // 3, 4, 5 strips: 5, 4, 3 sets
+    CHECK(pool_chain_lanes(1, 2432) == 4 && pool_chain_lanes(1, 2912) == 4 && pool_chain_lanes(1, 3840) == 4);     // 6, 7, 8 strips: two sets
+    CHECK(pool_chain_lanes(1, 3872) == 2 && pool_chain_lanes(1, 7232) == 2 && pool_chain_lanes(1, 7680) == 2);     // 9 .. 16 strips: one set
+    CHECK(pool_chain_lanes(1, 7712) == 0 && pool_chain_lanes(1, 8192) == 0);                                       // seventeen strips: none
+    // 16-bit and float: sixteen waves, one pass each, at least two passes: up to eight strips
+    for (int b : {2, 4}) {
+        bytes = b;
+        CHECK(pool_chain_lanes(b, 64) == 16 && pool_chain_lanes(b, 512) == 16 && pool_chain_lanes(b, 544) == 8 && pool_chain_lanes(b, 992) == 5);
+        CHECK(pool_chain_lanes(b, 1472) == 4 && pool_chain_lanes(b, 1952) == 3 && pool_chain_lanes(b, 2400) == 3 && pool_chain_lanes(b, 2432) == 2);
+        CHECK(pool_chain_lanes(b, 3392) == 2 && pool_chain_lanes(b, 3840) == 2 && pool_chain_lanes(b, 3872) == 0 && pool_chain_lanes(b, 8192) == 0);
+    }
+    // chain_waves: 8-bit sixteen waves shared out; the others thirty-two, sixteen a workgroup at most
+    bytes = 1;
+    CHECK(chain_waves(1, 1) == 16 && chain_waves(1, 2) == 8 && chain_waves(1, 4) == 4 && chain_waves(1, 8) == 2);
+    for (int b : {2, 4}) {
+        bytes = b;
+        CHECK(chain_waves(b, 1) == 16 && chain_waves(b, 2) == 16 && chain_waves(b, 4) == 8 && chain_waves(b, 8) == 4);
+    }
+    // pool_chain_groups: the largest power of two <= want, <= 8, whose workgroups still hold a set of nw waves
+    for (int b : {1, 2, 4}) {
+        bytes = b;
+        for (int want : {-1, 0, 1}) CHECK(pool_chain_groups(b, 512, want) == 1);
+        CHECK(pool_chain_groups(b, 512, 2) == 2 && pool_chain_groups(b, 512, 3) == 2 && pool_chain_groups(b, 512, 4) == 4);
+        CHECK(pool_chain_groups(b, 512, 7) == 4 && pool_chain_groups(b, 512, 8) == 8 && pool_chain_groups(b, 512, 9) == 8 && pool_chain_groups(b, 512, 64) == 8);
+    }
+    bytes = 1;  // 8-bit: 2 strips -> 8 (two waves each), 3 and 4 strips -> 4, 5 .. 8 strips -> 2, 9 and more -> 1
+    CHECK(pool_chain_groups(1, 544, 8) == 8 && pool_chain_groups(1, 960, 8) == 8 && pool_chain_groups(1, 992, 8) == 4 && pool_chain_groups(1, 1920, 8) == 4);
+    CHECK(pool_chain_groups(1, 1952, 8) == 2 && pool_chain_groups(1, 3840, 8) == 2 && pool_chain_groups(1, 3872, 8) == 1 && pool_chain_groups(1, 7680, 8) == 1);
+    CHECK(pool_chain_groups(1, 992, 2) == 2 && pool_chain_groups(1, 1952, 4) == 2 && pool_chain_groups(1, 3872, 2) == 1);
+    for (int b : {2, 4}) {  // 16-bit and float: up to 4 strips -> 8 (four waves each), 5 .. 8 strips -> 4
+        bytes = b;
+        CHECK(pool_chain_groups(b, 544, 8) == 8 && pool_chain_groups(b, 1472, 8) == 8 && pool_chain_groups(b, 1920, 8) == 8);
+        CHECK(pool_chain_groups(b, 1952, 8) == 4 && pool_chain_groups(b, 3840, 8) == 4 && pool_chain_groups(b, 3840, 2) == 2);
+    }
+}
+
+int main(int argc, char** argv)
+{
+    if (argc > 1 && strcmp(argv[1], "query") == 0) return query();
+    chain_rules();
     int reached[5][3] = {};  // [schedule][sample type]
     for (int bytes : {1, 2, 4}) {
         const int ti = bytes == 1 ? 0 : bytes == 2 ? 1 : 2;

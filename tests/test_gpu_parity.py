@@ -78,7 +78,9 @@ def test_host_frames_match_oracle(hip_lib, fmt, w, h, kw, pattern):
 # (sn_pool_dispatch.h), in each sample size: 256 and 480 columns (eight columns per thread, a barrier per row), 512 (strips:
 # one wave, no mailbox), 544 (two waves; fifteen smoothed rows, so the ghost lanes are refreshed twice), 7680 (sixteen waves,
 # 1 024 threads), 7712 and 8192 (eight columns per thread again, above the strips; at 8192 the 16-bit and float LDS lines
-# take 64 KiB, which a kernel has to ask for).
+# take 64 KiB, which a kernel has to ask for).  These are hand-picked points; the geometry of stage 2 and of the chains is walked
+# in tests/test_pool_geometry_gpu.py, from a table derived from the dispatch rules (tests/pool_geometry_cases.py): every strip
+# count, right-edge lane, row phase, x8 wave count and chain workgroup count, pools compared as well as pixels.
 POOL_STAGE2_CASES = [(fmt, w, h, {}) for fmt in ("Y8", "Y16", "Y32")
                      for w, h in ((256, 32), (480, 32), (512, 32), (544, 32), (7680, 24), (7712, 24), (8192, 24))]
 
