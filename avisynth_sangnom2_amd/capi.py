@@ -34,9 +34,10 @@ EXPORTS = (
     "sn_process_device_surfaces", "sn_aa_process_device_surfaces", "sn_get_surface_info", "sn_aa_get_surface_info",
     "sn_aa_get_reduce", "sn_reduce_device", "sn_aa_get_mask", "sn_mask_merge_device",
     "sn_aa_get_mask_ex", "sn_mask_merge_luma_device",
+    "sn_aa_get_sharpen", "sn_contra_sharpen_device",
 )
 # ... and the ones whose names end in a digit
-EXPORTS_NUMBERED = ("sn_aa_create_ex2", "sn_aa_create_ex3", "sn_aa_create_ex4")
+EXPORTS_NUMBERED = ("sn_aa_create_ex2", "sn_aa_create_ex3", "sn_aa_create_ex4", "sn_aa_create_ex5")
 
 # sn_aa_options.reduce: the anti-aliasing call with dh returns the frame at source size (sangnom_hip.h has the arithmetic)
 SN_AA_REDUCE_NONE, SN_AA_REDUCE_TENT, SN_AA_REDUCE_HALFBAND = 0, 1, 2
@@ -121,6 +122,16 @@ def aa_mask_ex(chroma="own") -> "SnAAMaskEx":
     if not isinstance(chroma, str) or chroma not in MASK_CHROMA:
         raise ValueError("mask_chroma must be 'own' or 'luma'")
     return SnAAMaskEx(struct_size=ctypes.sizeof(SnAAMaskEx), chroma=MASK_CHROMA[chroma])
+
+
+class SnAASharpen(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_int32), ("amount", ctypes.c_int32), ("chroma", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
+
+
+def aa_sharpen(amount=None, chroma=False) -> "SnAASharpen":
+    """sn_aa_sharpen: amount = None or 0 (off) or 1..255 (64 = unity); chroma = whether processed chroma planes are sharpened
+    too.  The library checks the values."""
+    return SnAASharpen(struct_size=ctypes.sizeof(SnAASharpen), amount=int(amount or 0), chroma=int(bool(chroma)))
 
 
 class SnPartsInfo(ctypes.Structure):
@@ -231,6 +242,10 @@ def load():
     L.sn_aa_create_ex4.argtypes = [ctypes.POINTER(SnConfig), ctypes.POINTER(SnPolicy), ctypes.POINTER(SnOptions), ctypes.POINTER(SnAAOptions),
                                    ctypes.POINTER(SnAAMask), ctypes.POINTER(SnAAMaskEx), ctypes.POINTER(vp)]
     L.sn_aa_get_mask_ex.argtypes = [vp, ctypes.POINTER(SnAAMaskEx)]
+    L.sn_aa_create_ex5.argtypes = [ctypes.POINTER(SnConfig), ctypes.POINTER(SnPolicy), ctypes.POINTER(SnOptions), ctypes.POINTER(SnAAOptions),
+                                   ctypes.POINTER(SnAAMask), ctypes.POINTER(SnAAMaskEx), ctypes.POINTER(SnAASharpen), ctypes.POINTER(vp)]
+    L.sn_aa_get_sharpen.argtypes = [vp, ctypes.POINTER(SnAASharpen)]
+    L.sn_contra_sharpen_device.argtypes = [vp, i32, i32, vp, i64, i32, vp, i64, i32, i32, i32, vp, i64, i32]
     L.sn_mask_merge_luma_device.argtypes = [vp, ctypes.POINTER(SnAAMask), i32, vp, i64, i32, i32, i32, p3v, p3l, p3i, p3v, p3l, p3i, i32, i32,
                                             p3v, p3l, p3i]
     L.sn_mask_merge_device.argtypes = [vp, ctypes.POINTER(SnAAMask), i32, vp, i64, i32, vp, i64, i32, i32, i32, vp, i64, i32]

@@ -2187,6 +2187,27 @@ int sn_mask_merge_device(sn_context* h, const sn_aa_mask* mask, int32_t nframes,
     return SN_OK;
 }
 
+int sn_contra_sharpen_device(sn_context* h, int32_t amount, int32_t nframes, const void* src, int64_t sfs, int32_t sp, const void* aa, int64_t afs, int32_t ap,
+                             int32_t width, int32_t height, void* dst, int64_t dfs, int32_t dp)
+{
+    Context* c = reinterpret_cast<Context*>(h);
+    if (!c) return sn::fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    const int B = c->cfg.bytes_per_sample;
+    if (amount < 1 || amount > 255) return sn::fail(c, SN_ERR_INVALID_ARG, "sn_contra_sharpen_device: amount must be 1..255");
+    if (!src || !aa || !dst || nframes < 0 || width <= 0 || height <= 0 || width > INT32_MAX / 8 || height > INT32_MAX / 2)
+        return sn::fail(c, SN_ERR_INVALID_ARG, "sn_contra_sharpen_device: bad pointer or size");
+    if (sp < width * B || ap < width * B || dp < width * B || sp % B || ap % B || dp % B || sfs % B || afs % B || dfs % B || (uintptr_t)src % B ||
+        (uintptr_t)aa % B || (uintptr_t)dst % B)
+        return sn::fail(c, SN_ERR_INVALID_ARG, "sn_contra_sharpen_device: pitch smaller than the row or misaligned");
+    if (dst == aa || dst == src)  // the stencil reads neighbours of both planes: no workgroup may overwrite what another still reads
+        return sn::fail(c, SN_ERR_INVALID_ARG, "sn_contra_sharpen_device: dst must overlap neither src nor aa");
+    SN_HIP(c, hipSetDevice(c->device));
+    SN_HIP(c, sn::launch_contra_sharpen(c->stream, B, c->cfg.bits_per_sample, amount, nframes, sn::PlaneView{static_cast<const uint8_t*>(src), sfs, sp},
+                                        sn::PlaneView{static_cast<const uint8_t*>(aa), afs, ap}, width, height,
+                                        sn::PlaneViewW{static_cast<uint8_t*>(dst), dfs, dp}));
+    return SN_OK;
+}
+
 int sn_mask_merge_luma_device(sn_context* h, const sn_aa_mask* mask, int32_t nframes, const void* luma, int64_t lfs, int32_t lp, int32_t sub_w, int32_t sub_h,
                               const void* const src[2], const int64_t sfs[2], const int32_t sp[2], const void* const aa[2], const int64_t afs[2],
                               const int32_t ap[2], int32_t width, int32_t height, void* const dst[2], const int64_t dfs[2], const int32_t dp[2])
@@ -2407,6 +2428,9 @@ int sn_debug_read_coupled_rows(sn_context* h, int32_t which, void* host_dst, siz
 // With a reduction (sn_aa_options.reduce, dh only) the second pass writes a fourth intermediate E in its own geometry
 // (ow x oh) and sn_reduce.hip brings it to the destination, which has the clip's geometry again (dstw x dsth): nine plane
 // sizes of intermediates per processed plane and frame instead of five.
+// With a contra-sharpening (sn_aa_sharpen.amount) the last step -- the second pass, or the reduction -- writes a sharpened
+// plane into one more intermediate of the destination's geometry and sn_sharpen.hip writes the destination from it and the
+// source: one plane size more per sharpened plane and frame.  The edge mask follows, unchanged.
 struct sn_aa_context {
     sn_config cfg{};
     sn_context* first = nullptr;   // the turned clip
@@ -2428,6 +2452,8 @@ struct sn_aa_context {
     int reduce = SN_AA_REDUCE_NONE;                        // dh only: the second pass's output goes through sn_reduce.hip on its way out
     sn_aa_mask mask{};                                     // kind != 0: the result is merged into the source through an edge mask (sn_mask.hip), last
     int mask_chroma = SN_AA_MASK_CHROMA_OWN;               // ... SN_AA_MASK_CHROMA_LUMA: planes 1 and 2 through the source luma plane's mask
+    sn_aa_sharpen sharpen{};                               // amount != 0: the result is contra-sharpened (sn_sharpen.hip) behind the last step, before the mask
+    bool sharpened[3] = {false, false, false};             // ... the planes it applies to: processed, and plane 0 unless sharpen.chroma
     int dstw[3] = {0, 0, 0}, dsth[3] = {0, 0, 0};          // the destination's geometry per plane: ow x oh, with reduce w x h
     int dstpitch[3] = {0, 0, 0};                           // ... of the library's own buffers of that geometry (host groups)
     int64_t dstbytes[3] = {0, 0, 0};
@@ -2436,6 +2462,7 @@ struct sn_aa_context {
     uint8_t* d_u1[3] = {nullptr, nullptr, nullptr};   // turned: its output (dh: twice as high)
     uint8_t* d_t2[3] = {nullptr, nullptr, nullptr};   // turned back: input of the second pass (kept lines only; dh: every line, twice as wide)
     uint8_t* d_e[3] = {nullptr, nullptr, nullptr};    // reduce: the second pass's output, opitch x oh
+    uint8_t* d_s[3] = {nullptr, nullptr, nullptr};    // sharpen: the last step's output of a sharpened plane, dstpitch x dsth
     // host frames: `per_group` slots form a group whose frames one batch works on; the ring's groups, then one group of
     // one slot for the synchronous call
     struct Slot {
@@ -2505,16 +2532,18 @@ static int aa_ensure_intermediates(sn_aa_context* a, int frames)
     if (frames <= a->cap) return SN_OK;
     int64_t per_frame = 0;
     for (int p = 0; p < a->planes; ++p)
-        if (a->process[p]) per_frame += a->tbytes[p] + a->u1bytes[p] + a->t2bytes[p] + (a->reduce ? a->obytes[p] : 0);
+        if (a->process[p]) per_frame += a->tbytes[p] + a->u1bytes[p] + a->t2bytes[p] + (a->reduce ? a->obytes[p] : 0) + (a->sharpened[p] ? a->dstbytes[p] : 0);
     const int64_t fit = per_frame > 0 ? scratch_budget(reinterpret_cast<Context*>(a->first)) / per_frame : frames;
     const int cap = (int)(fit < 1 ? 1 : fit < frames ? fit : frames);
     if (cap <= a->cap) return SN_OK;
     SN_AA_HIP(hipStreamSynchronize(a->stream));
     for (int p = 0; p < a->planes; ++p) {
         if (!a->process[p]) continue;  // copied from source to destination: no turn, no pass, no intermediate
-        const size_t nb[4] = {(size_t)a->tbytes[p] * cap, (size_t)a->u1bytes[p] * cap, (size_t)a->t2bytes[p] * cap, (size_t)a->obytes[p] * cap};
-        uint8_t** q[4] = {&a->d_t1[p], &a->d_u1[p], &a->d_t2[p], &a->d_e[p]};
-        for (int k = 0; k < (a->reduce ? 4 : 3); ++k) {
+        const size_t nb[5] = {(size_t)a->tbytes[p] * cap, (size_t)a->u1bytes[p] * cap, (size_t)a->t2bytes[p] * cap, (size_t)a->obytes[p] * cap,
+                              (size_t)a->dstbytes[p] * cap};
+        uint8_t** q[5] = {&a->d_t1[p], &a->d_u1[p], &a->d_t2[p], &a->d_e[p], &a->d_s[p]};
+        for (int k = 0; k < 5; ++k) {
+            if (k == 3 ? !a->reduce : k == 4 ? !a->sharpened[p] : false) continue;
             if (*q[k]) SN_AA_HIP(hipFree(*q[k]));
             *q[k] = nullptr;
             SN_AA_HIP(hipMalloc(reinterpret_cast<void**>(q[k]), nb[k]));
@@ -2536,7 +2565,7 @@ void sn_aa_destroy(sn_aa_context* a)
     if (a->second) sn_destroy(a->second);
     if (a->first) sn_destroy(a->first);  // owns the stream unless the caller gave one
     for (int p = 0; p < 3; ++p)
-        for (uint8_t* q : {a->d_t1[p], a->d_u1[p], a->d_t2[p], a->d_e[p]})
+        for (uint8_t* q : {a->d_t1[p], a->d_u1[p], a->d_t2[p], a->d_e[p], a->d_s[p]})
             if (q) (void)hipFree(q);
     for (const sn::PlaneViewW& q : {a->uv.in[0], a->uv.in[1], a->uv.out[0], a->uv.out[1], a->uv.y, a->uv.yo})
         if (q.base) (void)hipFree(q.base);
@@ -2568,6 +2597,12 @@ int sn_aa_create_ex3(const sn_config* cfg, const sn_policy* policy, const sn_opt
 
 int sn_aa_create_ex4(const sn_config* cfg, const sn_policy* policy, const sn_options* options, const sn_aa_options* aa_options, const sn_aa_mask* mask,
                      const sn_aa_mask_ex* mask_ex, sn_aa_context** out)
+{
+    return sn_aa_create_ex5(cfg, policy, options, aa_options, mask, mask_ex, nullptr, out);
+}
+
+int sn_aa_create_ex5(const sn_config* cfg, const sn_policy* policy, const sn_options* options, const sn_aa_options* aa_options, const sn_aa_mask* mask,
+                     const sn_aa_mask_ex* mask_ex, const sn_aa_sharpen* sharpen, sn_aa_context** out)
 {
     auto fail_aa = [](sn_aa_context* a, int code, const std::string& msg) {
         g_aa_error = msg;
@@ -2612,9 +2647,24 @@ int sn_aa_create_ex4(const sn_config* cfg, const sn_policy* policy, const sn_opt
     // the source luma plane reaches the device only where it is processed (the host routes upload no other plane)
     if (mask_chroma == SN_AA_MASK_CHROMA_LUMA && cfg->num_planes >= 3 && !cfg->dh && !cfg->luma && cfg->chroma)
         return fail_aa(nullptr, SN_ERR_CONFIG, "SangNomAA: a luma-derived chroma mask needs luma processed (luma=true)");
+    sn_aa_sharpen use_sharpen{};
+    use_sharpen.struct_size = (int32_t)sizeof(sn_aa_sharpen);
+    if (sharpen) {
+        if (sharpen->struct_size != (int32_t)sizeof(sn_aa_sharpen)) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_aa_sharpen.struct_size mismatch");
+        if (sharpen->amount < 0 || sharpen->amount > 255) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_aa_sharpen.amount must be 0 (off) or 1..255");
+        if (sharpen->amount) {  // with amount 0 the fields below it are ignored
+            if (sharpen->chroma < 0 || sharpen->chroma > 1) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_aa_sharpen.chroma must be 0 or 1");
+            for (int32_t r : sharpen->reserved)
+                if (r) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_aa_sharpen.reserved must be zero");
+            use_sharpen.amount = sharpen->amount, use_sharpen.chroma = sharpen->chroma;
+        }
+    }
+    if (use_sharpen.amount && cfg->dh && !reduce)
+        return fail_aa(nullptr, SN_ERR_CONFIG, "SangNomAA: sharpen needs the frame at source size (dh=false, or dh=true with reduce)");
     sn_aa_context* a = new (std::nothrow) sn_aa_context();
     if (!a) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "out of host memory");
     a->cfg = *cfg;
+    a->sharpen = use_sharpen;
     a->reduce = reduce;
     a->mask = use_mask;
     a->mask_chroma = mask_chroma;
@@ -2669,6 +2719,7 @@ int sn_aa_create_ex4(const sn_config* cfg, const sn_policy* policy, const sn_opt
         a->dsth[p] = reduce ? a->h[p] : a->oh[p];
         a->dstpitch[p] = reduce ? a->pitch[p] : a->opitch[p];
         a->dstbytes[p] = reduce ? a->cbytes[p] : a->obytes[p];
+        a->sharpened[p] = use_sharpen.amount && a->process[p] && (p == 0 || use_sharpen.chroma);
     }
     if (int rc2 = aa_ensure_intermediates(a, a->max_batch)) return fail_aa(a, rc2, a->err);
     *out = a;
@@ -2683,7 +2734,9 @@ static int aa_run(sn_aa_context* a, int n, const sn::PlaneView src[3], const sn:
     const int B = a->cfg.bytes_per_sample;
     hipStream_t st = a->stream;
     // the intermediates of a chunk: the turned source, the first pass's output, that turned back, the second pass's output of a reduce
-    sn::PlaneViewW t1[3], u1[3], t2[3], e[3];
+    // ... and, where a plane is contra-sharpened, the last step's output: that step writes `last`, the sharpening the destination
+    sn::PlaneViewW t1[3], u1[3], t2[3], e[3], last[3];
+    for (int p = 0; p < 3; ++p) last[p] = a->sharpened[p] ? sn::PlaneViewW{a->d_s[p], a->dstbytes[p], a->dstpitch[p]} : dst[p];
     for (int p = 0; p < 3; ++p) {
         t1[p] = sn::PlaneViewW{a->d_t1[p], a->tbytes[p], a->tpitch[p]}, u1[p] = sn::PlaneViewW{a->d_u1[p], a->u1bytes[p], a->tpitch[p]};
         t2[p] = sn::PlaneViewW{a->d_t2[p], a->t2bytes[p], a->t2pitch[p]}, e[p] = sn::PlaneViewW{a->d_e[p], a->obytes[p], a->opitch[p]};
@@ -2692,7 +2745,7 @@ static int aa_run(sn_aa_context* a, int n, const sn::PlaneView src[3], const sn:
     const void* s1[3] = {src[0].base, src[1].base, src[2].base};
     void* d1[3] = {dst[0].base, dst[1].base, dst[2].base};
     const void* s2[3] = {src[0].base, src[1].base, src[2].base};
-    const PlaneArrays out(src, dst);  // (the destination's frame strides and pitches as run_batch takes them)
+    const PlaneArrays out(src, last);  // (the last step's frame strides and pitches as run_batch takes them)
     for (int p = 0; p < a->planes; ++p)
         if (a->process[p]) s1[p] = a->d_t1[p], d1[p] = a->d_u1[p], s2[p] = a->d_t2[p];
     for (int f0 = 0; f0 < n; f0 += a->cap) {
@@ -2719,7 +2772,16 @@ static int aa_run(sn_aa_context* a, int n, const sn::PlaneView src[3], const sn:
         SN_AA_SN(a->first, run_batch(c1, st, 0, m, s1, a->tbytes, a->tpitch, d1, a->u1bytes, a->tpitch, par));
         if (int rc = turns(1)) return rc;
         void* d2[3] = {nullptr, nullptr, nullptr};
-        for (int p = 0; p < a->planes; ++p) d2[p] = dst[p].at(f0).base;
+        for (int p = 0; p < a->planes; ++p) d2[p] = a->sharpened[p] ? last[p].base : dst[p].at(f0).base;  // (an intermediate holds the chunk from its frame 0)
+        // the contra-sharpening, behind the last step: the destination from the source and that step's output; one launch per sharpened plane
+        auto sharpened = [&]() -> int {
+            for (int p = 0; p < a->planes; ++p) {
+                if (!a->sharpened[p]) continue;
+                SN_AA_HIP(sn::launch_contra_sharpen(st, B, a->cfg.bits_per_sample, a->sharpen.amount, m, src[p].at(f0), last[p], a->w[p], a->h[p],
+                                                    dst[p].at(f0)));
+            }
+            return SN_OK;
+        };
         // the edge mask, last: the chunk's result is merged into the source through the source's own mask, in place on the
         // destination (which has the source's size: creation has seen to it); one launch per processed plane
         auto masked = [&]() -> int {
@@ -2740,6 +2802,7 @@ static int aa_run(sn_aa_context* a, int n, const sn::PlaneView src[3], const sn:
         };
         if (!a->reduce) {
             SN_AA_SN(a->second, run_batch(c2, st, 0, m, s2, a->t2bytes, a->t2pitch, d2, out.dfs, out.dp, par));
+            if (int rc = sharpened()) return rc;
             if (int rc = masked()) return rc;
             continue;
         }
@@ -2751,9 +2814,10 @@ static int aa_run(sn_aa_context* a, int n, const sn::PlaneView src[3], const sn:
             const sn::FieldRun run = sn::field_run(par, g0, m, [c2](int q) { return sn::field_offset(c2->cfg.order, q); });
             for (int p = 0; p < a->planes; ++p)
                 SN_AA_HIP(sn::launch_reduce(st, B, a->cfg.bits_per_sample, a->reduce, run.end - g0, e[p].at(g0), a->w[p], a->h[p], 1 - run.offset, run.offset,
-                                            dst[p].at(f0 + g0)));
+                                            a->sharpened[p] ? last[p].at(g0) : dst[p].at(f0 + g0)));
             g0 = run.end;
         }
+        if (int rc = sharpened()) return rc;
         if (int rc = masked()) return rc;
     }
     return SN_OK;
@@ -2886,6 +2950,15 @@ int sn_aa_get_mask_ex(sn_aa_context* a, sn_aa_mask_ex* out)
     *out = sn_aa_mask_ex{};
     out->struct_size = (int32_t)sizeof(sn_aa_mask_ex);
     out->chroma = a->mask_chroma;
+    return SN_OK;
+}
+
+int sn_aa_get_sharpen(sn_aa_context* a, sn_aa_sharpen* out)
+{
+    if (!a) return aa_fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    if (!out || out->struct_size != (int32_t)sizeof(sn_aa_sharpen))
+        return aa_fail(a, SN_ERR_INVALID_ARG, "out is NULL or sn_aa_sharpen.struct_size mismatch");
+    *out = a->sharpen;
     return SN_OK;
 }
 

@@ -101,6 +101,11 @@ hipError_t launch_mask_merge(hipStream_t s, int bytes, int bits, int lo, int hi,
 hipError_t launch_mask_merge_luma(hipStream_t s, int bytes, int bits, int lo, int hi, int expand, int nframes, PlaneView luma, int sub_w, int sub_h,
                                   int planes, const PlaneView src[2], const PlaneView aa[2], int w, int h, const PlaneViewW dst[2]);
 
+// sn_sharpen.hip: the contra-sharpening of the anti-aliasing call (sangnom_hip.h, "Contra-sharpening", has the arithmetic).
+// aa (w x h, the call's result) is sharpened by amount / 64 (1..255) of an unsharp mask, limited by what src - aa allows
+// over 3 x 3, and written to dst.  dst must overlap neither src nor aa.
+hipError_t launch_contra_sharpen(hipStream_t s, int bytes, int bits, int amount, int nframes, PlaneView src, PlaneView aa, int w, int h, PlaneViewW dst);
+
 // sn_uv.hip: semi-planar chroma (a UV plane of U,V sample pairs: NV12 / P016 / NV16 / NV24) <-> a U and a V plane of cw x h
 // samples each.  line_parity 0 / 1: only the lines of that parity are read and written (the lines the pass that follows
 // keeps), < 0: all of them.  One side is never written: split reads uv, merge reads u and v.

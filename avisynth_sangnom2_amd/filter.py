@@ -328,6 +328,19 @@ class SangNom2:
                                                    W, H, dst.data_ptr(), dst.stride(0) * B, dst.stride(1) * B))
         return dst
 
+    def contra_sharpen(self, src, aa, dst, amount: int):
+        """sn_contra_sharpen_device: aa [N, H, W] (a filtered plane) is sharpened by amount / 64 (1..255) of an unsharp mask,
+        limited by what src - aa allows over 3 x 3, and written to dst (sangnom_hip.h, "Contra-sharpening").  dst must overlap
+        neither src nor aa.  Torch tensors on the device; asynchronous on the context's stream."""
+        B = self.clip.bytes
+        N, H, W = dst.shape
+        for t in (src, aa, dst):
+            if tuple(t.shape) != (N, H, W) or t.stride(2) != 1 or t.element_size() != B:
+                raise ValueError("contra_sharpen: src, aa and dst must be [N, H, W], x-contiguous and of the clip's sample type")
+        self._check(self._lib.sn_contra_sharpen_device(self._h, int(amount), N, src.data_ptr(), src.stride(0) * B, src.stride(1) * B, aa.data_ptr(),
+                                                       aa.stride(0) * B, aa.stride(1) * B, W, H, dst.data_ptr(), dst.stride(0) * B, dst.stride(1) * B))
+        return dst
+
     def mask_merge_luma(self, luma, src, aa, dst, lo: int, hi: int, expand: int = 1, sub_w: int = 1, sub_h: int = 1):
         """sn_mask_merge_luma_device: the Sobel edge mask of luma [N, H << sub_h, W << sub_w], reduced to chroma's geometry
         by the block mean, merges aa into src.  src, aa and dst are one tensor [N, H, W] or a pair of them (U and V in one
@@ -446,12 +459,15 @@ class _AAContext:
     mask=(lo, hi), mask_expand=0 | 1 (without dh, or with dh and reduce): the result is merged into the source through a Sobel
     edge mask of the source (sangnom_hip.h, "Edge mask"): flat areas and texture keep the source's samples.
     mask_chroma="own" | "luma": every processed plane through its own mask (the default), or chroma through the mask of the
-    source luma plane reduced to chroma's geometry, as anti-aliasing scripts do."""
+    source luma plane reduced to chroma's geometry, as anti-aliasing scripts do.
+    sharpen=None | 1..255 (64 = unity), sharpen_chroma=False (without dh, or with dh and reduce): the result is contra-sharpened
+    behind the last step and before the mask (sangnom_hip.h, "Contra-sharpening"): an unsharp mask, allowed only as far as the
+    filter changed the picture and only towards the source.  Plane 0, or every processed plane with sharpen_chroma."""
 
     def __init__(self, clip: ClipFormat, order: int = 1, aa: int = 48, aac: int = 0, luma: bool = True, chroma: bool = True,
                  device: int = 0, isolated_planes: bool = False, fresh_pool: bool = False, opt: int = -1, max_batch: int = 1,
                  host_depth: int = 0, stream: int | None = None, dh: bool = False, column_parts: int = 0, reduce=0, mask=None, mask_expand: int = 1,
-                 mask_chroma="own", **policy_kw):
+                 mask_chroma="own", sharpen=None, sharpen_chroma: bool = False, **policy_kw):
         if opt < -1 or opt > 1:
             raise SangNomError(capi.SN_ERR_CONFIG, "SangNom2: opt must be between -1..2.")  # sic, SangNom2.cpp:420
         self.clip = clip
@@ -460,6 +476,7 @@ class _AAContext:
         self.reduce = aopts.reduce
         amask = capi.aa_mask(mask, mask_expand)  # mask=(lo, hi): the result goes into the source through the source's edge mask
         amask_ex = capi.aa_mask_ex(mask_chroma)
+        asharpen = capi.aa_sharpen(sharpen, sharpen_chroma)
         self.max_batch = max_batch
         self._lib = capi.load()
         cfg = capi.SnConfig(
@@ -470,8 +487,8 @@ class _AAContext:
         self._h = ctypes.c_void_p()
         pol = capi.policy(**{k: policy_kw.get(k) for k in ("small_launches", "chain", "copy_threads", "scratch_budget_mb", "chroma_sweeps", "sse2_sweeps")})
         opts = capi.options(capi.arithmetic_of_opt(opt), column_parts=column_parts)
-        rc = self._lib.sn_aa_create_ex4(ctypes.byref(cfg), ctypes.byref(pol), ctypes.byref(opts), ctypes.byref(aopts), ctypes.byref(amask),
-                                        ctypes.byref(amask_ex), ctypes.byref(self._h))
+        rc = self._lib.sn_aa_create_ex5(ctypes.byref(cfg), ctypes.byref(pol), ctypes.byref(opts), ctypes.byref(aopts), ctypes.byref(amask),
+                                        ctypes.byref(amask_ex), ctypes.byref(asharpen), ctypes.byref(self._h))
         if rc != capi.SN_OK:
             self._h = None
             raise SangNomError(rc, self._lib.sn_aa_last_error(None).decode())
@@ -525,6 +542,13 @@ class _AAContext:
         """sn_aa_get_mask_ex: which mask merges chroma in this context."""
         m = capi.SnAAMaskEx(struct_size=ctypes.sizeof(capi.SnAAMaskEx))
         self._check(self._lib.sn_aa_get_mask_ex(self._h, ctypes.byref(m)))
+        return m
+
+    @property
+    def sharpen(self) -> capi.SnAASharpen:
+        """sn_aa_get_sharpen: the contra-sharpening of this context (amount 0 when it is off)."""
+        m = capi.SnAASharpen(struct_size=ctypes.sizeof(capi.SnAASharpen))
+        self._check(self._lib.sn_aa_get_sharpen(self._h, ctypes.byref(m)))
         return m
 
     def info(self, pass_: int) -> capi.SnInfo:

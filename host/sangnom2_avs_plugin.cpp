@@ -107,6 +107,9 @@ AVSValue __cdecl Create_SangNom2HIP(AVSValue args, void*, IScriptEnvironment* en
 // source, thresholds mlo <= mhi (0..255, defaults 8 and 32) and mexpand (0 | 1, default 1); the defaults are starting values
 // that nobody has tuned on real footage.  mluma=true: chroma is merged through the luma plane's mask (reduced to chroma's
 // geometry) instead of its own, as anti-aliasing scripts do; needs luma=true.
+// sharp=1..255 (default 0: off; at source size): the result is contra-sharpened behind the last step and before the mask -- an
+// unsharp mask of strength sharp / 64, allowed only as far as the filter changed the picture and only towards the source;
+// sharpc=true: every processed plane, not luma alone.  64 is a starting value that nobody has tuned on real footage.
 class SangNomAA : public GenericVideoFilter {
     sangnom::AAFilter<AvsHost> impl_;
 
@@ -139,6 +142,8 @@ AVSValue __cdecl Create_SangNomAA(AVSValue args, void*, IScriptEnvironment* env)
     a.mask_hi = args[15].AsInt(32);
     a.mask_expand = args[16].AsInt(1);
     a.mask_luma = args[17].AsBool(false);
+    a.sharpen = args[18].AsInt(0);
+    a.sharpen_chroma = args[19].AsBool(false);
     return new SangNomAA(args[0].AsClip(), a, env);
 }
 
@@ -162,7 +167,7 @@ extern "C" __declspec(dllexport) const char* __stdcall AvisynthPluginInit3(IScri
     env->AddFunction("SangNom", "c[order]i[aa]i[opt]i", Create_SangNom, 0);                                        // :482
     env->AddFunction("SangNom2HIP", "c[order]i[aa]i[aac]i[threads]i[dh]b[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i[device]i",
                      Create_SangNom2HIP, 0);
-    env->AddFunction("SangNomAA", "c[order]i[aa]i[aac]i[device]i[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i[dh]b[reduce]i[mask]b[mlo]i[mhi]i[mexpand]i[mluma]b",
+    env->AddFunction("SangNomAA", "c[order]i[aa]i[aac]i[device]i[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i[dh]b[reduce]i[mask]b[mlo]i[mhi]i[mexpand]i[mluma]b[sharp]i[sharpc]b",
                      Create_SangNomAA, 0);
     return "SangNom2";
 }

@@ -42,6 +42,8 @@ struct Args {  // SangNom2(clip, order, aa, aac, threads, dh, luma, chroma, opt)
     bool mask = false;      // SangNomAA only, at source size: the result is merged into the source through the source's Sobel edge mask
     int mask_lo = 8, mask_hi = 32, mask_expand = 1;  // ... sn_aa_mask.lo / hi / expand; starting values, not tuned on real footage
     bool mask_luma = false;  // ... chroma through the source luma plane's mask (sn_aa_mask_ex.chroma = SN_AA_MASK_CHROMA_LUMA), as the scripts do
+    int sharpen = 0;         // SangNomAA only, at source size: contra-sharpening behind the last step, sn_aa_sharpen.amount (0 off, 1..255, 64 = unity)
+    bool sharpen_chroma = false;  // ... of every processed plane, not of plane 0 alone (sn_aa_sharpen.chroma)
     int column_parts = -1;  // sn_options.column_parts (16-bit / float planes wider than 3840 in column parts); -1: $SANGNOM_COLUMN_PARTS or 0
     sn_policy policy{};     // scheduling only (sangnom_hip.h); zeros = the defaults
 };
@@ -252,6 +254,8 @@ private:
 // a Sobel edge mask of the source (sangnom_hip.h, "Edge mask"; mask_lo <= mask_hi in 0..255, mask_expand 0 or 1), which is
 // what the anti-aliasing scripts do behind the filter: flat areas and texture keep the source's samples.  Args::mask_luma
 // merges chroma through the luma plane's mask reduced to chroma's geometry instead of chroma's own (needs luma processed).
+// With Args::sharpen (1..255, 64 = unity; the clip at source size) the library contra-sharpens the result behind the last
+// step and before the mask (sangnom_hip.h, "Contra-sharpening"): plane 0, or with Args::sharpen_chroma every processed plane.
 template <class Host>
 class AAFilter {
 public:
@@ -280,6 +284,8 @@ public:
             if (a.mask_luma && Host::NumComponents(vi_) >= 3 && !a.dh && !a.luma && a.chroma)
                 env->ThrowError("%s: a luma-derived chroma mask needs luma processed (luma=true)", name);
         }
+        if (a.sharpen < 0 || a.sharpen > 255) env->ThrowError("%s: sn_aa_sharpen.amount must be 0 (off) or 1..255", name);
+        if (a.sharpen && a.dh && !a.reduce) env->ThrowError("%s: sharpen needs the frame at source size (dh=false, or dh=true with reduce)", name);
         sn_config c{};
         c.struct_size = (int32_t)sizeof c;
         c.width = Host::Width(vi_);
@@ -321,7 +327,10 @@ public:
         sn_aa_mask_ex mask_ex{};
         mask_ex.struct_size = (int32_t)sizeof mask_ex;
         mask_ex.chroma = a.mask_luma ? SN_AA_MASK_CHROMA_LUMA : SN_AA_MASK_CHROMA_OWN;
-        if (sn_aa_create_ex4(&c, &pol, &opts, &aopts, &mask, &mask_ex, &ctx_) != SN_OK) env->ThrowError("%s: %s", name, sn_aa_last_error(nullptr));
+        sn_aa_sharpen sharpen{};
+        sharpen.struct_size = (int32_t)sizeof sharpen;
+        sharpen.amount = a.sharpen, sharpen.chroma = a.sharpen_chroma ? 1 : 0;
+        if (sn_aa_create_ex5(&c, &pol, &opts, &aopts, &mask, &mask_ex, &sharpen, &ctx_) != SN_OK) env->ThrowError("%s: %s", name, sn_aa_last_error(nullptr));
         enlarged_ = a.dh && !a.reduce;
         if (enlarged_) {  // each pass doubles the height of what it is given: the clip comes out twice as wide and twice as high
             Host::SetWidth(vi_, Host::Width(vi_) * 2);

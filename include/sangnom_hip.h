@@ -358,6 +358,27 @@ int sn_mask_merge_luma_device(sn_context* ctx, const sn_aa_mask* mask, int32_t n
                               int32_t height /* of a chroma plane; luma is (width << sub_w) x (height << sub_h) */, void* const dst[2],
                               const int64_t dst_frame_stride[2], const int32_t dst_pitch[2]);
 
+/* The contra-sharpening of the anti-aliasing call (below: "Contra-sharpening", which defines the arithmetic).  amount 0: off,
+ * and the fields below it are ignored; 1..255 with 64 = unity.  The 64 the plugins document is a starting point: nobody has
+ * tuned it on real footage. */
+typedef struct sn_aa_sharpen {
+    int32_t struct_size; /* sizeof(sn_aa_sharpen) */
+    int32_t amount;      /* 0 = off (the fields below are ignored); 1..255, 64 = unity */
+    int32_t chroma;      /* 0: plane 0 only; 1: every processed plane */
+    int32_t reserved[5]; /* zero */
+} sn_aa_sharpen;         /* 32 bytes */
+
+/* The contra-sharpening on its own, for pipelines that keep frames on the device: `nframes` planes of width x height samples
+ * on the context's stream; `aa` (the filtered plane R) is sharpened towards `src` (the plane S it was filtered from) and
+ * written to dst (see "Contra-sharpening").  amount: 1..255; sample type and bit depth (the clamp) come from the context.
+ * Pitches >= width samples; pointers, pitches and frame strides multiples of the sample size (multiples of 16 on a side: 16
+ * bytes per lane and access on that side).  dst must overlap neither src nor aa, because the stencil reads neighbours of
+ * both: the same base as aa or src is refused with SN_ERR_INVALID_ARG, wider overlap is the caller's contract.  Nothing
+ * beyond width samples of a destination row is written.  A refused call queues nothing. */
+int sn_contra_sharpen_device(sn_context* ctx, int32_t amount, int32_t nframes, const void* src, int64_t src_frame_stride, int32_t src_pitch,
+                             const void* aa, int64_t aa_frame_stride, int32_t aa_pitch, int32_t width, int32_t height, void* dst,
+                             int64_t dst_frame_stride, int32_t dst_pitch);
+
 /* The anti-aliasing idiom TurnLeft().SangNom2(order, aa, aac).TurnRight().SangNom2(order, aa, aac) as ONE call with
  * host planes (README.md:3 of the reference: "mainly used in anti-aliasing scripts"): the frame
  * crosses PCIe once each way and stays on the device between the two passes (two filter instances -- one for the
@@ -387,7 +408,7 @@ int sn_mask_merge_luma_device(sn_context* ctx, const sn_aa_mask* mask, int32_t n
  * Anti-aliasing at source size (sn_aa_create_ex2 with sn_aa_options.reduce != 0; needs cfg.dh = 1, otherwise SN_ERR_CONFIG
  * "reduce needs dh"): both passes run exactly as above (sn_aa_get_info(ctx, 1) still reports the 2 width clip), their
  * 2W x 2H result E stays in an intermediate of the library (nine plane sizes with reduce, counted against
- * scratch_budget_mb like the others) and a reduction kernel writes the destination.  Every destination plane, pitch check
+ * scratch_budget_mb like the others; a contra-sharpened plane adds one: four without dh, ten with reduce) and a reduction kernel writes the destination.  Every destination plane, pitch check
  * and frame stride of EVERY sn_aa_* entry point then describes the source geometry W_p x H_p (a packed or semi-planar dst
  * has rows for W), and on the host path a frame of the source's size comes down.  No counterpart in the reference (it has
  * no resampler); the arithmetic is defined here, exactly:
@@ -455,7 +476,48 @@ int sn_mask_merge_luma_device(sn_context* ctx, const sn_aa_mask* mask, int32_t n
  *   Rules of the call: planes 1 and 2, where processed, are merged through mc; a Y clip accepts the option and it has no
  *   effect; chroma = 0 without dh copies chroma as without a mask; cfg.luma == 0 without dh and with chroma != 0 is refused
  *   before a device is touched, SN_ERR_CONFIG "SangNomAA: a luma-derived chroma mask needs luma processed (luma=true)" (the
- *   host routes never upload a plane that is not processed).  No scratch is added and neither pass changes. */
+ *   host routes never upload a plane that is not processed).  No scratch is added and neither pass changes.
+ *
+ * Contra-sharpening (sn_aa_create_ex5 with sharpen->amount != 0; opt-in): SangNom interpolates every second line from a
+ * smoothed cost field, and the result is softer than the source.  The scripts answer with a sharpening that is allowed only
+ * as far as the filter changed the picture and only in the direction of the source (daa, QTGMC's sharpening branch, the
+ * ContraSharpening helper of the *AA collections).  The stage runs behind the last step (the second pass, or the reduction)
+ * and before the edge mask, which then merges the SHARPENED result into the source (m = 0 still gives S exactly; the
+ * mask's own arithmetic, chroma through the luma mask included, does not change).  Like the mask it needs the frame at source
+ * size: amount != 0 with dh = 1 and no reduction is SN_ERR_CONFIG "SangNomAA: sharpen needs the frame at source size
+ * (dh=false, or dh=true with reduce)", before a device is touched.  Only processed planes are sharpened -- plane 0 with
+ * chroma = 0, every processed plane with chroma = 1 --; a plane that is merely copied stays a copy, and with chroma = 0
+ * planes 1 and 2 are what they are without the stage.  The last step writes each sharpened plane into one more intermediate
+ * of the library, of the destination's geometry: one plane size per sharpened plane and frame, counted against
+ * scratch_budget_mb like the others (four plane sizes instead of three without dh, ten instead of nine with reduce); the
+ * sharpening kernel writes the destination from it and the source.  Neither the reference nor any script defines these
+ * pixels; the arithmetic is the library's own, exactly:
+ *   S is the source plane (W x H), R the call's result for it, P(y, x) = P[clamp(y, 0, H-1)][clamp(x, 0, W-1)] for either
+ *   plane; amount is 1..255 and 64 is unity.
+ *   Integer samples (8..16 bit), all in signed 32-bit:
+ *     h(y, x) = R(y, x-1) + 2 R(y, x) + R(y, x+1)
+ *     B       = (h(y-1, x) + 2 h(y, x) + h(y+1, x) + 8) >> 4       ([1 2 1] x [1 2 1], rounded)
+ *     d       = R(y, x) - B                                        (what an unsharp mask of strength 1 adds)
+ *     d1      = sgn(d) * ((|d| * amount) >> 6)                      (|d| * 255 < 2^24)
+ *     D(j, i) = S(j, i) - R(j, i)                                   (what the filter took away, per sample)
+ *     mn      = min(0, min of D over the 3 x 3 neighbourhood),  mx = max(0, max of D over the same)  (clamped coordinates)
+ *     c       = min(max(d1, mn), mx)
+ *     out     = min(max(R(y, x) + c, 0), 2^bits_per_sample - 1)
+ *   Because mn <= 0 <= mx, c never exceeds d1 in magnitude, never points away from every nearby S - R, and is 0 wherever
+ *   the filter changed nothing in the neighbourhood: S == R over a 3 x 3 block gives out == R.  The clamp is to the clip's
+ *   range, as in the reduction: a sharpened 10-bit plane is always valid in an MSB or v210 destination.  Only without reduce
+ *   can R itself exceed that range (a container wider than the clip), and then it is clamped too.
+ *   Float samples: one rounding per written operation, no contraction:
+ *     h  = (R(y,x-1) + R(y,x+1)) + (R(y,x) + R(y,x));  v = (h(y-1) + h(y+1)) + (h(y) + h(y));  B = v * 0.0625f
+ *     d  = R(y,x) - B;  d1 = d * k,  k = (float)amount * 0.015625f (exact)
+ *     mn = mx = 0.0f;  for every (j, i) of the 3 x 3 neighbourhood: t = S(j,i) - R(j,i); if (t < mn) mn = t; if (t > mx) mx = t;
+ *       (a NaN t is ignored)
+ *     c  = d1; if (c < mn) c = mn; if (c > mx) c = mx;
+ *     out = R(y,x) if d1 is NaN or c == 0 (either zero);  else R(y,x) + c.        No clamp.
+ *   No NaN is generated into the output:
+ *     an infinite or NaN R(y,x) makes B infinite or NaN, so d = R - B and with it d1 is NaN, and R(y,x) is copied;
+ *     otherwise R(y,x) is finite, and c is d1, mn or mx, none of which is NaN here (mn and mx never take a NaN);
+ *     a finite value plus a value that is no NaN is no NaN: every output sample is a copy of R or such a sum. */
 enum { SN_AA_REDUCE_NONE = 0, SN_AA_REDUCE_TENT = 1, SN_AA_REDUCE_HALFBAND = 2 };
 typedef struct sn_aa_options {
     int32_t struct_size; /* sizeof(sn_aa_options) */
@@ -483,6 +545,13 @@ int sn_aa_get_mask(sn_aa_context* ctx, sn_aa_mask* out /* struct_size set by the
 int sn_aa_create_ex4(const sn_config* cfg, const sn_policy* policy, const sn_options* options, const sn_aa_options* aa_options /* NULL = defaults */,
                      const sn_aa_mask* mask /* NULL = none */, const sn_aa_mask_ex* mask_ex /* NULL = defaults */, sn_aa_context** out);
 int sn_aa_get_mask_ex(sn_aa_context* ctx, sn_aa_mask_ex* out /* struct_size set by the caller */); /* chroma 0 when there is no mask */
+/* sn_aa_create_ex4 is sn_aa_create_ex5 with sharpen = NULL (no contra-sharpening).  A bad struct_size, an amount outside
+ * 0..255, a chroma outside 0..1 or a non-zero reserved word: SN_ERR_INVALID_ARG, naming sn_aa_sharpen.<field>; with amount = 0
+ * only struct_size is looked at. */
+int sn_aa_create_ex5(const sn_config* cfg, const sn_policy* policy, const sn_options* options, const sn_aa_options* aa_options /* NULL = defaults */,
+                     const sn_aa_mask* mask /* NULL = none */, const sn_aa_mask_ex* mask_ex /* NULL = defaults */,
+                     const sn_aa_sharpen* sharpen /* NULL = off */, sn_aa_context** out);
+int sn_aa_get_sharpen(sn_aa_context* ctx, sn_aa_sharpen* out /* struct_size set by the caller */); /* amount 0 when off */
 int sn_aa_process_host(sn_aa_context* ctx, const void* const src[3], const int32_t src_pitch[3], void* const dst[3],
                        const int32_t dst_pitch[3], int32_t parity);
 const char* sn_aa_last_error(const sn_aa_context* ctx); /* ctx == NULL: last failed sn_aa_create on this thread */

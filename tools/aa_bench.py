@@ -12,10 +12,15 @@ the edge mask next to the call without it, in one run (device batches and --host
 half-band reduce kernel that writes the same plane, alternating; any of Y8 / Y16 / Y32 -- and the luma-derived chroma merge
 of a 4:2:0 frame of that size (sn_mask_merge_luma_device: U and V in one launch, in two launches) against the two own-mask
 merges of the same chroma planes.  --mask-chroma luma (with --mask): the masked call merges chroma through luma's mask.
+--sharpen AMOUNT (at source size; device batches): the call with the contra-sharpening (on top of --mask where given) next to
+the call without it.  --sharpen-bw: the sharpening kernel alone (sn_contra_sharpen_device) against the mask kernel (expand 1, not
+in place), both on noise and moving the same 3 W H B bytes per frame, alternating; any of Y8 / Y16 / Y32.
 usage: python tools/aa_bench.py [--frames 512] [--fresh 1] [--fmt Y8] [--size 3840x2160] [--dh [--composed]] [--reduce K] [--host [--depth 8]]
        python tools/aa_bench.py --reduce-bw [--fmt Y16] [--size 1920x1080] [--frames 64]
        python tools/aa_bench.py --mask 8,32,1 [--reduce halfband] [--size 1920x1080] [--host]
-       python tools/aa_bench.py --mask-bw [--fmt Y16] [--size 3840x2160] [--frames 32]"""
+       python tools/aa_bench.py --mask-bw [--fmt Y16] [--size 3840x2160] [--frames 32]
+       python tools/aa_bench.py --sharpen 64 --mask 8,32,1 --reduce halfband [--fmt YUV420P8]
+       python tools/aa_bench.py --sharpen-bw [--fmt Y16] [--size 3840x2160] [--frames 256] [--reps 5]"""
 import argparse
 import json
 import os
@@ -184,6 +189,45 @@ def mask_bandwidth(clip, a):
     return out
 
 
+def sharpen_bandwidth(clip, a):
+    """sn_contra_sharpen_device against sn_mask_merge_device (expand 1, into a third plane), both on noise, alternating: median,
+    minimum and maximum microseconds per frame over --reps launches of --frames frames.  Both read S and R and write dst:
+    3 W H B bytes per frame; `of_hbm_peak` is that over 8 TB/s over the median."""
+    dev = torch.device("cuda:0")
+    N, W, H, B = a.frames, clip.width, clip.height, clip.bytes
+    dt = {1: torch.uint8, 2: torch.int16, 4: torch.float32}[B]
+
+    def noise():
+        if B == 4:
+            return torch.rand((N, H, W), device=dev)
+        return torch.randint(0, 1 << clip.bits, (N, H, W), device=dev, dtype=torch.int32).to(dt)
+    S, R = noise(), noise()
+    dst = torch.empty((N, H, W), device=dev, dtype=dt)
+    lo, hi, _ = a.mask_values
+    amount = a.sharpen or 64
+    out = {"clip": f"{a.fmt} {W}x{H}", "frames": N, "plane_bytes": N * W * H * B, "mask": [lo, hi, 1], "sharpen": amount, "reps": a.reps}
+    with SangNom2(clip, max_batch=1) as flt:
+        runs = {"sharpen": lambda: flt.contra_sharpen(S, R, dst, amount), "mask1": lambda: flt.mask_merge(S, R, dst, lo, hi, 1)}
+        times = {k: [] for k in runs}
+        torch.cuda.synchronize()
+        for r in range(a.reps + 1):
+            for k, fn in runs.items():
+                flt.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                flt.synchronize()
+                if r:
+                    times[k].append(time.perf_counter() - t0)
+        for k, t in times.items():
+            t.sort()
+            med = t[len(t) // 2]
+            out[k + "_us_per_frame"] = round(1e6 * med / N, 2)
+            out[k + "_us_min_max"] = [round(1e6 * t[0] / N, 2), round(1e6 * t[-1] / N, 2)]
+            out[k + "_GBps"] = round(3 * N * W * H * B / med / 1e9, 1)
+            out[k + "_of_hbm_peak"] = round(3 * N * W * H * B / 8e12 / med, 3)
+    return out
+
+
 def luma_merge_times(clip, a, dev, dt, noise):
     """The chroma merge of a 4:2:0 frame whose luma plane is --size, in place on the result as the call uses it, expand 1, on
     noise: U and V through luma's mask in one launch (4 + 6 chroma-plane units of bytes: luma read, S and R read and dst
@@ -237,6 +281,9 @@ def main():
     ap.add_argument("--mask", help="lo,hi[,expand]: the call with the edge mask next to the call without it (at source size)")
     ap.add_argument("--mask-chroma", choices=["own", "luma"], default="own", help="--mask: which mask merges chroma (luma: the luma plane's, reduced)")
     ap.add_argument("--mask-bw", action="store_true", help="the mask kernel alone against the half-band reduce kernel on the same plane")
+    ap.add_argument("--sharpen", type=int, default=0, help="AMOUNT 1..255: the call with the contra-sharpening next to the call without it (at source size)")
+    ap.add_argument("--sharpen-chroma", action="store_true", help="--sharpen: every processed plane, not luma alone")
+    ap.add_argument("--sharpen-bw", action="store_true", help="the sharpening kernel alone against the mask kernel on the same planes")
     a = ap.parse_args()
     a.mask_values = ([int(x) for x in a.mask.split(",")] + [1])[:3] if a.mask else [8, 32, 1]
     mask_kw = dict(mask=tuple(a.mask_values[:2]), mask_expand=a.mask_values[2]) if a.mask else None
@@ -252,8 +299,13 @@ def main():
     if a.mask_bw:
         print(json.dumps(mask_bandwidth(clip, a)))
         return
+    if a.sharpen_bw:
+        print(json.dumps(sharpen_bandwidth(clip, a)))
+        return
     if clip.bytes != 1:
         sys.exit("aa_bench: 8-bit formats only")
+    if a.sharpen and ((a.dh and not a.reduce) or a.composed or a.host):
+        sys.exit("aa_bench: --sharpen needs the frame at source size (without --dh, or with --reduce) and device batches")
     if a.mask and ((a.dh and not a.reduce) or a.composed):
         sys.exit("aa_bench: --mask needs the frame at source size: without --dh, or with --reduce")
     if a.composed and (not a.dh or a.host or a.reduce):
@@ -282,7 +334,8 @@ def main():
         print(json.dumps(out))
         return
     reps = 5
-    for key, kw in [("aa_fps", {})] + ([("aa_mask_fps", mask_kw)] if a.mask else []):
+    sharpen_kw = dict(mask_kw or {}, sharpen=a.sharpen, sharpen_chroma=a.sharpen_chroma)
+    for key, kw in [("aa_fps", {})] + ([("aa_mask_fps", mask_kw)] if a.mask else []) + ([("aa_sharpen_fps", sharpen_kw)] if a.sharpen else []):
         with SangNomAA(clip, max_batch=N, fresh_pool=bool(a.fresh), aac=48 if clip.planes > 1 else 0, **(dict(dh=True) if a.dh else {}),
                        **(dict(reduce=a.reduce) if a.reduce else {}), **kw) as aa:
             torch.cuda.synchronize()
@@ -298,6 +351,9 @@ def main():
         out["mask"] = a.mask_values
         out["mask_chroma"] = a.mask_chroma
         out["mask_us_per_frame"] = round(1e6 / out["aa_mask_fps"] - 1e6 / out["aa_fps"], 2)
+    if a.sharpen:  # on top of the mask where one is given
+        out["sharpen"] = [a.sharpen, int(a.sharpen_chroma)]
+        out["sharpen_us_per_frame"] = round(1e6 / out["aa_sharpen_fps"] - 1e6 / out["aa_mask_fps" if a.mask else "aa_fps"], 2)
     with SangNom2(clip, max_batch=N) as flt:
         t = torch.empty((N, w, h), device=dev, dtype=torch.uint8)
         torch.cuda.synchronize()
