@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "sn_aa_plan.h"
 #include "sn_copier.h"
 #include "sn_pool_dispatch.h"
 #include "sn_route.h"
@@ -2150,21 +2151,6 @@ int sn_reduce_device(sn_context* h, int32_t kernel, int32_t nframes, const void*
     return SN_OK;
 }
 
-// sn_aa_mask as sn_aa_create_ex3 and sn_mask_merge_device take it: empty when it is fine, otherwise the message, naming the field
-static std::string mask_problem(const sn_aa_mask* m)
-{
-    if (m->struct_size != (int32_t)sizeof(sn_aa_mask)) return "sn_aa_mask.struct_size mismatch";
-    if (m->kind < SN_AA_MASK_NONE || m->kind > SN_AA_MASK_SOBEL) return "sn_aa_mask.kind must be 0 (none) or 1 (Sobel)";
-    if (m->kind == SN_AA_MASK_NONE) return "";
-    if (m->lo < 0 || m->lo > 255) return "sn_aa_mask.lo must be 0..255";
-    if (m->hi < 0 || m->hi > 255) return "sn_aa_mask.hi must be 0..255";
-    if (m->lo > m->hi) return "sn_aa_mask.lo must not be above sn_aa_mask.hi";
-    if (m->expand < 0 || m->expand > 1) return "sn_aa_mask.expand must be 0 or 1";
-    for (int32_t r : m->reserved)
-        if (r) return "sn_aa_mask.reserved must be zero";
-    return "";
-}
-
 int sn_mask_merge_device(sn_context* h, const sn_aa_mask* mask, int32_t nframes, const void* src, int64_t sfs, int32_t sp, const void* aa, int64_t afs,
                          int32_t ap, int32_t width, int32_t height, void* dst, int64_t dfs, int32_t dp)
 {
@@ -2172,7 +2158,7 @@ int sn_mask_merge_device(sn_context* h, const sn_aa_mask* mask, int32_t nframes,
     if (!c) return sn::fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
     const int B = c->cfg.bytes_per_sample;
     if (!mask) return sn::fail(c, SN_ERR_INVALID_ARG, "sn_mask_merge_device: mask is NULL");
-    const std::string problem = mask_problem(mask);
+    const std::string problem = sn::mask_problem(mask);
     if (!problem.empty()) return sn::fail(c, SN_ERR_INVALID_ARG, ("sn_mask_merge_device: " + problem).c_str());
     if (mask->kind != SN_AA_MASK_SOBEL) return sn::fail(c, SN_ERR_INVALID_ARG, "sn_mask_merge_device: sn_aa_mask.kind must be 1 (Sobel)");
     if (!src || !dst || nframes < 0 || width <= 0 || height <= 0 || width > INT32_MAX / 8 || height > INT32_MAX / 2)
@@ -2216,7 +2202,7 @@ int sn_mask_merge_luma_device(sn_context* h, const sn_aa_mask* mask, int32_t nfr
     if (!c) return sn::fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
     const int B = c->cfg.bytes_per_sample;
     if (!mask) return sn::fail(c, SN_ERR_INVALID_ARG, "sn_mask_merge_luma_device: mask is NULL");
-    const std::string problem = mask_problem(mask);
+    const std::string problem = sn::mask_problem(mask);
     if (!problem.empty()) return sn::fail(c, SN_ERR_INVALID_ARG, ("sn_mask_merge_luma_device: " + problem).c_str());
     if (mask->kind != SN_AA_MASK_SOBEL) return sn::fail(c, SN_ERR_INVALID_ARG, "sn_mask_merge_luma_device: sn_aa_mask.kind must be 1 (Sobel)");
     if (sub_w < 0 || sub_w > 2 || sub_h < 0 || sub_h > 2) return sn::fail(c, SN_ERR_INVALID_ARG, "sn_mask_merge_luma_device: sub_w and sub_h must be 0..2");
@@ -2437,32 +2423,9 @@ struct sn_aa_context {
     sn_context* second = nullptr;  // the clip itself, on first's stream
     hipStream_t stream = nullptr;
     hipStream_t up = nullptr, down = nullptr;  // host frames: H2D / D2H (created with the first group of slots)
-    int planes = 1;
-    int max_batch = 1;
-    bool process[3] = {true, true, true};
-    int w[3] = {0, 0, 0}, h[3] = {0, 0, 0};  // clip geometry per plane
-    int pitch[3] = {0, 0, 0}, tpitch[3] = {0, 0, 0};
-    int64_t cbytes[3] = {0, 0, 0}, tbytes[3] = {0, 0, 0};  // one frame of a plane: clip geometry / turned
-    int ow[3] = {0, 0, 0}, oh[3] = {0, 0, 0};              // the second pass's output per plane (dh: 2w x 2h)
-    int opitch[3] = {0, 0, 0};
-    int64_t obytes[3] = {0, 0, 0};
-    int64_t u1bytes[3] = {0, 0, 0};                        // the first pass's output: tpitch x ow lines
-    int t2pitch[3] = {0, 0, 0};                            // the second pass's input: ow wide, h high
-    int64_t t2bytes[3] = {0, 0, 0};
-    int reduce = SN_AA_REDUCE_NONE;                        // dh only: the second pass's output goes through sn_reduce.hip on its way out
-    sn_aa_mask mask{};                                     // kind != 0: the result is merged into the source through an edge mask (sn_mask.hip), last
-    int mask_chroma = SN_AA_MASK_CHROMA_OWN;               // ... SN_AA_MASK_CHROMA_LUMA: planes 1 and 2 through the source luma plane's mask
-    sn_aa_sharpen sharpen{};                               // amount != 0: the result is contra-sharpened (sn_sharpen.hip) behind the last step, before the mask
-    bool sharpened[3] = {false, false, false};             // ... the planes it applies to: processed, and plane 0 unless sharpen.chroma
-    int dstw[3] = {0, 0, 0}, dsth[3] = {0, 0, 0};          // the destination's geometry per plane: ow x oh, with reduce w x h
-    int dstpitch[3] = {0, 0, 0};                           // ... of the library's own buffers of that geometry (host groups)
-    int64_t dstbytes[3] = {0, 0, 0};
+    sn::AaPlan plan;                                   // every size, option and step of the call (sn_aa_plan.h)
     int cap = 0;                                       // frames the intermediates hold (a chunk)
-    uint8_t* d_t1[3] = {nullptr, nullptr, nullptr};   // turned: input of the first pass (only its kept lines are written; dh: every line)
-    uint8_t* d_u1[3] = {nullptr, nullptr, nullptr};   // turned: its output (dh: twice as high)
-    uint8_t* d_t2[3] = {nullptr, nullptr, nullptr};   // turned back: input of the second pass (kept lines only; dh: every line, twice as wide)
-    uint8_t* d_e[3] = {nullptr, nullptr, nullptr};    // reduce: the second pass's output, opitch x oh
-    uint8_t* d_s[3] = {nullptr, nullptr, nullptr};    // sharpen: the last step's output of a sharpened plane, dstpitch x dsth
+    uint8_t* d[sn::kAaBuffers][3] = {};                // the intermediates (sn::AaBuf; the caller's planes have none)
     // host frames: `per_group` slots form a group whose frames one batch works on; the ring's groups, then one group of
     // one slot for the synchronous call
     struct Slot {
@@ -2485,7 +2448,7 @@ struct sn_aa_context {
     std::vector<Group> groups;  // [0, ring_groups): the ring; [ring_groups]: the synchronous call's
     sn::UvScratch uv;           // sn_aa_process_device_surfaces
     bool luma_elsewhere = false;  // ... with an MSB-aligned side: luma that is not processed has gone from src to dst already
-    int depth = 0, per_group = 1, ring_groups = 0, ring_next = 0;
+    int ring_next = 0;
     bool ring_ready = false;
     Copier* copier = nullptr;  // the first context's
     std::string err;
@@ -2530,25 +2493,19 @@ static void aa_free_group(sn_aa_context::Group& g)
 static int aa_ensure_intermediates(sn_aa_context* a, int frames)
 {
     if (frames <= a->cap) return SN_OK;
-    int64_t per_frame = 0;
-    for (int p = 0; p < a->planes; ++p)
-        if (a->process[p]) per_frame += a->tbytes[p] + a->u1bytes[p] + a->t2bytes[p] + (a->reduce ? a->obytes[p] : 0) + (a->sharpened[p] ? a->dstbytes[p] : 0);
-    const int64_t fit = per_frame > 0 ? scratch_budget(reinterpret_cast<Context*>(a->first)) / per_frame : frames;
-    const int cap = (int)(fit < 1 ? 1 : fit < frames ? fit : frames);
+    const int cap = sn::aa_chunk_frames(a->plan, scratch_budget(reinterpret_cast<Context*>(a->first)), frames);
     if (cap <= a->cap) return SN_OK;
     SN_AA_HIP(hipStreamSynchronize(a->stream));
-    for (int p = 0; p < a->planes; ++p) {
-        if (!a->process[p]) continue;  // copied from source to destination: no turn, no pass, no intermediate
-        const size_t nb[5] = {(size_t)a->tbytes[p] * cap, (size_t)a->u1bytes[p] * cap, (size_t)a->t2bytes[p] * cap, (size_t)a->obytes[p] * cap,
-                              (size_t)a->dstbytes[p] * cap};
-        uint8_t** q[5] = {&a->d_t1[p], &a->d_u1[p], &a->d_t2[p], &a->d_e[p], &a->d_s[p]};
-        for (int k = 0; k < 5; ++k) {
-            if (k == 3 ? !a->reduce : k == 4 ? !a->sharpened[p] : false) continue;
-            if (*q[k]) SN_AA_HIP(hipFree(*q[k]));
-            *q[k] = nullptr;
-            SN_AA_HIP(hipMalloc(reinterpret_cast<void**>(q[k]), nb[k]));
+    for (int p = 0; p < a->plan.planes; ++p) {
+        for (int buf = 0; buf < sn::kAaBuffers; ++buf) {
+            if (!sn::aa_buf_needed(a->plan, p, buf)) continue;
+            const size_t nb = (size_t)sn::aa_buf_frame_bytes(a->plan, p, buf) * cap;
+            uint8_t*& q = a->d[buf][p];
+            if (q) SN_AA_HIP(hipFree(q));
+            q = nullptr;
+            SN_AA_HIP(hipMalloc(reinterpret_cast<void**>(&q), nb));
             // the turns write only the lines the next pass keeps: a pass that read another line would read this pattern
-            SN_AA_HIP(hipMemsetAsync(*q[k], 0xA5, nb[k], a->stream));
+            SN_AA_HIP(hipMemsetAsync(q, 0xA5, nb, a->stream));
         }
     }
     SN_AA_HIP(hipStreamSynchronize(a->stream));
@@ -2564,8 +2521,8 @@ void sn_aa_destroy(sn_aa_context* a)
         if (st) (void)hipStreamSynchronize(st);
     if (a->second) sn_destroy(a->second);
     if (a->first) sn_destroy(a->first);  // owns the stream unless the caller gave one
-    for (int p = 0; p < 3; ++p)
-        for (uint8_t* q : {a->d_t1[p], a->d_u1[p], a->d_t2[p], a->d_e[p], a->d_s[p]})
+    for (auto& planes : a->d)
+        for (uint8_t* q : planes)
             if (q) (void)hipFree(q);
     for (const sn::PlaneViewW& q : {a->uv.in[0], a->uv.in[1], a->uv.out[0], a->uv.out[1], a->uv.y, a->uv.yo})
         if (q.base) (void)hipFree(q.base);
@@ -2611,214 +2568,101 @@ int sn_aa_create_ex5(const sn_config* cfg, const sn_policy* policy, const sn_opt
     };
     if (!cfg || !out) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "cfg / out is NULL");
     *out = nullptr;
-    if (cfg->struct_size != (int32_t)sizeof(sn_config)) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_config.struct_size mismatch");
-    if (cfg->max_batch < 0) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "max_batch must be >= 0");
-    if (cfg->host_depth < 0 || cfg->host_depth > 256) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "host_depth must be 0..256");
-    int reduce = SN_AA_REDUCE_NONE;
-    if (aa_options) {
-        if (aa_options->struct_size != (int32_t)sizeof(sn_aa_options)) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_aa_options.struct_size mismatch");
-        if (aa_options->reduce < SN_AA_REDUCE_NONE || aa_options->reduce > SN_AA_REDUCE_HALFBAND)
-            return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_aa_options.reduce must be 0 (none), 1 (tent) or 2 (half-band)");
-        for (int32_t r : aa_options->reserved)
-            if (r) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_aa_options.reserved must be zero");
-        reduce = aa_options->reduce;
-    }
-    if (reduce && !cfg->dh) return fail_aa(nullptr, SN_ERR_CONFIG, "SangNomAA: reduce needs dh=true");
-    sn_aa_mask use_mask{};
-    use_mask.struct_size = (int32_t)sizeof(sn_aa_mask);
-    if (mask) {
-        const std::string problem = mask_problem(mask);
-        if (!problem.empty()) return fail_aa(nullptr, SN_ERR_INVALID_ARG, problem);
-        if (mask->kind != SN_AA_MASK_NONE) use_mask = *mask;
-    }
-    if (use_mask.kind && cfg->dh && !reduce)
-        return fail_aa(nullptr, SN_ERR_CONFIG, "SangNomAA: mask needs the frame at source size (dh=false, or dh=true with reduce)");
-    int mask_chroma = SN_AA_MASK_CHROMA_OWN;
-    if (mask_ex) {
-        if (mask_ex->struct_size != (int32_t)sizeof(sn_aa_mask_ex)) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_aa_mask_ex.struct_size mismatch");
-        if (use_mask.kind) {  // without a mask the fields below are ignored
-            if (mask_ex->chroma < SN_AA_MASK_CHROMA_OWN || mask_ex->chroma > SN_AA_MASK_CHROMA_LUMA)
-                return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_aa_mask_ex.chroma must be 0 (own) or 1 (luma)");
-            for (int32_t r : mask_ex->reserved)
-                if (r) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_aa_mask_ex.reserved must be zero");
-            mask_chroma = mask_ex->chroma;
-        }
-    }
-    // the source luma plane reaches the device only where it is processed (the host routes upload no other plane)
-    if (mask_chroma == SN_AA_MASK_CHROMA_LUMA && cfg->num_planes >= 3 && !cfg->dh && !cfg->luma && cfg->chroma)
-        return fail_aa(nullptr, SN_ERR_CONFIG, "SangNomAA: a luma-derived chroma mask needs luma processed (luma=true)");
-    sn_aa_sharpen use_sharpen{};
-    use_sharpen.struct_size = (int32_t)sizeof(sn_aa_sharpen);
-    if (sharpen) {
-        if (sharpen->struct_size != (int32_t)sizeof(sn_aa_sharpen)) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_aa_sharpen.struct_size mismatch");
-        if (sharpen->amount < 0 || sharpen->amount > 255) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_aa_sharpen.amount must be 0 (off) or 1..255");
-        if (sharpen->amount) {  // with amount 0 the fields below it are ignored
-            if (sharpen->chroma < 0 || sharpen->chroma > 1) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_aa_sharpen.chroma must be 0 or 1");
-            for (int32_t r : sharpen->reserved)
-                if (r) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "sn_aa_sharpen.reserved must be zero");
-            use_sharpen.amount = sharpen->amount, use_sharpen.chroma = sharpen->chroma;
-        }
-    }
-    if (use_sharpen.amount && cfg->dh && !reduce)
-        return fail_aa(nullptr, SN_ERR_CONFIG, "SangNomAA: sharpen needs the frame at source size (dh=false, or dh=true with reduce)");
+    // check, build the geometry, create the two passes, allocate (sn_aa_plan.h decides; nothing below does)
+    sn::AaOptions opt;
+    std::string msg;
+    if (int rc = sn::aa_check(*cfg, aa_options, mask, mask_ex, sharpen, opt, msg)) return fail_aa(nullptr, rc, msg);
     sn_aa_context* a = new (std::nothrow) sn_aa_context();
     if (!a) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "out of host memory");
     a->cfg = *cfg;
-    a->sharpen = use_sharpen;
-    a->reduce = reduce;
-    a->mask = use_mask;
-    a->mask_chroma = mask_chroma;
-    a->max_batch = cfg->max_batch > 1 ? cfg->max_batch : 1;
-    // the ring: two groups, so that one group uploads while the other is worked on; a group's frames are one batch
-    a->depth = cfg->host_depth > 0 ? cfg->host_depth : 4;
-    a->ring_groups = a->depth < 2 ? 1 : 2;
-    a->per_group = a->depth / a->ring_groups;
-    a->depth = a->ring_groups * a->per_group;
-    const int inner_batch = a->max_batch > a->per_group ? a->max_batch : a->per_group;
-    sn_config c1 = *cfg;  // TurnLeft: width <-> height, the chroma subsampling turns with it
-    c1.width = cfg->height;
-    c1.height = cfg->width;
-    c1.sub_w = cfg->sub_h;
-    c1.sub_h = cfg->sub_w;
-    c1.max_batch = inner_batch;
-    c1.mode = SN_MODE_AUTO;
+    a->plan = sn::aa_geometry(*cfg, opt);
+    sn::aa_steps(a->plan);
+    sn_config c1 = a->plan.c1, c2 = a->plan.c2;
+    c1.stream = cfg->stream;
     int rc = sn_create_ex(&c1, policy, options, &a->first);
     if (rc != SN_OK) return fail_aa(a, rc, sn_last_error(nullptr));
-    sn_config c2 = *cfg;  // TurnRight of the first pass's output: with dh that is twice as wide as the clip
-    if (cfg->dh) {
-        if (cfg->width > INT32_MAX / 2)  // what the second pass's own check would say, had 2W fitted its field
-            return fail_aa(a, SN_ERR_UNSUPPORTED, "width " + std::to_string(2 * (int64_t)cfg->width) + " exceeds the supported maximum of 8192");
-        c2.width = 2 * cfg->width;
-    }
-    c2.max_batch = inner_batch;
-    c2.mode = SN_MODE_AUTO;
+    if (cfg->dh && cfg->width > INT32_MAX / 2)  // what the second pass's own check would say, had 2W fitted its field
+        return fail_aa(a, SN_ERR_UNSUPPORTED, "width " + std::to_string(2 * (int64_t)cfg->width) + " exceeds the supported maximum of 8192");
     c2.stream = sn_get_stream(a->first);
     rc = sn_create_ex(&c2, policy, options, &a->second);
     if (rc != SN_OK) return fail_aa(a, rc, sn_last_error(nullptr));
     Context* f1 = reinterpret_cast<Context*>(a->first);
     f1->copies_elsewhere = reinterpret_cast<Context*>(a->second)->copies_elsewhere = true;
     a->stream = f1->stream;
-    a->planes = cfg->num_planes < 3 ? cfg->num_planes : 3;
-    const int B = cfg->bytes_per_sample;
-    for (int p = 0; p < a->planes; ++p) {
-        a->process[p] = cfg->dh || f1->process[p];  // dh forces every plane, as in the reference (SangNom2.cpp:361-366)
-        a->w[p] = p ? cfg->width >> cfg->sub_w : cfg->width;
-        a->h[p] = p ? cfg->height >> cfg->sub_h : cfg->height;
-        a->pitch[p] = (a->w[p] * B + 255) & ~255;
-        a->tpitch[p] = (a->h[p] * B + 255) & ~255;
-        a->cbytes[p] = (int64_t)a->pitch[p] * a->h[p];
-        a->tbytes[p] = (int64_t)a->tpitch[p] * a->w[p];
-        a->ow[p] = cfg->dh ? (p ? c2.width >> cfg->sub_w : c2.width) : a->w[p];
-        a->oh[p] = cfg->dh ? 2 * a->h[p] : a->h[p];
-        a->opitch[p] = (a->ow[p] * B + 255) & ~255;
-        a->obytes[p] = (int64_t)a->opitch[p] * a->oh[p];
-        a->u1bytes[p] = (int64_t)a->tpitch[p] * a->ow[p];
-        a->t2pitch[p] = a->opitch[p];
-        a->t2bytes[p] = (int64_t)a->t2pitch[p] * a->h[p];
-        a->dstw[p] = reduce ? a->w[p] : a->ow[p];
-        a->dsth[p] = reduce ? a->h[p] : a->oh[p];
-        a->dstpitch[p] = reduce ? a->pitch[p] : a->opitch[p];
-        a->dstbytes[p] = reduce ? a->cbytes[p] : a->obytes[p];
-        a->sharpened[p] = use_sharpen.amount && a->process[p] && (p == 0 || use_sharpen.chroma);
-    }
-    if (int rc2 = aa_ensure_intermediates(a, a->max_batch)) return fail_aa(a, rc2, a->err);
+    if (int rc2 = aa_ensure_intermediates(a, a->plan.max_batch)) return fail_aa(a, rc2, a->err);
     *out = a;
     return SN_OK;
 }
 
-// Frames [0, n) of a strided device batch through both passes, on the call's stream.
+// One step of the plan on frames [f0, f0 + m) of the batch, the chunk the intermediates hold from their frame 0.
+static int aa_step(sn_aa_context* a, const sn::AaStep& s, int f0, int m, const sn::PlaneView src[3], const sn::PlaneViewW dst[3], const int32_t* par)
+{
+    const sn::AaPlan& P = a->plan;
+    const int B = P.B;
+    hipStream_t st = a->stream;
+    auto wr = [&](int buf, int p) {
+        return buf == sn::kAaDst ? dst[p].at(f0) : sn::PlaneViewW{a->d[buf][p], sn::aa_buf_frame_bytes(P, p, buf), sn::aa_buf_pitch(P, p, buf)};
+    };
+    auto rd = [&](int buf, int p) { return buf == sn::kAaSrc ? src[p].at(f0) : sn::PlaneView(wr(buf, p)); };
+    if (s.kind == sn::kAaPass1 || s.kind == sn::kAaPass2) {
+        // planes that are not processed are never touched by the passes (copies_elsewhere): their pointers only have to be there
+        sn::PlaneView r[3];
+        sn::PlaneViewW w[3];
+        for (int p = 0; p < P.planes; ++p) {
+            r[p] = rd(s.read[0], p), w[p] = wr(s.write[p], p);
+            if (!s.on(p)) r[p].base = src[p].base, w[p].base = dst[p].at(f0).base;
+        }
+        const PlaneArrays v(r, w);
+        sn_context* h = s.kind == sn::kAaPass1 ? a->first : a->second;
+        SN_AA_SN(h, run_batch(reinterpret_cast<Context*>(h), st, 0, m, v.s, v.sfs, v.sp, v.d, v.dfs, v.dp, par));
+        return SN_OK;
+    }
+    const sn_aa_mask& mask = P.opt.mask;
+    for (int g0 = 0; g0 < m;) {
+        const sn::FieldRun run = sn::aa_step_run(P, s, par, g0, m);
+        const int n = run.end - g0;
+        if (s.kind == sn::kAaMaskLuma) {
+            const sn::PlaneView cs[2] = {rd(s.read[0], 1), rd(s.read[0], 2)}, ca[2] = {rd(s.read[1], 1), rd(s.read[1], 2)};
+            const sn::PlaneViewW cd[2] = {wr(s.write[1], 1), wr(s.write[2], 2)};
+            SN_AA_HIP(sn::launch_mask_merge_luma(st, B, P.bits, mask.lo, mask.hi, mask.expand, n, rd(s.read[0], 0), P.c2.sub_w, P.c2.sub_h, 2, cs, ca,
+                                                 P.plane[1].w, P.plane[1].h, cd));
+        }
+        for (int p = 0; p < P.planes && s.kind != sn::kAaMaskLuma; ++p) {
+            if (!s.on(p)) continue;
+            const sn::AaPlane& g = P.plane[p];
+            const sn::PlaneView from = rd(s.read[0], p).at(g0);
+            const sn::PlaneViewW to = wr(s.write[p], p).at(g0);
+            switch (s.kind) {
+            case sn::kAaTurnLeft:  // the clip's plane -> h wide, w high
+                SN_AA_HIP(sn::launch_turn(st, B, 0, n, from, g.w, g.h, to, run.offset));
+                break;
+            case sn::kAaTurnRight:  // of the first pass's output
+                SN_AA_HIP(sn::launch_turn(st, B, 1, n, from, g.h, g.ow, to, run.offset));
+                break;
+            case sn::kAaReduce:  // the run's field offset is where the source samples lie in E
+                SN_AA_HIP(sn::launch_reduce(st, B, P.bits, s.arg, n, from, g.w, g.h, 1 - run.offset, run.offset, to));
+                break;
+            case sn::kAaSharpen:
+                SN_AA_HIP(sn::launch_contra_sharpen(st, B, P.bits, s.arg, n, from, rd(s.read[1], p).at(g0), g.w, g.h, to));
+                break;
+            case sn::kAaMask:
+                SN_AA_HIP(sn::launch_mask_merge(st, B, P.bits, mask.lo, mask.hi, mask.expand, n, from, rd(s.read[1], p).at(g0), g.w, g.h, to));
+                break;
+            default: return aa_fail(a, SN_ERR_INVALID_ARG, "SangNomAA: a step of the plan that is none of its kinds");
+            }
+        }
+        g0 = run.end;
+    }
+    return SN_OK;
+}
+
+// Frames [0, n) of a strided device batch through the plan's steps, on the call's stream: in chunks of what the intermediates hold.
 static int aa_run(sn_aa_context* a, int n, const sn::PlaneView src[3], const sn::PlaneViewW dst[3], const int32_t* parity)
 {
-    Context* c1 = reinterpret_cast<Context*>(a->first);
-    Context* c2 = reinterpret_cast<Context*>(a->second);
-    const int B = a->cfg.bytes_per_sample;
-    hipStream_t st = a->stream;
-    // the intermediates of a chunk: the turned source, the first pass's output, that turned back, the second pass's output of a reduce
-    // ... and, where a plane is contra-sharpened, the last step's output: that step writes `last`, the sharpening the destination
-    sn::PlaneViewW t1[3], u1[3], t2[3], e[3], last[3];
-    for (int p = 0; p < 3; ++p) last[p] = a->sharpened[p] ? sn::PlaneViewW{a->d_s[p], a->dstbytes[p], a->dstpitch[p]} : dst[p];
-    for (int p = 0; p < 3; ++p) {
-        t1[p] = sn::PlaneViewW{a->d_t1[p], a->tbytes[p], a->tpitch[p]}, u1[p] = sn::PlaneViewW{a->d_u1[p], a->u1bytes[p], a->tpitch[p]};
-        t2[p] = sn::PlaneViewW{a->d_t2[p], a->t2bytes[p], a->t2pitch[p]}, e[p] = sn::PlaneViewW{a->d_e[p], a->obytes[p], a->opitch[p]};
-    }
-    // planes that are not processed are never touched by the passes (copies_elsewhere): their pointers only have to be there
-    const void* s1[3] = {src[0].base, src[1].base, src[2].base};
-    void* d1[3] = {dst[0].base, dst[1].base, dst[2].base};
-    const void* s2[3] = {src[0].base, src[1].base, src[2].base};
-    const PlaneArrays out(src, last);  // (the last step's frame strides and pitches as run_batch takes them)
-    for (int p = 0; p < a->planes; ++p)
-        if (a->process[p]) s1[p] = a->d_t1[p], d1[p] = a->d_u1[p], s2[p] = a->d_t2[p];
     for (int f0 = 0; f0 < n; f0 += a->cap) {
         const int m = n - f0 < a->cap ? n - f0 : a->cap;
-        const int32_t* par = parity ? parity + f0 : nullptr;
-        // a turn writes the lines its pass keeps: one launch per run of frames with the same field offset (field_run, as run_batch
-        // cuts them); a dh pass reads every line of its source: the whole form, one launch for the chunk
-        auto turns = [&](int right) -> int {
-            for (int g0 = 0; g0 < m;) {
-                sn::FieldRun run{m, -1};
-                if (!a->cfg.dh) run = sn::field_run(par, g0, m, [c1](int q) { return sn::field_offset(c1->cfg.order, q); });
-                for (int p = 0; p < a->planes; ++p) {
-                    if (!a->process[p]) continue;  // (dh forces every plane)
-                    if (!right)  // TurnLeft: the clip's plane -> h wide, w high
-                        SN_AA_HIP(sn::launch_turn(st, B, 0, run.end - g0, src[p].at(f0 + g0), a->w[p], a->h[p], t1[p].at(g0), run.offset));
-                    else  // TurnRight of the first pass's output
-                        SN_AA_HIP(sn::launch_turn(st, B, 1, run.end - g0, u1[p].at(g0), a->h[p], a->ow[p], t2[p].at(g0), run.offset));
-                }
-                g0 = run.end;
-            }
-            return SN_OK;
-        };
-        if (int rc = turns(0)) return rc;
-        SN_AA_SN(a->first, run_batch(c1, st, 0, m, s1, a->tbytes, a->tpitch, d1, a->u1bytes, a->tpitch, par));
-        if (int rc = turns(1)) return rc;
-        void* d2[3] = {nullptr, nullptr, nullptr};
-        for (int p = 0; p < a->planes; ++p) d2[p] = a->sharpened[p] ? last[p].base : dst[p].at(f0).base;  // (an intermediate holds the chunk from its frame 0)
-        // the contra-sharpening, behind the last step: the destination from the source and that step's output; one launch per sharpened plane
-        auto sharpened = [&]() -> int {
-            for (int p = 0; p < a->planes; ++p) {
-                if (!a->sharpened[p]) continue;
-                SN_AA_HIP(sn::launch_contra_sharpen(st, B, a->cfg.bits_per_sample, a->sharpen.amount, m, src[p].at(f0), last[p], a->w[p], a->h[p],
-                                                    dst[p].at(f0)));
-            }
-            return SN_OK;
-        };
-        // the edge mask, last: the chunk's result is merged into the source through the source's own mask, in place on the
-        // destination (which has the source's size: creation has seen to it); one launch per processed plane
-        auto masked = [&]() -> int {
-            // chroma through the source luma plane's mask: U and V in one launch
-            const bool by_luma = a->mask.kind && a->mask_chroma == SN_AA_MASK_CHROMA_LUMA && a->planes == 3 && a->process[1];
-            if (by_luma) {
-                const sn::PlaneView cs[2] = {src[1].at(f0), src[2].at(f0)}, ca[2] = {dst[1].at(f0), dst[2].at(f0)};
-                const sn::PlaneViewW cd[2] = {dst[1].at(f0), dst[2].at(f0)};
-                SN_AA_HIP(sn::launch_mask_merge_luma(st, B, a->cfg.bits_per_sample, a->mask.lo, a->mask.hi, a->mask.expand, m, src[0].at(f0), a->cfg.sub_w,
-                                                     a->cfg.sub_h, 2, cs, ca, a->w[1], a->h[1], cd));
-            }
-            for (int p = 0; p < (by_luma ? 1 : a->planes) && a->mask.kind; ++p) {
-                if (!a->process[p]) continue;
-                SN_AA_HIP(sn::launch_mask_merge(st, B, a->cfg.bits_per_sample, a->mask.lo, a->mask.hi, a->mask.expand, m, src[p].at(f0), dst[p].at(f0),
-                                                a->w[p], a->h[p], dst[p].at(f0)));
-            }
-            return SN_OK;
-        };
-        if (!a->reduce) {
-            SN_AA_SN(a->second, run_batch(c2, st, 0, m, s2, a->t2bytes, a->t2pitch, d2, out.dfs, out.dp, par));
-            if (int rc = sharpened()) return rc;
-            if (int rc = masked()) return rc;
-            continue;
-        }
-        // reduce (dh: every plane is processed): the second pass fills E, the reduction writes the destination -- one launch
-        // per run of frames with the same field offset, which is where the source samples lie in E
-        void* e2[3] = {a->d_e[0], a->d_e[1], a->d_e[2]};
-        SN_AA_SN(a->second, run_batch(c2, st, 0, m, s2, a->t2bytes, a->t2pitch, e2, a->obytes, a->opitch, par));
-        for (int g0 = 0; g0 < m;) {
-            const sn::FieldRun run = sn::field_run(par, g0, m, [c2](int q) { return sn::field_offset(c2->cfg.order, q); });
-            for (int p = 0; p < a->planes; ++p)
-                SN_AA_HIP(sn::launch_reduce(st, B, a->cfg.bits_per_sample, a->reduce, run.end - g0, e[p].at(g0), a->w[p], a->h[p], 1 - run.offset, run.offset,
-                                            a->sharpened[p] ? last[p].at(g0) : dst[p].at(f0 + g0)));
-            g0 = run.end;
-        }
-        if (int rc = sharpened()) return rc;
-        if (int rc = masked()) return rc;
+        for (int i = 0; i < a->plan.nsteps; ++i)
+            if (int rc = aa_step(a, a->plan.step[i], f0, m, src, dst, parity ? parity + f0 : nullptr)) return rc;
     }
     return SN_OK;
 }
@@ -2836,8 +2680,9 @@ static void plane_views(int planes, const void* const src[3], const int64_t sfs[
 // a plane that is not processed: source to destination, once; no turn and no pass
 static int aa_copy_plane(sn_aa_context* a, int p, int n, const sn::PlaneView& s, const sn::PlaneViewW& d)
 {
+    const sn::AaPlane& g = a->plan.plane[p];
     for (int f = 0; f < n; ++f)
-        SN_AA_HIP(hipMemcpy2DAsync(d.at(f).base, (size_t)d.pitch, s.at(f).base, (size_t)s.pitch, (size_t)a->w[p] * a->cfg.bytes_per_sample, a->h[p],
+        SN_AA_HIP(hipMemcpy2DAsync(d.at(f).base, (size_t)d.pitch, s.at(f).base, (size_t)s.pitch, (size_t)g.w * a->cfg.bytes_per_sample, g.h,
                                    hipMemcpyDeviceToDevice, a->stream));
     return SN_OK;
 }
@@ -2846,12 +2691,12 @@ int sn_aa_process_device_strided(sn_aa_context* a, int32_t nframes, const void* 
                                  void* const dst[3], const int64_t dfs[3], const int32_t dp[3], const int32_t* parity)
 {
     if (!a) return aa_fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
-    if (nframes < 0 || nframes > a->max_batch)
-        return aa_fail(a, SN_ERR_INVALID_ARG, "nframes " + std::to_string(nframes) + " outside 0..max_batch (" + std::to_string(a->max_batch) + ")");
+    if (nframes < 0 || nframes > a->plan.max_batch)
+        return aa_fail(a, SN_ERR_INVALID_ARG, "nframes " + std::to_string(nframes) + " outside 0..max_batch (" + std::to_string(a->plan.max_batch) + ")");
     if (!src || !sfs || !sp || !dst || !dfs || !dp) return aa_fail(a, SN_ERR_INVALID_ARG, "plane / stride array is NULL");
     const int B = a->cfg.bytes_per_sample;
-    for (int p = 0; p < a->planes; ++p) {
-        if (!src[p] || !dst[p] || sp[p] < a->w[p] * B || dp[p] < a->dstw[p] * B)
+    for (int p = 0; p < a->plan.planes; ++p) {
+        if (!src[p] || !dst[p] || sp[p] < a->plan.plane[p].w * B || dp[p] < a->plan.plane[p].dstw * B)
             return aa_fail(a, SN_ERR_INVALID_ARG, "plane pointer is NULL or pitch smaller than the row");
         if (sp[p] % B || dp[p] % B || sfs[p] % B || dfs[p] % B || (uintptr_t)src[p] % B || (uintptr_t)dst[p] % B)
             return aa_fail(a, SN_ERR_INVALID_ARG, "plane pointer / pitch / frame stride not aligned to the sample size");
@@ -2860,9 +2705,9 @@ int sn_aa_process_device_strided(sn_aa_context* a, int32_t nframes, const void* 
     SN_AA_HIP(hipSetDevice(a->cfg.device));
     sn::PlaneView sv[3];
     sn::PlaneViewW dv[3];
-    plane_views(a->planes, src, sfs, sp, dst, dfs, dp, sv, dv);
-    for (int p = 0; p < a->planes; ++p)
-        if (!a->process[p])
+    plane_views(a->plan.planes, src, sfs, sp, dst, dfs, dp, sv, dv);
+    for (int p = 0; p < a->plan.planes; ++p)
+        if (!a->plan.plane[p].process)
             if (int rc = aa_copy_plane(a, p, nframes, sv[p], dv[p])) return rc;
     return aa_run(a, nframes, sv, dv, parity);
 }
@@ -2870,7 +2715,7 @@ int sn_aa_process_device_strided(sn_aa_context* a, int32_t nframes, const void* 
 static int aa_surface_run(void* self, int m, const sn::PlaneView s[3], const sn::PlaneViewW d[3], const int32_t* parity)
 {
     sn_aa_context* a = static_cast<sn_aa_context*>(self);
-    if (!a->process[0] && !a->luma_elsewhere)  // luma that is not processed: source to destination, once (chroma: surface_walk)
+    if (!a->plan.plane[0].process && !a->luma_elsewhere)  // luma that is not processed: source to destination, once (chroma: surface_walk)
         if (int rc = aa_copy_plane(a, 0, m, s[0], d[0])) return rc;
     return aa_run(a, m, s, d, parity);
 }
@@ -2885,17 +2730,18 @@ int sn_aa_process_device_surfaces(sn_aa_context* a, int32_t nframes, const sn_su
     if (rc != SN_OK) return aa_fail(a, rc, msg);
     if (surface_plain(src) && surface_plain(dst))  // the planar call itself
         return sn_aa_process_device_strided(a, nframes, src->plane, src->frame_stride, src->pitch, dst->plane, dst->frame_stride, dst->pitch, parity);
-    if (nframes < 0 || nframes > a->max_batch)
-        return aa_fail(a, SN_ERR_INVALID_ARG, "nframes " + std::to_string(nframes) + " outside 0..max_batch (" + std::to_string(a->max_batch) + ")");
+    if (nframes < 0 || nframes > a->plan.max_batch)
+        return aa_fail(a, SN_ERR_INVALID_ARG, "nframes " + std::to_string(nframes) + " outside 0..max_batch (" + std::to_string(a->plan.max_batch) + ")");
     SurfaceGeometry g;
     g.B = a->cfg.bytes_per_sample;
     g.bits = a->cfg.bits_per_sample;
-    g.planes = a->planes;
+    g.planes = a->plan.planes;
     g.sub_w = a->cfg.sub_w, g.sub_h = a->cfg.sub_h;
-    g.max_batch = a->max_batch;
-    for (int p = 0; p < g.planes; ++p) g.w_in[p] = a->w[p], g.h_in[p] = a->h[p], g.w_out[p] = a->dstw[p], g.h_out[p] = a->dsth[p];
-    g.luma_processed = a->process[0];
-    g.chroma_processed = g.planes < 3 || a->process[1];
+    g.max_batch = a->plan.max_batch;
+    const sn::AaPlane* pl = a->plan.plane;
+    for (int p = 0; p < g.planes; ++p) g.w_in[p] = pl[p].w, g.h_in[p] = pl[p].h, g.w_out[p] = pl[p].dstw, g.h_out[p] = pl[p].dsth;
+    g.luma_processed = pl[0].process;
+    g.chroma_processed = g.planes < 3 || pl[1].process;
     g.all_lines = true;  // a turn reads whole source rows, whichever destination lines it writes
     SurfaceSide ss, ds;
     rc = surface_side("src", src, g.w_in, g, ss, msg);
@@ -2932,13 +2778,13 @@ int sn_aa_synchronize(sn_aa_context* a)
 
 void* sn_aa_get_stream(sn_aa_context* a) { return a ? reinterpret_cast<void*>(a->stream) : nullptr; }
 
-int sn_aa_get_reduce(sn_aa_context* a) { return a ? a->reduce : -1; }
+int sn_aa_get_reduce(sn_aa_context* a) { return a ? a->plan.opt.reduce : -1; }
 
 int sn_aa_get_mask(sn_aa_context* a, sn_aa_mask* out)
 {
     if (!a) return aa_fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
     if (!out || out->struct_size != (int32_t)sizeof(sn_aa_mask)) return aa_fail(a, SN_ERR_INVALID_ARG, "out is NULL or sn_aa_mask.struct_size mismatch");
-    *out = a->mask;
+    *out = a->plan.opt.mask;
     return SN_OK;
 }
 
@@ -2949,7 +2795,7 @@ int sn_aa_get_mask_ex(sn_aa_context* a, sn_aa_mask_ex* out)
         return aa_fail(a, SN_ERR_INVALID_ARG, "out is NULL or sn_aa_mask_ex.struct_size mismatch");
     *out = sn_aa_mask_ex{};
     out->struct_size = (int32_t)sizeof(sn_aa_mask_ex);
-    out->chroma = a->mask_chroma;
+    out->chroma = a->plan.opt.mask_chroma;
     return SN_OK;
 }
 
@@ -2958,7 +2804,7 @@ int sn_aa_get_sharpen(sn_aa_context* a, sn_aa_sharpen* out)
     if (!a) return aa_fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
     if (!out || out->struct_size != (int32_t)sizeof(sn_aa_sharpen))
         return aa_fail(a, SN_ERR_INVALID_ARG, "out is NULL or sn_aa_sharpen.struct_size mismatch");
-    *out = a->sharpen;
+    *out = a->plan.opt.sharpen;
     return SN_OK;
 }
 
@@ -2983,20 +2829,21 @@ int sn_aa_get_parts_info(sn_aa_context* a, int32_t pass, sn_parts_info* info)
 // -- host frames ------------------------------------------------------------------------------------------------
 static int aa_ensure_group(sn_aa_context* a, int gi, int n)
 {
+    const sn::AaPlane* pl = a->plan.plane;
     if (!a->up) {
         SN_AA_HIP(hipStreamCreateWithFlags(&a->up, hipStreamNonBlocking));
         SN_AA_HIP(hipStreamCreateWithFlags(&a->down, hipStreamNonBlocking));
-        a->groups.resize((size_t)a->ring_groups + 1);
+        a->groups.resize((size_t)a->plan.ring_groups + 1);
         ensure_copier(reinterpret_cast<Context*>(a->first));
         a->copier = reinterpret_cast<Context*>(a->first)->copier;  // the first pass's copy threads (it never uses them itself here)
     }
     sn_aa_context::Group& g = a->groups[(size_t)gi];
     if (g.n) return SN_OK;
-    for (int p = 0; p < a->planes; ++p) {
-        const size_t nb = (size_t)a->cbytes[p] * n, onb = (size_t)a->dstbytes[p] * n;
+    for (int p = 0; p < a->plan.planes; ++p) {
+        const size_t nb = (size_t)pl[p].cbytes * n, onb = (size_t)pl[p].dstbytes * n;
         // a plane that is not processed never visits the device: its staging carries it from submission to collection
         SN_AA_HIP(hipHostMalloc(reinterpret_cast<void**>(&g.h_src[p]), nb, hipHostMallocDefault));
-        if (!a->process[p]) continue;
+        if (!pl[p].process) continue;
         SN_AA_HIP(hipHostMalloc(reinterpret_cast<void**>(&g.h_dst[p]), onb, hipHostMallocDefault));
         SN_AA_HIP(hipMalloc(reinterpret_cast<void**>(&g.d_src[p]), nb));
         SN_AA_HIP(hipMalloc(reinterpret_cast<void**>(&g.d_out[p]), onb));
@@ -3010,9 +2857,9 @@ static int aa_ensure_group(sn_aa_context* a, int gi, int n)
 static int aa_ensure_ring(sn_aa_context* a)
 {
     if (a->ring_ready) return SN_OK;
-    for (int gi = 0; gi < a->ring_groups; ++gi)
-        if (int rc = aa_ensure_group(a, gi, a->per_group)) return rc;
-    if (int rc = aa_ensure_intermediates(a, a->per_group)) return rc;
+    for (int gi = 0; gi < a->plan.ring_groups; ++gi)
+        if (int rc = aa_ensure_group(a, gi, a->plan.per_group)) return rc;
+    if (int rc = aa_ensure_intermediates(a, a->plan.per_group)) return rc;
     SN_AA_SN(a->first, prepare_small_launch_scratch(reinterpret_cast<Context*>(a->first)));
     SN_AA_SN(a->second, prepare_small_launch_scratch(reinterpret_cast<Context*>(a->second)));
     a->ring_ready = true;
@@ -3022,8 +2869,8 @@ static int aa_ensure_ring(sn_aa_context* a)
 static int aa_check_host_planes(sn_aa_context* a, const void* const ptr[3], const int32_t pitch[3], bool out = false)
 {
     if (!ptr || !pitch) return aa_fail(a, SN_ERR_INVALID_ARG, "plane array is NULL");
-    for (int p = 0; p < a->planes; ++p)
-        if (!ptr[p] || pitch[p] < (out ? a->dstw[p] : a->w[p]) * a->cfg.bytes_per_sample)
+    for (int p = 0; p < a->plan.planes; ++p)
+        if (!ptr[p] || pitch[p] < (out ? a->plan.plane[p].dstw : a->plan.plane[p].w) * a->cfg.bytes_per_sample)
             return aa_fail(a, SN_ERR_INVALID_ARG, "plane pointer is NULL or pitch smaller than the row");
     return SN_OK;
 }
@@ -3033,28 +2880,29 @@ static int aa_check_host_planes(sn_aa_context* a, const void* const ptr[3], cons
 static int aa_stage(sn_aa_context* a, sn_aa_context::Group& g, int k, const void* const src[3], const int32_t sp[3], void* const dst[3],
                     const int32_t dp[3], int32_t parity)
 {
+    const sn::AaPlane* pl = a->plan.plane;
     const int B = a->cfg.bytes_per_sample;
     sn_aa_context::Slot sl{};
     sl.parity = parity;
     Copier::Job jobs[3];
     int nj = 0;
     bool direct[3] = {false, false, false};
-    for (int p = 0; p < a->planes; ++p) {
-        if (!a->process[p]) {  // host to host, once where the destination is known
+    for (int p = 0; p < a->plan.planes; ++p) {
+        if (!pl[p].process) {  // host to host, once where the destination is known
             sl.copied[p] = dst != nullptr;
-            jobs[nj++] = {dst ? static_cast<uint8_t*>(dst[p]) : g.h_src[p] + k * a->cbytes[p], static_cast<const uint8_t*>(src[p]),
-                          dst ? dp[p] : a->pitch[p], sp[p], a->w[p] * B, a->h[p]};
+            jobs[nj++] = {dst ? static_cast<uint8_t*>(dst[p]) : g.h_src[p] + k * pl[p].cbytes, static_cast<const uint8_t*>(src[p]),
+                          dst ? dp[p] : pl[p].pitch, sp[p], pl[p].w * B, pl[p].h};
             continue;
         }
-        direct[p] = sn::plane_is_pinned(src[p], sp[p], a->w[p] * B, a->h[p]);
-        if (!direct[p]) jobs[nj++] = {g.h_src[p] + k * a->cbytes[p], static_cast<const uint8_t*>(src[p]), a->pitch[p], sp[p], a->w[p] * B, a->h[p]};
-        if (dst && sn::plane_is_pinned(dst[p], dp[p], a->dstw[p] * B, a->dsth[p])) sl.out[p] = dst[p], sl.out_pitch[p] = dp[p];
+        direct[p] = sn::plane_is_pinned(src[p], sp[p], pl[p].w * B, pl[p].h);
+        if (!direct[p]) jobs[nj++] = {g.h_src[p] + k * pl[p].cbytes, static_cast<const uint8_t*>(src[p]), pl[p].pitch, sp[p], pl[p].w * B, pl[p].h};
+        if (dst && sn::plane_is_pinned(dst[p], dp[p], pl[p].dstw * B, pl[p].dsth)) sl.out[p] = dst[p], sl.out_pitch[p] = dp[p];
     }
     if (nj) a->copier->run(jobs, nj);
-    for (int p = 0; p < a->planes; ++p) {
-        if (!a->process[p]) continue;
-        SN_AA_HIP(hipMemcpy2DAsync(g.d_src[p] + k * a->cbytes[p], a->pitch[p], direct[p] ? src[p] : g.h_src[p] + k * a->cbytes[p],
-                                   direct[p] ? (size_t)sp[p] : (size_t)a->pitch[p], (size_t)a->w[p] * B, a->h[p], hipMemcpyHostToDevice, a->up));
+    for (int p = 0; p < a->plan.planes; ++p) {
+        if (!pl[p].process) continue;
+        SN_AA_HIP(hipMemcpy2DAsync(g.d_src[p] + k * pl[p].cbytes, pl[p].pitch, direct[p] ? src[p] : g.h_src[p] + k * pl[p].cbytes,
+                                   direct[p] ? (size_t)sp[p] : (size_t)pl[p].pitch, (size_t)pl[p].w * B, pl[p].h, hipMemcpyHostToDevice, a->up));
     }
     sl.state = Context::kStaged;
     g.slot[(size_t)k] = sl;
@@ -3065,34 +2913,32 @@ static int aa_stage(sn_aa_context* a, sn_aa_context::Group& g, int k, const void
 // The staged slots [lo, hi) of a group: one batch on the call's stream behind their uploads, their downloads behind it.
 static int aa_launch(sn_aa_context* a, sn_aa_context::Group& g)
 {
+    const sn::AaPlane* pl = a->plan.plane;
     const int n = g.hi - g.lo;
     if (n <= 0) return SN_OK;
     const int B = a->cfg.bytes_per_sample;
     SN_AA_HIP(hipEventRecord(g.arrived, a->up));
     SN_AA_HIP(hipStreamWaitEvent(a->stream, g.arrived, 0));
-    const void* s3[3] = {nullptr, nullptr, nullptr};
-    void* d3[3] = {nullptr, nullptr, nullptr};
     std::vector<int32_t> par((size_t)n);
     for (int k = 0; k < n; ++k) par[(size_t)k] = g.slot[(size_t)(g.lo + k)].parity;
-    bool any = false;
-    for (int p = 0; p < a->planes; ++p) {
-        any = any || a->process[p];
-        s3[p] = a->process[p] ? g.d_src[p] + g.lo * a->cbytes[p] : g.h_src[p];  // (not processed: never read on the device)
-        d3[p] = a->process[p] ? g.d_out[p] + g.lo * a->dstbytes[p] : g.h_src[p];
-    }
     sn::PlaneView sv[3];
     sn::PlaneViewW dv[3];
-    plane_views(a->planes, s3, a->cbytes, a->pitch, d3, a->dstbytes, a->dstpitch, sv, dv);
+    bool any = false;
+    for (int p = 0; p < a->plan.planes; ++p) {
+        any = any || pl[p].process;
+        sv[p] = sn::PlaneView{pl[p].process ? g.d_src[p] + g.lo * pl[p].cbytes : g.h_src[p], pl[p].cbytes, pl[p].pitch};  // (not processed: never read on the device)
+        dv[p] = sn::PlaneViewW{pl[p].process ? g.d_out[p] + g.lo * pl[p].dstbytes : g.h_src[p], pl[p].dstbytes, pl[p].dstpitch};
+    }
     if (any)
         if (int rc = aa_run(a, n, sv, dv, par.data())) return rc;
     SN_AA_HIP(hipEventRecord(g.swept, a->stream));
     SN_AA_HIP(hipStreamWaitEvent(a->down, g.swept, 0));
     for (int k = g.lo; k < g.hi; ++k) {
         sn_aa_context::Slot& sl = g.slot[(size_t)k];
-        for (int p = 0; p < a->planes; ++p) {
-            if (!a->process[p]) continue;
-            SN_AA_HIP(hipMemcpy2DAsync(sl.out[p] ? sl.out[p] : g.h_dst[p] + k * a->dstbytes[p], sl.out[p] ? (size_t)sl.out_pitch[p] : (size_t)a->dstpitch[p],
-                                       g.d_out[p] + k * a->dstbytes[p], a->dstpitch[p], (size_t)a->dstw[p] * B, a->dsth[p], hipMemcpyDeviceToHost, a->down));
+        for (int p = 0; p < a->plan.planes; ++p) {
+            if (!pl[p].process) continue;
+            SN_AA_HIP(hipMemcpy2DAsync(sl.out[p] ? sl.out[p] : g.h_dst[p] + k * pl[p].dstbytes, sl.out[p] ? (size_t)sl.out_pitch[p] : (size_t)pl[p].dstpitch,
+                                       g.d_out[p] + k * pl[p].dstbytes, pl[p].dstpitch, (size_t)pl[p].dstw * B, pl[p].dsth, hipMemcpyDeviceToHost, a->down));
         }
         sl.state = Context::kInFlight;
     }
@@ -3105,7 +2951,7 @@ int sn_aa_host_slots(sn_aa_context* a)
 {
     if (!a) return 0;
     if (hipSetDevice(a->cfg.device) != hipSuccess || aa_ensure_ring(a) != SN_OK) return 0;
-    return a->depth;
+    return a->plan.depth;
 }
 
 int sn_aa_submit_host(sn_aa_context* a, const void* const src[3], const int32_t sp[3], int32_t parity, int32_t* slot_out)
@@ -3115,13 +2961,13 @@ int sn_aa_submit_host(sn_aa_context* a, const void* const src[3], const int32_t 
     if (int rc = aa_check_host_planes(a, src, sp)) return rc;
     SN_AA_HIP(hipSetDevice(a->cfg.device));
     if (int rc = aa_ensure_ring(a)) return rc;
-    const int slot = a->ring_next, gi = slot / a->per_group, k = slot % a->per_group;
+    const int slot = a->ring_next, gi = slot / a->plan.per_group, k = slot % a->plan.per_group;
     sn_aa_context::Group& g = a->groups[(size_t)gi];
     if (g.slot[(size_t)k].state != Context::kFree)
-        return aa_fail(a, SN_ERR_BUSY, "all " + std::to_string(a->depth) + " host slots are in flight: collect slot " + std::to_string(slot) + " first");
+        return aa_fail(a, SN_ERR_BUSY, "all " + std::to_string(a->plan.depth) + " host slots are in flight: collect slot " + std::to_string(slot) + " first");
     if (k == 0) g.lo = g.hi = 0;  // the ring came round to this group again
     if (int rc = aa_stage(a, g, k, src, sp, nullptr, nullptr, parity)) return rc;
-    a->ring_next = (slot + 1) % a->depth;
+    a->ring_next = (slot + 1) % a->plan.depth;
     *slot_out = slot;
     return g.hi == g.n ? aa_launch(a, g) : SN_OK;
 }
@@ -3129,6 +2975,7 @@ int sn_aa_submit_host(sn_aa_context* a, const void* const src[3], const int32_t 
 // Waits for slot k of group g and brings its planes into the caller's.
 static int aa_finish(sn_aa_context* a, sn_aa_context::Group& g, int k, void* const dst[3], const int32_t dp[3])
 {
+    const sn::AaPlane* pl = a->plan.plane;
     const int B = a->cfg.bytes_per_sample;
     sn_aa_context::Slot& sl = g.slot[(size_t)k];
     if (sl.state == Context::kStaged)  // its group is not full yet: run what is staged
@@ -3136,13 +2983,13 @@ static int aa_finish(sn_aa_context* a, sn_aa_context::Group& g, int k, void* con
     SN_AA_HIP(hipEventSynchronize(g.done));
     Copier::Job jobs[3];
     int nj = 0;
-    for (int p = 0; p < a->planes; ++p) {
-        if (a->process[p] ? sl.out[p] == dst[p] : sl.copied[p]) continue;  // already there
+    for (int p = 0; p < a->plan.planes; ++p) {
+        if (pl[p].process ? sl.out[p] == dst[p] : sl.copied[p]) continue;  // already there
         // (a plane that is not processed has the clip's geometry on both sides: there is none with dh)
-        if (a->process[p])
-            jobs[nj++] = {static_cast<uint8_t*>(dst[p]), g.h_dst[p] + k * a->dstbytes[p], dp[p], a->dstpitch[p], a->dstw[p] * B, a->dsth[p]};
+        if (pl[p].process)
+            jobs[nj++] = {static_cast<uint8_t*>(dst[p]), g.h_dst[p] + k * pl[p].dstbytes, dp[p], pl[p].dstpitch, pl[p].dstw * B, pl[p].dsth};
         else
-            jobs[nj++] = {static_cast<uint8_t*>(dst[p]), g.h_src[p] + k * a->cbytes[p], dp[p], a->pitch[p], a->w[p] * B, a->h[p]};
+            jobs[nj++] = {static_cast<uint8_t*>(dst[p]), g.h_src[p] + k * pl[p].cbytes, dp[p], pl[p].pitch, pl[p].w * B, pl[p].h};
     }
     if (nj) a->copier->run(jobs, nj);
     sl = sn_aa_context::Slot{};
@@ -3152,11 +2999,12 @@ static int aa_finish(sn_aa_context* a, sn_aa_context::Group& g, int k, void* con
 int sn_aa_collect_host(sn_aa_context* a, int32_t slot, void* const dst[3], const int32_t dp[3])
 {
     if (!a) return aa_fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
-    if (!a->ring_ready || slot < 0 || slot >= a->depth || a->groups[(size_t)(slot / a->per_group)].slot[(size_t)(slot % a->per_group)].state == Context::kFree)
+    const int per_group = a->plan.per_group;
+    if (!a->ring_ready || slot < 0 || slot >= a->plan.depth || a->groups[(size_t)(slot / per_group)].slot[(size_t)(slot % per_group)].state == Context::kFree)
         return aa_fail(a, SN_ERR_INVALID_ARG, "slot " + std::to_string(slot) + " holds no frame");
     if (int rc = aa_check_host_planes(a, dst, dp, true)) return rc;
     SN_AA_HIP(hipSetDevice(a->cfg.device));
-    return aa_finish(a, a->groups[(size_t)(slot / a->per_group)], slot % a->per_group, dst, dp);
+    return aa_finish(a, a->groups[(size_t)(slot / per_group)], slot % per_group, dst, dp);
 }
 
 // The one-frame case: a slot of its own (so that frames in the ring stay where they are), staged, run and collected at once.
@@ -3170,8 +3018,8 @@ int sn_aa_process_host(sn_aa_context* a, const void* const src[3], const int32_t
     SN_AA_HIP(hipSetDevice(a->cfg.device));
     SN_AA_SN(a->first, prepare_small_launch_scratch(reinterpret_cast<Context*>(a->first)));
     SN_AA_SN(a->second, prepare_small_launch_scratch(reinterpret_cast<Context*>(a->second)));
-    if (int rc = aa_ensure_group(a, a->ring_groups, 1)) return rc;
-    sn_aa_context::Group& g = a->groups[(size_t)a->ring_groups];
+    if (int rc = aa_ensure_group(a, a->plan.ring_groups, 1)) return rc;
+    sn_aa_context::Group& g = a->groups[(size_t)a->plan.ring_groups];
     g.lo = g.hi = 0;
     if (int rc = aa_stage(a, g, 0, src, sp, dst, dp, parity)) return rc;
     return aa_finish(a, g, 0, dst, dp);

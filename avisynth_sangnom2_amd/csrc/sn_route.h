@@ -11,6 +11,7 @@
 #include <string>
 
 #include "sangnom_hip.h"
+#include "sn_surface_plan.h"
 #include "sn_sweep_args.h"
 
 namespace sn {
@@ -174,8 +175,7 @@ inline ClipPlan clip_plan(const sn_config& cfg, int arith, bool column_parts, co
         c.aaf[i] = cfg.bytes_per_sample < 4
                        ? (aa[i] * 21.0f / 16.0f) * (float)(1 << (cfg.bits_per_sample - 8))
                        : (aa[i] * 21.0f / 16.0f) / 256.0f;
-    c.process[0] = cfg.luma != 0;
-    c.process[1] = c.process[2] = cfg.chroma != 0;
+    for (int p = 0; p < 3; ++p) c.process[p] = plane_selected(cfg, p);
     c.out_height = cfg.dh ? cfg.height * 2 : cfg.height;
     c.stride_e = (cfg.width + 31) & ~31;
     c.bh = (c.out_height + 1) >> 1;
@@ -263,16 +263,7 @@ inline ClipPlan clip_plan(const sn_config& cfg, int arith, bool column_parts, co
 }
 
 // ---- fields and kept lines --------------------------------------------------------------------------------------------
-// GetFrame's field choice, SangNom2.cpp:336-341.
-inline int field_offset(int order, int parity)
-{
-    switch (order) {
-    case 0: return parity ? 0 : 1;
-    case 1: return 0;
-    default: return 1;
-    }
-}
-
+// (field_offset, GetFrame's field choice: sn_surface_plan.h, with the cutter of runs of frames)
 // Of a processed plane only the kept field is ever read (the other lines are the ones being interpolated,
 // SangNom2.cpp:361-366), so only those lines need to cross PCIe: line `first`, then every `step`-th, `rows` of them.  A
 // copied plane and a double-height clip (whose every line is kept) go as a whole.

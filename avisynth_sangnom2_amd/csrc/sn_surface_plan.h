@@ -3,13 +3,30 @@
 //   surface_plan(): from the two sides' layouts and what the context processes to the scratch parts the call needs, the launches
 //   that turn the source into planar LSB-aligned planes, where the passes read and write, and the launches that finish the
 //   destination.  surface_walk (sn_api.hip) executes a plan and decides nothing itself; surface_scratch allocates plan.need.
-//   field_run(): a batch cut into runs of frames with the same field offset.
+//   field_run(): a batch cut into runs of frames with the same field offset; field_offset() and plane_selected(): what a clip's
+//   configuration says of a frame's field and of a plane (here so that every host-only header has the one definition).
 #pragma once
 #include <stdint.h>
 
 #include <string>
 
+#include "sangnom_hip.h"
+
 namespace sn {
+
+// ---- fields and planes ---------------------------------------------------------------------------------------------------------
+// GetFrame's field choice, SangNom2.cpp:336-341.
+inline int field_offset(int order, int parity)
+{
+    switch (order) {
+    case 0: return parity ? 0 : 1;
+    case 1: return 0;
+    default: return 1;
+    }
+}
+
+// processPlane[p]: cfg.luma / cfg.chroma select the plane (dh forces every plane on top of this: ClipPlan::enabled)
+inline bool plane_selected(const sn_config& cfg, int p) { return p == 0 ? cfg.luma != 0 : cfg.chroma != 0; }
 
 // ---- runs of frames ------------------------------------------------------------------------------------------------------------
 // The run of frames with the same field offset that starts at frame f of [0, m): parity == nullptr means parity 1 for every

@@ -126,6 +126,31 @@ def test_a_tiny_scratch_budget_walks_a_batch_in_chunks(hip_lib, form):
             _assert_frame(want[f], chunked[f], f"frame {f} (script)", plain[f], [True])
 
 
+def test_every_stage_at_once_with_a_chunk_boundary_inside_a_field_run(hip_lib):
+    """dh, the half-band reduction, the sharpening on every plane and chroma through luma's mask, order 0 with parities 1,1,0,0,1
+    -- the reduction is cut into the runs {0,1}, {2,3}, {4} of equal field offset -- under a budget whose chunks cut across the
+    middle run.  A frame of intermediates is T1, U1, T2, E and S of every plane, each row padded to 256 bytes: for a w x h
+    plane 256 (w + 2 w + h + 2 h + h) bytes, 327 680 for the 128x64 4:2:0 frame, so 1 MB (the smallest budget there is) holds
+    three frames: chunks {0,1,2} and {3,4}."""
+    fmt, w, h, kw = sc.BATCH[7][:4]
+    parities = [1, 1, 0, 0, 1]
+    case = (fmt, w, h, dict(kw, order=0), {}, {}, parities)
+    clip = clip_format(fmt, w, h)
+    assert clip.bytes == 1 and max(w, 2 * w, h) <= 256  # every pitch is 256
+    per_frame = sum(256 * (pw + 2 * pw + ph + 2 * ph + ph) for pw, ph in [(w, h), (w >> clip.subw, h >> clip.subh), (w >> clip.subw, h >> clip.subh)])
+    cap = (1 << 20) // per_frame
+    assert per_frame == 327680 and cap == 3 and parities[cap - 1] == parities[cap]  # frames 2 and 3 are one run, in two chunks
+    frames, _, plain, want = sc.expected(case, "halfband", sc.AMOUNT, True, sc.MASK, count=5, mask_chroma="luma")
+    kw = dict(max_batch=5, sharpen=sc.AMOUNT, sharpen_chroma=True, **_mask_kw(sc.MASK, "luma"), **_form_kw("reduce"), **case[3])
+    with SangNomAA(clip, **kw) as aa:
+        one = _batch(aa, clip, frames, parities)
+    with SangNomAA(clip, scratch_budget_mb=1, **kw) as aa:
+        chunked = _batch(aa, clip, frames, parities)
+    for f in range(5):
+        _assert_frame(one[f], chunked[f], f"frame {f} (chunked against one chunk)")
+        _assert_frame(want[f], chunked[f], f"frame {f} (script)", plain[f], [True] * 3)
+
+
 @pytest.mark.parametrize("form", FORMS)
 @pytest.mark.parametrize("i", range(len(sc.HOST)), ids=[f"{c[0]}-{c[1]}x{c[2]}" for c in sc.HOST])
 def test_the_host_call_and_the_ring(hip_lib, i, form):
