@@ -35,9 +35,10 @@ EXPORTS = (
     "sn_aa_get_reduce", "sn_reduce_device", "sn_aa_get_mask", "sn_mask_merge_device",
     "sn_aa_get_mask_ex", "sn_mask_merge_luma_device",
     "sn_aa_get_sharpen", "sn_contra_sharpen_device",
+    "sn_aa_get_fields", "sn_merge_device", "sn_turn_merge_device",
 )
 # ... and the ones whose names end in a digit
-EXPORTS_NUMBERED = ("sn_aa_create_ex2", "sn_aa_create_ex3", "sn_aa_create_ex4", "sn_aa_create_ex5")
+EXPORTS_NUMBERED = ("sn_aa_create_ex2", "sn_aa_create_ex3", "sn_aa_create_ex4", "sn_aa_create_ex5", "sn_aa_create_ex6")
 
 # sn_aa_options.reduce: the anti-aliasing call with dh returns the frame at source size (sangnom_hip.h has the arithmetic)
 SN_AA_REDUCE_NONE, SN_AA_REDUCE_TENT, SN_AA_REDUCE_HALFBAND = 0, 1, 2
@@ -132,6 +133,22 @@ def aa_sharpen(amount=None, chroma=False) -> "SnAASharpen":
     """sn_aa_sharpen: amount = None or 0 (off) or 1..255 (64 = unity); chroma = whether processed chroma planes are sharpened
     too.  The library checks the values."""
     return SnAASharpen(struct_size=ctypes.sizeof(SnAASharpen), amount=int(amount or 0), chroma=int(bool(chroma)))
+
+
+# sn_aa_fields.mode: which fields a pass interpolates -- the one cfg.order names, or both (order 1 and order 2, averaged)
+SN_AA_FIELDS_ONE, SN_AA_FIELDS_BOTH = 0, 1
+FIELDS = {"one": SN_AA_FIELDS_ONE, "both": SN_AA_FIELDS_BOTH}
+
+
+class SnAAFields(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_int32), ("mode", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6)]
+
+
+def aa_fields(fields="one") -> "SnAAFields":
+    """sn_aa_fields: fields = "one" (a pass keeps one field, as ever) or "both" (sangnom_hip.h, "Both fields")."""
+    if not isinstance(fields, str) or fields not in FIELDS:
+        raise ValueError("fields must be 'one' or 'both'")
+    return SnAAFields(struct_size=ctypes.sizeof(SnAAFields), mode=FIELDS[fields])
 
 
 class SnPartsInfo(ctypes.Structure):
@@ -245,6 +262,12 @@ def load():
     L.sn_aa_create_ex5.argtypes = [ctypes.POINTER(SnConfig), ctypes.POINTER(SnPolicy), ctypes.POINTER(SnOptions), ctypes.POINTER(SnAAOptions),
                                    ctypes.POINTER(SnAAMask), ctypes.POINTER(SnAAMaskEx), ctypes.POINTER(SnAASharpen), ctypes.POINTER(vp)]
     L.sn_aa_get_sharpen.argtypes = [vp, ctypes.POINTER(SnAASharpen)]
+    L.sn_aa_create_ex6.argtypes = [ctypes.POINTER(SnConfig), ctypes.POINTER(SnPolicy), ctypes.POINTER(SnOptions), ctypes.POINTER(SnAAOptions),
+                                   ctypes.POINTER(SnAAMask), ctypes.POINTER(SnAAMaskEx), ctypes.POINTER(SnAASharpen), ctypes.POINTER(SnAAFields),
+                                   ctypes.POINTER(vp)]
+    L.sn_aa_get_fields.argtypes = [vp, ctypes.POINTER(SnAAFields)]
+    L.sn_merge_device.argtypes = [vp, i32, vp, i64, i32, vp, i64, i32, i32, i32, vp, i64, i32]
+    L.sn_turn_merge_device.argtypes = [vp, i32, i32, vp, i64, i32, vp, i64, i32, i32, i32, vp, i64, i32]
     L.sn_contra_sharpen_device.argtypes = [vp, i32, i32, vp, i64, i32, vp, i64, i32, i32, i32, vp, i64, i32]
     L.sn_mask_merge_luma_device.argtypes = [vp, ctypes.POINTER(SnAAMask), i32, vp, i64, i32, i32, i32, p3v, p3l, p3i, p3v, p3l, p3i, i32, i32,
                                             p3v, p3l, p3i]

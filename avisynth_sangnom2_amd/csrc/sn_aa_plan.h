@@ -1,11 +1,13 @@
 // sn_aa_plan.h -- what an anti-aliasing call (sn_aa_*) does, decided once at creation, on the host only (no HIP header and no
 // pointers: a host compiler takes this header as it is, tests/c/aa_plan_check.cpp checks it against lines written out by hand).
-//   aa_check():    what sn_aa_create_ex5 refuses of its option structs, and the options it keeps.
-//   aa_geometry(): every plane size and pitch of the call, the host ring's split and the two passes' configurations.
+//   aa_check():    what sn_aa_create_ex6 refuses of its option structs, and the options it keeps.
+//   aa_geometry(): every plane size and pitch of the call, the host ring's split and the passes' configurations.
 //   AaBuf:         the caller's planes and the intermediates, which of them a plane needs and how large a frame of each is.
 //   aa_steps():    the stages of a chunk in order -- which planes, what each reads and writes, how it is cut into launches.
 // aa_run (sn_api.hip) executes plan.step[] and decides nothing itself; aa_ensure_intermediates allocates what aa_buf_needed
 // names, in chunks of aa_chunk_frames.  The next stage of the call is a step kind here and a case there.
+// What a processed plane costs in intermediates, in plane sizes per frame: three (T1, U1, T2); with dh five, with a reduction
+// nine; with both fields (sn_aa_fields, never with dh) five (T1, U1, U1B, T2, D2); one more where the plane is sharpened.
 #pragma once
 #include <stdint.h>
 
@@ -38,13 +40,14 @@ struct AaOptions {
     sn_aa_mask mask{};                        // kind != 0: the result is merged into the source through an edge mask (sn_mask.hip), last
     int mask_chroma = SN_AA_MASK_CHROMA_OWN;  // ... SN_AA_MASK_CHROMA_LUMA: planes 1 and 2 through the source luma plane's mask
     sn_aa_sharpen sharpen{};                  // amount != 0: the result is contra-sharpened (sn_sharpen.hip) behind the last step, before the mask
+    int fields = SN_AA_FIELDS_ONE;            // SN_AA_FIELDS_BOTH: every pass twice (order 1, order 2) and the average of the two (sn_merge.hip)
     AaOptions() { mask.struct_size = (int32_t)sizeof(sn_aa_mask), sharpen.struct_size = (int32_t)sizeof(sn_aa_sharpen); }
 };
 
-// Every refusal sn_aa_create_ex5 makes of cfg's own fields and of the option structs (NULL: defaults), in the order it makes
+// Every refusal sn_aa_create_ex6 makes of cfg's own fields and of the option structs (NULL: defaults), in the order it makes
 // them: SN_OK and `out`, or the code and `msg`.  What the two passes refuse of cfg follows at their creation.
 inline int aa_check(const sn_config& cfg, const sn_aa_options* aa_options, const sn_aa_mask* mask, const sn_aa_mask_ex* mask_ex, const sn_aa_sharpen* sharpen,
-                    AaOptions& out, std::string& msg)
+                    const sn_aa_fields* fields, AaOptions& out, std::string& msg)
 {
     auto refuse = [&msg](int code, const char* text) {
         msg = text;
@@ -95,20 +98,44 @@ inline int aa_check(const sn_config& cfg, const sn_aa_options* aa_options, const
     }
     if (out.sharpen.amount && cfg.dh && !out.reduce)
         return refuse(SN_ERR_CONFIG, "SangNomAA: sharpen needs the frame at source size (dh=false, or dh=true with reduce)");
+    if (fields) {
+        if (fields->struct_size != (int32_t)sizeof(sn_aa_fields)) return refuse(SN_ERR_INVALID_ARG, "sn_aa_fields.struct_size mismatch");
+        if (fields->mode != SN_AA_FIELDS_ONE) {  // with one field the words below it are ignored
+            if (fields->mode != SN_AA_FIELDS_BOTH) return refuse(SN_ERR_INVALID_ARG, "sn_aa_fields.mode must be 0 (one) or 1 (both)");
+            for (int32_t r : fields->reserved)
+                if (r) return refuse(SN_ERR_INVALID_ARG, "sn_aa_fields.reserved must be zero");
+            out.fields = SN_AA_FIELDS_BOTH;
+        }
+    }
+    // the two dh results place the source on different lines: their average is a half-line blur (reduce needs dh and falls with it)
+    if (out.fields == SN_AA_FIELDS_BOTH && cfg.dh) return refuse(SN_ERR_CONFIG, "SangNomAA: both fields needs dh=false");
     msg.clear();
     return SN_OK;
 }
 
+// ... as sn_aa_create_ex5 makes them: one field per pass
+inline int aa_check(const sn_config& cfg, const sn_aa_options* aa_options, const sn_aa_mask* mask, const sn_aa_mask_ex* mask_ex, const sn_aa_sharpen* sharpen,
+                    AaOptions& out, std::string& msg)
+{
+    return aa_check(cfg, aa_options, mask, mask_ex, sharpen, nullptr, out, msg);
+}
+
 // ---- buffers and steps ---------------------------------------------------------------------------------------------------------
 // Where a plane of a chunk lies: the caller's source and destination, and the intermediates (one per processed plane each).
-//   T1  turned: input of the first pass (only its kept lines are written; dh: every line)
+//   T1  turned: input of the first pass (only its kept lines are written; dh and both fields: every line)
 //   U1  turned: its output (dh: twice as high)
-//   T2  turned back: input of the second pass (kept lines only; dh: every line, twice as wide)
+//   T2  turned back: input of the second pass (kept lines only; dh: every line, twice as wide; both fields: every line)
 //   E   reduce: the second pass's output, opitch x oh
 //   S   sharpen: the last step's output of a sharpened plane, dstpitch x dsth
-enum AaBuf : int8_t { kAaSrc, kAaDst, kAaT1, kAaU1, kAaT2, kAaE, kAaS, kAaBuffers, kAaNoBuf = -1 };
+//   U1B both fields: the first pass's order-2 output, as U1
+//   D2  both fields: the second pass's order-2 output, dstpitch x dsth (the order-1 output lies where the average goes)
+enum AaBuf : int8_t { kAaSrc, kAaDst, kAaT1, kAaU1, kAaT2, kAaE, kAaS, kAaU1B, kAaD2, kAaBuffers, kAaNoBuf = -1 };
 
-enum AaStepKind : int8_t { kAaTurnLeft, kAaPass1, kAaTurnRight, kAaPass2, kAaReduce, kAaSharpen, kAaMaskLuma, kAaMask };
+enum AaStepKind : int8_t {
+    kAaTurnLeft, kAaPass1, kAaTurnRight, kAaPass2, kAaReduce, kAaSharpen, kAaMaskLuma, kAaMask,
+    kAaPass1B, kAaTurnRightMerge, kAaPass2B, kAaMerge  // both fields
+};
+inline bool aa_is_pass(int kind) { return kind == kAaPass1 || kind == kAaPass2 || kind == kAaPass1B || kind == kAaPass2B; }
 
 // How a step's frames are cut into launches: the chunk in one piece (a turn then writes every line: line parity -1), or one
 // launch per run of frames with the same field offset (field_run), the offset being that of the first or the second pass's order.
@@ -116,7 +143,10 @@ enum AaCut : int8_t { kAaCutChunk, kAaCutRun1, kAaCutRun2 };
 
 // One stage of a chunk.  Within a step a run's planes come before the next run, the planes in ascending order.
 //   TurnLeft / TurnRight / Reduce / Sharpen / Mask  one launch per run and plane of `planes`: read[] -> write[p]
-//   Pass1 / Pass2   one run_batch for the chunk; a plane outside `planes` is not touched, its pointers only have to be there
+//   Pass1 / Pass2 / Pass1B / Pass2B   one run_batch for the chunk (B: of the order-2 twin); a plane outside `planes` is not
+//                   touched, its pointers only have to be there
+//   TurnRightMerge  one launch per plane: the turn of avg(read[0], read[1]) -> write[p]
+//   Merge           one launch per plane, in place: write[p] = avg(write[p], read[0])
 //   MaskLuma        one launch for planes 1 and 2, which also reads plane 0 of read[0]
 struct AaStep {
     int8_t kind = kAaTurnLeft;
@@ -127,7 +157,7 @@ struct AaStep {
     int32_t arg = 0;  // Reduce: the kernel (SN_AA_REDUCE_*); Sharpen: the amount
     bool on(int p) const { return (planes >> p) & 1; }
 };
-constexpr int kAaMaxSteps = 8;
+constexpr int kAaMaxSteps = 10;
 
 // ---- the plan ------------------------------------------------------------------------------------------------------------------
 struct AaPlane {
@@ -157,6 +187,7 @@ struct AaPlan {
     int depth = 0, ring_groups = 0, per_group = 1;
     int inner_batch = 1;  // max_batch of both passes
     sn_config c1{}, c2{};  // the passes' configurations, stream left null: the turned clip (subsampling swapped), the clip (dh: 2W wide)
+    sn_config c1b{}, c2b{};  // both fields: their twins -- c1 and c2 have order 1 then, these order 2, and nothing else differs
     AaPlane plane[3];
     int nsteps = 0;
     AaStep step[kAaMaxSteps];
@@ -182,6 +213,11 @@ inline AaPlan aa_geometry(const sn_config& cfg, const AaOptions& opt)
     P.c2 = cfg;  // TurnRight of the first pass's output: with dh that is twice as wide as the clip
     if (cfg.dh && cfg.width <= INT32_MAX / 2) P.c2.width = 2 * cfg.width;  // (a wider clip: creation refuses it between the passes' own checks)
     for (sn_config* c : {&P.c1, &P.c2}) c->max_batch = P.inner_batch, c->mode = SN_MODE_AUTO, c->stream = nullptr;
+    if (opt.fields == SN_AA_FIELDS_BOTH) {  // cfg.order has no influence: the twins are orders 1 and 2, which take no parity
+        P.c1.order = P.c2.order = 1;
+        P.c1b = P.c1, P.c2b = P.c2;
+        P.c1b.order = P.c2b.order = 2;
+    }
     P.planes = cfg.num_planes < 3 ? cfg.num_planes : 3;
     const int B = P.B;
     for (int p = 0; p < P.planes; ++p) {
@@ -214,6 +250,7 @@ inline bool aa_buf_needed(const AaPlan& P, int p, int buf)
 {
     const AaPlane& a = P.plane[p];
     if (p >= P.planes || !a.process) return false;  // copied from source to destination: no turn, no pass, no intermediate
+    if ((buf == kAaU1B || buf == kAaD2) && P.opt.fields == SN_AA_FIELDS_BOTH) return true;
     return buf == kAaT1 || buf == kAaU1 || buf == kAaT2 || (buf == kAaE && P.opt.reduce) || (buf == kAaS && a.sharpened);
 }
 
@@ -221,18 +258,18 @@ inline bool aa_buf_needed(const AaPlan& P, int p, int buf)
 inline int64_t aa_buf_frame_bytes(const AaPlan& P, int p, int buf)
 {
     const AaPlane& a = P.plane[p];
-    const int64_t nb[kAaBuffers] = {a.cbytes, a.dstbytes, a.tbytes, a.u1bytes, a.t2bytes, a.obytes, a.dstbytes};
+    const int64_t nb[kAaBuffers] = {a.cbytes, a.dstbytes, a.tbytes, a.u1bytes, a.t2bytes, a.obytes, a.dstbytes, a.u1bytes, a.dstbytes};
     return nb[buf];
 }
 inline int aa_buf_pitch(const AaPlan& P, int p, int buf)
 {
     const AaPlane& a = P.plane[p];
-    const int pitch[kAaBuffers] = {a.pitch, a.dstpitch, a.tpitch, a.tpitch, a.t2pitch, a.opitch, a.dstpitch};
+    const int pitch[kAaBuffers] = {a.pitch, a.dstpitch, a.tpitch, a.tpitch, a.t2pitch, a.opitch, a.dstpitch, a.tpitch, a.dstpitch};
     return pitch[buf];
 }
 
-// The intermediates of one frame: nine plane sizes per processed plane with a reduction instead of five (dh), one more per
-// sharpened plane.
+// The intermediates of one frame: nine plane sizes per processed plane with a reduction instead of five (dh), five instead of
+// three with both fields, one more per sharpened plane.
 inline int64_t aa_frame_bytes(const AaPlan& P)
 {
     int64_t per_frame = 0;
@@ -261,22 +298,31 @@ inline void aa_steps(AaPlan& P)
         AaStep& s = P.step[P.nsteps++] = AaStep();
         s.kind = kind, s.planes = planes, s.cut = cut, s.read[0] = r0, s.read[1] = r1;
         for (int p = 0; p < P.planes; ++p)
-            if (s.on(p) || kind == kAaPass1 || kind == kAaPass2) s.write[p] = w;
+            if (s.on(p) || aa_is_pass(kind)) s.write[p] = w;
         return s;
     };
+    const bool both = P.opt.fields == SN_AA_FIELDS_BOTH;
     // a turn writes the lines its pass keeps: one launch per run of frames with the same field offset, as run_batch cuts them;
-    // a dh pass reads every line of its source: the whole form, one launch for the chunk
-    const AaCut turn = P.dh ? kAaCutChunk : kAaCutRun1;
+    // a dh pass reads every line of its source, and so do the two passes of both fields together: the whole form, one launch
+    // for the chunk
+    const AaCut turn = P.dh || both ? kAaCutChunk : kAaCutRun1;
     if (processed) add(kAaTurnLeft, processed, turn, kAaSrc, kAaNoBuf, kAaT1);  // the clip's plane -> h wide, w high
     add(kAaPass1, processed, kAaCutChunk, kAaT1, kAaNoBuf, kAaU1);
-    if (processed) add(kAaTurnRight, processed, turn, kAaU1, kAaNoBuf, kAaT2);
-    // the last step -- the second pass, or the reduction -- writes the destination, or S where the plane is contra-sharpened
+    if (both) add(kAaPass1B, processed, kAaCutChunk, kAaT1, kAaNoBuf, kAaU1B);
+    if (processed && !both) add(kAaTurnRight, processed, turn, kAaU1, kAaNoBuf, kAaT2);
+    if (processed && both) add(kAaTurnRightMerge, processed, kAaCutChunk, kAaU1, kAaU1B, kAaT2);  // the average never reaches memory
+    // the last step -- the second pass, the reduction, or the average of both fields -- writes the destination, or S where the
+    // plane is contra-sharpened
     auto to_last = [&](AaStep& s) {
         for (int p = 0; p < P.planes; ++p)
             if ((sharpened >> p) & 1) s.write[p] = kAaS;
     };
     AaStep& pass2 = add(kAaPass2, processed, kAaCutChunk, kAaT2, kAaNoBuf, P.opt.reduce ? kAaE : kAaDst);
     if (!P.opt.reduce) to_last(pass2);
+    if (both) {  // the order-1 pass has written where the average goes: the average runs in place on it
+        add(kAaPass2B, processed, kAaCutChunk, kAaT2, kAaNoBuf, kAaD2);
+        if (processed) to_last(add(kAaMerge, processed, kAaCutChunk, kAaD2, kAaNoBuf, kAaDst));
+    }
     if (P.opt.reduce) {  // (dh: every plane is processed) one launch per run: the field offset is where the source samples lie in E
         AaStep& s = add(kAaReduce, processed, kAaCutRun2, kAaE, kAaNoBuf, kAaDst);
         s.arg = P.opt.reduce;

@@ -2194,6 +2194,69 @@ int sn_contra_sharpen_device(sn_context* h, int32_t amount, int32_t nframes, con
     return SN_OK;
 }
 
+// [first byte, one past the last byte) of `n` frames of `rows` rows of `row_bytes` each
+static void plane_span(const void* base, int64_t fs, int32_t pitch, int32_t n, int32_t rows, int64_t row_bytes, uintptr_t& lo, uintptr_t& hi)
+{
+    const int64_t last_frame = (int64_t)(n - 1) * fs, last_row = (int64_t)(rows - 1) * pitch;
+    lo = (uintptr_t)((intptr_t)base + (last_frame < 0 ? last_frame : 0));
+    hi = (uintptr_t)((intptr_t)base + (last_frame > 0 ? last_frame : 0) + last_row + row_bytes);
+}
+
+int sn_merge_device(sn_context* h, int32_t nframes, const void* a, int64_t afs, int32_t ap, const void* b, int64_t bfs, int32_t bp, int32_t width,
+                    int32_t height, void* dst, int64_t dfs, int32_t dp)
+{
+    Context* c = reinterpret_cast<Context*>(h);
+    if (!c) return sn::fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    const int B = c->cfg.bytes_per_sample;
+    if (!a || !b || !dst || nframes < 0 || width <= 0 || height <= 0 || width > INT32_MAX / 8 || height > INT32_MAX / 2)
+        return sn::fail(c, SN_ERR_INVALID_ARG, "sn_merge_device: bad pointer or size");
+    if (ap < width * B || bp < width * B || dp < width * B || ap % B || bp % B || dp % B || afs % B || bfs % B || dfs % B || (uintptr_t)a % B ||
+        (uintptr_t)b % B || (uintptr_t)dst % B)
+        return sn::fail(c, SN_ERR_INVALID_ARG, "sn_merge_device: pitch smaller than the row or misaligned");
+    if (nframes > 0) {  // in place on a or b exactly: each sample is read by the thread that overwrites it; nothing else may overlap
+        uintptr_t dlo, dhi;
+        plane_span(dst, dfs, dp, nframes, height, (int64_t)width * B, dlo, dhi);
+        const struct { const void* base; int64_t fs; int32_t pitch; } in[2] = {{a, afs, ap}, {b, bfs, bp}};
+        for (const auto& q : in) {
+            if (q.base == dst && q.fs == dfs && q.pitch == dp) continue;
+            uintptr_t lo, hi;
+            plane_span(q.base, q.fs, q.pitch, nframes, height, (int64_t)width * B, lo, hi);
+            if (lo < dhi && dlo < hi) return sn::fail(c, SN_ERR_INVALID_ARG, "sn_merge_device: dst overlaps a or b without being that very plane");
+        }
+    }
+    SN_HIP(c, hipSetDevice(c->device));
+    SN_HIP(c, sn::launch_merge(c->stream, B, nframes, sn::PlaneView{static_cast<const uint8_t*>(a), afs, ap},
+                               sn::PlaneView{static_cast<const uint8_t*>(b), bfs, bp}, width, height, sn::PlaneViewW{static_cast<uint8_t*>(dst), dfs, dp}));
+    return SN_OK;
+}
+
+int sn_turn_merge_device(sn_context* h, int32_t direction, int32_t nframes, const void* a, int64_t afs, int32_t ap, const void* b, int64_t bfs, int32_t bp,
+                         int32_t width, int32_t height, void* dst, int64_t dfs, int32_t dp)
+{
+    Context* c = reinterpret_cast<Context*>(h);
+    if (!c) return sn::fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    const int B = c->cfg.bytes_per_sample;
+    if (!a || !b || !dst || direction == 0 || nframes < 0 || width <= 0 || height <= 0 || width > INT32_MAX / 8 || height > INT32_MAX / 8)
+        return sn::fail(c, SN_ERR_INVALID_ARG, "sn_turn_merge_device: bad pointer, direction or size");
+    if (ap < width * B || bp < width * B || dp < height * B || ap % B || bp % B || dp % B || afs % B || bfs % B || dfs % B || (uintptr_t)a % B ||
+        (uintptr_t)b % B || (uintptr_t)dst % B)
+        return sn::fail(c, SN_ERR_INVALID_ARG, "sn_turn_merge_device: pitch smaller than the row or misaligned");
+    if (nframes > 0) {  // a tile's writes land where another tile still reads
+        uintptr_t dlo, dhi, lo, hi;
+        plane_span(dst, dfs, dp, nframes, width, (int64_t)height * B, dlo, dhi);
+        plane_span(a, afs, ap, nframes, height, (int64_t)width * B, lo, hi);
+        bool overlap = lo < dhi && dlo < hi;
+        plane_span(b, bfs, bp, nframes, height, (int64_t)width * B, lo, hi);
+        overlap = overlap || (lo < dhi && dlo < hi);
+        if (overlap) return sn::fail(c, SN_ERR_INVALID_ARG, "sn_turn_merge_device: dst must overlap neither a nor b");
+    }
+    SN_HIP(c, hipSetDevice(c->device));
+    SN_HIP(c, sn::launch_turn_merge(c->stream, B, direction > 0 ? 1 : 0, nframes, sn::PlaneView{static_cast<const uint8_t*>(a), afs, ap},
+                                    sn::PlaneView{static_cast<const uint8_t*>(b), bfs, bp}, width, height,
+                                    sn::PlaneViewW{static_cast<uint8_t*>(dst), dfs, dp}));
+    return SN_OK;
+}
+
 int sn_mask_merge_luma_device(sn_context* h, const sn_aa_mask* mask, int32_t nframes, const void* luma, int64_t lfs, int32_t lp, int32_t sub_w, int32_t sub_h,
                               const void* const src[2], const int64_t sfs[2], const int32_t sp[2], const void* const aa[2], const int64_t afs[2],
                               const int32_t ap[2], int32_t width, int32_t height, void* const dst[2], const int64_t dfs[2], const int32_t dp[2])
@@ -2417,10 +2480,15 @@ int sn_debug_read_coupled_rows(sn_context* h, int32_t which, void* host_dst, siz
 // With a contra-sharpening (sn_aa_sharpen.amount) the last step -- the second pass, or the reduction -- writes a sharpened
 // plane into one more intermediate of the destination's geometry and sn_sharpen.hip writes the destination from it and the
 // source: one plane size more per sharpened plane and frame.  The edge mask follows, unchanged.
+// With both fields (sn_aa_fields.mode; never with dh) each pass has an order-2 twin, a filter instance of its own on the same
+// stream: the turn writes every line, both instances of a pass read the same input, the turn back takes the average of the
+// first pass's two outputs (sn_turn.hip with a second source), and the second pass's two outputs are averaged in place where the
+// order-1 instance wrote (sn_merge.hip): five plane sizes of intermediates per processed plane and frame instead of three.
 struct sn_aa_context {
     sn_config cfg{};
     sn_context* first = nullptr;   // the turned clip
     sn_context* second = nullptr;  // the clip itself, on first's stream
+    sn_context* twin[2] = {nullptr, nullptr};  // both fields: the order-2 instances next to first and second, on first's stream
     hipStream_t stream = nullptr;
     hipStream_t up = nullptr, down = nullptr;  // host frames: H2D / D2H (created with the first group of slots)
     sn::AaPlan plan;                                   // every size, option and step of the call (sn_aa_plan.h)
@@ -2519,7 +2587,8 @@ void sn_aa_destroy(sn_aa_context* a)
     (void)hipSetDevice(a->cfg.device);
     for (hipStream_t st : {a->up, a->stream, a->down})  // frames in flight: in the order their work was queued
         if (st) (void)hipStreamSynchronize(st);
-    if (a->second) sn_destroy(a->second);
+    for (sn_context* t : {a->twin[1], a->twin[0], a->second})
+        if (t) sn_destroy(t);
     if (a->first) sn_destroy(a->first);  // owns the stream unless the caller gave one
     for (auto& planes : a->d)
         for (uint8_t* q : planes)
@@ -2561,6 +2630,12 @@ int sn_aa_create_ex4(const sn_config* cfg, const sn_policy* policy, const sn_opt
 int sn_aa_create_ex5(const sn_config* cfg, const sn_policy* policy, const sn_options* options, const sn_aa_options* aa_options, const sn_aa_mask* mask,
                      const sn_aa_mask_ex* mask_ex, const sn_aa_sharpen* sharpen, sn_aa_context** out)
 {
+    return sn_aa_create_ex6(cfg, policy, options, aa_options, mask, mask_ex, sharpen, nullptr, out);
+}
+
+int sn_aa_create_ex6(const sn_config* cfg, const sn_policy* policy, const sn_options* options, const sn_aa_options* aa_options, const sn_aa_mask* mask,
+                     const sn_aa_mask_ex* mask_ex, const sn_aa_sharpen* sharpen, const sn_aa_fields* fields, sn_aa_context** out)
+{
     auto fail_aa = [](sn_aa_context* a, int code, const std::string& msg) {
         g_aa_error = msg;
         if (a) sn_aa_destroy(a);
@@ -2568,10 +2643,10 @@ int sn_aa_create_ex5(const sn_config* cfg, const sn_policy* policy, const sn_opt
     };
     if (!cfg || !out) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "cfg / out is NULL");
     *out = nullptr;
-    // check, build the geometry, create the two passes, allocate (sn_aa_plan.h decides; nothing below does)
+    // check, build the geometry, create the passes, allocate (sn_aa_plan.h decides; nothing below does)
     sn::AaOptions opt;
     std::string msg;
-    if (int rc = sn::aa_check(*cfg, aa_options, mask, mask_ex, sharpen, opt, msg)) return fail_aa(nullptr, rc, msg);
+    if (int rc = sn::aa_check(*cfg, aa_options, mask, mask_ex, sharpen, fields, opt, msg)) return fail_aa(nullptr, rc, msg);
     sn_aa_context* a = new (std::nothrow) sn_aa_context();
     if (!a) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "out of host memory");
     a->cfg = *cfg;
@@ -2589,6 +2664,15 @@ int sn_aa_create_ex5(const sn_config* cfg, const sn_policy* policy, const sn_opt
     Context* f1 = reinterpret_cast<Context*>(a->first);
     f1->copies_elsewhere = reinterpret_cast<Context*>(a->second)->copies_elsewhere = true;
     a->stream = f1->stream;
+    if (opt.fields == SN_AA_FIELDS_BOTH) {  // the order-2 twins: the same configuration, policy and options, on the same stream
+        sn_config cb[2] = {a->plan.c1b, a->plan.c2b};
+        for (int k = 0; k < 2; ++k) {
+            cb[k].stream = c2.stream;
+            rc = sn_create_ex(&cb[k], policy, options, &a->twin[k]);
+            if (rc != SN_OK) return fail_aa(a, rc, sn_last_error(nullptr));
+            reinterpret_cast<Context*>(a->twin[k])->copies_elsewhere = true;
+        }
+    }
     if (int rc2 = aa_ensure_intermediates(a, a->plan.max_batch)) return fail_aa(a, rc2, a->err);
     *out = a;
     return SN_OK;
@@ -2604,7 +2688,7 @@ static int aa_step(sn_aa_context* a, const sn::AaStep& s, int f0, int m, const s
         return buf == sn::kAaDst ? dst[p].at(f0) : sn::PlaneViewW{a->d[buf][p], sn::aa_buf_frame_bytes(P, p, buf), sn::aa_buf_pitch(P, p, buf)};
     };
     auto rd = [&](int buf, int p) { return buf == sn::kAaSrc ? src[p].at(f0) : sn::PlaneView(wr(buf, p)); };
-    if (s.kind == sn::kAaPass1 || s.kind == sn::kAaPass2) {
+    if (sn::aa_is_pass(s.kind)) {
         // planes that are not processed are never touched by the passes (copies_elsewhere): their pointers only have to be there
         sn::PlaneView r[3];
         sn::PlaneViewW w[3];
@@ -2613,7 +2697,7 @@ static int aa_step(sn_aa_context* a, const sn::AaStep& s, int f0, int m, const s
             if (!s.on(p)) r[p].base = src[p].base, w[p].base = dst[p].at(f0).base;
         }
         const PlaneArrays v(r, w);
-        sn_context* h = s.kind == sn::kAaPass1 ? a->first : a->second;
+        sn_context* h = s.kind == sn::kAaPass1 ? a->first : s.kind == sn::kAaPass2 ? a->second : a->twin[s.kind == sn::kAaPass2B];
         SN_AA_SN(h, run_batch(reinterpret_cast<Context*>(h), st, 0, m, v.s, v.sfs, v.sp, v.d, v.dfs, v.dp, par));
         return SN_OK;
     }
@@ -2638,6 +2722,12 @@ static int aa_step(sn_aa_context* a, const sn::AaStep& s, int f0, int m, const s
                 break;
             case sn::kAaTurnRight:  // of the first pass's output
                 SN_AA_HIP(sn::launch_turn(st, B, 1, n, from, g.h, g.ow, to, run.offset));
+                break;
+            case sn::kAaTurnRightMerge:  // of the average of the first pass's two outputs
+                SN_AA_HIP(sn::launch_turn_merge(st, B, 1, n, from, rd(s.read[1], p).at(g0), g.h, g.ow, to));
+                break;
+            case sn::kAaMerge:  // in place: the order-1 output lies where the average goes
+                SN_AA_HIP(sn::launch_merge(st, B, n, sn::PlaneView(to), from, g.dstw, g.dsth, to));
                 break;
             case sn::kAaReduce:  // the run's field offset is where the source samples lie in E
                 SN_AA_HIP(sn::launch_reduce(st, B, P.bits, s.arg, n, from, g.w, g.h, 1 - run.offset, run.offset, to));
@@ -2772,6 +2862,8 @@ int sn_aa_synchronize(sn_aa_context* a)
     SN_AA_HIP(hipSetDevice(a->cfg.device));
     SN_AA_SN(a->first, sn_synchronize(a->first));  // the call's stream, and what a chain may have to report
     SN_AA_SN(a->second, sn_synchronize(a->second));
+    for (sn_context* t : a->twin)
+        if (t) SN_AA_SN(t, sn_synchronize(t));
     if (a->down) SN_AA_HIP(hipStreamSynchronize(a->down));
     return SN_OK;
 }
@@ -2808,11 +2900,31 @@ int sn_aa_get_sharpen(sn_aa_context* a, sn_aa_sharpen* out)
     return SN_OK;
 }
 
+int sn_aa_get_fields(sn_aa_context* a, sn_aa_fields* out)
+{
+    if (!a) return aa_fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    if (!out || out->struct_size != (int32_t)sizeof(sn_aa_fields)) return aa_fail(a, SN_ERR_INVALID_ARG, "out is NULL or sn_aa_fields.struct_size mismatch");
+    *out = sn_aa_fields{};
+    out->struct_size = (int32_t)sizeof(sn_aa_fields);
+    out->mode = a->plan.opt.fields;
+    return SN_OK;
+}
+
+// the filter instance `pass` names: 0 / 1, and with both fields 2 / 3 for their order-2 twins
+static sn_context* aa_instance(sn_aa_context* a, int32_t pass)
+{
+    if (pass == 0 || pass == 1) return pass ? a->second : a->first;
+    if ((pass == 2 || pass == 3) && a->twin[0]) return a->twin[pass - 2];
+    aa_fail(a, SN_ERR_INVALID_ARG, a->twin[0] ? "pass must be 0 (the turned clip), 1 (the clip), or 2 / 3 (their order-2 twins)"
+                                             : "pass must be 0 (the turned clip) or 1 (the clip)");
+    return nullptr;
+}
+
 int sn_aa_get_info(sn_aa_context* a, int32_t pass, sn_info* info)
 {
     if (!a) return aa_fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
-    if (pass != 0 && pass != 1) return aa_fail(a, SN_ERR_INVALID_ARG, "pass must be 0 (the turned clip) or 1 (the clip)");
-    sn_context* c = pass ? a->second : a->first;
+    sn_context* c = aa_instance(a, pass);
+    if (!c) return SN_ERR_INVALID_ARG;
     SN_AA_SN(c, sn_get_info(c, info));
     return SN_OK;
 }
@@ -2820,8 +2932,8 @@ int sn_aa_get_info(sn_aa_context* a, int32_t pass, sn_info* info)
 int sn_aa_get_parts_info(sn_aa_context* a, int32_t pass, sn_parts_info* info)
 {
     if (!a) return aa_fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
-    if (pass != 0 && pass != 1) return aa_fail(a, SN_ERR_INVALID_ARG, "pass must be 0 (the turned clip) or 1 (the clip)");
-    sn_context* c = pass ? a->second : a->first;
+    sn_context* c = aa_instance(a, pass);
+    if (!c) return SN_ERR_INVALID_ARG;
     SN_AA_SN(c, sn_get_parts_info(c, info));
     return SN_OK;
 }
@@ -2862,6 +2974,8 @@ static int aa_ensure_ring(sn_aa_context* a)
     if (int rc = aa_ensure_intermediates(a, a->plan.per_group)) return rc;
     SN_AA_SN(a->first, prepare_small_launch_scratch(reinterpret_cast<Context*>(a->first)));
     SN_AA_SN(a->second, prepare_small_launch_scratch(reinterpret_cast<Context*>(a->second)));
+    for (sn_context* t : a->twin)
+        if (t) SN_AA_SN(t, prepare_small_launch_scratch(reinterpret_cast<Context*>(t)));
     a->ring_ready = true;
     return SN_OK;
 }
@@ -3018,6 +3132,8 @@ int sn_aa_process_host(sn_aa_context* a, const void* const src[3], const int32_t
     SN_AA_HIP(hipSetDevice(a->cfg.device));
     SN_AA_SN(a->first, prepare_small_launch_scratch(reinterpret_cast<Context*>(a->first)));
     SN_AA_SN(a->second, prepare_small_launch_scratch(reinterpret_cast<Context*>(a->second)));
+    for (sn_context* t : a->twin)
+        if (t) SN_AA_SN(t, prepare_small_launch_scratch(reinterpret_cast<Context*>(t)));
     if (int rc = aa_ensure_group(a, a->plan.ring_groups, 1)) return rc;
     sn_aa_context::Group& g = a->groups[(size_t)a->plan.ring_groups];
     g.lo = g.hi = 0;

@@ -86,6 +86,14 @@ struct PlaneViewW {
 // line_parity 0 / 1: only the destination lines of that parity are written, < 0: all of them
 hipError_t launch_turn(hipStream_t s, int bytes, int right, int nframes, PlaneView src, int w, int h, PlaneViewW dst, int line_parity = -1);
 
+// ... and the turn of avg(a, b) (sn_avg.h; the both-fields call): every line is written
+hipError_t launch_turn_merge(hipStream_t s, int bytes, int right, int nframes, PlaneView a, PlaneView b, int w, int h, PlaneViewW dst);
+
+// sn_merge.hip: dst = avg(a, b) of the both-fields anti-aliasing call, sample by sample (sangnom_hip.h, "Both fields": integers
+// (a + b + 1) >> 1, float (a + b) * 0.5f with every NaN as 0x7FC00000).  dst may be the plane a or b lies in (same base, pitch
+// and frame stride); any other overlap is the caller's to refuse.
+hipError_t launch_merge(hipStream_t s, int bytes, int nframes, PlaneView a, PlaneView b, int w, int h, PlaneViewW dst);
+
 // sn_reduce.hip: the 2w x 2h plane of the anti-aliasing call with dh back to w x h (of dst): kernel 1 = tent [1 2 1],
 // 2 = half-band [-1 0 9 16 9 0 -1], centred on src[2y + oy][2x + ox], edges clamped; integer results clamped to `bits`
 hipError_t launch_reduce(hipStream_t s, int bytes, int bits, int kernel, int nframes, PlaneView src, int w, int h, int ox, int oy, PlaneViewW dst);

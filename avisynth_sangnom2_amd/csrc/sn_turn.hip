@@ -10,18 +10,22 @@
 // Field form (line_parity 0 / 1): only the destination lines of that parity are written -- the lines the SangNom2 pass
 // that follows keeps, the only ones it reads.  A destination line is a source column, so a tile still reads whole source
 // rows but writes 32 of its 64 lines: 1.5 x W x H x B bytes.  The other lines of the destination are left as they were.
+// With a second source (kMerge; the both-fields call, sangnom_hip.h "Both fields") the tile is filled with avg(src, src2)
+// instead of src, on both paths; everything behind the fill is the same code.  3 x W x H x B bytes, where the average as a
+// kernel of its own and a turn behind it would move five.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sn_avg.h"
 #include "sn_internal.h"
 
 namespace sn {
 
 constexpr int kTile = 64;
 
-template <class T>
-__global__ void __launch_bounds__(256) k_turn(const uint8_t* src, int64_t sfs, int spitch, int w, int h, uint8_t* dst, int64_t dfs, int dpitch,
-                                             int right, int dword_ok, int line_parity)
+template <class T, bool kMerge>
+__global__ void __launch_bounds__(256) k_turn(const uint8_t* src, int64_t sfs, int spitch, const uint8_t* src2, int64_t sfs2, int spitch2, int w, int h,
+                                             uint8_t* dst, int64_t dfs, int dpitch, int right, int dword_ok, int line_parity)
 {
     constexpr int P = 4 / (int)sizeof(T);  // samples per dword
     constexpr int RD = kTile / P;          // dwords per tile row
@@ -30,6 +34,7 @@ __global__ void __launch_bounds__(256) k_turn(const uint8_t* src, int64_t sfs, i
     const int f = blockIdx.z;
     const int x0 = blockIdx.x * kTile, y0 = blockIdx.y * kTile;  // tile origin in the source
     const uint8_t* s = src + (int64_t)f * sfs;
+    const uint8_t* s2 = kMerge ? src2 + (int64_t)f * sfs2 : nullptr;
     uint8_t* d = dst + (int64_t)f * dfs;
 
     // Whole tiles with dword-aligned rows move as dwords on both sides (a byte-wide global access wastes most of
@@ -37,7 +42,9 @@ __global__ void __launch_bounds__(256) k_turn(const uint8_t* src, int64_t sfs, i
     if (dword_ok && x0 + kTile <= w && y0 + kTile <= h) {
         for (int i = threadIdx.x; i < kTile * RD; i += 256) {
             const int r = i / RD, q = i % RD;
-            tile32[r][q] = reinterpret_cast<const uint32_t*>(s + (int64_t)(y0 + r) * spitch)[x0 / P + q];
+            uint32_t v = reinterpret_cast<const uint32_t*>(s + (int64_t)(y0 + r) * spitch)[x0 / P + q];
+            if constexpr (kMerge) v = avg_dword<(int)sizeof(T)>(v, reinterpret_cast<const uint32_t*>(s2 + (int64_t)(y0 + r) * spitch2)[x0 / P + q]);
+            tile32[r][q] = v;
         }
         __syncthreads();
         // destination line of tile column r: x0 + r (right) or w - 1 - x0 - r (left); the field form takes every other column
@@ -62,7 +69,11 @@ __global__ void __launch_bounds__(256) k_turn(const uint8_t* src, int64_t sfs, i
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;  // 64 x 4 threads
     for (int r = ty; r < kTile; r += 4) {
         const int x = x0 + tx, y = y0 + r;
-        if (x < w && y < h) tile[r][tx] = reinterpret_cast<const T*>(s + (int64_t)y * spitch)[x];
+        if (x < w && y < h) {
+            T v = reinterpret_cast<const T*>(s + (int64_t)y * spitch)[x];
+            if constexpr (kMerge) v = (T)avg_sample<(int)sizeof(T)>(v, reinterpret_cast<const T*>(s2 + (int64_t)y * spitch2)[x]);
+            tile[r][tx] = v;
+        }
     }
     __syncthreads();
     // destination rows correspond to source columns; a destination row segment is a source column segment
@@ -79,25 +90,48 @@ __global__ void __launch_bounds__(256) k_turn(const uint8_t* src, int64_t sfs, i
     }
 }
 
-hipError_t launch_turn(hipStream_t st, int bytes, int right, int nframes, PlaneView s, int w, int h, PlaneViewW d, int line_parity)
+// s2.base == nullptr: the turn of s; otherwise of avg(s, s2)
+static hipError_t turn(hipStream_t st, int bytes, int right, int nframes, PlaneView s, PlaneView s2, int w, int h, PlaneViewW d, int line_parity)
 {
     const uint8_t* const src = s.base;
+    const uint8_t* const src2 = s2.base;
     uint8_t* const dst = d.base;
-    const int64_t sfs = s.fs, dfs = d.fs;
-    const int spitch = s.pitch, dpitch = d.pitch;
+    const int64_t sfs = s.fs, sfs2 = s2.fs, dfs = d.fs;
+    const int spitch = s.pitch, spitch2 = s2.pitch, dpitch = d.pitch;
     if (nframes <= 0 || w <= 0 || h <= 0) return hipSuccess;
     dim3 grid((w + kTile - 1) / kTile, (h + kTile - 1) / kTile, nframes), block(256);
     const int per = 4 / bytes;  // samples per dword: the turned tile must start on a dword of the destination row
     const int dword_ok = ((uintptr_t)src % 4 == 0 && (uintptr_t)dst % 4 == 0 && spitch % 4 == 0 && dpitch % 4 == 0 && sfs % 4 == 0 && dfs % 4 == 0 &&
-                          (!right || h % per == 0))
+                          (!src2 || ((uintptr_t)src2 % 4 == 0 && spitch2 % 4 == 0 && sfs2 % 4 == 0)) && (!right || h % per == 0))
                              ? 1
                              : 0;
+#define SN_TURN(T)                                                                                                                                  \
+    do {                                                                                                                                            \
+        if (src2)                                                                                                                                   \
+            hipLaunchKernelGGL((k_turn<T, true>), grid, block, 0, st, src, sfs, spitch, src2, sfs2, spitch2, w, h, dst, dfs, dpitch, right, dword_ok, \
+                               line_parity);                                                                                                        \
+        else                                                                                                                                        \
+            hipLaunchKernelGGL((k_turn<T, false>), grid, block, 0, st, src, sfs, spitch, src2, sfs2, spitch2, w, h, dst, dfs, dpitch, right, dword_ok, \
+                               line_parity);                                                                                                        \
+    } while (0)
     switch (bytes) {
-    case 1: hipLaunchKernelGGL(k_turn<uint8_t>, grid, block, 0, st, src, sfs, spitch, w, h, dst, dfs, dpitch, right, dword_ok, line_parity); break;
-    case 2: hipLaunchKernelGGL(k_turn<uint16_t>, grid, block, 0, st, src, sfs, spitch, w, h, dst, dfs, dpitch, right, dword_ok, line_parity); break;
-    default: hipLaunchKernelGGL(k_turn<uint32_t>, grid, block, 0, st, src, sfs, spitch, w, h, dst, dfs, dpitch, right, dword_ok, line_parity); break;
+    case 1: SN_TURN(uint8_t); break;
+    case 2: SN_TURN(uint16_t); break;
+    default: SN_TURN(uint32_t); break;
     }
+#undef SN_TURN
     return hipGetLastError();
+}
+
+hipError_t launch_turn(hipStream_t st, int bytes, int right, int nframes, PlaneView s, int w, int h, PlaneViewW d, int line_parity)
+{
+    return turn(st, bytes, right, nframes, s, PlaneView{}, w, h, d, line_parity);
+}
+
+hipError_t launch_turn_merge(hipStream_t st, int bytes, int right, int nframes, PlaneView a, PlaneView b, int w, int h, PlaneViewW d)
+{
+    if (!b.base) return hipErrorInvalidValue;
+    return turn(st, bytes, right, nframes, a, b, w, h, d, -1);
 }
 
 }  // namespace sn

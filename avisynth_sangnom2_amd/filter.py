@@ -341,6 +341,30 @@ class SangNom2:
                                                        aa.stride(0) * B, aa.stride(1) * B, W, H, dst.data_ptr(), dst.stride(0) * B, dst.stride(1) * B))
         return dst
 
+    def merge(self, a, b, dst):
+        """sn_merge_device: dst = avg(a, b), sample by sample (sangnom_hip.h, "Both fields": integers (a + b + 1) >> 1, float
+        (a + b) * 0.5f with every NaN as 0x7FC00000).  a, b and dst are [N, H, W]; dst may be a or b itself, any other overlap is
+        refused.  Torch tensors on the device; asynchronous on the context's stream."""
+        B = self.clip.bytes
+        N, H, W = dst.shape
+        for t in (a, b, dst):
+            if tuple(t.shape) != (N, H, W) or t.stride(2) != 1 or t.element_size() != B:
+                raise ValueError("merge: a, b and dst must be [N, H, W], x-contiguous and of the clip's sample type")
+        self._check(self._lib.sn_merge_device(self._h, N, a.data_ptr(), a.stride(0) * B, a.stride(1) * B, b.data_ptr(), b.stride(0) * B, b.stride(1) * B,
+                                              W, H, dst.data_ptr(), dst.stride(0) * B, dst.stride(1) * B))
+        return dst
+
+    def turn_merge(self, a, b, dst, direction: int):
+        """sn_turn_merge_device: the quarter turn (direction > 0 clockwise, < 0 anti-clockwise) of avg(a, b) in one kernel.  a and b
+        are [N, H, W], dst is [N, W, H] and overlaps neither.  Torch tensors on the device; asynchronous on the context's stream."""
+        B = self.clip.bytes
+        N, H, W = a.shape
+        if tuple(b.shape) != (N, H, W) or any(t.stride(2) != 1 or t.element_size() != B for t in (a, b, dst)) or tuple(dst.shape) != (N, W, H):
+            raise ValueError("turn_merge: a and b must be [N, H, W] and dst [N, W, H], x-contiguous and of the clip's sample type")
+        self._check(self._lib.sn_turn_merge_device(self._h, int(direction), N, a.data_ptr(), a.stride(0) * B, a.stride(1) * B, b.data_ptr(),
+                                                   b.stride(0) * B, b.stride(1) * B, W, H, dst.data_ptr(), dst.stride(0) * B, dst.stride(1) * B))
+        return dst
+
     def mask_merge_luma(self, luma, src, aa, dst, lo: int, hi: int, expand: int = 1, sub_w: int = 1, sub_h: int = 1):
         """sn_mask_merge_luma_device: the Sobel edge mask of luma [N, H << sub_h, W << sub_w], reduced to chroma's geometry
         by the block mean, merges aa into src.  src, aa and dst are one tensor [N, H, W] or a pair of them (U and V in one
@@ -462,12 +486,15 @@ class _AAContext:
     source luma plane reduced to chroma's geometry, as anti-aliasing scripts do.
     sharpen=None | 1..255 (64 = unity), sharpen_chroma=False (without dh, or with dh and reduce): the result is contra-sharpened
     behind the last step and before the mask (sangnom_hip.h, "Contra-sharpening"): an unsharp mask, allowed only as far as the
-    filter changed the picture and only towards the source.  Plane 0, or every processed plane with sharpen_chroma."""
+    filter changed the picture and only towards the source.  Plane 0, or every processed plane with sharpen_chroma.
+    fields="one" | "both" (without dh): "both" interpolates both fields in every pass -- two filter instances, order 1 and
+    order 2 -- and averages the two results on the device (sangnom_hip.h, "Both fields"); `order` and the per-frame parity
+    then have no influence.  Sharpening and mask follow the averaged result."""
 
     def __init__(self, clip: ClipFormat, order: int = 1, aa: int = 48, aac: int = 0, luma: bool = True, chroma: bool = True,
                  device: int = 0, isolated_planes: bool = False, fresh_pool: bool = False, opt: int = -1, max_batch: int = 1,
                  host_depth: int = 0, stream: int | None = None, dh: bool = False, column_parts: int = 0, reduce=0, mask=None, mask_expand: int = 1,
-                 mask_chroma="own", sharpen=None, sharpen_chroma: bool = False, **policy_kw):
+                 mask_chroma="own", sharpen=None, sharpen_chroma: bool = False, fields="one", **policy_kw):
         if opt < -1 or opt > 1:
             raise SangNomError(capi.SN_ERR_CONFIG, "SangNom2: opt must be between -1..2.")  # sic, SangNom2.cpp:420
         self.clip = clip
@@ -477,6 +504,7 @@ class _AAContext:
         amask = capi.aa_mask(mask, mask_expand)  # mask=(lo, hi): the result goes into the source through the source's edge mask
         amask_ex = capi.aa_mask_ex(mask_chroma)
         asharpen = capi.aa_sharpen(sharpen, sharpen_chroma)
+        afields = capi.aa_fields(fields)
         self.max_batch = max_batch
         self._lib = capi.load()
         cfg = capi.SnConfig(
@@ -487,8 +515,8 @@ class _AAContext:
         self._h = ctypes.c_void_p()
         pol = capi.policy(**{k: policy_kw.get(k) for k in ("small_launches", "chain", "copy_threads", "scratch_budget_mb", "chroma_sweeps", "sse2_sweeps")})
         opts = capi.options(capi.arithmetic_of_opt(opt), column_parts=column_parts)
-        rc = self._lib.sn_aa_create_ex5(ctypes.byref(cfg), ctypes.byref(pol), ctypes.byref(opts), ctypes.byref(aopts), ctypes.byref(amask),
-                                        ctypes.byref(amask_ex), ctypes.byref(asharpen), ctypes.byref(self._h))
+        rc = self._lib.sn_aa_create_ex6(ctypes.byref(cfg), ctypes.byref(pol), ctypes.byref(opts), ctypes.byref(aopts), ctypes.byref(amask),
+                                        ctypes.byref(amask_ex), ctypes.byref(asharpen), ctypes.byref(afields), ctypes.byref(self._h))
         if rc != capi.SN_OK:
             self._h = None
             raise SangNomError(rc, self._lib.sn_aa_last_error(None).decode())
@@ -551,8 +579,15 @@ class _AAContext:
         self._check(self._lib.sn_aa_get_sharpen(self._h, ctypes.byref(m)))
         return m
 
+    @property
+    def fields(self) -> capi.SnAAFields:
+        """sn_aa_get_fields: which fields the passes of this context interpolate (mode 0 one, 1 both)."""
+        m = capi.SnAAFields(struct_size=ctypes.sizeof(capi.SnAAFields))
+        self._check(self._lib.sn_aa_get_fields(self._h, ctypes.byref(m)))
+        return m
+
     def info(self, pass_: int) -> capi.SnInfo:
-        """sn_get_info of one of the two filter instances: 0 the turned clip's, 1 the clip's."""
+        """sn_get_info of one of the filter instances: 0 the turned clip's, 1 the clip's; fields="both": 2 and 3 their order-2 twins."""
         i = capi.SnInfo(struct_size=ctypes.sizeof(capi.SnInfo))
         self._check(self._lib.sn_aa_get_info(self._h, int(pass_), ctypes.byref(i)))
         return i

@@ -110,6 +110,8 @@ AVSValue __cdecl Create_SangNom2HIP(AVSValue args, void*, IScriptEnvironment* en
 // sharp=1..255 (default 0: off; at source size): the result is contra-sharpened behind the last step and before the mask -- an
 // unsharp mask of strength sharp / 64, allowed only as far as the filter changed the picture and only towards the source;
 // sharpc=true: every processed plane, not luma alone.  64 is a starting value that nobody has tuned on real footage.
+// both=true (without dh; "SangNomAA: both fields needs dh=false"): every pass interpolates both fields -- order 1 and order 2 --
+// and the two results are averaged on the device, as daa does; order and the frames' parity then have no influence.
 class SangNomAA : public GenericVideoFilter {
     sangnom::AAFilter<AvsHost> impl_;
 
@@ -144,6 +146,7 @@ AVSValue __cdecl Create_SangNomAA(AVSValue args, void*, IScriptEnvironment* env)
     a.mask_luma = args[17].AsBool(false);
     a.sharpen = args[18].AsInt(0);
     a.sharpen_chroma = args[19].AsBool(false);
+    a.both_fields = args[20].AsBool(false);
     return new SangNomAA(args[0].AsClip(), a, env);
 }
 
@@ -167,7 +170,7 @@ extern "C" __declspec(dllexport) const char* __stdcall AvisynthPluginInit3(IScri
     env->AddFunction("SangNom", "c[order]i[aa]i[opt]i", Create_SangNom, 0);                                        // :482
     env->AddFunction("SangNom2HIP", "c[order]i[aa]i[aac]i[threads]i[dh]b[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i[device]i",
                      Create_SangNom2HIP, 0);
-    env->AddFunction("SangNomAA", "c[order]i[aa]i[aac]i[device]i[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i[dh]b[reduce]i[mask]b[mlo]i[mhi]i[mexpand]i[mluma]b[sharp]i[sharpc]b",
+    env->AddFunction("SangNomAA", "c[order]i[aa]i[aac]i[device]i[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i[dh]b[reduce]i[mask]b[mlo]i[mhi]i[mexpand]i[mluma]b[sharp]i[sharpc]b[both]b",
                      Create_SangNomAA, 0);
     return "SangNom2";
 }

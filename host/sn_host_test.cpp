@@ -15,7 +15,8 @@
 // SN_HOST_TEST_FRESH=1 sets Args::fresh, SN_HOST_TEST_REDUCE=<1|2> Args::reduce (SangNomAA with dh: frames of source size),
 // SN_HOST_TEST_MASK=lo,hi,expand Args::mask with those values (SangNomAA: the result merged through the source's edge mask),
 // SN_HOST_TEST_MASK_LUMA=1 Args::mask_luma (chroma through the luma plane's mask),
-// SN_HOST_TEST_SHARPEN=amount,chroma Args::sharpen and Args::sharpen_chroma (SangNomAA: contra-sharpening behind the last step).
+// SN_HOST_TEST_SHARPEN=amount,chroma Args::sharpen and Args::sharpen_chroma (SangNomAA: contra-sharpening behind the last step),
+// SN_HOST_TEST_FIELDS=both Args::both_fields (SangNomAA: both fields per pass, averaged).
 // out.bin: per frame the output planes in the filter's own geometry (its GetInfo()), tightly packed.  On a constructor error: exit code 3 and
 //          the message on stdout.
 #include <cstdio>
@@ -89,6 +90,7 @@ int main(int argc, char** argv)
         int chroma = 0;
         if (sscanf(e, "%d,%d", &a.sharpen, &chroma) == 2) a.sharpen_chroma = chroma != 0;
     }
+    if (const char* e = getenv("SN_HOST_TEST_FIELDS")) a.both_fields = strcmp(e, "both") == 0;
     const bool aa_idiom = argc > 3 && strncmp(argv[3], "aa", 2) == 0 && (argv[3][2] == 0 || argv[3][2] == ':');
     if (aa_idiom && argv[3][2] == ':') a.lookahead = atoi(argv[3] + 3);
     if (argc > 3 && !aa_idiom) a.lookahead = atoi(argv[3]);

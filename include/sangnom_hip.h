@@ -379,6 +379,31 @@ int sn_contra_sharpen_device(sn_context* ctx, int32_t amount, int32_t nframes, c
                              const void* aa, int64_t aa_frame_stride, int32_t aa_pitch, int32_t width, int32_t height, void* dst,
                              int64_t dst_frame_stride, int32_t dst_pitch);
 
+/* Which fields a pass of the anti-aliasing call interpolates (below: "Both fields", which defines the arithmetic).
+ * SN_AA_FIELDS_ONE: the field cfg.order names, as a context made without this struct does.  SN_AA_FIELDS_BOTH: every pass
+ * runs twice, order 1 and order 2, and the two results are averaged on the device. */
+enum { SN_AA_FIELDS_ONE = 0, SN_AA_FIELDS_BOTH = 1 };
+typedef struct sn_aa_fields {
+    int32_t struct_size; /* sizeof(sn_aa_fields) */
+    int32_t mode;        /* SN_AA_FIELDS_*; with SN_AA_FIELDS_ONE the fields below are ignored */
+    int32_t reserved[6]; /* zero */
+} sn_aa_fields;          /* 32 bytes */
+
+/* The average of the both-fields call on its own (below: "Both fields" defines avg), for pipelines that keep frames on the
+ * device: `nframes` planes of width x height samples on the context's stream, dst = avg(a, b) sample by sample; the sample
+ * type comes from the context.  Pitches >= width samples; pointers, pitches and frame strides multiples of the sample size
+ * (rows of all three planes that start on multiples of 16 bytes: 16 bytes per lane and access).  dst may be a or b exactly
+ * (same pointer, pitch and frame stride: each sample is read by the thread that overwrites it); a dst whose bytes overlap a
+ * or b in any other way is refused with SN_ERR_INVALID_ARG.  Nothing beyond width samples of a destination row is written.
+ * A refused call queues nothing. */
+int sn_merge_device(sn_context* ctx, int32_t nframes, const void* a, int64_t a_frame_stride, int32_t a_pitch, const void* b, int64_t b_frame_stride,
+                    int32_t b_pitch, int32_t width, int32_t height, void* dst, int64_t dst_frame_stride, int32_t dst_pitch);
+/* sn_turn_device of avg(a, b) in one kernel (the planes are read once and the average never reaches memory): a and b are
+ * width x height, dst is height wide and width high; direction as for sn_turn_device.  dst must overlap neither a nor b. */
+int sn_turn_merge_device(sn_context* ctx, int32_t direction, int32_t nframes, const void* a, int64_t a_frame_stride, int32_t a_pitch, const void* b,
+                         int64_t b_frame_stride, int32_t b_pitch, int32_t width, int32_t height, void* dst, int64_t dst_frame_stride,
+                         int32_t dst_pitch);
+
 /* The anti-aliasing idiom TurnLeft().SangNom2(order, aa, aac).TurnRight().SangNom2(order, aa, aac) as ONE call with
  * host planes (README.md:3 of the reference: "mainly used in anti-aliasing scripts"): the frame
  * crosses PCIe once each way and stays on the device between the two passes (two filter instances -- one for the
@@ -517,7 +542,34 @@ int sn_contra_sharpen_device(sn_context* ctx, int32_t amount, int32_t nframes, c
  *   No NaN is generated into the output:
  *     an infinite or NaN R(y,x) makes B infinite or NaN, so d = R - B and with it d1 is NaN, and R(y,x) is copied;
  *     otherwise R(y,x) is finite, and c is d1, mn or mx, none of which is NaN here (mn and mx never take a NaN);
- *     a finite value plus a value that is no NaN is no NaN: every output sample is a copy of R or such a sum. */
+ *     a finite value plus a value that is no NaN is no NaN: every output sample is a copy of R or such a sum.
+ *
+ * Both fields (sn_aa_create_ex6 with fields->mode = SN_AA_FIELDS_BOTH; opt-in): a pass keeps one field and interpolates the
+ * other, so half of the lines of each pass come out untouched.  The single-field scripts the contra-sharpening comes from
+ * (daa and its relatives) interpolate BOTH fields and average: Merge(SangNom2(order=1), SangNom2(order=2)).  Every line is
+ * then half source and half interpolation, and the result is symmetric in the two fields.  The definition is the library's own:
+ *   For a clip c let A(c) = avg(SangNom2(c, order=1), SangNom2(c, order=2)), sample by sample.  The two SangNom2 are two
+ *   separate filter instances, each with its own pool and history.
+ *   The call computes A( A(c.TurnLeft()).TurnRight() ): four instances in all.  Each carries history exactly as a reference
+ *   instance would: widths that are not a multiple of 32 carry state from frame to frame, and Y, U and V share the pool
+ *   unless isolated_planes or fresh_pool is set.
+ *   avg, per sample type:
+ *     integer samples of any depth in 8- or 16-bit containers: (a + b + 1) >> 1, computed without overflow;
+ *     float samples: (a + b) * 0.5f in single precision, in that order; any NaN result is written as the one pattern
+ *     0x7FC00000 (x86 and gfx950 disagree on which NaN an add returns).
+ * The four instances are created from the same configuration with only `order` replaced: cfg.order and the per-frame parity
+ * have NO influence in this mode -- the twins always use orders 1 and 2, which take no parity.  Mask (own and luma-derived),
+ * sharpening, luma / chroma, isolated_planes, fresh_pool, arithmetic, column_parts, policy and options apply unchanged; the
+ * sharpening and the mask see the averaged result of the second pass.  mode = BOTH with cfg.dh is SN_ERR_CONFIG "SangNomAA: both
+ * fields needs dh=false", before a device is touched: the two dh results place the source on different lines, and their
+ * average is a half-line blur, not an anti-aliaser (reduce needs dh and falls with it).  A chunk runs: turn left (every line,
+ * one launch), first pass order 1, first pass order 2, turn right of the average of the two (one kernel, sn_turn_merge_device),
+ * second pass order 1 into the destination (or the sharpening's intermediate), second pass order 2 into one more intermediate,
+ * the average in place (sn_merge_device), then sharpening and mask as ever.  A processed plane costs five plane sizes of
+ * intermediates per frame instead of three (six instead of four where it is sharpened), counted against scratch_budget_mb.
+ * sn_aa_get_info / sn_aa_get_parts_info take pass 2 and 3 for the order-2 twins of passes 0 and 1 (SN_ERR_INVALID_ARG in
+ * one-field mode).  Measured on one MI355X the call takes 1.97 times the one-field call at 1080p 4:2:0 and 1.99 times at 2160p
+ * Y8: the passes dominate and double. */
 enum { SN_AA_REDUCE_NONE = 0, SN_AA_REDUCE_TENT = 1, SN_AA_REDUCE_HALFBAND = 2 };
 typedef struct sn_aa_options {
     int32_t struct_size; /* sizeof(sn_aa_options) */
@@ -552,6 +604,13 @@ int sn_aa_create_ex5(const sn_config* cfg, const sn_policy* policy, const sn_opt
                      const sn_aa_mask* mask /* NULL = none */, const sn_aa_mask_ex* mask_ex /* NULL = defaults */,
                      const sn_aa_sharpen* sharpen /* NULL = off */, sn_aa_context** out);
 int sn_aa_get_sharpen(sn_aa_context* ctx, sn_aa_sharpen* out /* struct_size set by the caller */); /* amount 0 when off */
+/* sn_aa_create_ex5 is sn_aa_create_ex6 with fields = NULL (one field per pass).  A bad struct_size, a mode outside 0..1 or a
+ * non-zero reserved word: SN_ERR_INVALID_ARG, naming sn_aa_fields.<field>; with mode = SN_AA_FIELDS_ONE only struct_size is
+ * looked at. */
+int sn_aa_create_ex6(const sn_config* cfg, const sn_policy* policy, const sn_options* options, const sn_aa_options* aa_options /* NULL = defaults */,
+                     const sn_aa_mask* mask /* NULL = none */, const sn_aa_mask_ex* mask_ex /* NULL = defaults */,
+                     const sn_aa_sharpen* sharpen /* NULL = off */, const sn_aa_fields* fields /* NULL = one field */, sn_aa_context** out);
+int sn_aa_get_fields(sn_aa_context* ctx, sn_aa_fields* out /* struct_size set by the caller */);
 int sn_aa_process_host(sn_aa_context* ctx, const void* const src[3], const int32_t src_pitch[3], void* const dst[3],
                        const int32_t dst_pitch[3], int32_t parity);
 const char* sn_aa_last_error(const sn_aa_context* ctx); /* ctx == NULL: last failed sn_aa_create on this thread */
@@ -571,7 +630,8 @@ int sn_aa_process_device_strided(sn_aa_context* ctx, int32_t nframes, const void
 int sn_aa_synchronize(sn_aa_context* ctx);
 /* The hipStream_t of the call's device work (cfg.stream if one was given); NULL for a NULL context. */
 void* sn_aa_get_stream(sn_aa_context* ctx);
-/* sn_get_info of one of the two filter instances: pass 0 is the turned clip's, pass 1 the clip's. */
+/* sn_get_info of one of the filter instances: pass 0 is the turned clip's, pass 1 the clip's; with SN_AA_FIELDS_BOTH pass 2
+ * and 3 are their order-2 twins (the instances of pass 0 and 1 then run order 1). */
 int sn_aa_get_info(sn_aa_context* ctx, int32_t pass, sn_info* info);
 int sn_aa_get_parts_info(sn_aa_context* ctx, int32_t pass, sn_parts_info* info);
 /* The host ring of the anti-aliasing call, with the contract of sn_host_slots / sn_submit_host / sn_collect_host: slots

@@ -15,12 +15,18 @@ merges of the same chroma planes.  --mask-chroma luma (with --mask): the masked 
 --sharpen AMOUNT (at source size; device batches): the call with the contra-sharpening (on top of --mask where given) next to
 the call without it.  --sharpen-bw: the sharpening kernel alone (sn_contra_sharpen_device) against the mask kernel (expand 1, not
 in place), both on noise and moving the same 3 W H B bytes per frame, alternating; any of Y8 / Y16 / Y32.
+--fields both (without --dh; device batches): the call with both fields per pass next to the one-field call, alternating, with
+the ratio of their medians (on top of --mask / --sharpen where given).  --merge-bw: the averaging kernel alone (sn_merge_device)
+against the mask kernel (expand 1), both on noise and moving 3 W H B bytes per frame, and the turn of the average
+(sn_turn_merge_device, 3 W H B) against the turn (2 W H B), alternating; any of Y8 / Y16 / Y32.
 usage: python tools/aa_bench.py [--frames 512] [--fresh 1] [--fmt Y8] [--size 3840x2160] [--dh [--composed]] [--reduce K] [--host [--depth 8]]
        python tools/aa_bench.py --reduce-bw [--fmt Y16] [--size 1920x1080] [--frames 64]
        python tools/aa_bench.py --mask 8,32,1 [--reduce halfband] [--size 1920x1080] [--host]
        python tools/aa_bench.py --mask-bw [--fmt Y16] [--size 3840x2160] [--frames 32]
        python tools/aa_bench.py --sharpen 64 --mask 8,32,1 --reduce halfband [--fmt YUV420P8]
-       python tools/aa_bench.py --sharpen-bw [--fmt Y16] [--size 3840x2160] [--frames 256] [--reps 5]"""
+       python tools/aa_bench.py --sharpen-bw [--fmt Y16] [--size 3840x2160] [--frames 256] [--reps 5]
+       python tools/aa_bench.py --fields both [--fmt YUV420P8] [--size 1920x1080] [--frames 256] [--reps 9]
+       python tools/aa_bench.py --merge-bw [--fmt Y16] [--size 3840x2160] [--frames 256] [--reps 9]"""
 import argparse
 import json
 import os
@@ -228,6 +234,73 @@ def sharpen_bandwidth(clip, a):
     return out
 
 
+def merge_bandwidth(clip, a):
+    """sn_merge_device against sn_mask_merge_device (expand 1, into a third plane), both on noise and moving 3 W H B bytes per
+    frame, and sn_turn_merge_device (3 W H B) against sn_turn_device (2 W H B), alternating: median, minimum and maximum
+    microseconds per frame over --reps launches of --frames frames; `of_hbm_peak` is the bytes over 8 TB/s over the median."""
+    dev = torch.device("cuda:0")
+    N, W, H, B = a.frames, clip.width, clip.height, clip.bytes
+    dt = {1: torch.uint8, 2: torch.int16, 4: torch.float32}[B]
+
+    def noise():
+        if B == 4:
+            return torch.rand((N, H, W), device=dev)
+        return torch.randint(0, 1 << clip.bits, (N, H, W), device=dev, dtype=torch.int32).to(dt)
+    S, R = noise(), noise()
+    dst = torch.empty((N, H, W), device=dev, dtype=dt)
+    turned = torch.empty((N, W, H), device=dev, dtype=dt)
+    lo, hi, _ = a.mask_values
+    out = {"clip": f"{a.fmt} {W}x{H}", "frames": N, "plane_bytes": N * W * H * B, "mask": [lo, hi, 1], "reps": a.reps}
+    with SangNom2(clip, max_batch=1) as flt:
+        runs = {"merge": (3, lambda: flt.merge(S, R, dst)), "merge_in_place": (3, lambda: flt.merge(dst, R, dst)),
+                "mask1": (3, lambda: flt.mask_merge(S, R, dst, lo, hi, 1)),
+                "turn_merge": (3, lambda: flt.turn_merge(S, R, turned, 1)), "turn": (2, lambda: flt.turn(S, turned, 1))}
+        times = {k: [] for k in runs}
+        torch.cuda.synchronize()
+        for r in range(a.reps + 1):
+            for k, (_, fn) in runs.items():
+                flt.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                flt.synchronize()
+                if r:
+                    times[k].append(time.perf_counter() - t0)
+        for k, t in times.items():
+            t.sort()
+            med, moved = t[len(t) // 2], runs[k][0] * N * W * H * B
+            out[k + "_us_per_frame"] = round(1e6 * med / N, 2)
+            out[k + "_us_min_max"] = [round(1e6 * t[0] / N, 2), round(1e6 * t[-1] / N, 2)]
+            out[k + "_GBps"] = round(moved / med / 1e9, 1)
+            out[k + "_of_hbm_peak"] = round(moved / 8e12 / med, 3)
+    return out
+
+
+def fields_rates(clip, a, src, dst, kw):
+    """The call with both fields next to the one-field call with the same other options, on the same frames, alternating:
+    median, minimum and maximum frames/s over --reps batches of --frames frames each, and the ratio of the median times."""
+    N = a.frames
+    common = dict(max_batch=N, fresh_pool=bool(a.fresh), aac=48 if clip.planes > 1 else 0, **kw)
+    with SangNomAA(clip, **common) as one, SangNomAA(clip, fields="both", **common) as both:
+        ctx = {"one": one, "both": both}
+        times = {k: [] for k in ctx}
+        torch.cuda.synchronize()
+        for r in range(a.reps + 2):  # two rounds of warm-up
+            for k, aa in ctx.items():
+                aa.synchronize()
+                t0 = time.perf_counter()
+                aa.process_batch(src, dst)
+                aa.synchronize()
+                if r >= 2:
+                    times[k].append(time.perf_counter() - t0)
+    out = {}
+    for k, t in times.items():
+        t.sort()
+        out[f"aa_{k}_fps"] = round(N / t[len(t) // 2], 1)
+        out[f"aa_{k}_fps_min_max"] = [round(N / t[-1], 1), round(N / t[0], 1)]
+    out["both_over_one"] = round(times["both"][len(times["both"]) // 2] / times["one"][len(times["one"]) // 2], 3)
+    return out
+
+
 def luma_merge_times(clip, a, dev, dt, noise):
     """The chroma merge of a 4:2:0 frame whose luma plane is --size, in place on the result as the call uses it, expand 1, on
     noise: U and V through luma's mask in one launch (4 + 6 chroma-plane units of bytes: luma read, S and R read and dst
@@ -284,6 +357,8 @@ def main():
     ap.add_argument("--sharpen", type=int, default=0, help="AMOUNT 1..255: the call with the contra-sharpening next to the call without it (at source size)")
     ap.add_argument("--sharpen-chroma", action="store_true", help="--sharpen: every processed plane, not luma alone")
     ap.add_argument("--sharpen-bw", action="store_true", help="the sharpening kernel alone against the mask kernel on the same planes")
+    ap.add_argument("--fields", choices=["one", "both"], default="one", help="both: the both-fields call next to the one-field call, alternating")
+    ap.add_argument("--merge-bw", action="store_true", help="the averaging kernel alone against the mask kernel, and the turn of the average against the turn")
     a = ap.parse_args()
     a.mask_values = ([int(x) for x in a.mask.split(",")] + [1])[:3] if a.mask else [8, 32, 1]
     mask_kw = dict(mask=tuple(a.mask_values[:2]), mask_expand=a.mask_values[2]) if a.mask else None
@@ -302,8 +377,13 @@ def main():
     if a.sharpen_bw:
         print(json.dumps(sharpen_bandwidth(clip, a)))
         return
+    if a.merge_bw:
+        print(json.dumps(merge_bandwidth(clip, a)))
+        return
     if clip.bytes != 1:
         sys.exit("aa_bench: 8-bit formats only")
+    if a.fields == "both" and (a.dh or a.composed or a.host):
+        sys.exit("aa_bench: --fields both goes without --dh, on device batches")
     if a.sharpen and ((a.dh and not a.reduce) or a.composed or a.host):
         sys.exit("aa_bench: --sharpen needs the frame at source size (without --dh, or with --reduce) and device batches")
     if a.mask and ((a.dh and not a.reduce) or a.composed):
@@ -331,6 +411,12 @@ def main():
         out["reduce"] = a.reduce
     if a.composed:
         out["composed_fps"] = composed_dh_rate(clip, a, src, dst)
+        print(json.dumps(out))
+        return
+    if a.fields == "both":
+        kw = dict(mask_kw or {}, **(dict(sharpen=a.sharpen, sharpen_chroma=a.sharpen_chroma) if a.sharpen else {}))
+        out.update(reps=a.reps, **({"mask": a.mask_values} if a.mask else {}), **({"sharpen": a.sharpen} if a.sharpen else {}))
+        out.update(fields_rates(clip, a, src, dst, kw))
         print(json.dumps(out))
         return
     reps = 5
