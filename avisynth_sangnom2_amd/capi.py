@@ -36,9 +36,10 @@ EXPORTS = (
     "sn_aa_get_mask_ex", "sn_mask_merge_luma_device",
     "sn_aa_get_sharpen", "sn_contra_sharpen_device",
     "sn_aa_get_fields", "sn_merge_device", "sn_turn_merge_device",
+    "sn_aa_get_repair", "sn_repair_device",
 )
 # ... and the ones whose names end in a digit
-EXPORTS_NUMBERED = ("sn_aa_create_ex2", "sn_aa_create_ex3", "sn_aa_create_ex4", "sn_aa_create_ex5", "sn_aa_create_ex6")
+EXPORTS_NUMBERED = ("sn_aa_create_ex2", "sn_aa_create_ex3", "sn_aa_create_ex4", "sn_aa_create_ex5", "sn_aa_create_ex6", "sn_aa_create_ex7")
 
 # sn_aa_options.reduce: the anti-aliasing call with dh returns the frame at source size (sangnom_hip.h has the arithmetic)
 SN_AA_REDUCE_NONE, SN_AA_REDUCE_TENT, SN_AA_REDUCE_HALFBAND = 0, 1, 2
@@ -149,6 +150,18 @@ def aa_fields(fields="one") -> "SnAAFields":
     if not isinstance(fields, str) or fields not in FIELDS:
         raise ValueError("fields must be 'one' or 'both'")
     return SnAAFields(struct_size=ctypes.sizeof(SnAAFields), mode=FIELDS[fields])
+
+
+class SnAARepair(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_int32), ("rank", ctypes.c_int32), ("chroma", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
+
+
+def aa_repair(rank=None, chroma=False) -> "SnAARepair":
+    """sn_aa_repair: rank = None or 0 (off) or 1..4 (sangnom_hip.h, "Rank repair"); chroma = whether processed chroma planes
+    are repaired too."""
+    if rank is not None and (isinstance(rank, bool) or not isinstance(rank, int) or rank < 0 or rank > 4):
+        raise ValueError("repair must be None or 0 (off) or 1..4")
+    return SnAARepair(struct_size=ctypes.sizeof(SnAARepair), rank=int(rank or 0), chroma=int(bool(chroma)))
 
 
 class SnPartsInfo(ctypes.Structure):
@@ -266,6 +279,11 @@ def load():
                                    ctypes.POINTER(SnAAMask), ctypes.POINTER(SnAAMaskEx), ctypes.POINTER(SnAASharpen), ctypes.POINTER(SnAAFields),
                                    ctypes.POINTER(vp)]
     L.sn_aa_get_fields.argtypes = [vp, ctypes.POINTER(SnAAFields)]
+    L.sn_aa_create_ex7.argtypes = [ctypes.POINTER(SnConfig), ctypes.POINTER(SnPolicy), ctypes.POINTER(SnOptions), ctypes.POINTER(SnAAOptions),
+                                   ctypes.POINTER(SnAAMask), ctypes.POINTER(SnAAMaskEx), ctypes.POINTER(SnAASharpen), ctypes.POINTER(SnAAFields),
+                                   ctypes.POINTER(SnAARepair), ctypes.POINTER(vp)]
+    L.sn_aa_get_repair.argtypes = [vp, ctypes.POINTER(SnAARepair)]
+    L.sn_repair_device.argtypes = [vp, i32, i32, vp, i64, i32, vp, i64, i32, i32, i32, vp, i64, i32]
     L.sn_merge_device.argtypes = [vp, i32, vp, i64, i32, vp, i64, i32, i32, i32, vp, i64, i32]
     L.sn_turn_merge_device.argtypes = [vp, i32, i32, vp, i64, i32, vp, i64, i32, i32, i32, vp, i64, i32]
     L.sn_contra_sharpen_device.argtypes = [vp, i32, i32, vp, i64, i32, vp, i64, i32, i32, i32, vp, i64, i32]

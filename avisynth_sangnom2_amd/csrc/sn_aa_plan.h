@@ -1,6 +1,6 @@
 // sn_aa_plan.h -- what an anti-aliasing call (sn_aa_*) does, decided once at creation, on the host only (no HIP header and no
 // pointers: a host compiler takes this header as it is, tests/c/aa_plan_check.cpp checks it against lines written out by hand).
-//   aa_check():    what sn_aa_create_ex6 refuses of its option structs, and the options it keeps.
+//   aa_check():    what sn_aa_create_ex7 refuses of its option structs, and the options it keeps.
 //   aa_geometry(): every plane size and pitch of the call, the host ring's split and the passes' configurations.
 //   AaBuf:         the caller's planes and the intermediates, which of them a plane needs and how large a frame of each is.
 //   aa_steps():    the stages of a chunk in order -- which planes, what each reads and writes, how it is cut into launches.
@@ -41,13 +41,18 @@ struct AaOptions {
     int mask_chroma = SN_AA_MASK_CHROMA_OWN;  // ... SN_AA_MASK_CHROMA_LUMA: planes 1 and 2 through the source luma plane's mask
     sn_aa_sharpen sharpen{};                  // amount != 0: the result is contra-sharpened (sn_sharpen.hip) behind the last step, before the mask
     int fields = SN_AA_FIELDS_ONE;            // SN_AA_FIELDS_BOTH: every pass twice (order 1, order 2) and the average of the two (sn_merge.hip)
-    AaOptions() { mask.struct_size = (int32_t)sizeof(sn_aa_mask), sharpen.struct_size = (int32_t)sizeof(sn_aa_sharpen); }
+    sn_aa_repair repair{};                    // rank != 0: the result is clamped into the source's 3 x 3 rank range (sn_repair.hip), before the mask
+    AaOptions()
+    {
+        mask.struct_size = (int32_t)sizeof(sn_aa_mask), sharpen.struct_size = (int32_t)sizeof(sn_aa_sharpen);
+        repair.struct_size = (int32_t)sizeof(sn_aa_repair);
+    }
 };
 
-// Every refusal sn_aa_create_ex6 makes of cfg's own fields and of the option structs (NULL: defaults), in the order it makes
+// Every refusal sn_aa_create_ex7 makes of cfg's own fields and of the option structs (NULL: defaults), in the order it makes
 // them: SN_OK and `out`, or the code and `msg`.  What the two passes refuse of cfg follows at their creation.
 inline int aa_check(const sn_config& cfg, const sn_aa_options* aa_options, const sn_aa_mask* mask, const sn_aa_mask_ex* mask_ex, const sn_aa_sharpen* sharpen,
-                    const sn_aa_fields* fields, AaOptions& out, std::string& msg)
+                    const sn_aa_fields* fields, const sn_aa_repair* repair, AaOptions& out, std::string& msg)
 {
     auto refuse = [&msg](int code, const char* text) {
         msg = text;
@@ -109,15 +114,34 @@ inline int aa_check(const sn_config& cfg, const sn_aa_options* aa_options, const
     }
     // the two dh results place the source on different lines: their average is a half-line blur (reduce needs dh and falls with it)
     if (out.fields == SN_AA_FIELDS_BOTH && cfg.dh) return refuse(SN_ERR_CONFIG, "SangNomAA: both fields needs dh=false");
+    if (repair) {
+        if (repair->struct_size != (int32_t)sizeof(sn_aa_repair)) return refuse(SN_ERR_INVALID_ARG, "sn_aa_repair.struct_size mismatch");
+        if (repair->rank < 0 || repair->rank > 4) return refuse(SN_ERR_INVALID_ARG, "sn_aa_repair.rank must be 0 (off) or 1..4");
+        if (repair->rank) {  // with rank 0 the fields below it are ignored
+            if (repair->chroma < 0 || repair->chroma > 1) return refuse(SN_ERR_INVALID_ARG, "sn_aa_repair.chroma must be 0 or 1");
+            for (int32_t r : repair->reserved)
+                if (r) return refuse(SN_ERR_INVALID_ARG, "sn_aa_repair.reserved must be zero");
+            out.repair.rank = repair->rank, out.repair.chroma = repair->chroma;
+        }
+    }
+    if (out.repair.rank && cfg.dh && !out.reduce)
+        return refuse(SN_ERR_CONFIG, "SangNomAA: repair needs the frame at source size (dh=false, or dh=true with reduce)");
     msg.clear();
     return SN_OK;
+}
+
+// ... as sn_aa_create_ex6 makes them: no rank repair
+inline int aa_check(const sn_config& cfg, const sn_aa_options* aa_options, const sn_aa_mask* mask, const sn_aa_mask_ex* mask_ex, const sn_aa_sharpen* sharpen,
+                    const sn_aa_fields* fields, AaOptions& out, std::string& msg)
+{
+    return aa_check(cfg, aa_options, mask, mask_ex, sharpen, fields, nullptr, out, msg);
 }
 
 // ... as sn_aa_create_ex5 makes them: one field per pass
 inline int aa_check(const sn_config& cfg, const sn_aa_options* aa_options, const sn_aa_mask* mask, const sn_aa_mask_ex* mask_ex, const sn_aa_sharpen* sharpen,
                     AaOptions& out, std::string& msg)
 {
-    return aa_check(cfg, aa_options, mask, mask_ex, sharpen, nullptr, out, msg);
+    return aa_check(cfg, aa_options, mask, mask_ex, sharpen, nullptr, nullptr, out, msg);
 }
 
 // ---- buffers and steps ---------------------------------------------------------------------------------------------------------
@@ -133,7 +157,8 @@ enum AaBuf : int8_t { kAaSrc, kAaDst, kAaT1, kAaU1, kAaT2, kAaE, kAaS, kAaU1B, k
 
 enum AaStepKind : int8_t {
     kAaTurnLeft, kAaPass1, kAaTurnRight, kAaPass2, kAaReduce, kAaSharpen, kAaMaskLuma, kAaMask,
-    kAaPass1B, kAaTurnRightMerge, kAaPass2B, kAaMerge  // both fields
+    kAaPass1B, kAaTurnRightMerge, kAaPass2B, kAaMerge,  // both fields
+    kAaRepair                                           // (appended: no earlier value moves)
 };
 inline bool aa_is_pass(int kind) { return kind == kAaPass1 || kind == kAaPass2 || kind == kAaPass1B || kind == kAaPass2B; }
 
@@ -142,7 +167,7 @@ inline bool aa_is_pass(int kind) { return kind == kAaPass1 || kind == kAaPass2 |
 enum AaCut : int8_t { kAaCutChunk, kAaCutRun1, kAaCutRun2 };
 
 // One stage of a chunk.  Within a step a run's planes come before the next run, the planes in ascending order.
-//   TurnLeft / TurnRight / Reduce / Sharpen / Mask  one launch per run and plane of `planes`: read[] -> write[p]
+//   TurnLeft / TurnRight / Reduce / Sharpen / Repair / Mask  one launch per run and plane of `planes`: read[] -> write[p]
 //   Pass1 / Pass2 / Pass1B / Pass2B   one run_batch for the chunk (B: of the order-2 twin); a plane outside `planes` is not
 //                   touched, its pointers only have to be there
 //   TurnRightMerge  one launch per plane: the turn of avg(read[0], read[1]) -> write[p]
@@ -154,15 +179,16 @@ struct AaStep {
     int8_t cut = kAaCutChunk;
     int8_t read[2] = {kAaNoBuf, kAaNoBuf};
     int8_t write[3] = {kAaNoBuf, kAaNoBuf, kAaNoBuf};  // per plane
-    int32_t arg = 0;  // Reduce: the kernel (SN_AA_REDUCE_*); Sharpen: the amount
+    int32_t arg = 0;  // Reduce: the kernel (SN_AA_REDUCE_*); Sharpen: the amount; Repair: the rank
     bool on(int p) const { return (planes >> p) & 1; }
 };
-constexpr int kAaMaxSteps = 10;
+constexpr int kAaMaxSteps = 11;  // both fields + sharpen + repair + luma mask + own mask
 
 // ---- the plan ------------------------------------------------------------------------------------------------------------------
 struct AaPlane {
     bool process = false;    // the passes work on it (dh forces every plane); otherwise it is copied from source to destination elsewhere
     bool sharpened = false;  // processed, and plane 0 unless sharpen.chroma
+    bool repaired = false;   // processed, and plane 0 unless repair.chroma
     int w = 0, h = 0;        // clip geometry
     int pitch = 0, tpitch = 0;
     int64_t cbytes = 0, tbytes = 0;  // one frame of the plane: clip geometry / turned
@@ -241,6 +267,7 @@ inline AaPlan aa_geometry(const sn_config& cfg, const AaOptions& opt)
         a.dstpitch = opt.reduce ? a.pitch : a.opitch;
         a.dstbytes = opt.reduce ? a.cbytes : a.obytes;
         a.sharpened = opt.sharpen.amount && a.process && (p == 0 || opt.sharpen.chroma);
+        a.repaired = opt.repair.rank && a.process && (p == 0 || opt.repair.chroma);
     }
     return P;
 }
@@ -291,8 +318,11 @@ inline int aa_chunk_frames(const AaPlan& P, int64_t budget_bytes, int frames)
 // surface walk and the host staging copy them.
 inline void aa_steps(AaPlan& P)
 {
-    uint8_t processed = 0, sharpened = 0;
-    for (int p = 0; p < P.planes; ++p) processed |= (uint8_t)(P.plane[p].process << p), sharpened |= (uint8_t)(P.plane[p].sharpened << p);
+    uint8_t processed = 0, sharpened = 0, repaired = 0;
+    for (int p = 0; p < P.planes; ++p) {
+        processed |= (uint8_t)(P.plane[p].process << p), sharpened |= (uint8_t)(P.plane[p].sharpened << p);
+        repaired |= (uint8_t)(P.plane[p].repaired << p);
+    }
     P.nsteps = 0;
     auto add = [&P](AaStepKind kind, uint8_t planes, AaCut cut, AaBuf r0, AaBuf r1, AaBuf w) -> AaStep& {
         AaStep& s = P.step[P.nsteps++] = AaStep();
@@ -330,6 +360,9 @@ inline void aa_steps(AaPlan& P)
     }
     // the contra-sharpening: the destination from the source and the last step's output
     if (sharpened) add(kAaSharpen, sharpened, kAaCutChunk, kAaSrc, kAaS, kAaDst).arg = P.opt.sharpen.amount;
+    // the rank repair: the result so far is clamped into the source's 3 x 3 rank range, in place on the destination (which has
+    // the source's size: aa_check has seen to it); no intermediate
+    if (repaired) add(kAaRepair, repaired, kAaCutChunk, kAaSrc, kAaDst, kAaDst).arg = P.opt.repair.rank;
     // the edge mask, last: the chunk's result is merged into the source through the source's own mask, in place on the destination
     // (which has the source's size: aa_check has seen to it) -- chroma through the source luma plane's mask: U and V in one launch
     const bool by_luma = P.opt.mask.kind && P.opt.mask_chroma == SN_AA_MASK_CHROMA_LUMA && P.planes == 3 && P.plane[1].process;

@@ -2257,6 +2257,34 @@ int sn_turn_merge_device(sn_context* h, int32_t direction, int32_t nframes, cons
     return SN_OK;
 }
 
+int sn_repair_device(sn_context* h, int32_t rank, int32_t nframes, const void* src, int64_t sfs, int32_t sp, const void* aa, int64_t afs, int32_t ap,
+                     int32_t width, int32_t height, void* dst, int64_t dfs, int32_t dp)
+{
+    Context* c = reinterpret_cast<Context*>(h);
+    if (!c) return sn::fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    const int B = c->cfg.bytes_per_sample;
+    if (rank < 1 || rank > 4) return sn::fail(c, SN_ERR_INVALID_ARG, "sn_repair_device: rank must be 1..4");
+    if (!src || !aa || !dst || nframes < 0 || width <= 0 || height <= 0 || width > INT32_MAX / 8 || height > INT32_MAX / 2)
+        return sn::fail(c, SN_ERR_INVALID_ARG, "sn_repair_device: bad pointer or size");
+    if (sp < width * B || ap < width * B || dp < width * B || sp % B || ap % B || dp % B || sfs % B || afs % B || dfs % B || (uintptr_t)src % B ||
+        (uintptr_t)aa % B || (uintptr_t)dst % B)
+        return sn::fail(c, SN_ERR_INVALID_ARG, "sn_repair_device: pitch smaller than the row or misaligned");
+    if (nframes > 0) {  // other workgroups read the neighbours of src; R is read by the thread that overwrites it, in place exactly
+        uintptr_t dlo, dhi, lo, hi;
+        plane_span(dst, dfs, dp, nframes, height, (int64_t)width * B, dlo, dhi);
+        plane_span(src, sfs, sp, nframes, height, (int64_t)width * B, lo, hi);
+        if (lo < dhi && dlo < hi) return sn::fail(c, SN_ERR_INVALID_ARG, "sn_repair_device: dst must not overlap src");
+        if (!(aa == dst && afs == dfs && ap == dp)) {
+            plane_span(aa, afs, ap, nframes, height, (int64_t)width * B, lo, hi);
+            if (lo < dhi && dlo < hi) return sn::fail(c, SN_ERR_INVALID_ARG, "sn_repair_device: dst and aa overlap without being the same plane");
+        }
+    }
+    SN_HIP(c, hipSetDevice(c->device));
+    SN_HIP(c, sn::launch_repair(c->stream, B, rank, nframes, sn::PlaneView{static_cast<const uint8_t*>(src), sfs, sp},
+                                sn::PlaneView{static_cast<const uint8_t*>(aa), afs, ap}, width, height, sn::PlaneViewW{static_cast<uint8_t*>(dst), dfs, dp}));
+    return SN_OK;
+}
+
 int sn_mask_merge_luma_device(sn_context* h, const sn_aa_mask* mask, int32_t nframes, const void* luma, int64_t lfs, int32_t lp, int32_t sub_w, int32_t sub_h,
                               const void* const src[2], const int64_t sfs[2], const int32_t sp[2], const void* const aa[2], const int64_t afs[2],
                               const int32_t ap[2], int32_t width, int32_t height, void* const dst[2], const int64_t dfs[2], const int32_t dp[2])
@@ -2484,6 +2512,8 @@ int sn_debug_read_coupled_rows(sn_context* h, int32_t which, void* host_dst, siz
 // stream: the turn writes every line, both instances of a pass read the same input, the turn back takes the average of the
 // first pass's two outputs (sn_turn.hip with a second source), and the second pass's two outputs are averaged in place where the
 // order-1 instance wrote (sn_merge.hip): five plane sizes of intermediates per processed plane and frame instead of three.
+// With a rank repair (sn_aa_repair.rank) sn_repair.hip clamps the result so far into the source's 3 x 3 rank range, in place on
+// the destination, behind the sharpening and before the edge mask: no intermediate.
 struct sn_aa_context {
     sn_config cfg{};
     sn_context* first = nullptr;   // the turned clip
@@ -2636,6 +2666,12 @@ int sn_aa_create_ex5(const sn_config* cfg, const sn_policy* policy, const sn_opt
 int sn_aa_create_ex6(const sn_config* cfg, const sn_policy* policy, const sn_options* options, const sn_aa_options* aa_options, const sn_aa_mask* mask,
                      const sn_aa_mask_ex* mask_ex, const sn_aa_sharpen* sharpen, const sn_aa_fields* fields, sn_aa_context** out)
 {
+    return sn_aa_create_ex7(cfg, policy, options, aa_options, mask, mask_ex, sharpen, fields, nullptr, out);
+}
+
+int sn_aa_create_ex7(const sn_config* cfg, const sn_policy* policy, const sn_options* options, const sn_aa_options* aa_options, const sn_aa_mask* mask,
+                     const sn_aa_mask_ex* mask_ex, const sn_aa_sharpen* sharpen, const sn_aa_fields* fields, const sn_aa_repair* repair, sn_aa_context** out)
+{
     auto fail_aa = [](sn_aa_context* a, int code, const std::string& msg) {
         g_aa_error = msg;
         if (a) sn_aa_destroy(a);
@@ -2646,7 +2682,7 @@ int sn_aa_create_ex6(const sn_config* cfg, const sn_policy* policy, const sn_opt
     // check, build the geometry, create the passes, allocate (sn_aa_plan.h decides; nothing below does)
     sn::AaOptions opt;
     std::string msg;
-    if (int rc = sn::aa_check(*cfg, aa_options, mask, mask_ex, sharpen, fields, opt, msg)) return fail_aa(nullptr, rc, msg);
+    if (int rc = sn::aa_check(*cfg, aa_options, mask, mask_ex, sharpen, fields, repair, opt, msg)) return fail_aa(nullptr, rc, msg);
     sn_aa_context* a = new (std::nothrow) sn_aa_context();
     if (!a) return fail_aa(nullptr, SN_ERR_INVALID_ARG, "out of host memory");
     a->cfg = *cfg;
@@ -2734,6 +2770,9 @@ static int aa_step(sn_aa_context* a, const sn::AaStep& s, int f0, int m, const s
                 break;
             case sn::kAaSharpen:
                 SN_AA_HIP(sn::launch_contra_sharpen(st, B, P.bits, s.arg, n, from, rd(s.read[1], p).at(g0), g.w, g.h, to));
+                break;
+            case sn::kAaRepair:  // in place: R is read by the thread that overwrites it
+                SN_AA_HIP(sn::launch_repair(st, B, s.arg, n, from, rd(s.read[1], p).at(g0), g.w, g.h, to));
                 break;
             case sn::kAaMask:
                 SN_AA_HIP(sn::launch_mask_merge(st, B, P.bits, mask.lo, mask.hi, mask.expand, n, from, rd(s.read[1], p).at(g0), g.w, g.h, to));
@@ -2897,6 +2936,14 @@ int sn_aa_get_sharpen(sn_aa_context* a, sn_aa_sharpen* out)
     if (!out || out->struct_size != (int32_t)sizeof(sn_aa_sharpen))
         return aa_fail(a, SN_ERR_INVALID_ARG, "out is NULL or sn_aa_sharpen.struct_size mismatch");
     *out = a->plan.opt.sharpen;
+    return SN_OK;
+}
+
+int sn_aa_get_repair(sn_aa_context* a, sn_aa_repair* out)
+{
+    if (!a) return aa_fail(nullptr, SN_ERR_INVALID_ARG, "ctx is NULL");
+    if (!out || out->struct_size != (int32_t)sizeof(sn_aa_repair)) return aa_fail(a, SN_ERR_INVALID_ARG, "out is NULL or sn_aa_repair.struct_size mismatch");
+    *out = a->plan.opt.repair;
     return SN_OK;
 }
 

@@ -114,6 +114,11 @@ hipError_t launch_mask_merge_luma(hipStream_t s, int bytes, int bits, int lo, in
 // over 3 x 3, and written to dst.  dst must overlap neither src nor aa.
 hipError_t launch_contra_sharpen(hipStream_t s, int bytes, int bits, int amount, int nframes, PlaneView src, PlaneView aa, int w, int h, PlaneViewW dst);
 
+// sn_repair.hip: the rank repair of the anti-aliasing call (sangnom_hip.h, "Rank repair", has the arithmetic).  Each sample of
+// aa (w x h, the call's result) is clamped into [a[rank], a[10 - rank]] of the nine src samples around it (rank 1..4) and
+// written to dst.  dst may be the plane aa lies in (same base, pitch and frame stride); src must not overlap dst.
+hipError_t launch_repair(hipStream_t s, int bytes, int rank, int nframes, PlaneView src, PlaneView aa, int w, int h, PlaneViewW dst);
+
 // sn_uv.hip: semi-planar chroma (a UV plane of U,V sample pairs: NV12 / P016 / NV16 / NV24) <-> a U and a V plane of cw x h
 // samples each.  line_parity 0 / 1: only the lines of that parity are read and written (the lines the pass that follows
 // keeps), < 0: all of them.  One side is never written: split reads uv, merge reads u and v.

@@ -365,6 +365,19 @@ class SangNom2:
                                                    b.stride(0) * B, b.stride(1) * B, W, H, dst.data_ptr(), dst.stride(0) * B, dst.stride(1) * B))
         return dst
 
+    def repair(self, src, aa, dst, rank: int):
+        """sn_repair_device: each sample of aa [N, H, W] (a filtered plane) is clamped into the range of the rank-th smallest
+        and rank-th largest (rank 1..4) of the nine samples of src around it and written to dst (sangnom_hip.h, "Rank
+        repair").  dst may be aa itself; it must not overlap src.  Torch tensors on the device; asynchronous on the context's stream."""
+        B = self.clip.bytes
+        N, H, W = dst.shape
+        for t in (src, aa, dst):
+            if tuple(t.shape) != (N, H, W) or t.stride(2) != 1 or t.element_size() != B:
+                raise ValueError("repair: src, aa and dst must be [N, H, W], x-contiguous and of the clip's sample type")
+        self._check(self._lib.sn_repair_device(self._h, int(rank), N, src.data_ptr(), src.stride(0) * B, src.stride(1) * B, aa.data_ptr(),
+                                               aa.stride(0) * B, aa.stride(1) * B, W, H, dst.data_ptr(), dst.stride(0) * B, dst.stride(1) * B))
+        return dst
+
     def mask_merge_luma(self, luma, src, aa, dst, lo: int, hi: int, expand: int = 1, sub_w: int = 1, sub_h: int = 1):
         """sn_mask_merge_luma_device: the Sobel edge mask of luma [N, H << sub_h, W << sub_w], reduced to chroma's geometry
         by the block mean, merges aa into src.  src, aa and dst are one tensor [N, H, W] or a pair of them (U and V in one
@@ -489,12 +502,16 @@ class _AAContext:
     filter changed the picture and only towards the source.  Plane 0, or every processed plane with sharpen_chroma.
     fields="one" | "both" (without dh): "both" interpolates both fields in every pass -- two filter instances, order 1 and
     order 2 -- and averages the two results on the device (sangnom_hip.h, "Both fields"); `order` and the per-frame parity
-    then have no influence.  Sharpening and mask follow the averaged result."""
+    then have no influence.  Sharpening and mask follow the averaged result.
+    repair=None | 1..4, repair_chroma=False (without dh, or with dh and reduce): behind the sharpening and before the mask each
+    sample of the result is clamped into the range of the repair-th smallest and repair-th largest of the nine source samples
+    around it (sangnom_hip.h, "Rank repair"), in place.  Plane 0, or every processed plane with repair_chroma."""
 
     def __init__(self, clip: ClipFormat, order: int = 1, aa: int = 48, aac: int = 0, luma: bool = True, chroma: bool = True,
                  device: int = 0, isolated_planes: bool = False, fresh_pool: bool = False, opt: int = -1, max_batch: int = 1,
                  host_depth: int = 0, stream: int | None = None, dh: bool = False, column_parts: int = 0, reduce=0, mask=None, mask_expand: int = 1,
-                 mask_chroma="own", sharpen=None, sharpen_chroma: bool = False, fields="one", **policy_kw):
+                 mask_chroma="own", sharpen=None, sharpen_chroma: bool = False, fields="one", repair=None,
+                 repair_chroma: bool = False, **policy_kw):
         if opt < -1 or opt > 1:
             raise SangNomError(capi.SN_ERR_CONFIG, "SangNom2: opt must be between -1..2.")  # sic, SangNom2.cpp:420
         self.clip = clip
@@ -505,6 +522,7 @@ class _AAContext:
         amask_ex = capi.aa_mask_ex(mask_chroma)
         asharpen = capi.aa_sharpen(sharpen, sharpen_chroma)
         afields = capi.aa_fields(fields)
+        arepair = capi.aa_repair(repair, repair_chroma)
         self.max_batch = max_batch
         self._lib = capi.load()
         cfg = capi.SnConfig(
@@ -515,8 +533,9 @@ class _AAContext:
         self._h = ctypes.c_void_p()
         pol = capi.policy(**{k: policy_kw.get(k) for k in ("small_launches", "chain", "copy_threads", "scratch_budget_mb", "chroma_sweeps", "sse2_sweeps")})
         opts = capi.options(capi.arithmetic_of_opt(opt), column_parts=column_parts)
-        rc = self._lib.sn_aa_create_ex6(ctypes.byref(cfg), ctypes.byref(pol), ctypes.byref(opts), ctypes.byref(aopts), ctypes.byref(amask),
-                                        ctypes.byref(amask_ex), ctypes.byref(asharpen), ctypes.byref(afields), ctypes.byref(self._h))
+        rc = self._lib.sn_aa_create_ex7(ctypes.byref(cfg), ctypes.byref(pol), ctypes.byref(opts), ctypes.byref(aopts), ctypes.byref(amask),
+                                        ctypes.byref(amask_ex), ctypes.byref(asharpen), ctypes.byref(afields), ctypes.byref(arepair),
+                                        ctypes.byref(self._h))
         if rc != capi.SN_OK:
             self._h = None
             raise SangNomError(rc, self._lib.sn_aa_last_error(None).decode())
@@ -577,6 +596,13 @@ class _AAContext:
         """sn_aa_get_sharpen: the contra-sharpening of this context (amount 0 when it is off)."""
         m = capi.SnAASharpen(struct_size=ctypes.sizeof(capi.SnAASharpen))
         self._check(self._lib.sn_aa_get_sharpen(self._h, ctypes.byref(m)))
+        return m
+
+    @property
+    def repair(self) -> capi.SnAARepair:
+        """sn_aa_get_repair: the rank repair of this context (rank 0 when it is off)."""
+        m = capi.SnAARepair(struct_size=ctypes.sizeof(capi.SnAARepair))
+        self._check(self._lib.sn_aa_get_repair(self._h, ctypes.byref(m)))
         return m
 
     @property

@@ -112,6 +112,9 @@ AVSValue __cdecl Create_SangNom2HIP(AVSValue args, void*, IScriptEnvironment* en
 // sharpc=true: every processed plane, not luma alone.  64 is a starting value that nobody has tuned on real footage.
 // both=true (without dh; "SangNomAA: both fields needs dh=false"): every pass interpolates both fields -- order 1 and order 2 --
 // and the two results are averaged on the device, as daa does; order and the frames' parity then have no influence.
+// repair=1..4 (default 0: off; at source size): behind the sharpening and before the mask each sample of the result is clamped
+// into the range of the repair-th smallest and repair-th largest of the nine source samples around it, as Repair(filtered,
+// source, mode) of RemoveGrain does with modes 1..4; repairc=true: every processed plane, not luma alone.
 class SangNomAA : public GenericVideoFilter {
     sangnom::AAFilter<AvsHost> impl_;
 
@@ -147,6 +150,8 @@ AVSValue __cdecl Create_SangNomAA(AVSValue args, void*, IScriptEnvironment* env)
     a.sharpen = args[18].AsInt(0);
     a.sharpen_chroma = args[19].AsBool(false);
     a.both_fields = args[20].AsBool(false);
+    a.repair = args[21].AsInt(0);
+    a.repair_chroma = args[22].AsBool(false);
     return new SangNomAA(args[0].AsClip(), a, env);
 }
 
@@ -170,7 +175,7 @@ extern "C" __declspec(dllexport) const char* __stdcall AvisynthPluginInit3(IScri
     env->AddFunction("SangNom", "c[order]i[aa]i[opt]i", Create_SangNom, 0);                                        // :482
     env->AddFunction("SangNom2HIP", "c[order]i[aa]i[aac]i[threads]i[dh]b[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i[device]i",
                      Create_SangNom2HIP, 0);
-    env->AddFunction("SangNomAA", "c[order]i[aa]i[aac]i[device]i[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i[dh]b[reduce]i[mask]b[mlo]i[mhi]i[mexpand]i[mluma]b[sharp]i[sharpc]b[both]b",
+    env->AddFunction("SangNomAA", "c[order]i[aa]i[aac]i[device]i[luma]b[chroma]b[opt]i[isolated]b[fresh]b[lookahead]i[dh]b[reduce]i[mask]b[mlo]i[mhi]i[mexpand]i[mluma]b[sharp]i[sharpc]b[both]b[repair]i[repairc]b",
                      Create_SangNomAA, 0);
     return "SangNom2";
 }

@@ -45,6 +45,8 @@ struct Args {  // SangNom2(clip, order, aa, aac, threads, dh, luma, chroma, opt)
     int sharpen = 0;         // SangNomAA only, at source size: contra-sharpening behind the last step, sn_aa_sharpen.amount (0 off, 1..255, 64 = unity)
     bool sharpen_chroma = false;  // ... of every processed plane, not of plane 0 alone (sn_aa_sharpen.chroma)
     bool both_fields = false;  // SangNomAA only, without dh: every pass interpolates both fields and averages (sn_aa_fields.mode = SN_AA_FIELDS_BOTH)
+    int repair = 0;            // SangNomAA only, at source size: rank repair behind the sharpening, sn_aa_repair.rank (0 off, 1..4)
+    bool repair_chroma = false;  // ... of every processed plane, not of plane 0 alone (sn_aa_repair.chroma)
     int column_parts = -1;  // sn_options.column_parts (16-bit / float planes wider than 3840 in column parts); -1: $SANGNOM_COLUMN_PARTS or 0
     sn_policy policy{};     // scheduling only (sangnom_hip.h); zeros = the defaults
 };
@@ -259,6 +261,9 @@ private:
 // step and before the mask (sangnom_hip.h, "Contra-sharpening"): plane 0, or with Args::sharpen_chroma every processed plane.
 // With Args::both_fields (without dh) every pass runs for order 1 and for order 2 and the library averages the two results
 // (sangnom_hip.h, "Both fields"), as daa and its relatives do: Args::order and the frames' parity then have no influence.
+// With Args::repair (1..4; the clip at source size) the library clamps each sample of the result into the range of the
+// repair-th smallest and repair-th largest of the nine source samples around it (sangnom_hip.h, "Rank repair"), behind the
+// sharpening and before the mask: plane 0, or with Args::repair_chroma every processed plane.
 template <class Host>
 class AAFilter {
 public:
@@ -290,6 +295,8 @@ public:
         if (a.sharpen < 0 || a.sharpen > 255) env->ThrowError("%s: sn_aa_sharpen.amount must be 0 (off) or 1..255", name);
         if (a.sharpen && a.dh && !a.reduce) env->ThrowError("%s: sharpen needs the frame at source size (dh=false, or dh=true with reduce)", name);
         if (a.both_fields && a.dh) env->ThrowError("%s: both fields needs dh=false", name);
+        if (a.repair < 0 || a.repair > 4) env->ThrowError("%s: sn_aa_repair.rank must be 0 (off) or 1..4", name);
+        if (a.repair && a.dh && !a.reduce) env->ThrowError("%s: repair needs the frame at source size (dh=false, or dh=true with reduce)", name);
         sn_config c{};
         c.struct_size = (int32_t)sizeof c;
         c.width = Host::Width(vi_);
@@ -337,7 +344,10 @@ public:
         sn_aa_fields fields{};
         fields.struct_size = (int32_t)sizeof fields;
         fields.mode = a.both_fields ? SN_AA_FIELDS_BOTH : SN_AA_FIELDS_ONE;
-        if (sn_aa_create_ex6(&c, &pol, &opts, &aopts, &mask, &mask_ex, &sharpen, &fields, &ctx_) != SN_OK)
+        sn_aa_repair repair{};
+        repair.struct_size = (int32_t)sizeof repair;
+        repair.rank = a.repair, repair.chroma = a.repair_chroma ? 1 : 0;
+        if (sn_aa_create_ex7(&c, &pol, &opts, &aopts, &mask, &mask_ex, &sharpen, &fields, &repair, &ctx_) != SN_OK)
             env->ThrowError("%s: %s", name, sn_aa_last_error(nullptr));
         enlarged_ = a.dh && !a.reduce;
         if (enlarged_) {  // each pass doubles the height of what it is given: the clip comes out twice as wide and twice as high

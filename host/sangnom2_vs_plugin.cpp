@@ -5,7 +5,8 @@
 //     core.sangnomhip.SangNom(clip, order=1, dh=False, aa=48, aac=0, luma=True, chroma=True,
 //                             isolated=False, fresh=False)
 //     core.sangnomhip.SangNomAA(clip, order=1, aa=48, aac=0, luma=True, chroma=True, isolated=False, fresh=False, dh=False, reduce=0,
-//                               mask=False, mlo=8, mhi=32, mexpand=1, mluma=False, sharp=0, sharpc=False, both=False)
+//                               mask=False, mlo=8, mhi=32, mexpand=1, mluma=False, sharp=0, sharpc=False, both=False,
+//                               repair=0, repairc=False)
 // SangNomAA is the anti-aliasing idiom (a quarter turn, SangNom, the turn back, SangNom) as one call of the library
 // (sn_aa_process_host); with dh=True both passes double the height: the clip comes out twice as wide and twice as high;
 // with reduce=1 (tent) or 2 (half-band) on top of dh the library reduces it on the device and the clip keeps its size.
@@ -16,6 +17,8 @@
 // by what the filter changed); sharpc=True: every processed plane, not luma alone.  64 is a starting value, not tuned on real footage.
 // both=True (without dh) interpolates both fields in every pass (order 1 and order 2) and averages the two on the device; order
 // then has no influence.
+// repair=1..4 (at source size) clamps each sample of the result into the range of the repair-th smallest and repair-th largest of
+// the nine source samples around it, behind the sharpening and before the mask; repairc=True: every processed plane, not luma alone.
 // It needs the VapourSynth SDK header VapourSynth4.h, a third-party file that is not part of this repository or
 // of the build image: without it this file compiles to nothing, so it has NOT been compiled or run here
 // (INTEGRATION.md says so).  With the SDK:  make -C host VS_INCLUDE_DIR=<dir of VapourSynth4.h>.
@@ -159,7 +162,10 @@ void VS_CC sangnomCreate(const VSMap* in, VSMap* out, void* userData, VSCore* co
     fl.struct_size = (int32_t)sizeof fl;
     fl.mode = aa && geti("both", 0) ? SN_AA_FIELDS_BOTH : SN_AA_FIELDS_ONE;
     if (fl.mode == SN_AA_FIELDS_BOTH && c.dh) return fail("both fields needs dh=false");
-    if (aa ? sn_aa_create_ex6(&c, nullptr, nullptr, &ao, &mk, &mx, &sh, &fl, &d->aa) != SN_OK : sn_create(&c, &d->ctx) != SN_OK) return fail(bare(aa ? sn_aa_last_error(nullptr) : sn_last_error(nullptr)));
+    sn_aa_repair rp{};
+    rp.struct_size = (int32_t)sizeof rp;
+    rp.rank = aa ? geti("repair", 0) : 0, rp.chroma = aa && geti("repairc", 0) ? 1 : 0;
+    if (aa ? sn_aa_create_ex7(&c, nullptr, nullptr, &ao, &mk, &mx, &sh, &fl, &rp, &d->aa) != SN_OK : sn_create(&c, &d->ctx) != SN_OK) return fail(bare(aa ? sn_aa_last_error(nullptr) : sn_last_error(nullptr)));
     d->planes = c.num_planes;
     if (c.dh && !ao.reduce) d->vi.height *= 2;
     if (c.dh && aa && !ao.reduce) d->vi.width *= 2;  // both passes double the height of what they are given
@@ -181,7 +187,7 @@ VS_EXTERNAL_API(void) VapourSynthPluginInit2(VSPlugin* plugin, const VSPLUGINAPI
                              "clip:vnode;", sangnomCreate, nullptr, plugin);
     static int aa_tag = 1;
     vspapi->registerFunction("SangNomAA",
-                             "clip:vnode;order:int:opt;aa:int:opt;aac:int:opt;luma:int:opt;chroma:int:opt;isolated:int:opt;fresh:int:opt;dh:int:opt;reduce:int:opt;mask:int:opt;mlo:int:opt;mhi:int:opt;mexpand:int:opt;mluma:int:opt;sharp:int:opt;sharpc:int:opt;both:int:opt;",
+                             "clip:vnode;order:int:opt;aa:int:opt;aac:int:opt;luma:int:opt;chroma:int:opt;isolated:int:opt;fresh:int:opt;dh:int:opt;reduce:int:opt;mask:int:opt;mlo:int:opt;mhi:int:opt;mexpand:int:opt;mluma:int:opt;sharp:int:opt;sharpc:int:opt;both:int:opt;repair:int:opt;repairc:int:opt;",
                              "clip:vnode;", sangnomCreate, &aa_tag, plugin);
 }
 #endif  // SN_HAVE_VAPOURSYNTH

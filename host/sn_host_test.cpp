@@ -16,7 +16,8 @@
 // SN_HOST_TEST_MASK=lo,hi,expand Args::mask with those values (SangNomAA: the result merged through the source's edge mask),
 // SN_HOST_TEST_MASK_LUMA=1 Args::mask_luma (chroma through the luma plane's mask),
 // SN_HOST_TEST_SHARPEN=amount,chroma Args::sharpen and Args::sharpen_chroma (SangNomAA: contra-sharpening behind the last step),
-// SN_HOST_TEST_FIELDS=both Args::both_fields (SangNomAA: both fields per pass, averaged).
+// SN_HOST_TEST_FIELDS=both Args::both_fields (SangNomAA: both fields per pass, averaged),
+// SN_HOST_TEST_REPAIR=rank,chroma Args::repair and Args::repair_chroma (SangNomAA: rank repair behind the sharpening).
 // out.bin: per frame the output planes in the filter's own geometry (its GetInfo()), tightly packed.  On a constructor error: exit code 3 and
 //          the message on stdout.
 #include <cstdio>
@@ -91,6 +92,10 @@ int main(int argc, char** argv)
         if (sscanf(e, "%d,%d", &a.sharpen, &chroma) == 2) a.sharpen_chroma = chroma != 0;
     }
     if (const char* e = getenv("SN_HOST_TEST_FIELDS")) a.both_fields = strcmp(e, "both") == 0;
+    if (const char* e = getenv("SN_HOST_TEST_REPAIR")) {
+        int chroma = 0;
+        if (sscanf(e, "%d,%d", &a.repair, &chroma) == 2) a.repair_chroma = chroma != 0;
+    }
     const bool aa_idiom = argc > 3 && strncmp(argv[3], "aa", 2) == 0 && (argv[3][2] == 0 || argv[3][2] == ':');
     if (aa_idiom && argv[3][2] == ':') a.lookahead = atoi(argv[3] + 3);
     if (argc > 3 && !aa_idiom) a.lookahead = atoi(argv[3]);

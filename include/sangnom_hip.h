@@ -404,6 +404,29 @@ int sn_turn_merge_device(sn_context* ctx, int32_t direction, int32_t nframes, co
                          int64_t b_frame_stride, int32_t b_pitch, int32_t width, int32_t height, void* dst, int64_t dst_frame_stride,
                          int32_t dst_pitch);
 
+/* The rank repair of the anti-aliasing call (below: "Rank repair", which defines the arithmetic).  rank 0: off, and the
+ * fields below it are ignored; 1..4 is the rank of the two order statistics of the source's 3 x 3 neighbourhood that bound
+ * the result, as modes 1..4 of Repair in RemoveGrain / RgTools. */
+typedef struct sn_aa_repair {
+    int32_t struct_size; /* sizeof(sn_aa_repair) */
+    int32_t rank;        /* 0 = off (the fields below are ignored); 1..4 */
+    int32_t chroma;      /* 0: plane 0 only; 1: every processed plane */
+    int32_t reserved[5]; /* zero */
+} sn_aa_repair;          /* 32 bytes */
+
+/* The rank repair on its own, for pipelines that keep frames on the device: `nframes` planes of width x height samples on
+ * the context's stream; each sample of `aa` (the filtered plane R) is clamped into the rank range of the nine samples of
+ * `src` (the plane S it was filtered from) around it and written to dst (see "Rank repair").  rank: 1..4; the sample type
+ * comes from the context.  Pitches >= width samples; pointers, pitches and frame strides multiples of the sample size
+ * (multiples of 16 on a side: 16 bytes per lane and access on that side).  dst must not overlap src, because the stencil
+ * reads its neighbours.  dst may be aa exactly (same pointer, pitch and frame stride: each sample of R is read by the
+ * thread that overwrites it); a dst whose bytes overlap src at all, or aa in any other way, is refused with
+ * SN_ERR_INVALID_ARG ("... overlap ...").  Nothing beyond width samples of a destination row is written.  A refused call
+ * queues nothing. */
+int sn_repair_device(sn_context* ctx, int32_t rank, int32_t nframes, const void* src, int64_t src_frame_stride, int32_t src_pitch, const void* aa,
+                     int64_t aa_frame_stride, int32_t aa_pitch, int32_t width, int32_t height, void* dst, int64_t dst_frame_stride,
+                     int32_t dst_pitch);
+
 /* The anti-aliasing idiom TurnLeft().SangNom2(order, aa, aac).TurnRight().SangNom2(order, aa, aac) as ONE call with
  * host planes (README.md:3 of the reference: "mainly used in anti-aliasing scripts"): the frame
  * crosses PCIe once each way and stays on the device between the two passes (two filter instances -- one for the
@@ -569,7 +592,37 @@ int sn_turn_merge_device(sn_context* ctx, int32_t direction, int32_t nframes, co
  * intermediates per frame instead of three (six instead of four where it is sharpened), counted against scratch_budget_mb.
  * sn_aa_get_info / sn_aa_get_parts_info take pass 2 and 3 for the order-2 twins of passes 0 and 1 (SN_ERR_INVALID_ARG in
  * one-field mode).  Measured on one MI355X the call takes 1.97 times the one-field call at 1080p 4:2:0 and 1.99 times at 2160p
- * Y8: the passes dominate and double. */
+ * Y8: the passes dominate and double.
+ *
+ * Rank repair (sn_aa_create_ex7 with repair->rank != 0; opt-in): where SangNom's cost ladder picks a wrong direction, an
+ * interpolated sample is the mean of two samples up to three columns away on the neighbouring lines; it can lie outside
+ * anything the source has nearby and shows as a bright or dark speck on or beside an edge.  The contra-sharpening only
+ * limits its own correction, and the mask hands edges through.  The scripts answer with Repair(filtered, source, mode) of
+ * RemoveGrain / RgTools, modes 1..4: each filtered sample is clamped into the range spanned by the rank-th smallest and
+ * the rank-th largest of the nine source samples around it.  The stage runs behind the contra-sharpening (or behind the
+ * last step where there is none) and before the edge mask, in place on the destination: a sample's result depends on R at
+ * that sample only, so no workgroup reads what another writes.  It adds no intermediate and nothing to scratch_budget_mb.
+ * Like the mask it needs the frame at source size: rank != 0 with dh = 1 and no reduction is SN_ERR_CONFIG "SangNomAA:
+ * repair needs the frame at source size (dh=false, or dh=true with reduce)", before a device is touched.  It works with
+ * both fields, either mask form and the sharpening, through every sn_aa_* entry point.  Only processed planes are repaired
+ * -- plane 0 with chroma = 0, every processed plane with chroma = 1 --; a plane that is merely copied stays a copy.  The
+ * arithmetic is the library's own, exactly:
+ *   S is the source plane (W x H), R the call's result for it (sharpened, where the call sharpens);
+ *   S(y, x) = S[clamp(y, 0, H-1)][clamp(x, 0, W-1)];
+ *   a[1] <= ... <= a[9] are the nine samples S(y+j, x+i), j, i in {-1, 0, 1}, the centre included;
+ *   lo = a[rank], hi = a[10 - rank].
+ *   Integer samples (8..16 bit): out = min(max(R(y,x), lo), hi).  No range clamp: out is R, or a source sample.
+ *   Float samples:
+ *     if R(y,x) is a NaN, or any of the nine source samples is a NaN: out = R(y,x), bit for bit;
+ *     otherwise the nine are ordered by <, with -0.0 and +0.0 equal;
+ *     out = R(y,x), bit for bit, where lo <= R(y,x) <= hi; otherwise out is the bound that R crossed, and a bound that is a
+ *     zero is written as +0.0 (by a select, not by an addition: which of two equal zeros a selection network delivers
+ *     does not show).  Infinities are ordinary values.  No NaN is generated, and there is no float arithmetic at all.
+ *   What the ranks mean for samples the filter did not touch: without dh the kept lines of R are copies of S.  Rank 1 leaves
+ *   them alone, because the centre is one of the nine and so lies within [a[1], a[9]].  Ranks 2..4 also move a SOURCE sample
+ *   that is one of the rank - 1 smallest or rank - 1 largest of its own neighbourhood -- an isolated bright or dark pixel
+ *   of the source is pulled in --, exactly as Repair does in the scripts; the mask, which runs later, gives flat areas back
+ *   to the source.  Modes 5 and up of Repair (line pairs, modes built on the centre) are not offered. */
 enum { SN_AA_REDUCE_NONE = 0, SN_AA_REDUCE_TENT = 1, SN_AA_REDUCE_HALFBAND = 2 };
 typedef struct sn_aa_options {
     int32_t struct_size; /* sizeof(sn_aa_options) */
@@ -611,6 +664,14 @@ int sn_aa_create_ex6(const sn_config* cfg, const sn_policy* policy, const sn_opt
                      const sn_aa_mask* mask /* NULL = none */, const sn_aa_mask_ex* mask_ex /* NULL = defaults */,
                      const sn_aa_sharpen* sharpen /* NULL = off */, const sn_aa_fields* fields /* NULL = one field */, sn_aa_context** out);
 int sn_aa_get_fields(sn_aa_context* ctx, sn_aa_fields* out /* struct_size set by the caller */);
+/* sn_aa_create_ex6 is sn_aa_create_ex7 with repair = NULL (no rank repair).  A bad struct_size, a rank outside 0..4, a chroma
+ * outside 0..1 or a non-zero reserved word: SN_ERR_INVALID_ARG, naming sn_aa_repair.<field>; with rank = 0 only struct_size
+ * is looked at. */
+int sn_aa_create_ex7(const sn_config* cfg, const sn_policy* policy, const sn_options* options, const sn_aa_options* aa_options /* NULL = defaults */,
+                     const sn_aa_mask* mask /* NULL = none */, const sn_aa_mask_ex* mask_ex /* NULL = defaults */,
+                     const sn_aa_sharpen* sharpen /* NULL = off */, const sn_aa_fields* fields /* NULL = one field */,
+                     const sn_aa_repair* repair /* NULL = off */, sn_aa_context** out);
+int sn_aa_get_repair(sn_aa_context* ctx, sn_aa_repair* out /* struct_size set by the caller */); /* rank 0 when off */
 int sn_aa_process_host(sn_aa_context* ctx, const void* const src[3], const int32_t src_pitch[3], void* const dst[3],
                        const int32_t dst_pitch[3], int32_t parity);
 const char* sn_aa_last_error(const sn_aa_context* ctx); /* ctx == NULL: last failed sn_aa_create on this thread */

@@ -19,6 +19,10 @@ in place), both on noise and moving the same 3 W H B bytes per frame, alternatin
 the ratio of their medians (on top of --mask / --sharpen where given).  --merge-bw: the averaging kernel alone (sn_merge_device)
 against the mask kernel (expand 1), both on noise and moving 3 W H B bytes per frame, and the turn of the average
 (sn_turn_merge_device, 3 W H B) against the turn (2 W H B), alternating; any of Y8 / Y16 / Y32.
+--repair K (1..4; at source size; device batches): the call with the rank repair (on top of --mask / --sharpen where given)
+next to the call without it; --repair-chroma: every processed plane.  --repair-bw: the repair kernel alone (sn_repair_device,
+ranks 1..4, and rank --repair or 1 in place) against the mask kernel (expand 1) and the sharpening kernel, all on noise and
+moving the same 3 W H B bytes per frame, alternating; any of Y8 / Y16 / Y32.
 usage: python tools/aa_bench.py [--frames 512] [--fresh 1] [--fmt Y8] [--size 3840x2160] [--dh [--composed]] [--reduce K] [--host [--depth 8]]
        python tools/aa_bench.py --reduce-bw [--fmt Y16] [--size 1920x1080] [--frames 64]
        python tools/aa_bench.py --mask 8,32,1 [--reduce halfband] [--size 1920x1080] [--host]
@@ -26,7 +30,9 @@ usage: python tools/aa_bench.py [--frames 512] [--fresh 1] [--fmt Y8] [--size 38
        python tools/aa_bench.py --sharpen 64 --mask 8,32,1 --reduce halfband [--fmt YUV420P8]
        python tools/aa_bench.py --sharpen-bw [--fmt Y16] [--size 3840x2160] [--frames 256] [--reps 5]
        python tools/aa_bench.py --fields both [--fmt YUV420P8] [--size 1920x1080] [--frames 256] [--reps 9]
-       python tools/aa_bench.py --merge-bw [--fmt Y16] [--size 3840x2160] [--frames 256] [--reps 9]"""
+       python tools/aa_bench.py --merge-bw [--fmt Y16] [--size 3840x2160] [--frames 256] [--reps 9]
+       python tools/aa_bench.py --repair 2 --mask 8,32,1 [--reduce halfband] [--fmt YUV420P8] [--frames 64]
+       python tools/aa_bench.py --repair-bw [--fmt Y16] [--size 3840x2160] [--frames 256] [--reps 5]"""
 import argparse
 import json
 import os
@@ -234,6 +240,49 @@ def sharpen_bandwidth(clip, a):
     return out
 
 
+def repair_bandwidth(clip, a):
+    """sn_repair_device at every rank (and in place on R at rank --repair or 1) against sn_mask_merge_device (expand 1, into a
+    third plane) and sn_contra_sharpen_device, all on noise, alternating: median, minimum and maximum microseconds per frame over
+    --reps launches of --frames frames.  All read S and R and write dst: 3 W H B bytes per frame; `of_hbm_peak` is that over
+    8 TB/s over the median."""
+    dev = torch.device("cuda:0")
+    N, W, H, B = a.frames, clip.width, clip.height, clip.bytes
+    dt = {1: torch.uint8, 2: torch.int16, 4: torch.float32}[B]
+
+    def noise():
+        if B == 4:
+            return torch.rand((N, H, W), device=dev)
+        return torch.randint(0, 1 << clip.bits, (N, H, W), device=dev, dtype=torch.int32).to(dt)
+    S, R = noise(), noise()
+    dst = torch.empty((N, H, W), device=dev, dtype=dt)
+    lo, hi, _ = a.mask_values
+    amount = a.sharpen or 64
+    out = {"clip": f"{a.fmt} {W}x{H}", "frames": N, "plane_bytes": N * W * H * B, "mask": [lo, hi, 1], "sharpen": amount, "reps": a.reps}
+    with SangNom2(clip, max_batch=1) as flt:
+        runs = {"mask1": lambda: flt.mask_merge(S, R, dst, lo, hi, 1), "sharpen": lambda: flt.contra_sharpen(S, R, dst, amount)}
+        for rank in (1, 2, 3, 4):
+            runs[f"repair{rank}"] = lambda rank=rank: flt.repair(S, R, dst, rank)
+        runs["repair_in_place"] = lambda: flt.repair(S, dst, dst, a.repair or 1)  # (on the last rank's output: the same traffic)
+        times = {k: [] for k in runs}
+        torch.cuda.synchronize()
+        for r in range(a.reps + 1):
+            for k, fn in runs.items():
+                flt.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                flt.synchronize()
+                if r:
+                    times[k].append(time.perf_counter() - t0)
+        for k, t in times.items():
+            t.sort()
+            med = t[len(t) // 2]
+            out[k + "_us_per_frame"] = round(1e6 * med / N, 2)
+            out[k + "_us_min_max"] = [round(1e6 * t[0] / N, 2), round(1e6 * t[-1] / N, 2)]
+            out[k + "_GBps"] = round(3 * N * W * H * B / med / 1e9, 1)
+            out[k + "_of_hbm_peak"] = round(3 * N * W * H * B / 8e12 / med, 3)
+    return out
+
+
 def merge_bandwidth(clip, a):
     """sn_merge_device against sn_mask_merge_device (expand 1, into a third plane), both on noise and moving 3 W H B bytes per
     frame, and sn_turn_merge_device (3 W H B) against sn_turn_device (2 W H B), alternating: median, minimum and maximum
@@ -359,6 +408,9 @@ def main():
     ap.add_argument("--sharpen-bw", action="store_true", help="the sharpening kernel alone against the mask kernel on the same planes")
     ap.add_argument("--fields", choices=["one", "both"], default="one", help="both: the both-fields call next to the one-field call, alternating")
     ap.add_argument("--merge-bw", action="store_true", help="the averaging kernel alone against the mask kernel, and the turn of the average against the turn")
+    ap.add_argument("--repair", type=int, default=0, help="K 1..4: the call with the rank repair next to the call without it (at source size)")
+    ap.add_argument("--repair-chroma", action="store_true", help="--repair: every processed plane, not luma alone")
+    ap.add_argument("--repair-bw", action="store_true", help="the repair kernel alone against the mask and sharpening kernels on the same planes")
     a = ap.parse_args()
     a.mask_values = ([int(x) for x in a.mask.split(",")] + [1])[:3] if a.mask else [8, 32, 1]
     mask_kw = dict(mask=tuple(a.mask_values[:2]), mask_expand=a.mask_values[2]) if a.mask else None
@@ -380,12 +432,17 @@ def main():
     if a.merge_bw:
         print(json.dumps(merge_bandwidth(clip, a)))
         return
+    if a.repair_bw:
+        print(json.dumps(repair_bandwidth(clip, a)))
+        return
     if clip.bytes != 1:
         sys.exit("aa_bench: 8-bit formats only")
     if a.fields == "both" and (a.dh or a.composed or a.host):
         sys.exit("aa_bench: --fields both goes without --dh, on device batches")
     if a.sharpen and ((a.dh and not a.reduce) or a.composed or a.host):
         sys.exit("aa_bench: --sharpen needs the frame at source size (without --dh, or with --reduce) and device batches")
+    if a.repair and ((a.dh and not a.reduce) or a.composed or a.host or a.fields == "both"):
+        sys.exit("aa_bench: --repair needs the frame at source size (without --dh, or with --reduce) and device batches of one field")
     if a.mask and ((a.dh and not a.reduce) or a.composed):
         sys.exit("aa_bench: --mask needs the frame at source size: without --dh, or with --reduce")
     if a.composed and (not a.dh or a.host or a.reduce):
@@ -421,7 +478,10 @@ def main():
         return
     reps = 5
     sharpen_kw = dict(mask_kw or {}, sharpen=a.sharpen, sharpen_chroma=a.sharpen_chroma)
-    for key, kw in [("aa_fps", {})] + ([("aa_mask_fps", mask_kw)] if a.mask else []) + ([("aa_sharpen_fps", sharpen_kw)] if a.sharpen else []):
+    before_repair = dict(sharpen_kw if a.sharpen else mask_kw or {})
+    repair_kw = dict(before_repair, repair=a.repair, repair_chroma=a.repair_chroma)
+    for key, kw in [("aa_fps", {})] + ([("aa_mask_fps", mask_kw)] if a.mask else []) + ([("aa_sharpen_fps", sharpen_kw)] if a.sharpen else []) + \
+            ([("aa_repair_fps", repair_kw)] if a.repair else []):
         with SangNomAA(clip, max_batch=N, fresh_pool=bool(a.fresh), aac=48 if clip.planes > 1 else 0, **(dict(dh=True) if a.dh else {}),
                        **(dict(reduce=a.reduce) if a.reduce else {}), **kw) as aa:
             torch.cuda.synchronize()
@@ -440,6 +500,9 @@ def main():
     if a.sharpen:  # on top of the mask where one is given
         out["sharpen"] = [a.sharpen, int(a.sharpen_chroma)]
         out["sharpen_us_per_frame"] = round(1e6 / out["aa_sharpen_fps"] - 1e6 / out["aa_mask_fps" if a.mask else "aa_fps"], 2)
+    if a.repair:  # on top of the sharpening and the mask where given
+        out["repair"] = [a.repair, int(a.repair_chroma)]
+        out["repair_us_per_frame"] = round(1e6 / out["aa_repair_fps"] - 1e6 / out["aa_sharpen_fps" if a.sharpen else "aa_mask_fps" if a.mask else "aa_fps"], 2)
     with SangNom2(clip, max_batch=N) as flt:
         t = torch.empty((N, w, h), device=dev, dtype=torch.uint8)
         torch.cuda.synchronize()
